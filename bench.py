@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the DR-NMF hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
           --master-port P bench.py --gpus N ...; a bare `python bench.py --gpus N` starts exactly that
           as a child process before anything touches the GPU and relays its output)
@@ -15,6 +15,12 @@ mask head) + loss + BPTT + Adam over the batch (`train_on_batch`); with N > 1 GP
 all-reduce of the flat gradient (RCCL through libdrnmf's C ABI).  The forward alone -- the
 north-star target and round 1's headline -- is timed the same way and reported beside it as
 `forward` with its own roofline block.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps of the headline and prints its line; the rooflines,
+the step breakdown, the forward block, the extra lines and the CPU baseline take runs of their own
+and come with --full.  --dump-outputs DIR writes what the timed path computed in its last step (the
+loss and the trained weights of the training step; the masks of --forward-only) as DIR/<name>.npy:
+the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -61,7 +67,16 @@ def parse():
     ap.add_argument("--no-extras", action="store_true", help="headline + forward blocks only")
     ap.add_argument("--cpu-frames", type=int, default=0,
                     help="frame-steps of the CPU baseline sample (0 = auto, ~15-25 s)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: rooflines and step breakdown, the forward "
+                         "block, the bf16x3 line, the extra lines and the CPU baseline (the --no-* options "
+                         "thin this out); without it the run times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def synth_on_device(torch, dev, B, T, F, r, seed, want_clean=False):
@@ -968,6 +983,39 @@ def config1_bench(torch, dev):
     return out
 
 
+DUMP_LIMIT_BYTES = 60 << 20      # all arrays together, under the 64 MB --dump-outputs promises
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: [(name, numpy array)] -> dirname/<name>.npy, float32 kept, anything else as float64.
+    Arrays are filled smallest first, each up to an even share of what DUMP_LIMIT_BYTES has left; an array
+    larger than its share is replaced by a sample of its flattened elements at sorted indices drawn by
+    PCG64(7654) -- the same elements in every run at the same shape and arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_LIMIT_BYTES
+    arrays = sorted(((n, np.asarray(v)) for n, v in arrays), key=lambda nv: nv[1].size)
+    for i, (name, v) in enumerate(arrays):
+        v = v.astype(np.float32 if v.dtype == np.float32 else np.float64, copy=False)
+        cap = max(1, left // (len(arrays) - i) // v.itemsize)
+        if v.size > cap:
+            rng = np.random.Generator(np.random.PCG64(7654))
+            v = v.reshape(-1)[np.unique(rng.integers(0, v.size, cap))]
+        np.save(os.path.join(dirname, name + ".npy"), v)
+        left -= v.nbytes
+
+
+def finish(out, rank, dist):
+    """Print the result line on rank 0, leave the process group; exit 4 when there is no headline value."""
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist is not None:
+        from drnmf_amd import dp
+        dp.comm_destroy()
+        dist.destroy_process_group()
+    if out.get("value") is None:
+        raise SystemExit(4)
+
+
 def spawn_ranks(a):
     """`python bench.py --gpus N` outside a launcher: start N ranks with torch.distributed.run as
     a CHILD process (nothing in this process has touched the GPU yet) and leave with its code."""
@@ -1062,8 +1110,8 @@ def main():
 
     n_chain = T * (2 * K - 1)            # launches of one pass over the batch (forward or BPTT)
     flops_per_launch = 2.0 * B * F * N    # one B x F x N contraction
-    traffic, traffic_src = pmc_traffic()
-    prof = rocprof_launch_us()
+    traffic, traffic_src = pmc_traffic() if a.full else (None, None)
+    prof = rocprof_launch_us() if a.full else None
 
     # ---------------- headline: forward + loss + BPTT + Adam (the metric's "fwd+bwd") ----------
     out = {}
@@ -1132,6 +1180,11 @@ def main():
             losses = []
             wall, ev_ms = timed(lambda: losses.append(model.train_on_batch(X, Y, wts)),
                                 a.steps, a.warmup)
+            if a.dump_outputs and rank == 0:   # the last timed step's loss and the weights it trained
+                dump_outputs(a.dump_outputs, [("loss", np.array([float(losses[-1])]))] +
+                             [("weight_" + n, t.detach().cpu().numpy()) for n, t in model._train_items])
+            if not a.full:
+                return dict(wall=wall, ev_ms=ev_ms, losses=losses)
             pe = model.phase_events            # events of the LAST timed step
             phases = {k: v[0].elapsed_time(v[1]) for k, v in pe.items()}
             model.phase_events = None
@@ -1176,10 +1229,6 @@ def main():
     if train is not None and "error" not in train:
         wall, ev_ms = train["wall"], train["ev_ms"]
         value = world * B * T * a.steps / wall
-        fwd_ms, bwd_chain_ms = train["phases"]["cell_forward"], train["bp"]["chain_ms"]
-        launches = n_chain + train["bp"]["chain_launches"]
-        launch_us = (fwd_ms + bwd_chain_ms) * 1e3 / launches
-        ach = flops_per_launch / (launch_us * 1e-6) / 1e12
         flops_step = (12.0 * F * N * K - 2.0 * F * N) * B * T
         out = {
             "metric": "STFT frames/sec (fwd+bwd), %d-bin x %d-frame, K=%d unrolls" % (F, T, K),
@@ -1197,7 +1246,17 @@ def main():
                        "comm_rank_world_as_reported_by_drnmf_comm_info": comm_seen,
                        "allreduce_bytes": (train.get("allreduce") or {}).get("bytes"),
                        "allreduce_ms": (train.get("allreduce") or {}).get("ms")},
-            "roofline": {
+            "whole_step_tflops_algorithmic": flops_step / (ev_ms / a.steps * 1e-3) / 1e12,
+            "whole_step_frac_of_f32_mfma_peak":
+                flops_step / (ev_ms / a.steps * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS,
+            "loss_first": float(train["losses"][0]), "loss_last": float(train["losses"][-1]),
+        }
+        if a.full:      # the step's phases and the bracketed BPTT pass: measured in headline()
+            fwd_ms, bwd_chain_ms = train["phases"]["cell_forward"], train["bp"]["chain_ms"]
+            launches = n_chain + train["bp"]["chain_launches"]
+            launch_us = (fwd_ms + bwd_chain_ms) * 1e3 / launches
+            ach = flops_per_launch / (launch_us * 1e-6) / 1e12
+            out["roofline"] = {
                 "bound": "mfma", "achieved": ach, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
                 "frac": ach / PEAK_F32_MFMA_TFLOPS, "traffic": traffic, "traffic_from_profile": traffic_src,
                 "kernel": "the chain kernels cell_a / cell_b (forward) and cell_b / bwd_a (BPTT): "
@@ -1217,18 +1276,13 @@ def main():
                                           "launch exchanges (h in, residual out or the reverse: B (N + F) fp32); "
                                           "`traffic` is the PMC figure of the same launch (L2-side, every XCD's "
                                           "fetch of a shared operand counted)",
-            },
-            "step_breakdown_ms": {
+            }
+            out["step_breakdown_ms"] = {
                 "cell_forward_chain": fwd_ms, "head_and_loss": train["phases"]["head_and_loss"],
                 "cell_backward_total": train["phases"]["cell_backward"],
                 "bptt_sequential_pass": bwd_chain_ms,
                 "bptt_time_batched_weight_gradients": train["bp"]["batched_ms"],
-                "hip_event_ms_per_step": ev_ms / a.steps},
-            "whole_step_tflops_algorithmic": flops_step / (ev_ms / a.steps * 1e-3) / 1e12,
-            "whole_step_frac_of_f32_mfma_peak":
-                flops_step / (ev_ms / a.steps * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS,
-            "loss_first": float(train["losses"][0]), "loss_last": float(train["losses"][-1]),
-        }
+                "hip_event_ms_per_step": ev_ms / a.steps}
         if train.get("x3"):
             x3 = train["x3"]
             out["headline_bf16x3"] = {
@@ -1245,6 +1299,8 @@ def main():
         out = {"metric": "STFT frames/sec (fwd+bwd), %d-bin x %d-frame, K=%d unrolls" % (F, T, K),
                "value": None, "unit": "frames/s", "n_gpus": world, "steps": a.steps,
                "warmup": a.warmup, "error": train["error"]}
+    if not (a.full or a.forward_only):
+        return finish(out, rank, dist)
 
     # release the training state (hall, dz, dR: ~60 GB at the headline shape) before the rest
     model._opt_state = model._flat = model._gview = model._mflat = model._vflat = None
@@ -1271,13 +1327,15 @@ def main():
         cell_ev[1].synchronize()
         cell_ms.append(cell_ev[0].elapsed_time(cell_ev[1]))
     fwall, fev_ms = timed(fwd_step, a.steps, a.warmup)
+    if a.dump_outputs and a.forward_only and rank == 0:     # the masks of the last timed forward
+        dump_outputs(a.dump_outputs, [("mask", m_buf.cpu().numpy())])
     cell_ms = cell_ms[-a.steps:]
     ok = bool(torch.isfinite(m_buf).all().item()) and float(m_buf.min()) > 0.0
     f_launch_us = (sum(cell_ms) / len(cell_ms)) * 1e3 / n_chain
     f_ach = flops_per_launch / (f_launch_us * 1e-6) / 1e12
     whole = (B * T * a.steps) * 4.0 * F * N * K / (fev_ms * 1e-3) / 1e12
     per_kernel = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and a.full:
         try:   # launch-by-launch HIP events over the first frames (plain launches, no graph)
             desc = model.cell._desc(B, T)
             per_kernel = ops.cell_profile(X, -1., model.cell._params_block, desc, model.cell.log_h0,
@@ -1315,6 +1373,8 @@ def main():
                           "K": K, "untied": not a.tied},
                "roofline": forward["roofline"]}
     out["forward"] = forward
+    if not a.full:
+        return finish(out, rank, dist)
 
     extra = {}
     if rank == 0 and world == 1 and not a.no_extras:
@@ -1417,14 +1477,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(F, r, K, B, a.cpu_frames, a.tied)
         except Exception as e:           # noqa: BLE001 -- the GPU line is still valid without it
             out["cpu_baseline"] = {"error": repr(e)[:300]}
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        from drnmf_amd import dp
-        dp.comm_destroy()
-        dist.destroy_process_group()
-    if out.get("value") is None:
-        raise SystemExit(4)
+    finish(out, rank, dist)
 
 
 if __name__ == "__main__":

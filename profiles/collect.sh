@@ -19,14 +19,14 @@ stats() {   # stats <name> <program args...>: rocprofv3 --kernel-trace --stats s
     find "$OUT/$name" -name '*kernel_trace.csv' -size +8M -delete
     find "$OUT/$name" -name "*.db" -delete
 }
-# 1. the default bench line (fwd+bwd headline, forward block, extras, CPU baseline)
-python3 "$B" > "$OUT/bench_full.json" 2> "$OUT/bench_full.err"
+# 1. the full bench line (fwd+bwd headline, forward block, extras, CPU baseline)
+python3 "$B" --full > "$OUT/bench_full.json" 2> "$OUT/bench_full.err"
 # 2. kernel trace + stats of the headline workload alone: one warm-up + one timed training step
 #    (forward chain, head, loss, BPTT chain, time-batched weight gradients, Adam) and the forward
 #    block; the extra lines reuse the same kernel templates at other shapes and would blur the means
-stats bench "$B" --steps 1 --warmup 1 --no-cpu-baseline --no-extras
+stats bench "$B" --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras
 # 3. the forward alone (what the PMC passes below also run)
-stats fwd "$B" --forward-only --steps 1 --warmup 1 --no-cpu-baseline --no-extras
+stats fwd "$B" --full --forward-only --steps 1 --warmup 1 --no-cpu-baseline --no-extras
 # 4. frame-parallel ISTA GEMMs, the config-5 shape (fp32 and fp16 operands), the shipped training config
 stats ista "$ROOT/tools/ista_profile.py" 32768 513 2000 25
 stats c5 "$ROOT/tools/c5_profile.py" 16
@@ -46,8 +46,8 @@ rm -rf "$OUT/x3pmc"
 stats snmf_train "$ROOT/tools/snmf_profile.py" 32768 513 1000 20
 python3 "$ROOT/tools/snmf_profile.py" 32768 513 1000 20 > "$OUT/snmf_train_unprofiled.txt" 2>&1
 # the reference's inference slab (250 utterances) and B = 1024: forward only, sub-batches on side streams
-stats fwd_b250 "$B" --forward-only --batch 250 --frames 200 --steps 1 --warmup 1 --no-cpu-baseline --no-extras
-stats fwd_b1024 "$B" --forward-only --batch 1024 --frames 100 --steps 1 --warmup 1 --no-cpu-baseline --no-extras
+stats fwd_b250 "$B" --full --forward-only --batch 250 --frames 200 --steps 1 --warmup 1 --no-cpu-baseline --no-extras
+stats fwd_b1024 "$B" --full --forward-only --batch 1024 --frames 100 --steps 1 --warmup 1 --no-cpu-baseline --no-extras
 python3 "$ROOT/tools/batch_sweep.py" 400 64 128 250 512 1024 2048 > "$OUT/batch_sweep.txt" 2> "$OUT/batch_sweep.err"
 python3 "$ROOT/tools/batch_sweep.py" 2000 250 >> "$OUT/batch_sweep.txt" 2>> "$OUT/batch_sweep.err"
 # HIP API calls of 20 steady-state optimiser steps (with-steps minus zero-steps trace): no synchronising call
@@ -67,13 +67,13 @@ DRNMF_PERSIST=0 python3 "$ROOT/tools/small_shapes.py" 20 > "$OUT/small_shapes_pe
 # EXPLICITLY (RCCL refuses two ranks on one device); the only multi-rank run a 1-GPU box allows
 DRNMF_BENCH_BACKEND=gloo DRNMF_BENCH_DEVICE=0 DRNMF_DP_BACKEND=torch timeout 900 python3 -m torch.distributed.run \
     --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 "$B" --gpus 2 --frames 400 \
-    --steps 2 --warmup 1 --no-extras --no-cpu-baseline > "$OUT/n2_gloo_one_gpu.json" 2> "$OUT/n2_gloo_one_gpu.err"
+    --steps 2 --warmup 1 --no-extras --no-cpu-baseline --full > "$OUT/n2_gloo_one_gpu.json" 2> "$OUT/n2_gloo_one_gpu.err"
 # ... and EIGHT ranks on the one device through bench.py's own spawn_ranks (build lock, rendezvous, rank-0 JSON)
 # (round 5: with the multi-rank extras -- configs[3] data-parallel training, configs[4] replicas -- at toy shapes, and rank 0's CPU baseline)
 ( cd "$ROOT" && DRNMF_BENCH_TINY=1 DRNMF_BENCH_BACKEND=gloo DRNMF_BENCH_DEVICE=0 DRNMF_DP_BACKEND=torch timeout 900 python3 bench.py --gpus 8 --batch 4 \
-    --frames 8 --steps 2 --warmup 1 2> "$OUT/n8_gloo_one_gpu.err" | tail -1 > "$OUT/n8_gloo_one_gpu.json" )
+    --frames 8 --steps 2 --warmup 1 --full 2> "$OUT/n8_gloo_one_gpu.err" | tail -1 > "$OUT/n8_gloo_one_gpu.json" )
 # 5. PMC passes, 20 frames of the headline forward (cell + head only)
-SMALL="--forward-only --frames 20 --steps 1 --warmup 0 --no-cpu-baseline --no-extras"
+SMALL="--full --forward-only --frames 20 --steps 1 --warmup 0 --no-cpu-baseline --no-extras"
 timeout 600 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE TCC_HIT_sum -d "$OUT/pmc_fetch" -o p -- python3 "$B" $SMALL \
     > /dev/null 2> "$OUT/pmc_fetch.err"
 timeout 600 rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE TCC_MISS_sum TCC_REQ_sum -d "$OUT/pmc_write" -o p -- python3 "$B" $SMALL \
@@ -83,7 +83,7 @@ timeout 600 rocprofv3 --kernel-trace --output-format csv --pmc SQ_WAVE_CYCLES SQ
     > /dev/null 2> "$OUT/pmc_sq.err"
 python3 "$ROOT/profiles/summarize_pmc.py" "$OUT/pmc_summary.json" "$OUT/pmc_fetch" "$OUT/pmc_write" "$OUT/pmc_sq"
 # 5b. the same passes at the reference's inference slab (B = 250; two sub-batches on side streams)
-SLAB="--forward-only --batch 250 --frames 20 --steps 1 --warmup 0 --no-cpu-baseline --no-extras"
+SLAB="--full --forward-only --batch 250 --frames 20 --steps 1 --warmup 0 --no-cpu-baseline --no-extras"
 timeout 600 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE TCC_HIT_sum -d "$OUT/pmc_fetch_b250" -o p -- python3 "$B" $SLAB \
     > /dev/null 2> "$OUT/pmc_fetch_b250.err"
 timeout 600 rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE TCC_MISS_sum TCC_REQ_sum -d "$OUT/pmc_write_b250" -o p -- python3 "$B" $SLAB \

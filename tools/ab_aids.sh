@@ -4,7 +4,7 @@
 set -u
 line() {  # line <label> <bench args...>
   local label=$1; shift
-  python3 bench.py "$@" --no-extras --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
+  python3 bench.py "$@" --full --no-extras --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 f = d.get('forward', {})
