@@ -1169,6 +1169,7 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
     // are reported by drnmf_check_status / drnmf_status_take_device only.)
     int rc = validate_cell_desc(h, d);
     if (rc) return rc;
+    ++h->call_seq;                   // (a top-level call: the graphs it takes are pinned until it returns)
     // operand_f16: the forward ran on fp16 matrix-core operands; its BPTT is computed in fp32 from
     // the stored hiddens and the fp32 dictionary packings kept in the same prepared block
     // (rounding treated as the identity: mixed-precision training)
@@ -1355,101 +1356,56 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
                                      dim3(64 * (NW_G + 1)), kp, 0, stream));
         persist_mark(h, stream);
     }
-    uint32_t beta_bits;
-    memcpy(&beta_bits, &beta, 4);
-    std::vector<uint64_t> key = {(W.gram ? 0xB00Cull : 0xB00Bull) + ((uint64_t)d->divergence << 16) +
-                                     ((uint64_t)beta_bits << 32), (uint64_t)B, (uint64_t)T, (uint64_t)F, (uint64_t)N,
-                                 (uint64_t)K, (uint64_t)d->n_D, (uint64_t)(uintptr_t)params,
-                                 (uint64_t)(uintptr_t)hall, (uint64_t)(uintptr_t)d_out,
-                                 (uint64_t)(uintptr_t)fwd_workspace,
-                                 (uint64_t)(uintptr_t)bwd_workspace};
-    {
-        uint32_t b0, b1, b2;
-        memcpy(&b0, &u0_diag, 4); memcpy(&b1, &u0_off, 4); memcpy(&b2, &uk_off, 4);
-        key.push_back(b0); key.push_back(b1); key.push_back(b2);
-    }
-    // several frames per graph, as in the forward (cell_forward.hip)
-    int fpg_max = 800 / (2 * K - 1);         // ~800 kernel nodes per graph
-    fpg_max = fpg_max < 1 ? 1 : (fpg_max > 64 ? 64 : fpg_max);
-    if (fpg_max > T) fpg_max = T;
-    auto get_graph = [&](int fpg, hipGraphExec_t* out) -> int32_t {
-    std::vector<uint64_t> gkey = key;
-    gkey.push_back((uint64_t)fpg);
-    GraphEntry* entry = nullptr;
-    for (auto& g : h->graphs)
-        if (g.key == gkey) { entry = &g; break; }
-    if (!entry) {
-        {   // bounded cache: the oldest entry is retired without synchronising (common.h)
-            const int32_t erc = graph_cache_make_room(h, stream, 24);
-            if (erc) return erc;
-        }
-        GraphEntry ge;
-        ge.key = gkey;
-        DRNMF_HIP(h, hipGraphCreate(&ge.graph, 0));
-        hipGraphNode_t last = nullptr;
-        auto add = [&](void* func, dim3 grid, unsigned block, void** kp) -> hipError_t {
-            hipKernelNodeParams p;
-            memset(&p, 0, sizeof(p));
-            p.func = func; p.gridDim = grid; p.blockDim = dim3(block);
-            p.sharedMemBytes = 0; p.kernelParams = kp; p.extra = nullptr;
-            hipGraphNode_t node;
-            hipError_t e = hipGraphAddKernelNode(&node, ge.graph, last ? &last : nullptr,
-                                                 last ? 1 : 0, &p);
-            last = node;
-            return e;
-        };
-        for (int rep = 0; rep < fpg; ++rep) {
-            void* ke[1] = {&ea};
-            DRNMF_HIP(h, add((void*)&bwd_edge_kernel, grid_a, 256, ke));
-            for (int k = K - 1; k >= kmin; --k) {
-                if (W.gram) {
-                    GramBwdArgs g = make_g(k);
-                    void* kg[1] = {&g};
-                    DRNMF_HIP(h, add(pick_gram_bwd(W.Np / 16), grid_g, 64 * NW_G, kg));
-                    continue;
-                }
-                CellBArgs b = make_b(k);
-                DRNMF_HIP(h, add(pick_b_func(nch_ks_b, W.RB, false, qred), grid_b, 64 * NW_B, CellBParams(b).p));
-                if (nonlin) {                          // d x^ = d r * dg/dx^ (x_t, x^_{t,k}), in place
-                    const float* xpp = (const float*)(fw + W.off_xp);
-                    const float* xh = (const float*)(fw + W.off_xhat);
-                    float* drp = drpart;
-                    const int* crd = cA;
-                    const unsigned char* vp = valid;
-                    int Tv = T, kv = k, Kv = K, dv = d->divergence, Fv = F, Fpv = W.Fp, Bpv = W.Bp;
-                    float bt = beta;
-                    void* ks[13] = {&xpp, &xh, &drp, &crd, &vp, &Tv, &kv, &Kv, &dv, &bt, &Fv, &Fpv, &Bpv};
-                    DRNMF_HIP(h, add((void*)&dgdx_scale_kernel,
-                                     dim3((unsigned)((size_t)W.Bp * W.Fp / 256)), 256, ks));
-                }
-                BwdAArgs a = make_a(k);
-                DRNMF_HIP(h, add(pick_bwd_a(nft, W.KS, qred, nonlin && k == 0), grid_a, 256, BwdAParams(a).p));
+    // one frame in reverse time: the edge kernel, then the chain down the layers
+    auto frame = [&](Launcher& chain, int) -> int32_t {
+        void* ke[1] = {&ea};
+        DRNMF_HIP(h, chain.add((void*)&bwd_edge_kernel, grid_a, 256, ke));
+        for (int k = K - 1; k >= kmin; --k) {
+            if (W.gram) {
+                GramBwdArgs g = make_g(k);
+                void* kg[1] = {&g};
+                DRNMF_HIP(h, chain.add(pick_gram_bwd(W.Np / 16), grid_g, 64 * NW_G, kg));
+                continue;
             }
-            if (edge_only) {
-                int* cp = cA;
-                void* kc[1] = {&cp};
-                DRNMF_HIP(h, add((void*)&advance_frame_kernel, dim3(1), 1, kc));
+            CellBArgs b = make_b(k);
+            DRNMF_HIP(h, chain.add(pick_b_func(nch_ks_b, W.RB, false, qred), grid_b, 64 * NW_B, CellBParams(b).p));
+            if (nonlin) {                          // d x^ = d r * dg/dx^ (x_t, x^_{t,k}), in place
+                const float* xpp = (const float*)(fw + W.off_xp);
+                const float* xh = (const float*)(fw + W.off_xhat);
+                float* drp = drpart;
+                const int* crd = cA;
+                const unsigned char* vp = valid;
+                int Tv = T, kv = k, Kv = K, dv = d->divergence, Fv = F, Fpv = W.Fp, Bpv = W.Bp;
+                float bt = beta;
+                void* ks[13] = {&xpp, &xh, &drp, &crd, &vp, &Tv, &kv, &Kv, &dv, &bt, &Fv, &Fpv, &Bpv};
+                DRNMF_HIP(h, chain.add((void*)&dgdx_scale_kernel,
+                                       dim3((unsigned)((size_t)W.Bp * W.Fp / 256)), 256, ks));
             }
+            BwdAArgs a = make_a(k);
+            DRNMF_HIP(h, chain.add(pick_bwd_a(nft, W.KS, qred, nonlin && k == 0), grid_a, 256, BwdAParams(a).p));
         }
-        DRNMF_HIP(h, hipGraphInstantiate(&ge.exec, ge.graph, nullptr, nullptr, 0));
-        h->graphs.push_back(ge);
-        entry = &h->graphs.back();
-    }
-    entry->last_stream = stream;
-    *out = entry->exec;
-    return DRNMF_OK;
+        if (edge_only) {
+            int* cp = cA;
+            void* kc[1] = {&cp};
+            DRNMF_HIP(h, chain.add((void*)&advance_frame_kernel, dim3(1), 1, kc));
+        }
+        return DRNMF_OK;
     };
     if (!persist) {
-        hipGraphExec_t exec_n = nullptr, exec_1 = nullptr;
-        int32_t grc = get_graph(fpg_max, &exec_n);
+        uint32_t bb[4];
+        memcpy(&bb[0], &beta, 4);
+        memcpy(&bb[1], &u0_diag, 4); memcpy(&bb[2], &u0_off, 4); memcpy(&bb[3], &uk_off, 4);
+        const std::vector<uint64_t> key = {
+            (uint64_t)W.gram, (uint64_t)d->divergence, bb[0], (uint64_t)B, (uint64_t)T, (uint64_t)F, (uint64_t)N,
+            (uint64_t)K, (uint64_t)d->n_D, (uint64_t)(uintptr_t)params, (uint64_t)(uintptr_t)hall,
+            (uint64_t)(uintptr_t)d_out, (uint64_t)(uintptr_t)fwd_workspace, (uint64_t)(uintptr_t)bwd_workspace,
+            bb[1], bb[2], bb[3]};
+        // several frames per graph, as in the forward (cell_forward.hip)
+        int fpg = 800 / (2 * K - 1);         // ~800 kernel nodes per graph
+        fpg = fpg < 1 ? 1 : (fpg > 64 ? 64 : fpg);
+        if (fpg > T) fpg = T;
+        const int32_t grc = replay_frames(h, stream, GraphKind::Backward, key, {fpg, 1}, 0, T, frame);
         if (grc) return grc;
-        int t = 0;
-        for (; t + fpg_max <= T; t += fpg_max) DRNMF_HIP(h, hipGraphLaunch(exec_n, stream));
-        if (t < T) {
-            grc = get_graph(1, &exec_1);
-            if (grc) return grc;
-            for (; t < T; ++t) DRNMF_HIP(h, hipGraphLaunch(exec_1, stream));
-        }
     }
     if (!persist) hipLaunchKernelGGL(bwd_edge_kernel, grid_a, dim3(256), 0, stream, ea);   // t = -1
     hipLaunchKernelGGL(dlogh0_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, dh0_part,

@@ -425,6 +425,7 @@ static int32_t dense_forward_impl(drnmf_handle_t h, const drnmf_dense_desc_t* d,
     if (!h) return DRNMF_ERR_INVALID_ARG;
     int rc = validate_dense_desc(h, d);
     if (rc) return rc;
+    ++h->call_seq;                   // (a top-level call: the graphs it takes are pinned until it returns)
     if (!x || !params || !h_out || !workspace || (!h0 && !initial_state))
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "dense_cell_forward: NULL pointer argument");
     const DenseLayout D = dense_layout(d);
@@ -499,93 +500,30 @@ static int32_t dense_forward_impl(drnmf_handle_t h, const drnmf_dense_desc_t* d,
                         : (nw == 8 ? dense_func<4, 8>(last, wo) : dense_func<4, 4>(last, wo));
     };
 
+    // one frame = K launches (K = 1: and the frame-counter advance)
+    auto frame = [&](Launcher& chain, int) -> int32_t {
+        for (int k = 0; k < K; ++k) {
+            DenseArgs a = make(k);
+            void* kp[1] = {&a};
+            DRNMF_HIP(h, chain.add(func(k), grid, 64 * nw, kp));
+        }
+        if (K == 1) {
+            int* tp = tA;
+            void* kt[1] = {&tp};
+            DRNMF_HIP(h, chain.add((void*)&advance_frame_kernel, dim3(1), 1, kt));
+        }
+        return DRNMF_OK;
+    };
     int fpg = 400 / K;
     fpg = fpg < 1 ? 1 : (fpg > 64 ? 64 : fpg);
     if (fpg > d->T) fpg = d->T;
-    const bool use_graph = tune_env("DRNMF_NO_GRAPH") == nullptr;
-    if (!use_graph) {
-        for (int t = 0; t < d->T; ++t) {
-            for (int k = 0; k < K; ++k) {
-                DenseArgs a = make(k);
-                void* kp[1] = {&a};
-                DRNMF_HIP(h, hipLaunchKernel(func(k), grid, dim3(64 * nw), kp, 0, stream));
-            }
-            if (K == 1) hipLaunchKernelGGL(advance_frame_kernel, dim3(1), dim3(1), 0, stream, tA);
-        }
-        DRNMF_HIP(h, hipGetLastError());
-    } else {
-        auto get_graph = [&](int frames, hipGraphExec_t* out) -> int32_t {
-            std::vector<uint64_t> key = {
-                0xDE05Eull, (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->N,
-                (uint64_t)d->K, (uint64_t)d->connect_input, (uint64_t)d->activation,
-                (uint64_t)d->return_all_hidden + 2 * (uint64_t)(d->operand_f16 != 0), (uint64_t)(uintptr_t)params,
-                (uint64_t)(uintptr_t)h_out, (uint64_t)(uintptr_t)workspace, (uint64_t)frames, (uint64_t)nw};
-            // (as the fused path, cell_forward.hip: a hit moves to the back -- eviction is least-recently-used --
-            // and is pinned by THIS call, whose sequence number dense_forward_impl advanced)
-            for (size_t gi = 0; gi < h->graphs.size(); ++gi)
-                if (h->graphs[gi].key == key) {
-                    if (gi + 1 != h->graphs.size()) {
-                        GraphEntry hit = h->graphs[gi];
-                        h->graphs.erase(h->graphs.begin() + (ptrdiff_t)gi);
-                        h->graphs.push_back(hit);
-                    }
-                    h->graphs.back().last_stream = stream;
-                    h->graphs.back().pin = h->call_seq;
-                    *out = h->graphs.back().exec;
-                    return DRNMF_OK;
-                }
-            {   // bounded cache: the least recently used entry is retired without synchronising (common.h)
-                const int32_t erc = graph_cache_make_room(h, stream, 24);
-                if (erc) return erc;
-            }
-            GraphEntry ge;
-            ge.key = key;
-            DRNMF_HIP(h, hipGraphCreate(&ge.graph, 0));
-            hipGraphNode_t last = nullptr;
-            auto add = [&](void* f, dim3 g, unsigned block, void** kp) -> hipError_t {
-                hipKernelNodeParams p;
-                memset(&p, 0, sizeof(p));
-                p.func = f;
-                p.gridDim = g;
-                p.blockDim = dim3(block);
-                p.kernelParams = kp;
-                hipGraphNode_t node;
-                hipError_t e = hipGraphAddKernelNode(&node, ge.graph, last ? &last : nullptr,
-                                                     last ? 1 : 0, &p);
-                last = node;
-                return e;
-            };
-            for (int rep = 0; rep < frames; ++rep) {
-                for (int k = 0; k < K; ++k) {
-                    DenseArgs a = make(k);
-                    void* kp[1] = {&a};
-                    DRNMF_HIP(h, add(func(k), grid, 64 * nw, kp));
-                }
-                if (K == 1) {
-                    int* tp = tA;
-                    void* kt[1] = {&tp};
-                    DRNMF_HIP(h, add((void*)&advance_frame_kernel, dim3(1), 1, kt));
-                }
-            }
-            DRNMF_HIP(h, hipGraphInstantiate(&ge.exec, ge.graph, nullptr, nullptr, 0));
-            ge.last_stream = stream;
-            ge.pin = h->call_seq;
-            h->graphs.push_back(ge);
-            *out = ge.exec;
-            return DRNMF_OK;
-        };
-        ++h->call_seq;       // (a top-level call: entries pinned by an EARLIER call become evictable again)
-        hipGraphExec_t ex = nullptr;
-        rc = get_graph(fpg, &ex);
-        if (rc) return rc;
-        int t = 0;
-        for (; t + fpg <= d->T; t += fpg) DRNMF_HIP(h, hipGraphLaunch(ex, stream));
-        if (t < d->T) {
-            rc = get_graph(1, &ex);
-            if (rc) return rc;
-            for (; t < d->T; ++t) DRNMF_HIP(h, hipGraphLaunch(ex, stream));
-        }
-    }
+    const std::vector<uint64_t> key = {
+        (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->N, (uint64_t)d->K,
+        (uint64_t)d->connect_input, (uint64_t)d->activation,
+        (uint64_t)d->return_all_hidden + 2 * (uint64_t)(d->operand_f16 != 0), (uint64_t)(uintptr_t)params,
+        (uint64_t)(uintptr_t)h_out, (uint64_t)(uintptr_t)workspace, (uint64_t)nw};
+    rc = replay_frames(h, stream, GraphKind::Dense, key, {fpg, 1}, 0, d->T, frame);
+    if (rc) return rc;
     if (final_state && drop_u) {
         hipLaunchKernelGGL(dense_store_state_unmasked_kernel, dim3(d->B), dim3(256), 0, stream, h_out,
                            initial_state, h0, valid, final_state, d->T, d->N, D.Bp,

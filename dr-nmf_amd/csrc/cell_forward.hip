@@ -1006,46 +1006,19 @@ static int32_t cell_forward_gram(drnmf_handle_t h, const drnmf_cell_desc_t* d, c
         a.cp_mask = cp_mask;
         return a;
     };
-    std::vector<uint64_t> key = {
-        0x6A4Dull, (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->N, (uint64_t)K,
-        (uint64_t)d->n_D, (uint64_t)d->return_all_hidden, (uint64_t)(uintptr_t)params,
-        (uint64_t)(uintptr_t)h_out, (uint64_t)(uintptr_t)workspace};
-    {
-        uint32_t b0, b1, b2;
-        memcpy(&b0, &u0_diag, 4); memcpy(&b1, &u0_off, 4); memcpy(&b2, &uk_off, 4);
-        key.push_back(b0); key.push_back(b1); key.push_back(b2);
-    }
-    auto get_graph = [&](int frames, hipGraphExec_t* out) -> int32_t {
-        std::vector<uint64_t> gkey = key;
-        gkey.push_back((uint64_t)frames);
-        for (auto& g : h->graphs)
-            if (g.key == gkey) { g.last_stream = stream; *out = g.exec; return DRNMF_OK; }
-        const int32_t erc = graph_cache_make_room(h, stream, 24);
-        if (erc) return erc;
-        GraphEntry ge;
-        ge.key = gkey;
-        DRNMF_HIP(h, hipGraphCreate(&ge.graph, 0));
-        hipGraphNode_t last = nullptr;
-        for (int rep = 0; rep < frames; ++rep) {
-            for (int k = 1; k < K; ++k) {
-                GramFwdArgs a = make(k, rep & 1);
-                void* kp[1] = {&a};
-                hipKernelNodeParams p;
-                memset(&p, 0, sizeof(p));
-                p.func = pick_gram_fwd(NAC, k == 1, k == K - 1);
-                p.gridDim = grid;
-                p.blockDim = dim3(64 * NW_G);
-                p.kernelParams = kp;
-                hipGraphNode_t node;
-                DRNMF_HIP(h, hipGraphAddKernelNode(&node, ge.graph, last ? &last : nullptr,
-                                                   last ? 1 : 0, &p));
-                last = node;
-            }
+    uint32_t ub[3];
+    memcpy(&ub[0], &u0_diag, 4); memcpy(&ub[1], &u0_off, 4); memcpy(&ub[2], &uk_off, 4);
+    const std::vector<uint64_t> key = {
+        (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->N, (uint64_t)K, (uint64_t)d->n_D,
+        (uint64_t)d->return_all_hidden, (uint64_t)(uintptr_t)params, (uint64_t)(uintptr_t)h_out,
+        (uint64_t)(uintptr_t)workspace, ub[0], ub[1], ub[2]};
+    // one frame: K-1 launches; the frame's parity inside its block selects the q buffers
+    auto frame = [&](Launcher& chain, int i) -> int32_t {
+        for (int k = 1; k < K; ++k) {
+            GramFwdArgs a = make(k, i & 1);
+            void* kp[1] = {&a};
+            DRNMF_HIP(h, chain.add(pick_gram_fwd(NAC, k == 1, k == K - 1), grid, 64 * NW_G, kp));
         }
-        DRNMF_HIP(h, hipGraphInstantiate(&ge.exec, ge.graph, nullptr, nullptr, 0));
-        ge.last_stream = stream;
-        h->graphs.push_back(ge);
-        *out = ge.exec;
         return DRNMF_OK;
     };
     // Few tiles per row tile: every row tile runs as an independent persistent chain on its own XCD
@@ -1097,26 +1070,12 @@ static int32_t cell_forward_gram(drnmf_handle_t h, const drnmf_cell_desc_t* d, c
     // divides the block length
     int fpg = 2;
     while (fpg * 2 <= GRAM_TB && fpg * 2 * (K - 1) <= 800) fpg *= 2;
-    hipGraphExec_t ex = nullptr;
     for (int j = 0; j * GRAM_TB < d->T; ++j) {
         const int t1 = (j + 1) * GRAM_TB < d->T ? (j + 1) * GRAM_TB : d->T;
-        int t = j * GRAM_TB;
-        if (t1 - t >= fpg) {
-            int32_t rc = get_graph(fpg, &ex);
-            if (rc) return rc;
-            for (; t + fpg <= t1; t += fpg) DRNMF_HIP(h, hipGraphLaunch(ex, stream));
-        }
-        if (t1 - t >= 2) {
-            int32_t rc = get_graph(2, &ex);
-            if (rc) return rc;
-            for (; t + 2 <= t1; t += 2) DRNMF_HIP(h, hipGraphLaunch(ex, stream));
-        }
-        if (t < t1) {                    // (t is even here: a single frame of parity 0)
-            int32_t rc = get_graph(1, &ex);
-            if (rc) return rc;
-            DRNMF_HIP(h, hipGraphLaunch(ex, stream));
-        }
-        int32_t rc = compute_block(j + 2);
+        // (a lone last frame starts at an even t: parity 0)
+        int32_t rc = replay_frames(h, stream, GraphKind::GramForward, key, {fpg, 2, 1}, j * GRAM_TB, t1, frame);
+        if (rc) return rc;
+        rc = compute_block(j + 2);
         if (rc) return rc;
     }
     return DRNMF_OK;
@@ -1300,20 +1259,17 @@ static int32_t cell_forward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, c
     // measurement aid: DRNMF_ABLATE=1 launches the same grids but every workgroup exits at once
     // (launch/boundary floor of the frame graph; results are garbage)
     const bool ablate = measure_env("DRNMF_ABLATE") != nullptr;
-    std::vector<uint64_t> key = {
+    uint32_t ub[3];
+    memcpy(&ub[0], &u0_diag, 4); memcpy(&ub[1], &u0_off, 4); memcpy(&ub[2], &uk_off, 4);
+    const std::vector<uint64_t> key = {
         (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->N, (uint64_t)d->K,
         (uint64_t)d->n_D, (uint64_t)d->return_all_hidden + 2 * (uint64_t)(d->operand_f16 != 0),
         (uint64_t)(uintptr_t)params,
         (uint64_t)(uintptr_t)h_out, (uint64_t)(uintptr_t)workspace, (uint64_t)ablate,
         // the layout choices baked into the nodes: a sub-batch of a split call and a direct call of the same
         // B take different row blockings (workspace_layout's `need`), and the tuning variables move them too
-        (uint64_t)W.RB | ((uint64_t)W.RBa << 8) | ((uint64_t)W.KS << 16) | ((uint64_t)W.nch_ks << 24)};
-    {
-        uint32_t b0, b1, b2;
-        memcpy(&b0, &u0_diag, 4); memcpy(&b1, &u0_off, 4); memcpy(&b2, &uk_off, 4);
-        key.push_back(b0); key.push_back(b1); key.push_back(b2);
-    }
-    const bool use_graph = tune_env("DRNMF_NO_GRAPH") == nullptr && profile_frames <= 0;
+        (uint64_t)W.RB | ((uint64_t)W.RBa << 8) | ((uint64_t)W.KS << 16) | ((uint64_t)W.nch_ks << 24),
+        ub[0], ub[1], ub[2]};
     // frames per graph: the kernels advance the device-side frame counters themselves, so a
     // graph may hold several frames' worth of nodes (fewer graph launches from the host)
     // (measured at the C2 shape: 1 / 2 / 4 / 8 / 20 frames per graph -> 251.1k / 253.9k / 255.6k /
@@ -1420,156 +1376,86 @@ static int32_t cell_forward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, c
         return b;
     };
 
-    if (!use_graph) {
-        // plain launches; in profile mode every launch is bracketed by HIP events on the stream
-        const int T_run = profile_frames > 0 ? (profile_frames < d->T ? profile_frames : d->T)
-                                             : d->T;
-        std::vector<hipEvent_t> ev;
-        std::vector<int> kind;   // 0 = cell_a middle layer, 1 = cell_b, 2 = other
-        auto mark = [&](int k_) -> hipError_t {
-            if (profile_frames <= 0) return hipSuccess;
-            hipEvent_t e;
-            hipError_t er = hipEventCreate(&e);
-            if (er != hipSuccess) return er;
-            ev.push_back(e);
-            kind.push_back(k_);
-            return hipEventRecord(e, stream);
-        };
+
+    // profile mode (drnmf_cell_profile): plain launches, each bracketed by a HIP event on the stream
+    std::vector<hipEvent_t> ev;
+    std::vector<int> kind;   // 0 = cell_a middle layer, 1 = cell_b, 2 = other
+    auto mark = [&](int k_) -> hipError_t {
+        if (profile_frames <= 0) return hipSuccess;
+        hipEvent_t e;
+        hipError_t er = hipEventCreate(&e);
+        if (er != hipSuccess) return er;
+        ev.push_back(e);
+        kind.push_back(k_);
+        return hipEventRecord(e, stream);
+    };
+    // one frame = 2K-1 launches (K = 1: cell_a and the frame-counter advance)
+    auto frame = [&](Launcher& chain, int) -> int32_t {
+        for (int k = 0; k < K; ++k) {
+            CellAArgs a = make_a(k);
+            CellAParams ka(a);
+            DRNMF_HIP(h, mark((k > 0 && k < K - 1) ? 0 : 2));
+            DRNMF_HIP(h, chain.add(ablate ? (void*)&noop_kernel
+                                          : pick_a_func(a.nchunks, W.KS, W.RBa, k == 0, k == K - 1,
+                                                        d->return_all_hidden != 0, half, qred),
+                                   grid_a, 64 * (NW_A + (half ? 1 : 0)), ka.p));
+            if (k < K - 1) {
+                CellBArgs b = make_b(k);
+                CellBParams kb(b);
+                DRNMF_HIP(h, mark(1));
+                DRNMF_HIP(h, chain.add(ablate ? (void*)&noop_kernel : pick_b_func(W.nch_ks, W.RB, half, qred),
+                                       grid_b, 64 * NW_B, kb.p));
+            }
+        }
+        if (K == 1) {
+            int* tp = tA;
+            void* kt[1] = {&tp};
+            DRNMF_HIP(h, mark(2));
+            DRNMF_HIP(h, chain.add((void*)&advance_frame_kernel, dim3(1), 1, kt));
+        }
+        return DRNMF_OK;
+    };
+
+    if (profile_frames > 0) {
+        const int T_run = profile_frames < d->T ? profile_frames : d->T;
+        Launcher direct{nullptr, stream};
         for (int t = 0; t < T_run; ++t) {
-            for (int k = 0; k < K; ++k) {
-                CellAArgs a = make_a(k);
-                CellAParams kpa(a);
-                void** kp = kpa.p;
-                DRNMF_HIP(h, mark((k > 0 && k < K - 1) ? 0 : 2));
-                DRNMF_HIP(h, hipLaunchKernel(pick_a_func(a.nchunks, W.KS, W.RBa, k == 0, k == K - 1,
-                                                         d->return_all_hidden != 0, half, qred),
-                                             grid_a, dim3(64 * (NW_A + (half ? 1 : 0))), kp, 0, stream));
-                if (k < K - 1) {
-                    CellBArgs b = make_b(k);
-                    CellBParams kb(b);
-                    DRNMF_HIP(h, mark(1));
-                    DRNMF_HIP(h, hipLaunchKernel(pick_b_func(W.nch_ks, W.RB, half, qred), grid_b, dim3(64 * NW_B), kb.p, 0,
-                                                 stream));
-                }
-            }
-            if (K == 1) {
-                DRNMF_HIP(h, mark(2));
-                hipLaunchKernelGGL(advance_frame_kernel, dim3(1), dim3(1), 0, stream, tA);
-            }
+            rc = frame(direct, t);
+            if (rc) return rc;
         }
         DRNMF_HIP(h, mark(3));
         DRNMF_HIP(h, hipGetLastError());
-        if (profile_frames > 0) {
-            DRNMF_HIP(h, hipStreamSynchronize(stream));
-            double sum[3] = {0, 0, 0};
-            long cnt[3] = {0, 0, 0};
-            const size_t per_frame = (ev.size() - 1) / (size_t)T_run;
-            const size_t skip = T_run > 1 ? per_frame : 0;          // first frame = warm-up
-            for (size_t i = skip; i + 1 < ev.size(); ++i) {
-                float ms = 0.f;
-                DRNMF_HIP(h, hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-                if (kind[i] < 2) { sum[kind[i]] += ms; cnt[kind[i]]++; }
-                sum[2] += ms;
-            }
-            const int frames_timed = T_run > 1 ? T_run - 1 : 1;
-            if (out_us) {
-                out_us[0] = cnt[0] ? (float)(sum[0] / cnt[0] * 1e3) : 0.f;
-                out_us[1] = cnt[1] ? (float)(sum[1] / cnt[1] * 1e3) : 0.f;
-                out_us[2] = (float)(sum[2] / frames_timed * 1e3);
-            }
-            for (auto e : ev) (void)hipEventDestroy(e);
+        DRNMF_HIP(h, hipStreamSynchronize(stream));
+        double sum[3] = {0, 0, 0};
+        long cnt[3] = {0, 0, 0};
+        const size_t per_frame = (ev.size() - 1) / (size_t)T_run;
+        const size_t skip = T_run > 1 ? per_frame : 0;          // first frame = warm-up
+        for (size_t i = skip; i + 1 < ev.size(); ++i) {
+            float ms = 0.f;
+            DRNMF_HIP(h, hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+            if (kind[i] < 2) { sum[kind[i]] += ms; cnt[kind[i]]++; }
+            sum[2] += ms;
         }
+        const int frames_timed = T_run > 1 ? T_run - 1 : 1;
+        if (out_us) {
+            out_us[0] = cnt[0] ? (float)(sum[0] / cnt[0] * 1e3) : 0.f;
+            out_us[1] = cnt[1] ? (float)(sum[1] / cnt[1] * 1e3) : 0.f;
+            out_us[2] = (float)(sum[2] / frames_timed * 1e3);
+        }
+        for (auto e : ev) (void)hipEventDestroy(e);
         return store_final(W);
     }
-
-    auto get_graph = [&](int fpg, hipGraphExec_t* out) -> int32_t {
-    std::vector<uint64_t> gkey = key;
-    gkey.push_back((uint64_t)fpg);
-    GraphEntry* entry = nullptr;
-    for (size_t gi = 0; gi < h->graphs.size(); ++gi)
-        if (h->graphs[gi].key == gkey) {
-            // (a hit moves to the back: eviction is least-recently-used)
-            if (gi + 1 != h->graphs.size()) {
-                GraphEntry hit = h->graphs[gi];
-                h->graphs.erase(h->graphs.begin() + (ptrdiff_t)gi);
-                h->graphs.push_back(hit);
-            }
-            entry = &h->graphs.back();
-            break;
-        }
-    if (!entry) {
-        {   // bounded cache: the least recently used entry is retired without synchronising (params.hip)
-            const int32_t erc = graph_cache_make_room(h, stream, 24);
-            if (erc) return erc;
-        }
-        GraphEntry ge;
-        ge.key = gkey;
-        DRNMF_HIP(h, hipGraphCreate(&ge.graph, 0));
-        hipGraphNode_t last = nullptr;
-        auto add = [&](void* func, dim3 grid, unsigned block, void** kp) -> hipError_t {
-            hipKernelNodeParams p;
-            memset(&p, 0, sizeof(p));
-            p.func = func;
-            p.gridDim = grid;
-            p.blockDim = dim3(block);
-            p.sharedMemBytes = 0;
-            p.kernelParams = kp;
-            p.extra = nullptr;
-            hipGraphNode_t node;
-            hipError_t e = hipGraphAddKernelNode(&node, ge.graph, last ? &last : nullptr,
-                                                 last ? 1 : 0, &p);
-            last = node;
-            return e;
-        };
-        for (int rep = 0; rep < fpg; ++rep) {
-            for (int k = 0; k < K; ++k) {
-                CellAArgs a = make_a(k);
-                CellAParams ka_(a);
-                void** ka = ka_.p;
-                DRNMF_HIP(h, add(ablate ? (void*)&noop_kernel : pick_a_func(a.nchunks, W.KS, W.RBa, k == 0, k == K - 1, d->return_all_hidden != 0, half, qred), grid_a, 64 * (NW_A + (half ? 1 : 0)), ka));
-                if (k < K - 1) {
-                    CellBArgs b = make_b(k);
-                    DRNMF_HIP(h, add(ablate ? (void*)&noop_kernel : pick_b_func(W.nch_ks, W.RB, half, qred), grid_b, 64 * NW_B, CellBParams(b).p));
-                }
-            }
-            if (K == 1) {
-                int* tp = tA;
-                void* kt[1] = {&tp};
-                DRNMF_HIP(h, add((void*)&advance_frame_kernel, dim3(1), 1, kt));
-            }
-        }
-        DRNMF_HIP(h, hipGraphInstantiate(&ge.exec, ge.graph, nullptr, nullptr, 0));
-        h->graphs.push_back(ge);
-        entry = &h->graphs.back();
-    }
-    entry->last_stream = stream;
-    entry->pin = h->call_seq;
-    *out = entry->exec;
-    return DRNMF_OK;
-    };
-    hipGraphExec_t exec_n = nullptr, exec_1 = nullptr;
-    int32_t grc = get_graph(fpg_max, &exec_n);
-    if (grc) return grc;
-    if (plan) {
-        plan->exec_n = exec_n;
+    if (plan && !tune_env("DRNMF_NO_GRAPH")) {
+        // (both executables stay pinned by this call until the caller has enqueued their launches)
+        rc = graph_cache_get(h, stream, GraphKind::Forward, key, fpg_max, frame, &plan->exec_n);
+        if (rc) return rc;
         plan->fpg = fpg_max;
         plan->n_full = d->T / fpg_max;
         plan->n_rem = d->T % fpg_max;
-        if (plan->n_rem) {
-            grc = get_graph(1, &exec_1);
-            if (grc) return grc;
-            plan->exec_1 = exec_1;
-        }
-        return DRNMF_OK;
+        return plan->n_rem ? graph_cache_get(h, stream, GraphKind::Forward, key, 1, frame, &plan->exec_1) : DRNMF_OK;
     }
-    int t = 0;
-    for (; t + fpg_max <= d->T; t += fpg_max) DRNMF_HIP(h, hipGraphLaunch(exec_n, stream));
-    if (t < d->T) {
-        grc = get_graph(1, &exec_1);     // (may evict; exec_n is not used again)
-        if (grc) return grc;
-        for (; t < d->T; ++t) DRNMF_HIP(h, hipGraphLaunch(exec_1, stream));
-    }
-    return store_final(W);
+    rc = replay_frames(h, stream, GraphKind::Forward, key, {fpg_max, 1}, 0, d->T, frame);
+    return rc ? rc : store_final(W);
 }
 
 extern "C" int32_t drnmf_cell_forward(drnmf_handle_t h, const drnmf_cell_desc_t* d, const float* x,
@@ -1627,6 +1513,7 @@ extern "C" int32_t drnmf_cell_forward_ista(drnmf_handle_t h, const drnmf_cell_de
                    workspace_bytes, W.total);
     if (((uintptr_t)workspace & 255) || ((uintptr_t)params & 255))
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "workspace/params must be 256-byte aligned");
+    ++h->call_seq;                   // (a top-level call: the graphs it takes are pinned until it returns)
     hipStream_t stream = (hipStream_t)stream_;
     const ParamsLayout L = params_layout(d);
     char* ws = (char*)workspace;
@@ -1723,11 +1610,11 @@ extern "C" int32_t drnmf_cell_forward_ista(drnmf_handle_t h, const drnmf_cell_de
     const int div = d->divergence;
     int F = d->F, Fp = W.Fp, Bp = W.Bp;
 
-    // one frame's launches, through `emit(func, grid, block, kernelParams)`
-    auto frame = [&](auto&& emit) -> int32_t {
+    // one frame = 3K launches
+    auto frame = [&](Launcher& chain, int) -> int32_t {
         for (int k = 0; k < K; ++k) {
             CellBArgs b = make_b(k);
-            DRNMF_HIP(h, emit(pick_b_func(W.nch_ks, W.RB, false), grid_b, 64 * NW_B, CellBParams(b).p));
+            DRNMF_HIP(h, chain.add(pick_b_func(W.nch_ks, W.RB, false), grid_b, 64 * NW_B, CellBParams(b).p));
             const float* xpp = xp;
             float* rp = rpart;
             const int* trd = (k == 0) ? tB : tA;
@@ -1737,83 +1624,27 @@ extern "C" int32_t drnmf_cell_forward_ista(drnmf_handle_t h, const drnmf_cell_de
             float* xsv = W.off_xhat ? (float*)(ws + W.off_xhat) + (size_t)k * Bp * Fp : nullptr;
             size_t xst = (size_t)K * Bp * Fp;
             void* kr[11] = {&xpp, &rp, &trd, &twr, &dv, &bt, &F, &Fp, &Bp, &xsv, &xst};
-            DRNMF_HIP(h, emit((void*)&resid_div_kernel, grid_r, 256, kr));
+            DRNMF_HIP(h, chain.add((void*)&resid_div_kernel, grid_r, 256, kr));
             CellAArgs a = make_a(k);
             CellAParams ka(a);
             // (never the IS_FIRST variant: layer 0 is a full ISTA step from the state)
-            DRNMF_HIP(h, emit(pick_a_func(nft, W.KS, W.RB, false, k == K - 1,
-                                          d->return_all_hidden != 0, false),
-                              grid_a, 64 * NW_A, ka.p));
+            DRNMF_HIP(h, chain.add(pick_a_func(nft, W.KS, W.RB, false, k == K - 1,
+                                               d->return_all_hidden != 0, false),
+                                   grid_a, 64 * NW_A, ka.p));
         }
         return DRNMF_OK;
     };
-
-    const bool use_graph = tune_env("DRNMF_NO_GRAPH") == nullptr;
-    if (!use_graph) {
-        for (int t = 0; t < d->T; ++t) {
-            rc = frame([&](void* f, dim3 g, unsigned blk, void** kp) {
-                return hipLaunchKernel(f, g, dim3(blk), kp, 0, stream);
-            });
-            if (rc) return rc;
-        }
-        DRNMF_HIP(h, hipGetLastError());
-    } else {
-        int fpg = 600 / (3 * K);
-        fpg = fpg < 1 ? 1 : (fpg > 64 ? 64 : fpg);
-        if (fpg > d->T) fpg = d->T;
-        uint32_t bbits;
-        memcpy(&bbits, &beta, 4);
-        auto get_graph = [&](int frames, hipGraphExec_t* out) -> int32_t {
-            std::vector<uint64_t> key = {
-                0x157AULL, (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->N,
-                (uint64_t)d->K, (uint64_t)d->n_D, (uint64_t)d->return_all_hidden,
-                (uint64_t)d->divergence, (uint64_t)bbits, (uint64_t)(uintptr_t)params,
-                (uint64_t)(uintptr_t)h_out, (uint64_t)(uintptr_t)workspace, (uint64_t)frames};
-            for (auto& g : h->graphs)
-                if (g.key == key) { *out = g.exec; return DRNMF_OK; }
-            if (h->graphs.size() >= 24) {
-                DRNMF_HIP(h, hipDeviceSynchronize());
-                (void)hipGraphExecDestroy(h->graphs.front().exec);
-                (void)hipGraphDestroy(h->graphs.front().graph);
-                h->graphs.erase(h->graphs.begin());
-            }
-            GraphEntry ge;
-            ge.key = key;
-            DRNMF_HIP(h, hipGraphCreate(&ge.graph, 0));
-            hipGraphNode_t last = nullptr;
-            auto add = [&](void* f, dim3 g, unsigned blk, void** kp) -> hipError_t {
-                hipKernelNodeParams p;
-                memset(&p, 0, sizeof(p));
-                p.func = f;
-                p.gridDim = g;
-                p.blockDim = dim3(blk);
-                p.kernelParams = kp;
-                hipGraphNode_t node;
-                hipError_t e = hipGraphAddKernelNode(&node, ge.graph, last ? &last : nullptr,
-                                                     last ? 1 : 0, &p);
-                last = node;
-                return e;
-            };
-            for (int rep = 0; rep < frames; ++rep) {
-                int32_t r2 = frame(add);
-                if (r2) return r2;
-            }
-            DRNMF_HIP(h, hipGraphInstantiate(&ge.exec, ge.graph, nullptr, nullptr, 0));
-            h->graphs.push_back(ge);
-            *out = ge.exec;
-            return DRNMF_OK;
-        };
-        hipGraphExec_t ex = nullptr;
-        rc = get_graph(fpg, &ex);
-        if (rc) return rc;
-        int t = 0;
-        for (; t + fpg <= d->T; t += fpg) DRNMF_HIP(h, hipGraphLaunch(ex, stream));
-        if (t < d->T) {
-            rc = get_graph(1, &ex);
-            if (rc) return rc;
-            for (; t < d->T; ++t) DRNMF_HIP(h, hipGraphLaunch(ex, stream));
-        }
-    }
+    int fpg = 600 / (3 * K);
+    fpg = fpg < 1 ? 1 : (fpg > 64 ? 64 : fpg);
+    if (fpg > d->T) fpg = d->T;
+    uint32_t bbits;
+    memcpy(&bbits, &beta, 4);
+    const std::vector<uint64_t> key = {
+        (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->N, (uint64_t)d->K, (uint64_t)d->n_D,
+        (uint64_t)d->return_all_hidden, (uint64_t)d->divergence, (uint64_t)bbits, (uint64_t)(uintptr_t)params,
+        (uint64_t)(uintptr_t)h_out, (uint64_t)(uintptr_t)workspace};
+    rc = replay_frames(h, stream, GraphKind::IstaForward, key, {fpg, 1}, 0, d->T, frame);
+    if (rc) return rc;
     if (final_state) {
         const size_t tot = (size_t)d->B * d->N;
         hipLaunchKernelGGL(store_state_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,

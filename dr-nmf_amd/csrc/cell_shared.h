@@ -316,7 +316,7 @@ cell_b_kernel(const void* Dn_next, const float* h_in, const float* xp, float* rp
     DRNMF_STAMP(0, 5);
 }
 
-// kernelParams array of cell_b_kernel for hipLaunchKernel / hipGraphAddKernelNode
+// kernelParams array of cell_b_kernel for Launcher::add (common.h) / hipLaunchKernel
 struct CellBParams {
     void* p[15];
     explicit CellBParams(CellBArgs& b)

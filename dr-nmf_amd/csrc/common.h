@@ -6,6 +6,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <vector>
 
@@ -135,8 +137,9 @@ static inline int pad_f(int F) { return round_up(F, 16); }
 static inline int pad_f_mode(int F, bool half) { return round_up(F, half ? 32 : 16); }
 static inline int pad_n(int N) { return round_up(N, 32); }
 
+// One entry of the frame-graph cache (graph_cache_get, params.hip).
 struct GraphEntry {
-    std::vector<uint64_t> key;
+    std::vector<uint64_t> key;           // GraphKind, the site's fields, frames per graph
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     hipStream_t last_stream = nullptr;   // stream of the most recent replay (eviction waits on it)
@@ -160,10 +163,12 @@ struct drnmf_handle_s {
     std::vector<X3Scratch> x3_scratch;
     std::vector<void*> x3_parked;
     char err[512] = {0};
-    std::vector<GraphEntry> graphs;      // least recently used first
-    uint64_t call_seq = 0;               // top-level forward calls so far (GraphEntry::pin)
+    // frame graphs of every recurrent cell, least recently used first; touched only by graph_cache_get,
+    // its eviction and drnmf_destroy
+    std::vector<GraphEntry> graphs;
+    uint64_t call_seq = 0;               // top-level cell calls so far (GraphEntry::pin)
     // graphs dropped from the bounded cache: destroyed once the work that was enqueued when they
-    // were retired has completed (graph_cache_insert, no device-wide synchronisation)
+    // were retired has completed (no device-wide synchronisation)
     struct Retired { GraphEntry g; hipEvent_t done; };
     std::vector<Retired> retired;
     // STFT window / twiddle tables (stft.hip): filled once per FFT size 2^6 .. 2^12
@@ -224,11 +229,49 @@ bool persist_admit(drnmf_handle_t h, hipStream_t stream); // false: another stre
 void persist_mark(drnmf_handle_t h, hipStream_t stream);  // after a call's persistent launches
 void persist_query_occupancy(int device, int* per_cu, int* n_cu);   // cell_forward.hip, at drnmf_create
 
-// Bounded graph cache shared by the forward / backward / dense cells.  Evicting an entry must not
-// synchronise the device (ABI contract: calls only enqueue): the evicted executable may still be
-// replaying on `stream`, so it is parked with an event recorded on that stream and destroyed by a
-// later call once the event has completed.
-int32_t graph_cache_make_room(drnmf_handle_t h, hipStream_t stream, size_t max_entries);
+// ---- frame graphs of the recurrent cells (params.hip) --------------------------------------------
+// One frame's kernels, described once per cell against this chain: `add` appends a kernel node that
+// depends on the previous one to `graph`, or -- no graph (DRNMF_NO_GRAPH, profile runs) -- launches the
+// kernel on `stream` at once.  Node and launch parameters are copied by the call.
+struct Launcher {
+    hipGraph_t graph = nullptr;
+    hipStream_t stream = nullptr;
+    hipGraphNode_t last = nullptr;
+    hipError_t add(const void* func, dim3 grid, dim3 block, void** kparams, size_t shmem = 0) {
+        if (!graph) return hipLaunchKernel(func, grid, block, kparams, shmem, stream);
+        hipKernelNodeParams p;
+        memset(&p, 0, sizeof(p));
+        p.func = const_cast<void*>(func);
+        p.gridDim = grid;
+        p.blockDim = block;
+        p.sharedMemBytes = (unsigned)shmem;
+        p.kernelParams = kparams;
+        hipGraphNode_t node;
+        const hipError_t e = hipGraphAddKernelNode(&node, graph, last ? &last : nullptr, last ? 1 : 0, &p);
+        last = node;
+        return e;
+    }
+};
+// frame(chain, i): enqueue the kernels of the i-th frame of a block (i counts from the block's first frame)
+using FrameFn = std::function<int32_t(Launcher&, int)>;
+enum class GraphKind : uint64_t { GramForward = 1, Forward, IstaForward, Backward, Dense };
+
+// The executable of `frames` consecutive frames of one cell call, from the handle's bounded cache
+// (GRAPH_CACHE_ENTRIES).  The key is `kind`, the site's `fields` (every shape, pointer, scalar and layout
+// choice its nodes bake in) and `frames`; `frame` runs only on a miss.  One policy for every cell:
+//  - least recently used eviction: a hit moves to the back;
+//  - the entries the current call took (GraphEntry::pin == call_seq; every top-level entry point advances
+//    call_seq once, the sub-batches of a split call do not) are never evicted by it;
+//  - no device synchronisation (ABI contract: calls only enqueue): an evicted executable may still be
+//    replaying on its last_stream, so it is parked behind an event recorded there and destroyed by a
+//    later call once that event has completed.
+constexpr size_t GRAPH_CACHE_ENTRIES = 24;
+int32_t graph_cache_get(drnmf_handle_t h, hipStream_t stream, GraphKind kind, const std::vector<uint64_t>& fields,
+                        int frames, const FrameFn& frame, hipGraphExec_t* exec);
+// Frames [t0, t1): as many graphs of fpg[0] frames as fit, then of fpg[1], ... (descending, the last 1);
+// DRNMF_NO_GRAPH: every frame launched directly (frame(chain, t - t0)).
+int32_t replay_frames(drnmf_handle_t h, hipStream_t stream, GraphKind kind, const std::vector<uint64_t>& fields,
+                      std::initializer_list<int> fpg, int t0, int t1, const FrameFn& frame);
 
 extern char g_create_err[512];
 

@@ -10,6 +10,7 @@
 #include <sys/file.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <string>
@@ -305,7 +306,7 @@ extern "C" int32_t drnmf_destroy(drnmf_handle_t h) {
     return DRNMF_OK;
 }
 
-int32_t graph_cache_make_room(drnmf_handle_t h, hipStream_t stream, size_t max_entries) {
+static int32_t graph_cache_make_room(drnmf_handle_t h, hipStream_t stream, size_t max_entries) {
     // reap retired graphs whose last replay has completed (a query, never a wait)
     for (size_t i = 0; i < h->retired.size();) {
         if (hipEventQuery(h->retired[i].done) == hipSuccess) {
@@ -332,6 +333,66 @@ int32_t graph_cache_make_room(drnmf_handle_t h, hipStream_t stream, size_t max_e
         // never ran): everything enqueued there so far precedes the event
         DRNMF_HIP(h, hipEventRecord(r.done, r.g.last_stream ? r.g.last_stream : stream));
         h->retired.push_back(r);
+    }
+    return DRNMF_OK;
+}
+
+int32_t graph_cache_get(drnmf_handle_t h, hipStream_t stream, GraphKind kind, const std::vector<uint64_t>& fields,
+                        int frames, const FrameFn& frame, hipGraphExec_t* exec) {
+    std::vector<uint64_t> key;
+    key.reserve(fields.size() + 2);
+    key.push_back((uint64_t)kind);
+    key.insert(key.end(), fields.begin(), fields.end());
+    key.push_back((uint64_t)frames);
+    auto& gs = h->graphs;
+    const auto hit = std::find_if(gs.begin(), gs.end(), [&](const GraphEntry& g) { return g.key == key; });
+    if (hit != gs.end()) {
+        std::rotate(hit, hit + 1, gs.end());          // most recently used: the back
+    } else {
+        int32_t rc = graph_cache_make_room(h, stream, GRAPH_CACHE_ENTRIES);
+        if (rc) return rc;
+        GraphEntry ge;
+        ge.key = std::move(key);
+        DRNMF_HIP(h, hipGraphCreate(&ge.graph, 0));
+        Launcher chain{ge.graph, stream};
+        for (int i = 0; i < frames && !rc; ++i) rc = frame(chain, i);
+        if (!rc) {
+            const hipError_t e = hipGraphInstantiate(&ge.exec, ge.graph, nullptr, nullptr, 0);
+            if (e != hipSuccess) {
+                snprintf(h->err, sizeof(h->err), "hipGraphInstantiate failed: %s", hipGetErrorString(e));
+                rc = DRNMF_ERR_HIP;
+            }
+        }
+        if (rc) {
+            (void)hipGraphDestroy(ge.graph);
+            return rc;
+        }
+        gs.push_back(std::move(ge));
+    }
+    gs.back().last_stream = stream;
+    gs.back().pin = h->call_seq;
+    *exec = gs.back().exec;
+    return DRNMF_OK;
+}
+
+int32_t replay_frames(drnmf_handle_t h, hipStream_t stream, GraphKind kind, const std::vector<uint64_t>& fields,
+                      std::initializer_list<int> fpg, int t0, int t1, const FrameFn& frame) {
+    if (tune_env("DRNMF_NO_GRAPH")) {
+        Launcher direct{nullptr, stream};
+        for (int t = t0; t < t1; ++t) {
+            const int32_t rc = frame(direct, t - t0);
+            if (rc) return rc;
+        }
+        DRNMF_HIP(h, hipGetLastError());
+        return DRNMF_OK;
+    }
+    int t = t0;
+    for (const int n : fpg) {
+        if (t1 - t < n) continue;
+        hipGraphExec_t exec = nullptr;
+        const int32_t rc = graph_cache_get(h, stream, kind, fields, n, frame, &exec);
+        if (rc) return rc;
+        for (; t + n <= t1; t += n) DRNMF_HIP(h, hipGraphLaunch(exec, stream));
     }
     return DRNMF_OK;
 }

@@ -159,15 +159,72 @@ def test_cell_forward_return_all_hidden(dev):
     _check_h(h, ref)
 
 
+def _bptt(dev, P, alt, labels, N, K, divergence="ed"):
+    """Training forward (all K hiddens) and BPTT of one problem through the C ABI: [h, every gradient]."""
+    from drnmf_amd import ops
+    X = P["X"]
+    B, T, F = X.shape
+    stack = lambda name: np.stack([alt[k] for k in dict.fromkeys(labels[name])], 0)
+    logD, logA, logL = stack("log_D"), stack("log_alph"), stack("log_lam1")
+    desc = ops.make_desc(B, T, F, N, K, n_D=logD.shape[0], n_alph=logA.shape[0],
+                         alph_len=int(np.asarray(logA[0]).size), n_lam=logL.shape[0],
+                         return_all_hidden=True, divergence=divergence)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+    params = ops.prepare_params(desc, t(logD), t(logA.reshape(logA.shape[0], -1)), t(logL.reshape(-1)))
+    ws = ops.cell_workspace(desc, dev)
+    if divergence == "ed":
+        u = O.u_scalars(alt, np.float32)
+        h = ops.cell_forward(t(X), -1.0, params, desc, t(P["log_h0"]), u, workspace=ws)
+    else:
+        u = (1.0, 0.0, 0.0)
+        h = ops.cell_forward_ista(t(X), -1.0, params, desc, t(P["log_h0"]), beta=1.5, workspace=ws)
+    d_out = t(np.random.default_rng(7).standard_normal((B, T, N)))
+    g = ops.cell_backward(t(X), params, desc, t(P["log_h0"]), u, h, d_out, ws,
+                          beta=None if divergence == "ed" else 1.5)
+    torch.cuda.synchronize()
+    return [h.cpu().numpy()] + [g[k].cpu().numpy() for k in sorted(g)]
+
+
 def test_cell_forward_is_deterministic_and_graph_equals_plain_launches(dev, monkeypatch):
     K = 4
     P, alt, labels, N = _problem(5, 7, 65, 20, K)
     h1, _, _ = _run_cell(dev, P, alt, labels, N, K)
     h2, _, _ = _run_cell(dev, P, alt, labels, N, K)
     np.testing.assert_array_equal(h1, h2)
+    # ... and the KL / beta cell, and the BPTT of the reference cell (factored or Gram form, by cell_form; the
+    # Gram chains as frame graphs, not as the persistent kernels) and of the KL / beta cell: every gradient
+    Pk = dict(P, X=np.where(P["X"] == -1.0, -1.0, P["X"] + 0.05).astype(np.float32))
+    monkeypatch.setenv("DRNMF_PERSIST", "0")
+    runs = lambda: [_bptt(dev, P, alt, labels, N, K)] + [_bptt(dev, Pk, alt, labels, N, K, dv)
+                                                         for dv in ("kl", "beta")]
+    graphs = runs()
     monkeypatch.setenv("DRNMF_NO_GRAPH", "1")
+    for a, b in zip(graphs, runs()):
+        for u, v in zip(a, b):
+            np.testing.assert_array_equal(u, v)
+    monkeypatch.delenv("DRNMF_PERSIST")
     h3, _, _ = _run_cell(dev, P, alt, labels, N, K)
     np.testing.assert_array_equal(h1, h3)
+
+
+def test_kl_forward_evicts_through_the_shared_graph_cache(dev, monkeypatch):
+    """More distinct KL / beta frame graphs than a handle caches (24), interleaved with a factored forward on the
+    same handle: entries are evicted least recently used first, without a device synchronisation, and a call
+    whose graphs were evicted (or kept) computes the same bits again."""
+    monkeypatch.setenv("DRNMF_GRAM", "0")
+    K = 2
+    P, alt, labels, N = _problem(3, 30, 21, 6, K, density=0.3)
+    P["X"] = np.where(P["X"] == -1.0, -1.0, P["X"] + 0.05).astype(np.float32)
+    Pf, altf, labelsf, Nf = _problem(4, 9, 33, 8, 3)
+    kl = lambda T: _run_ista_cell(dev, dict(P, X=P["X"][:, :T]), alt, labels, N, K, "kl")
+    fac = lambda: _run_cell(dev, Pf, altf, labelsf, Nf, 3)[0]
+    kl0, fac0 = kl(1), fac()
+    for T in range(2, 31):
+        kl(T)
+        if T % 4 == 0:
+            fac()
+    np.testing.assert_array_equal(kl(1), kl0)
+    np.testing.assert_array_equal(fac(), fac0)
 
 
 def test_cell_reference_dense_form_agrees(dev):
