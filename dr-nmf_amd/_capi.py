@@ -1,4 +1,4 @@
-"""ctypes binding of libdrnmf.so (C ABI in include/drnmf.h).
+"""ctypes binding of libdrnmf.so (C ABI in include/drnmf.h; the LSTM baseline's in include/drnmf_lstm.h).
 
 The library is the product path: there is NO fallback.  If the shared object is missing or a
 call fails, an exception is raised.
@@ -135,6 +135,23 @@ SIGNATURES = {
     "drnmf_sdr_project": (_i32, [_vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+
+class LstmDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "T", "F", "H", "K", "recurrent_activation")]
+
+
+_LDP = C.POINTER(LstmDesc)
+
+# name -> (restype, argtypes); mirrors include/drnmf_lstm.h one to one (a table of its own: SIGNATURES is
+# drnmf.h's)
+LSTM_SIGNATURES = {
+    "drnmf_lstm_params_bytes": (_sz, [_LDP]),
+    "drnmf_lstm_prepare_params": (_i32, [_vp, _LDP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "drnmf_lstm_workspace_bytes": (_sz, [_LDP]),
+    "drnmf_lstm_forward": (_i32, [_vp, _LDP, _vp, _f32, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "drnmf_lstm_head_forward": (_i32, [_vp, _LDP, _vp, _i32, _vp, _vp, _vp]),
+}
+
 _lib = None
 _handles = {}
 
@@ -156,7 +173,7 @@ def lib():
         # to initialise reports "no ROCm-capable device".
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(LSTM_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

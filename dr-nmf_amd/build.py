@@ -39,7 +39,8 @@ def _sources():
 
 def _deps():
     return _sources() + glob.glob(os.path.join(CSRC, "*.h")) + \
-        [os.path.join(os.path.dirname(HERE), "include", "drnmf.h"), os.path.abspath(__file__)]
+        [os.path.join(os.path.dirname(HERE), "include", n) for n in ("drnmf.h", "drnmf_lstm.h")] + \
+        [os.path.abspath(__file__)]
 
 
 STAMP = LIB + ".srchash"

@@ -326,6 +326,12 @@ class Group(object):
                           "H5Gcreate2(%s)" % name), file=self._file)
 
     def create_dataset(self, name, data):
+        parent, _, leaf = name.rpartition("/")
+        if parent:      # intermediate groups are created, as h5py does (Keras names weights '<layer>/kernel:0')
+            g = self
+            for part in parent.split("/"):
+                g = g[part] if part in g else g.create_group(part)
+            return g.create_dataset(leaf, data)
         L = lib()
         arr = np.asarray(data)
         # (0-d arrays -- Keras' scalar weights, build_alt's log_alph / log_lam1 -- keep a scalar dataspace as

@@ -6,6 +6,8 @@ Same names, constructor arguments and protocol as the reference (custom_layers.p
     from drnmf_amd.layers import (SimpleDeepRNN, DenseNonNegW, DivideAbyAplusB,
                                   divide_A_by_AplusB, build_alt, build_unfolded_snmf)
 
+and, for the comparison model (enhance.py:321-345), `from drnmf_amd.layers import build_lstm`.
+
 Weights live in torch tensors on the GPU (containers only); every forward goes through the
 hand-written HIP kernels in libdrnmf.so: the fused factored kernels for the configuration
 build_unfolded_snmf constructs, the general dense-matrix kernel (SimpleDeepRNN.step as written) for
@@ -17,6 +19,7 @@ is no CPU/oracle fallback: what the kernels do not cover raises NotImplementedEr
 trains on the dense-matrix path).  The KL / beta extension of the cell trains through its own BPTT
 (drnmf_cell_backward_ista).
 """
+import ctypes
 from collections import OrderedDict
 
 import re
@@ -234,6 +237,14 @@ class TimeDistributed(_Layer):
 
     def _weights_changed(self):
         self.layer._weights_changed()
+
+    @property
+    def weight_names(self):
+        return self.layer.weight_names     # (AttributeError -- hasattr False -- for layers without names)
+
+    @property
+    def ordered_weights(self):
+        return getattr(self.layer, 'ordered_weights', False)
 
     def __call__(self, inputs):
         return self.layer(inputs)
@@ -932,28 +943,20 @@ class DeviceLoss(object):
         return np.asarray(self._get(), dtype=dtype or np.float64)
 
 
-class UnfoldedSNMFModel(object):
-    """Masking -> SimpleDeepRNN -> [:r]/[r:] -> DenseNonNegW x2 -> (square) -> A/(A+B).
-    Exposes the slice of keras.Model that enhance.py uses: layers, get/set_weights,
-    predict_on_batch; `forward` keeps everything on the device."""
+class _SequenceModel(object):
+    """What the Keras models of this module share, independent of the layers inside: the weight files
+    (Keras' save_weights layout, .npz or HDF5) and the slab loop of predict / predict_on_batch.  A subclass
+    supplies `layers`, `mask_value`, `forward(x)` (device [b,T,F] -> device [b,T,Fo]) and the three hooks
+    below."""
 
-    def __init__(self, layers, cell, clean, noise, mask_value, square):
-        self.layers = layers
-        self.cell, self.clean, self.noise = cell, clean, noise
-        self.mask_value, self.square = mask_value, square
+    def _device(self):
+        raise NotImplementedError
 
-    @property
-    def weights(self):
-        return self.cell.weights + self.clean.weights + self.noise.weights
+    def _output_width(self):
+        raise NotImplementedError
 
-    def get_weights(self):
-        return [np.array(w.detach().cpu().numpy(), copy=True) for w in self.weights]
-
-    def set_weights(self, weights):
-        n = len(self.cell.weights)
-        self.cell.set_weights(weights[:n])
-        self.clean.set_weights(weights[n:n + 1])
-        self.noise.set_weights(weights[n + 1:n + 2])
+    def _stateful(self):
+        return False
 
     # -- weight files (enhance.py:1096, 1119-1129, 1135, 1160-1166: ModelCheckpoint(
     #    save_weights_only=True) / save_weights / load_weights on Keras HDF5 files) ------------
@@ -983,7 +986,8 @@ class UnfoldedSNMFModel(object):
     def load_weights_tree(self, tree):
         """Inverse of weights_tree, with Keras' topological matching (layers that own weights, in
         order); inside the recurrent cell weights are matched BY NAME, because the reference's
-        order there is Python-2 dict order (custom_layers.py:216-228)."""
+        order there is Python-2 dict order (custom_layers.py:216-228).  Standard Keras layers
+        (`ordered_weights`: LSTM, Dense) are matched in order, as Keras does."""
         file_layers = [str(n) for n in tree['layer_names']
                        if len(tree[str(n) + '/weight_names']) > 0]
         mine = self._weighted_layers()
@@ -993,7 +997,7 @@ class UnfoldedSNMFModel(object):
         for fname, layer in zip(file_layers, mine):
             wn = [str(n) for n in tree[fname + '/weight_names']]
             vals = [np.asarray(tree[fname + '/' + n]) for n in wn]
-            if hasattr(layer, 'weight_names'):
+            if hasattr(layer, 'weight_names') and not getattr(layer, 'ordered_weights', False):
                 strip = lambda n, pre: n[len(pre) + 1:] if n.startswith(pre + '_') else n
                 by_key = {strip(n.split(':')[0], fname): v for n, v in zip(wn, vals)}
                 want = [strip(n, layer.name) for n in layer.weight_names]
@@ -1041,16 +1045,6 @@ class UnfoldedSNMFModel(object):
                 for n in wn:
                     tree[ln + '/' + n] = np.asarray(g0[ln][n])
         return self.load_weights_tree(tree)
-
-    def forward(self, x, want_hidden=False):
-        """Device tensors in, device tensors out, nothing waited for: a fault on the device (a persistent
-        small-shape chain that timed out) is NOT raised here -- call ops.check_status(device) once you have
-        synchronised, as predict_on_batch does after its copy; a later training / test step drops such a stale
-        word instead of charging it to itself (_drop_stale_fault)."""
-        h = self.cell.call(x, mask_value=self.mask_value)
-        mask = ops.head_forward(h, self.clean.kernel, self.noise.kernel, square=self.square,
-                                h_off=h.shape[-1] - self.cell.output_dim)
-        return (mask, h) if want_hidden else mask
 
     def predict_on_batch(self, x, lengths=None):
         # (one slab of `predict`: pinned staging both ways -- a pageable device-to-host copy runs at a sixth
@@ -1117,13 +1111,13 @@ class UnfoldedSNMFModel(object):
         bs = int(batch_size)
         if bs <= 0:
             raise ValueError('predict: batch_size must be positive')
-        dev = self.cell.device
-        Fo = int(self.clean.kernel.shape[1])
+        dev = self._device()
+        Fo = self._output_width()
         out = np.empty((n, T, Fo), dtype=np.float32)
         if n == 0 or T == 0:
             return out
         bs = min(bs, n)
-        stateful = bool(getattr(self.cell, 'stateful', False))
+        stateful = self._stateful()
         if length_aware and not stateful:
             if lengths is None:
                 lens = self.valid_lengths(x, self.mask_value)
@@ -1239,6 +1233,49 @@ class UnfoldedSNMFModel(object):
         if pool is not None:
             pool.shutdown(wait=True)
             self._host_pool_obj = None
+
+
+class UnfoldedSNMFModel(_SequenceModel):
+    """Masking -> SimpleDeepRNN -> [:r]/[r:] -> DenseNonNegW x2 -> (square) -> A/(A+B).
+    Exposes the slice of keras.Model that enhance.py uses: layers, get/set_weights,
+    predict_on_batch; `forward` keeps everything on the device."""
+
+    def __init__(self, layers, cell, clean, noise, mask_value, square):
+        self.layers = layers
+        self.cell, self.clean, self.noise = cell, clean, noise
+        self.mask_value, self.square = mask_value, square
+
+    @property
+    def weights(self):
+        return self.cell.weights + self.clean.weights + self.noise.weights
+
+    def get_weights(self):
+        return [np.array(w.detach().cpu().numpy(), copy=True) for w in self.weights]
+
+    def set_weights(self, weights):
+        n = len(self.cell.weights)
+        self.cell.set_weights(weights[:n])
+        self.clean.set_weights(weights[n:n + 1])
+        self.noise.set_weights(weights[n + 1:n + 2])
+
+    def _device(self):
+        return self.cell.device
+
+    def _output_width(self):
+        return int(self.clean.kernel.shape[1])
+
+    def _stateful(self):
+        return bool(getattr(self.cell, 'stateful', False))
+
+    def forward(self, x, want_hidden=False):
+        """Device tensors in, device tensors out, nothing waited for: a fault on the device (a persistent
+        small-shape chain that timed out) is NOT raised here -- call ops.check_status(device) once you have
+        synchronised, as predict_on_batch does after its copy; a later training / test step drops such a stale
+        word instead of charging it to itself (_drop_stale_fault)."""
+        h = self.cell.call(x, mask_value=self.mask_value)
+        mask = ops.head_forward(h, self.clean.kernel, self.noise.kernel, square=self.square,
+                                h_off=h.shape[-1] - self.cell.output_dim)
+        return (mask, h) if want_hidden else mask
 
     __call__ = forward
 
@@ -1955,3 +1992,209 @@ def build_unfolded_snmf(params_unfolded_snmf, device=None):
                    Lambda('square', name='noise_est_xformed')]
     layers.append(DivideAbyAplusB())
     return UnfoldedSNMFModel(layers, cell, clean, noise, mask_value, transform == 'square')
+
+
+# ------------------------------------------------------------------------------------------
+# LSTM baseline: build_lstm  (enhance.py:321-345), inference
+# ------------------------------------------------------------------------------------------
+def _orthogonal(shape):
+    """keras.initializers.Orthogonal(gain=1) [K2.0.4-memory]: the SVD factor of a Gaussian matrix whose shape
+    is `shape` -- orthonormal rows for a wide matrix (recurrent_kernel [H, 4H]: q q^T = I)."""
+    a = np.random.normal(0.0, 1.0, shape)
+    u, _, v = np.linalg.svd(a, full_matrices=False)
+    q = u if u.shape == tuple(shape) else v
+    return np.ascontiguousarray(q.reshape(shape), dtype=np.float32)
+
+
+def _glorot_uniform(shape):
+    lim = np.sqrt(6.0 / (shape[0] + shape[-1]))
+    return np.random.uniform(-lim, lim, shape).astype(np.float32)
+
+
+class LSTM(_Layer):
+    """keras.layers.LSTM as build_lstm uses it (enhance.py:333-335) [K2.0.4-memory]: weights kernel [in, 4H]
+    (glorot_uniform), recurrent_kernel [H, 4H] (orthogonal), bias [4H] (zeros, unit_forget_bias=True: the f
+    block bias[H:2H] = 1); gate columns i, f, c, o; activation tanh, recurrent_activation hard_sigmoid by
+    default (sigmoid selectable); zero initial states.  The forward runs as part of LSTMModel (csrc/lstm.hip)."""
+    ordered_weights = True
+
+    def __init__(self, units, return_sequences=False, input_shape=None, activation='tanh',
+                 recurrent_activation='hard_sigmoid', kernel_initializer='glorot_uniform',
+                 recurrent_initializer='orthogonal', bias_initializer='zeros', unit_forget_bias=True,
+                 device=None, **kw):
+        super(LSTM, self).__init__(**kw)
+        if not return_sequences:
+            raise NotImplementedError('LSTM: only return_sequences=True (build_lstm, enhance.py:334)')
+        if activation != 'tanh':
+            raise NotImplementedError('LSTM: only activation=tanh (the Keras default build_lstm uses)')
+        if recurrent_activation not in ops.LSTM_ACTIVATIONS:
+            raise ValueError('LSTM: recurrent_activation must be one of %s' % sorted(ops.LSTM_ACTIVATIONS))
+        if (kernel_initializer, recurrent_initializer, bias_initializer) != ('glorot_uniform', 'orthogonal',
+                                                                            'zeros'):
+            raise NotImplementedError('LSTM: only the Keras default initializers')
+        self.units = int(units)
+        self.return_sequences = True
+        self.input_shape = input_shape
+        self.activation, self.recurrent_activation = activation, recurrent_activation
+        self.unit_forget_bias = bool(unit_forget_bias)
+        self.device = torch.device(device if device is not None else 'cuda')
+        self.kernel = self.recurrent_kernel = self.bias = None
+
+    def build(self, input_shape):
+        H = self.units
+        bias = np.zeros((4 * H,), np.float32)
+        if self.unit_forget_bias:
+            bias[H:2 * H] = 1.0
+        to = lambda a: torch.from_numpy(a).to(self.device)
+        self.kernel = to(_glorot_uniform((int(input_shape[-1]), 4 * H)))
+        self.recurrent_kernel = to(_orthogonal((H, 4 * H)))
+        self.bias = to(bias)
+        self.built = True
+
+    @property
+    def weights(self):
+        return [] if self.kernel is None else [self.kernel, self.recurrent_kernel, self.bias]
+
+    @property
+    def weight_names(self):
+        return [self.name + '/kernel:0', self.name + '/recurrent_kernel:0', self.name + '/bias:0']
+
+
+class Dense(_Layer):
+    """keras.layers.Dense(units) [K2.0.4-memory]: kernel [in, units] glorot_uniform, bias [units] zeros,
+    linear.  Inside LSTMModel its product runs in the head kernel (csrc/lstm.hip)."""
+    ordered_weights = True
+
+    def __init__(self, units, activation=None, use_bias=True, device=None, **kw):
+        super(Dense, self).__init__(**kw)
+        if activation not in (None, 'linear') or not use_bias:
+            raise NotImplementedError('Dense: only the linear layer with bias (enhance.py:341)')
+        self.units = int(units)
+        self.device = torch.device(device if device is not None else 'cuda')
+        self.kernel = self.bias = None
+
+    def build(self, input_shape):
+        self.kernel = torch.from_numpy(_glorot_uniform((int(input_shape[-1]), self.units))).to(self.device)
+        self.bias = torch.zeros((self.units,), dtype=torch.float32, device=self.device)
+        self.built = True
+
+    @property
+    def weights(self):
+        return [] if self.kernel is None else [self.kernel, self.bias]
+
+    @property
+    def weight_names(self):
+        return [self.name + '/kernel:0', self.name + '/bias:0']
+
+
+class Activation(_Layer):
+    """keras.layers.Activation; build_lstm's 'sigmoid' (enhance.py:344) is fused into the head kernel."""
+
+    def __init__(self, activation, **kw):
+        super(Activation, self).__init__(**kw)
+        if activation != 'sigmoid':
+            raise NotImplementedError("Activation: only 'sigmoid' (enhance.py:344)")
+        self.activation = activation
+
+
+class LSTMModel(_SequenceModel):
+    """Masking -> LSTM(H, return_sequences=True) x K -> TimeDistributed(Dense(F)) -> sigmoid, the slice of
+    keras.Model enhance.py's LSTM branch uses for inference: layers, get/set_weights, save/load_weights,
+    predict / predict_on_batch (the shared slab loop, length-aware).  `forward` keeps everything on the device:
+    one drnmf_lstm_forward (input projection + T + K - 1 wavefront launches) and one head launch."""
+
+    def __init__(self, layers, lstms, dense, mask_value, device):
+        self.layers = layers
+        self.lstms, self.dense = lstms, dense
+        self.mask_value = mask_value
+        self.device = device
+        self._prepared = None        # (weight versions, desc key, params block)
+        self._ws = None
+
+    @property
+    def weights(self):
+        return [w for l in self.lstms for w in l.weights] + self.dense.weights
+
+    def get_weights(self):
+        return [np.array(w.detach().cpu().numpy(), copy=True) for w in self.weights]
+
+    def set_weights(self, weights):
+        """Keras order: per LSTM [kernel, recurrent_kernel, bias], then the Dense [kernel, bias]."""
+        if len(weights) != 3 * len(self.lstms) + 2:
+            raise ValueError('expected %d weight arrays, got %d' % (3 * len(self.lstms) + 2, len(weights)))
+        for k, l in enumerate(self.lstms):
+            l.set_weights(weights[3 * k:3 * k + 3])
+        self.dense.set_weights(weights[-2:])
+
+    def _device(self):
+        return self.device
+
+    def _output_width(self):
+        return self.dense.units
+
+    def compile(self, *args, **kwargs):
+        raise NotImplementedError('LSTMModel: training (compile / fit / train_on_batch) is not implemented; '
+                                  'the LSTM baseline runs inference only')
+
+    def _desc(self, B, T):
+        l0 = self.lstms[0]
+        return ops.make_lstm_desc(B, T, self.dense.units, l0.units, len(self.lstms), l0.recurrent_activation)
+
+    def _params(self, desc):
+        """The prepared block, rebuilt only when a weight tensor changed (torch's in-place version counter)."""
+        vers = tuple((w.data_ptr(), w._version) for w in self.weights)
+        key = (desc.F, desc.H, desc.K, desc.recurrent_activation)
+        if self._prepared is None or self._prepared[0] != vers or self._prepared[1] != key:
+            out = self._prepared[2] if self._prepared is not None and self._prepared[1] == key else None
+            p = ops.lstm_prepare_params(desc, [l.kernel for l in self.lstms],
+                                        [l.recurrent_kernel for l in self.lstms], [l.bias for l in self.lstms],
+                                        self.dense.kernel, self.dense.bias, out=out)
+            self._prepared = (vers, key, p)
+        return self._prepared[2]
+
+    def forward(self, x, want_hidden=False):
+        """x [B,T,F] device float32 -> sigmoid output [B,T,F] (and the last LSTM layer's [B,T,H])."""
+        if x.dim() != 3 or x.shape[-1] != self.dense.units:
+            raise ValueError('forward: x must be (B, T, %d), got %s' % (self.dense.units, tuple(x.shape)))
+        desc = self._desc(x.shape[0], x.shape[1])
+        params = self._params(desc)
+        need = _capi.lib().drnmf_lstm_workspace_bytes(ctypes.byref(desc))
+        if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        h = ops.lstm_forward(x, self.mask_value, params, desc, workspace=self._ws)
+        y = ops.lstm_head_forward(h, params, desc)
+        return (y, h) if want_hidden else y
+
+    __call__ = forward
+
+    def free_predict_buffers(self):
+        super(LSTMModel, self).free_predict_buffers()
+        self._ws = None
+
+
+def build_lstm(params_lstm, device=None):
+    """enhance.py:321-345 with the same parameter dictionary keys (mask_value, maxseq, input_dim, output_dim,
+    K_layers, hidden_dim); 'recurrent_activation' (optional, a Keras LSTM argument) selects 'sigmoid' instead
+    of the default 'hard_sigmoid'."""
+    p = params_lstm
+    mask_value, maxseq = p['mask_value'], p['maxseq']
+    input_dim, output_dim = int(p['input_dim']), int(p['output_dim'])
+    K, H = int(p['K_layers']), int(p['hidden_dim'])
+    if output_dim != input_dim:
+        raise ValueError('output_dim must equal input_dim (enhance.py:548-549; the kernels share one F)')
+    if K < 1 or H < 1:
+        raise ValueError('K_layers and hidden_dim must be positive')
+    dev = torch.device(device if device is not None else 'cuda')
+    inp = InputLayer((maxseq, input_dim), name='masking_1_input')
+    masking = Masking(mask_value=mask_value, input_shape=(maxseq, input_dim))
+    lstms = []
+    for k in range(K):
+        l = LSTM(H, return_sequences=True, input_shape=(maxseq, input_dim),
+                 recurrent_activation=p.get('recurrent_activation', 'hard_sigmoid'), device=dev)
+        l.build((None, maxseq, input_dim if k == 0 else H))
+        lstms.append(l)
+    dense = Dense(output_dim, device=dev)
+    dense.build((None, maxseq, H))
+    layers = [inp, masking] + lstms + [TimeDistributed(dense), TimeDistributed(Activation('sigmoid'))]
+    return LSTMModel(layers, lstms, dense, mask_value, dev)

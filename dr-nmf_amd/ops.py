@@ -982,3 +982,105 @@ def to_int16_wav(x):
                            _stream())
     _capi.check(rc, h, "drnmf_wav_int16")
     return out
+
+
+# ---- LSTM baseline (build_lstm, enhance.py:321-345; C ABI in include/drnmf_lstm.h) -----------------------
+LSTM_ACTIVATIONS = {"hard_sigmoid": _capi.ACTIVATIONS["hard_sigmoid"], "sigmoid": _capi.ACTIVATIONS["sigmoid"]}
+
+
+def make_lstm_desc(B, T, F, H, K, recurrent_activation="hard_sigmoid"):
+    if recurrent_activation not in LSTM_ACTIVATIONS:
+        raise ValueError("recurrent_activation must be one of %s" % sorted(LSTM_ACTIVATIONS))
+    return _capi.LstmDesc(int(B), int(T), int(F), int(H), int(K), LSTM_ACTIVATIONS[recurrent_activation])
+
+
+def lstm_prepare_params(desc, kernels, recurrents, biases, w_out, b_out, out=None):
+    """Keras layouts: kernels = [kernel_0 [F,4H], kernel_1..K-1 [H,4H]], recurrents [K] x [H,4H], biases [K] x [4H],
+    w_out [H,F], b_out [F] (device tensors) -> prepared block (uint8)."""
+    L = _capi.lib()
+    K, H, F = desc.K, desc.H, desc.F
+    if len(kernels) != K or len(recurrents) != K or len(biases) != K:
+        raise ValueError("lstm_prepare_params: K = %d kernels / recurrent kernels / biases expected" % K)
+    k0 = _f32c(kernels[0], "kernel_0")
+    h = _capi.handle(_dev_index(k0))
+    if tuple(k0.shape) != (F, 4 * H):
+        raise ValueError("kernel_0 must have shape (F,4H) = (%d,%d)" % (F, 4 * H))
+    for k in range(1, K):
+        if tuple(kernels[k].shape) != (H, 4 * H):
+            raise ValueError("kernel_%d must have shape (H,4H) = (%d,%d)" % (k, H, 4 * H))
+    for k in range(K):
+        if tuple(recurrents[k].shape) != (H, 4 * H) or tuple(biases[k].shape) != (4 * H,):
+            raise ValueError("recurrent_kernel / bias of layer %d must have shapes (H,4H) / (4H,)" % k)
+    rest = _f32c(torch.stack([t.float() for t in kernels[1:]]), "kernel_rest") if K > 1 else None
+    rec = _f32c(torch.stack([t.float() for t in recurrents]), "recurrent_kernel")
+    bias = _f32c(torch.stack([t.float() for t in biases]), "bias")
+    w_out, b_out = _f32c(w_out, "w_out"), _f32c(b_out, "b_out")
+    if tuple(w_out.shape) != (H, F) or tuple(b_out.shape) != (F,):
+        raise ValueError("w_out / b_out must have shapes (H,F) / (F,) = (%d,%d) / (%d,)" % (H, F, F))
+    nbytes = L.drnmf_lstm_params_bytes(C.byref(desc))
+    if out is None or out.numel() < nbytes:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=k0.device)
+    rc = L.drnmf_lstm_prepare_params(h, C.byref(desc), _capi.ptr(k0), _capi.ptr(rest), _capi.ptr(rec),
+                                     _capi.ptr(bias), _capi.ptr(w_out), _capi.ptr(b_out), _capi.ptr(out),
+                                     out.numel(), _stream())
+    _capi.check(rc, h, "drnmf_lstm_prepare_params")
+    return out
+
+
+def lstm_workspace(desc, device):
+    nbytes = _capi.lib().drnmf_lstm_workspace_bytes(C.byref(desc))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def lstm_hidden_ld(H):
+    """Row stride of the hidden buffers lstm_forward allocates: round_up(H, 4) (the head's vectorised path)."""
+    return (int(H) + 3) // 4 * 4
+
+
+def _hidden_ld(t, desc, what):
+    """Row stride of a (B,T,H) float32 tensor whose rows may be padded: t.stride() == (T*ld, ld, 1), ld >= H."""
+    if t.dtype != torch.float32 or tuple(t.shape) != (desc.B, desc.T, desc.H):
+        raise ValueError("%s must be a (B,T,H) = (%d,%d,%d) float32 tensor" % (what, desc.B, desc.T, desc.H))
+    ld = t.stride(1)
+    if t.stride(2) != 1 or ld < desc.H or (desc.B > 1 and t.stride(0) != desc.T * ld):
+        raise ValueError("%s must have strides (T*ld, ld, 1) with ld >= H" % what)
+    return int(ld)
+
+
+def lstm_forward(x, mask_value, params, desc, out=None, workspace=None):
+    """K stacked Keras LSTM layers (return_sequences=True) behind Masking(mask_value): x [B,T,F] -> the last
+    layer's outputs [B,T,H], by default a view of a [B,T,lstm_hidden_ld(H)] buffer whose padding columns the
+    kernel zeroes (`out`: any (B,T,H) tensor with strides (T*ld, ld, 1)).  mask_value None: no frame is masked."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(x))
+    x = _f32c(x, "x")
+    if tuple(x.shape) != (desc.B, desc.T, desc.F):
+        raise ValueError("x has shape %s, descriptor says (%d,%d,%d)" % (tuple(x.shape), desc.B, desc.T, desc.F))
+    if out is None:
+        ld = lstm_hidden_ld(desc.H)
+        out = torch.empty((desc.B, desc.T, ld), dtype=torch.float32, device=x.device)[..., :desc.H]
+    else:
+        ld = _hidden_ld(out, desc, "out")
+    if workspace is None:
+        workspace = lstm_workspace(desc, x.device)
+    mv = float("nan") if mask_value is None else float(mask_value)
+    rc = L.drnmf_lstm_forward(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), _capi.ptr(out), ld,
+                              _capi.ptr(workspace), workspace.numel(), _stream())
+    _capi.check(rc, h, "drnmf_lstm_forward")
+    return out
+
+
+def lstm_head_forward(hidden, params, desc, out=None):
+    """TimeDistributed(Dense(F)) + sigmoid on every frame: hidden [B,T,H] -> [B,T,F].  hidden: contiguous, or
+    rows padded to a stride ld as lstm_forward returns them (padding columns finite)."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(hidden))
+    ld = _hidden_ld(hidden, desc, "hidden")
+    if out is None:
+        out = torch.empty((desc.B, desc.T, desc.F), dtype=torch.float32, device=hidden.device)
+    elif tuple(out.shape) != (desc.B, desc.T, desc.F) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous (B,T,F) float32 tensor")
+    rc = L.drnmf_lstm_head_forward(h, C.byref(desc), _capi.ptr(hidden), ld, _capi.ptr(params), _capi.ptr(out),
+                                   _stream())
+    _capi.check(rc, h, "drnmf_lstm_head_forward")
+    return out

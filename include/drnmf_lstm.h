@@ -1,0 +1,63 @@
+/*
+ * drnmf_lstm.h -- C ABI of the LSTM baseline in libdrnmf.so: build_lstm (enhance.py:321-345), the paper's
+ * comparison model,
+ *     Masking(mask_value) -> LSTM(H, return_sequences=True) x K -> TimeDistributed(Dense(F))
+ *                         -> TimeDistributed(Activation('sigmoid')),
+ * inference path.  Conventions as in drnmf.h: device pointers, caller-owned memory (nothing is allocated
+ * inside an enqueue call), the caller's stream, the handle's mutex, never a synchronisation, status codes.
+ *
+ * Keras 2.0.4 LSTM semantics [K2.0.4-memory] -- Keras is not part of the reference repository:
+ *   weights kernel [in][4H], recurrent_kernel [H][4H], bias [4H], gate column order i, f, c, o;
+ *   z = x_t kernel + h_{t-1} recurrent_kernel + bias;
+ *   i = s(z_i), f = s(z_f), c_t = f c_{t-1} + i tanh(z_c), o = s(z_o), h_t = o tanh(c_t);
+ *   s = hard_sigmoid = clip(0.2 x + 0.5, 0, 1) by default (recurrent_activation), sigmoid selectable;
+ *   zero initial h and c.
+ * Masking as Theano's masked K.rnn: a frame whose bins ALL equal mask_value is masked; at a masked step the
+ * output and both states are the previous step's (zeros before the first valid step), in every layer.
+ */
+#ifndef DRNMF_LSTM_H
+#define DRNMF_LSTM_H
+
+#include "drnmf.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct drnmf_lstm_desc {
+    int32_t B, T;                  /* sequences, frames                                              */
+    int32_t F;                     /* input bins = Dense output width (enhance.py: output_dim = input_dim) */
+    int32_t H;                     /* hidden_dim (units of every LSTM layer)                         */
+    int32_t K;                     /* K_layers                                                       */
+    int32_t recurrent_activation;  /* DRNMF_ACT_HARD_SIGMOID (Keras default) or DRNMF_ACT_SIGMOID    */
+} drnmf_lstm_desc_t;
+
+/* Prepared parameter block (B, T ignored).  Inputs in Keras layouts, float32 row-major:
+ *   kernel0 [F][4H]; kernel_rest [K-1][H][4H] (NULL when K == 1); recurrent [K][H][4H]; bias [K][4H];
+ *   w_out [H][F]; b_out [F].  params: 256-byte aligned, params_bytes >= drnmf_lstm_params_bytes(d)
+ *   (else DRNMF_ERR_WORKSPACE). */
+size_t drnmf_lstm_params_bytes(const drnmf_lstm_desc_t* d);
+int32_t drnmf_lstm_prepare_params(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* kernel0,
+                                  const float* kernel_rest, const float* recurrent, const float* bias,
+                                  const float* w_out, const float* b_out, void* params, size_t params_bytes,
+                                  void* stream);
+
+/* Forward of the K stacked LSTM layers: x [B][T][F] -> h_out [B][T][ld_h] (the last layer's outputs in columns
+ * 0 .. H-1, zeros in columns H .. ld_h-1; ld_h >= H).  ld_h = round_up(H, 4) keeps the head on its vectorised
+ * path.  workspace: 256-byte aligned, >= drnmf_lstm_workspace_bytes(d) (else DRNMF_ERR_WORKSPACE). */
+size_t drnmf_lstm_workspace_bytes(const drnmf_lstm_desc_t* d);
+int32_t drnmf_lstm_forward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x, float mask_value,
+                           const void* params, float* h_out, int32_t ld_h, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
+/* Head: out [B*T][F] = sigmoid(hidden . w_out + b_out), every frame (masked ones included); hidden rows have
+ * stride ld_h >= H.  With ld_h >= round_up(H, 4) the columns H .. round_up(H, 4)-1 are read and must be finite
+ * (drnmf_lstm_forward writes zeros there). */
+int32_t drnmf_lstm_head_forward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* hidden, int32_t ld_h,
+                                const void* params, float* out, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* DRNMF_LSTM_H */
