@@ -388,9 +388,14 @@ inline bool thin_applies(const Operands& g) {
     const char* te = measure_env("DRNMF_THIN");                  // measurement aid: 0 = a tile column of its own
     return vec_ok(g) && g.ktail == 0 && g.N > BN && g.N % BN == 1 && !(te && atoi(te) == 0);
 }
+// ... and launch() takes it: in the fp32 kernel only.  gemm_nt_x3_kernel<THIN> lost the rider column of some
+// rows (two rows = lanes 48..63 of a wave at a time) once two workgroups shared a CU -- M >= ~25000 frames,
+// K >= 224 (tests/test_gpu_lstm_edges.py, the 513-bin head at B = 250, T = 500); the split-operand mode gives
+// the odd column a tile column of its own instead.
+inline bool thin_taken(const Operands& g) { return tl_matrix_mode != DRNMF_MATRIX_BF16X3 && thin_applies(g); }
 // workgroups of launch(g, ...) = partials a REDUCE epilogue leaves at red_out[0 .. launch_tiles)
 inline int64_t launch_tiles(const Operands& g) {
-    const int n = thin_applies(g) ? g.N - 1 : g.N;
+    const int n = thin_taken(g) ? g.N - 1 : g.N;
     return ((g.M + BM - 1) / BM) * ((n + BN - 1) / BN);
 }
 
@@ -402,7 +407,7 @@ template <class Epi>
 inline hipError_t launch(const Operands& g_in, const Epi& epi, hipStream_t stream) {
     Operands g = g_in;
     const bool vec = vec_ok(g);
-    const bool thin = thin_applies(g);
+    const bool thin = thin_taken(g);
     if (thin) { g.N -= 1; g.thin = 1; }
     const int64_t tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
     if (tiles <= 0 || tiles > 0x7fffffff || g.M > 0x7fffff00 || g.ktail < 0 || g.ktail > 2)

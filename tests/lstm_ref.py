@@ -65,8 +65,11 @@ def head(h, w_out, b_out):
     return torch.sigmoid(h @ w_out + b_out)
 
 
-def model_forward(x, weights, K, mask_value=-1.0, recurrent_activation="hard_sigmoid"):
-    """weights in Keras order (LSTMModel.get_weights) -> (sigmoid output, last hidden), fp64 numpy."""
+def model_forward(x, weights, K, mask_value=-1.0, recurrent_activation="hard_sigmoid", rows=None):
+    """weights in Keras order (LSTMModel.get_weights) -> (sigmoid output, last hidden), fp64 numpy.  rows: the
+    sequences to run (an index list into x's first axis; rows never interact), outputs in that order."""
+    if rows is not None:
+        x = x[torch.as_tensor(list(rows))] if isinstance(x, torch.Tensor) else np.asarray(x)[list(rows)]
     ks, rs, bs = weights[0:3 * K:3], weights[1:3 * K:3], weights[2:3 * K:3]
     hs = lstm_layers(x, ks, rs, bs, mask_value, recurrent_activation)
     y = head(hs[-1], weights[3 * K], weights[3 * K + 1])
@@ -96,3 +99,61 @@ def ragged_input(rng, B, T, F, mask_value=-1.0, all_masked_row=True):
     for b in range(B):
         x[b, lens[b]:] = mask_value
     return x, lens
+
+
+MASK_PATTERNS = ("none", "trailing", "leading", "interior", "partial", "all", "combo")
+
+
+def masked_input(rng, B, T, F, pattern="mixed", mask_value=-1.0):
+    """x [B,T,F] float32 and the frame validity it was built with, valid [B,T] bool (independent of
+    valid_frames).  Valid frames hold bins in (0, 1] with about one bin in ten set to mask_value (a valid frame
+    may contain the mask value; silence in a magnitude spectrogram is 0); a masked frame holds mask_value in
+    every bin.  pattern, per row (one of MASK_PATTERNS, or 'mixed': row b takes MASK_PATTERNS[b % 7]):
+      none      every frame valid
+      trailing  a masked suffix (the reference's padding layout)
+      leading   a masked prefix (the states stay zero until the first valid frame)
+      interior  one or two masked runs strictly inside the sequence (the states carry across them)
+      partial   about a third of the frames have every bin but one equal to mask_value (still valid; the
+                surviving bin is never bin 0 when F > 1)
+      all       every frame masked
+      combo     a masked prefix, an interior run, partial frames and a masked suffix in one row"""
+    mv = np.float32(mask_value)
+    x = (1.0 - rng.random((B, T, F))).astype(np.float32)
+    x[rng.random((B, T, F)) < 0.1] = mv
+    valid = np.ones((B, T), dtype=bool)
+
+    def run(lo, hi):
+        return (int(lo), int(max(lo, hi)))
+
+    for b in range(B):
+        kind = MASK_PATTERNS[b % len(MASK_PATTERNS)] if pattern == "mixed" else pattern
+        if kind not in MASK_PATTERNS:
+            raise ValueError(pattern)
+        masked, partial = [], []
+        if kind == "all":
+            masked.append((0, T))
+        if kind in ("trailing", "combo") and T > 1:
+            masked.append(run(T - rng.integers(1, max(2, T // 4 + 1)), T))
+        if kind in ("leading", "combo") and T > 1:
+            masked.append(run(0, rng.integers(1, max(2, T // 4 + 1))))
+        if kind in ("interior", "combo") and T > 2:
+            lo, hi = T // 4 + 1, max(T // 4 + 2, 3 * T // 4)
+            a = int(rng.integers(lo, hi)) if hi > lo else lo
+            a = min(a, T - 2)
+            masked.append(run(a, min(T - 1, a + 1 + rng.integers(0, max(1, T // 8)))))
+            if kind == "interior" and T > 6 and a > 2:            # a second run, before the first
+                masked.append(run(1, 2))
+        if kind in ("partial", "combo"):
+            partial = [t for t in range(T) if rng.random() < 1 / 3]
+        for lo, hi in masked:
+            x[b, lo:hi] = mv
+            valid[b, lo:hi] = False
+        for t in partial:
+            if not valid[b, t]:
+                continue
+            keep = int(rng.integers(1, F)) if F > 1 else 0
+            x[b, t] = mv
+            x[b, t, keep] = 1.0 - rng.random()
+    lost = valid & (x == mv).all(axis=-1)            # a valid frame that the sprinkled mask values covered
+    x[lost, -1] = 0.5
+    return x, valid

@@ -63,6 +63,79 @@ def test_reference_padding_repeats_the_last_output(act):
     assert float(empty.abs().max()) == 0.0
 
 
+def _torch_lstm(w, K):
+    F, H = w[0].shape[0], w[1].shape[0]
+    net = torch.nn.LSTM(F, H, num_layers=K, batch_first=True).double()
+    with torch.no_grad():
+        for k in range(K):
+            getattr(net, "weight_ih_l%d" % k).copy_(torch.from_numpy(w[3 * k].T.astype(np.float64)))
+            getattr(net, "weight_hh_l%d" % k).copy_(torch.from_numpy(w[3 * k + 1].T.astype(np.float64)))
+            getattr(net, "bias_ih_l%d" % k).copy_(torch.from_numpy(w[3 * k + 2].astype(np.float64)))
+            getattr(net, "bias_hh_l%d" % k).zero_()
+    return net
+
+
+def test_masked_input_patterns():
+    """masked_input builds what it says: the validity it reports is keras Masking's, the masked runs sit where
+    the pattern puts them, and a partly masked frame (every bin but one = mask_value) is valid."""
+    for mv in (-1.0, 0.0):
+        x, valid = R.masked_input(np.random.default_rng(2), 14, 40, 9, "mixed", mv)
+        np.testing.assert_array_equal(R.valid_frames(x, mv).numpy(), valid)
+        kinds = [R.MASK_PATTERNS[b % len(R.MASK_PATTERNS)] for b in range(14)]
+        for b, kind in enumerate(kinds):
+            v = valid[b]
+            first, last = (np.nonzero(v)[0][[0, -1]] if v.any() else (None, None))
+            assert (kind == "all") == (not v.any())
+            assert (kind in ("leading", "combo")) == (v.any() and first > 0)
+            assert (kind in ("trailing", "combo")) == (v.any() and last < 39)
+            interior = v.any() and not v[first:last + 1].all()
+            assert (kind in ("interior", "combo")) == interior, kind
+            nmask = (x[b] == np.float32(mv)).sum(-1)
+            partial = v & (nmask == 8)
+            assert (kind in ("partial", "combo")) == bool(partial.any()), kind
+            assert not np.any(x[b][partial][:, 0] != np.float32(mv))       # the surviving bin is not bin 0
+
+
+@pytest.mark.parametrize("mask_value", [-1.0, 0.0])
+@pytest.mark.parametrize("K", [1, 3])
+def test_reference_masking_equals_torch_lstm_on_the_valid_frames(K, mask_value):
+    """Masking semantics of the reference against a second implementation that shares none of its masking
+    logic: torch.nn.LSTM (sigmoid gates) run on each sequence's valid frames only, compacted.  The reference's
+    frames at valid positions are those outputs; a masked frame repeats the last valid output, or is zero before
+    the first valid frame -- in every layer (K = 3: the layers below carry their states across the gaps too)."""
+    rng = np.random.default_rng(10 + K)
+    B, T, F, H = 14, 23, 7, 5
+    w = R.random_weights(rng, F, H, K, scale=2.0)
+    x, valid = R.masked_input(rng, B, T, F, "mixed", mask_value)
+    hs = R.lstm_layers(x, w[0:3 * K:3], w[1:3 * K:3], w[2:3 * K:3], mask_value, "sigmoid")[-1]
+    net = _torch_lstm(w, K)
+    for b in range(B):
+        idx = np.nonzero(valid[b])[0]
+        if len(idx):
+            with torch.no_grad():
+                comp, _ = net(torch.from_numpy(x[b, idx].astype(np.float64))[None])
+            assert float((hs[b, idx] - comp[0]).abs().max()) <= 1e-12
+        for t in range(T):
+            if valid[b, t]:
+                continue
+            before = idx[idx < t]
+            if len(before):
+                assert torch.equal(hs[b, t], hs[b, before[-1]])
+                assert float((hs[b, t] - comp[0, len(before) - 1]).abs().max()) <= 1e-12
+            else:
+                assert float(hs[b, t].abs().max()) == 0.0
+
+
+def test_reference_row_subset():
+    rng = np.random.default_rng(4)
+    B, T, F, H, K = 6, 8, 5, 3, 2
+    w = R.random_weights(rng, F, H, K, scale=2.0)
+    x, _ = R.masked_input(rng, B, T, F)
+    y, h = R.model_forward(x, w, K)
+    ys, hsub = R.model_forward(x, w, K, rows=[4, 0, 5])
+    assert np.array_equal(ys, y[[4, 0, 5]]) and np.array_equal(hsub, h[[4, 0, 5]])
+
+
 def _params(K=3, H=13, F=20):
     return dict(mask_value=-1., maxseq=10, input_dim=F, output_dim=F, K_layers=K, hidden_dim=H)
 
