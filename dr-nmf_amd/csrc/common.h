@@ -254,7 +254,8 @@ struct Launcher {
 };
 // frame(chain, i): enqueue the kernels of the i-th frame of a block (i counts from the block's first frame)
 using FrameFn = std::function<int32_t(Launcher&, int)>;
-enum class GraphKind : uint64_t { GramForward = 1, Forward, IstaForward, Backward, Dense, Lstm };
+enum class GraphKind : uint64_t { GramForward = 1, Forward, IstaForward, Backward, Dense, Lstm, LstmBackward,
+                                  LstmTrain };
 
 // The executable of `frames` consecutive frames of one cell call, from the handle's bounded cache
 // (GRAPH_CACHE_ENTRIES).  The key is `kind`, the site's `fields` (every shape, pointer, scalar and layout

@@ -20,6 +20,7 @@
 // The head (sigmoid(h . W_out + b_out)) is one more gemm::launch with the sigmoid in its epilogue.
 #include "common.h"
 #include "gemm_nt.h"
+#include "gemm_tn.h"
 #include "../../include/drnmf_lstm.h"
 
 namespace {
@@ -205,6 +206,13 @@ struct LstmStepArgs {
     const int* d_rd;           // diagonal counter read by every workgroup ...
     int* d_wr;                 // ... and the other one, advanced by workgroup (0, 0, 0)
     int B, T, H, K, Bp, Hc, numU, NC, act, ld_h;
+    // training forward only (lstm_step_kernel<true>): xproj / valid in the training layout (row b (T+1) + t + 1)
+    // and the stash of every (layer, frame): gate pre-activations, c_t and h_t at that row of layer k's block
+    float* zst;                // [K][zk][NC]   packed columns
+    float* cst;                // [K][Bp (T+1)][Hc]
+    float* hst;                // [K][Bp (T+1)][Hq]
+    size_t zk;                 // rows of one layer's block of zst (Bp (T+1) + 1: a zero row behind the last)
+    int Hq;
 };
 
 // One launch = one diagonal d: workgroup (ab, mb, k) computes frame t = d - k of layer k for rows
@@ -214,6 +222,9 @@ struct LstmStepArgs {
 // 16-byte piece, which is the order the matrix packing puts the rows in.  Ring slots: (k, t) writes slot
 // t & 1 of layer k; in the same launch (k + 1, t - 1) and (k, t) read slot (t - 1) & 1 of layer k, and (k, t)
 // reads slot t & 1 of layer k - 1, which (k - 1, t + 1) does not write (it writes slot (t + 1) & 1).
+// STASH (the training forward): the same arithmetic, plus the stash writes; lstm_step_kernel<false> is the
+// inference kernel.
+template <bool STASH>
 __global__ void __launch_bounds__(64 * LSTM_NW) lstm_step_kernel(const LstmStepArgs a) {
     __shared__ __attribute__((aligned(16))) float red[LSTM_NW * 16 * 32];
     const int ab = blockIdx.x, mb = blockIdx.y, k = blockIdx.z;
@@ -266,12 +277,21 @@ __global__ void __launch_bounds__(64 * LSTM_NW) lstm_step_kernel(const LstmStepA
     const int r = tid >> 3, u = tid & 7;
     const int b = mb * 16 + r, n = ab * LSTM_UNITS + u;
     const size_t frame = (size_t)b * a.T + t;
+    const size_t frame_x = STASH ? (size_t)b * (a.T + 1) + t + 1 : frame;
     const bool real = b < a.B;
     if (n >= a.H) {                                     // padded units stay zero (they meet zero matrix rows)
         if (k == a.K - 1 && real && n < a.ld_h) a.out[frame * a.ld_h + n] = 0.f;
+        if constexpr (STASH) {
+            const size_t srow = (size_t)k * a.Bp * (a.T + 1) + (size_t)b * (a.T + 1) + t + 1;
+            float* zp = a.zst + ((size_t)k * a.zk + (size_t)b * (a.T + 1) + t + 1) * a.NC + ab * 32 + u;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) zp[g * 8] = 0.f;
+            a.cst[srow * a.Hc + n] = 0.f;
+            if (n < a.Hq) a.hst[srow * a.Hq + n] = 0.f;
+        }
         return;
     }
-    const float* pre = k == 0 ? a.xproj + (real ? frame : 0) * a.NC : a.bias + (size_t)k * a.NC;
+    const float* pre = k == 0 ? a.xproj + (real ? frame_x : 0) * a.NC : a.bias + (size_t)k * a.NC;
     float z[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -283,7 +303,7 @@ __global__ void __launch_bounds__(64 * LSTM_NW) lstm_step_kernel(const LstmStepA
     const size_t e_prev = ((size_t)k * 2 + ((t + 1) & 1)) * slab + (size_t)b * Hc + n;
     const size_t e_cur = ((size_t)k * 2 + (t & 1)) * slab + (size_t)b * Hc + n;
     float cn = a.cring[e_prev], hn = a.hring[e_prev];   // K.rnn masking: a masked step keeps both states
-    if (real && a.valid[frame]) {
+    if (real && a.valid[frame_x]) {
         const float ig = gate_act(z[0], a.act), fg = gate_act(z[1], a.act), og = gate_act(z[3], a.act);
         cn = fg * cn + ig * tanhf(z[2]);
         hn = og * tanhf(cn);
@@ -291,6 +311,14 @@ __global__ void __launch_bounds__(64 * LSTM_NW) lstm_step_kernel(const LstmStepA
     a.cring[e_cur] = cn;
     a.hring[e_cur] = hn;
     if (k == a.K - 1 && real) a.out[frame * a.ld_h + n] = hn;
+    if constexpr (STASH) {
+        const size_t srow = (size_t)k * a.Bp * (a.T + 1) + (size_t)b * (a.T + 1) + t + 1;
+        float* zp = a.zst + ((size_t)k * a.zk + (size_t)b * (a.T + 1) + t + 1) * a.NC + ab * 32 + u;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) zp[g * 8] = z[g];
+        a.cst[srow * a.Hc + n] = cn;
+        a.hst[srow * a.Hq + n] = hn;
+    }
 }
 
 }  // namespace
@@ -410,7 +438,7 @@ extern "C" int32_t drnmf_lstm_forward(drnmf_handle_t h, const drnmf_lstm_desc_t*
             a.d_rd = ctr + 16 * p;
             a.d_wr = ctr + 16 * (1 - p);
             void* kp[1] = {&a};
-            DRNMF_HIP(h, chain.add((const void*)&lstm_step_kernel, grid, dim3(64 * LSTM_NW), kp));
+            DRNMF_HIP(h, chain.add((const void*)&lstm_step_kernel<false>, grid, dim3(64 * LSTM_NW), kp));
         }
         return DRNMF_OK;
     };
@@ -445,5 +473,646 @@ extern "C" int32_t drnmf_lstm_head_forward(drnmf_handle_t h, const drnmf_lstm_de
     g.lda = ld_h;
     g.ldb = L.Hq;
     DRNMF_HIP(h, gemm::launch(g, EpiLstmHead{out, (const float*)(pb + L.off_bo), d->F}, (hipStream_t)stream_));
+    return DRNMF_OK;
+}
+
+// ---- training: forward with stash, loss head + its backward, BPTT as a reverse wavefront -------------------
+//
+// The three training entry points share one workspace (drnmf_lstm_train_workspace_bytes), run in this order on
+// it: drnmf_lstm_train_forward -> drnmf_lstm_loss_head_backward -> drnmf_lstm_backward.
+//
+// Training layout of the frames: row b (T + 1) + t + 1 holds frame t of sequence b, row b (T + 1) is a zero
+// frame.  The masked input xz, xproj, valid and the stash (z, c, h of every layer) use it, so that the
+// recurrent-kernel gradient sum_t h_{k,t-1}^T dz_{k,t} is ONE gemm_tn over B (T + 1) rows with the dz operand
+// one row ahead (a masked frame copies h, so row t is the state that entered step t).  The stash blocks have
+// Bp (T + 1) rows per layer (the BPTT's 16-row tiles read padded rows), the z / dz block one more zero row.
+//
+// BPTT [K2.0.4-memory: Theano's autodiff of the masked K.rnn]: (k, t) needs (k + 1, t) and (k, t + 1) only,
+// so one launch per diagonal d = k + t, from T + K - 2 down to 0.  Workgroup (tile of 32 units, 16 rows, k)
+// contracts [dz_{k+1,t} | dz_{k,t+1}] (top layer: dz_{K-1,t+1} alone) with the transposed stacked matrix
+// [kernel_{k+1}; recurrent_k]^T and adds, in its epilogue, d_hidden_t (top layer) and the pass-through carried
+// from a masked (k, t + 1).  With G_h that sum and G_c the carried dc:
+//   valid (k, t):  dc = G_c + G_h o (1 - tanh^2 c_t);  dz_i = dc tanh(z_c) s'(z_i), dz_f = dc c_{t-1} s'(z_f),
+//                  dz_c = dc i (1 - tanh^2 z_c), dz_o = G_h tanh(c_t) s'(z_o);  carried to t - 1: dh 0, dc f;
+//   masked (k, t): dz = 0;  carried to t - 1: dh = G_h, dc = G_c (both states were copies).
+// s' of hard_sigmoid is 0.2 on the CLOSED interval 0 <= 0.2 z + 0.5 <= 1 (Theano's clip), hence z is stashed,
+// not the gate.  dz overwrites z in place: only (k, t) reads z_{k,t}, and dz_{k,t} is read one diagonal later.
+namespace {
+
+constexpr int LSTM_WG_SPLITS = 32;     // upper bound of the split-K count of a weight-gradient product
+
+struct LstmTrainLayout {
+    LstmLayout L;
+    int NB, NBc;                       // BPTT output tiles of 32 units, NB * 32
+    size_t R1, RS, zk, part_floats, cpart_floats;
+    size_t off_xz, off_valid, off_xproj, off_h, off_c, off_ctr, off_z, off_cst, off_hst;
+    size_t off_s, off_dpre, off_wop, off_lpart, off_mt, off_ph, off_pc, off_bctr, off_part, off_cpart, total;
+};
+
+LstmTrainLayout lstm_train_layout(const drnmf_lstm_desc_t* d) {
+    LstmTrainLayout W;
+    W.L = lstm_layout(d);
+    const LstmLayout& L = W.L;
+    const size_t B = d->B > 0 ? d->B : 0, T = d->T > 0 ? d->T : 0, K = d->K, F = d->F, H = d->H;
+    W.NB = (d->H + 31) / 32;
+    W.NBc = W.NB * 32;
+    W.R1 = B * (T + 1);
+    W.RS = (size_t)L.Bp * (T + 1);
+    W.zk = W.RS + 1;
+    const size_t mmax = (size_t)(L.Fq > L.Hq ? L.Fq : L.Hq), nmax = (size_t)(L.NC > L.Fq ? L.NC : L.Fq);
+    W.part_floats = (size_t)LSTM_WG_SPLITS * mmax * nmax;
+    W.cpart_floats = (size_t)LSTM_WG_SPLITS * nmax;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t at = o; o += round_up_sz(bytes, 256); return at; };
+    W.off_xz = take(W.R1 * L.Fq * 4);
+    W.off_valid = take(W.R1);
+    W.off_xproj = take(W.R1 * L.NC * 4);
+    W.off_h = take(K * 2 * L.Bp * L.Hc * 4);
+    W.off_c = take(K * 2 * L.Bp * L.Hc * 4);
+    W.off_ctr = take(256);
+    W.off_z = take(K * W.zk * L.NC * 4);
+    W.off_cst = take(K * W.RS * L.Hc * 4);
+    W.off_hst = take(K * W.RS * L.Hq * 4);
+    W.off_s = take(B * T * F * 4);
+    W.off_dpre = take(B * T * L.Fq * 4);
+    W.off_wop = take(H * L.Fq * 4);
+    W.off_lpart = take((B * T + 3) / 4 * 2 * 4);
+    W.off_mt = take(K * 2 * L.NC * W.NBc * 4);
+    W.off_ph = take(K * 2 * L.Bp * W.NBc * 4);
+    W.off_pc = take(K * 2 * L.Bp * W.NBc * 4);
+    W.off_bctr = take(256);
+    W.off_part = take(W.part_floats * 4);
+    W.off_cpart = take(W.cpart_floats * 4);
+    W.total = o;
+    return W;
+}
+
+// x [B][T][F] -> xz [B (T+1)][Fq] and valid in the training layout (zero frame at row b (T + 1), not valid)
+__global__ void __launch_bounds__(256)
+lstm_pack_x_train_kernel(const float* __restrict__ x, float* __restrict__ xz, unsigned char* __restrict__ valid,
+                         float mask_value, size_t rows, int T, int F, int Fq) {
+    const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const size_t row = (size_t)blockIdx.x * 4 + wv;
+    if (row >= rows) return;
+    const size_t b = row / (T + 1), j = row % (T + 1);
+    float* dst = xz + row * Fq;
+    if (j == 0) {
+        for (int f = l; f < Fq; f += 64) dst[f] = 0.f;
+        if (l == 0) valid[row] = 0;
+        return;
+    }
+    const float* src = x + (b * T + j - 1) * F;
+    bool any = false;
+    for (int f = l; f < F; f += 64) any |= (src[f] != mask_value);
+    any = __any(any);
+    for (int f = l; f < Fq; f += 64) dst[f] = (any && f < F) ? src[f] : 0.f;
+    if (l == 0) valid[row] = any ? 1 : 0;
+}
+
+// zero rows of the stash: per layer, row b (T + 1) of z / c / h for every b < Bp and z's trailing row
+__global__ void __launch_bounds__(256)
+lstm_stash_init_kernel(float* __restrict__ zst, float* __restrict__ cst, float* __restrict__ hst, int Bp, int T,
+                       size_t zk, size_t RS, int NC, int Hc, int Hq) {
+    const int k = blockIdx.y, b = blockIdx.x;      // b == Bp: the trailing z row
+    const size_t T1 = (size_t)T + 1;
+    float* zr = zst + ((size_t)k * zk + (size_t)b * T1) * NC;
+    for (int i = threadIdx.x; i < NC; i += 256) zr[i] = 0.f;
+    if (b == Bp) return;
+    const size_t srow = (size_t)k * RS + (size_t)b * T1;
+    for (int i = threadIdx.x; i < Hc; i += 256) cst[srow * Hc + i] = 0.f;
+    for (int i = threadIdx.x; i < Hq; i += 256) hst[srow * Hq + i] = 0.f;
+}
+
+// ---- loss head --------------------------------------------------------------------------------------------
+
+// w_out [H][F] -> [H][Fq] (zero columns F .. Fq-1): the "Bt" of d_hidden = dpre . w_out^T on the vector path
+__global__ void __launch_bounds__(256)
+lstm_pad_wo_kernel(const float* __restrict__ wo, float* __restrict__ out, int F, int Fq, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const size_t r = i / Fq;
+    const int f = (int)(i % Fq);
+    out[i] = f < F ? wo[r * F + f] : 0.f;
+}
+
+// mse_of_masked (enhance.py:1260-1312): one wave per frame r = b T + t, xm = the Masking layer's output (the
+// training-layout xz row), s = sigmoid output, e = xm s - y:  loss_r = w mean_F e^2,
+// dpre = w (2 / F) e xm s (1 - s) (zeros in the padding bins).  Block partials {sum loss_r, #(w != 0)}.
+__global__ void __launch_bounds__(256)
+lstm_loss_rows_kernel(const float* __restrict__ xz, const float* __restrict__ S, const float* __restrict__ y,
+                      const float* __restrict__ w, float* __restrict__ dpre, float* __restrict__ part,
+                      size_t rows, int T, int F, int Fq) {
+    __shared__ float sl[4], sc[4];
+    const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const size_t row = (size_t)blockIdx.x * 4 + wv;
+    float acc = 0.f, cnt = 0.f;
+    if (row < rows) {
+        const size_t b = row / T, t = row % T;
+        const float* xm = xz + (b * (T + 1) + t + 1) * Fq;
+        const float* s = S + row * F;
+        const float* yy = y + row * F;
+        const float wr = w[row], g = wr * (2.f / (float)F);
+        float* dp = dpre + row * Fq;
+        for (int f = l; f < Fq; f += 64) {
+            float v = 0.f;
+            if (f < F) {
+                const float xs = xm[f] * s[f], e = xs - yy[f];
+                acc += e * e;
+                v = g * e * xs * (1.f - s[f]);
+            }
+            dp[f] = v;
+        }
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        acc = wr * (acc / (float)F);
+        cnt = wr != 0.f ? 1.f : 0.f;
+    }
+    if (l == 0) { sl[wv] = acc; sc[wv] = cnt; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part[2 * (size_t)blockIdx.x] = (sl[0] + sl[1]) + (sl[2] + sl[3]);
+        part[2 * (size_t)blockIdx.x + 1] = (sc[0] + sc[1]) + (sc[2] + sc[3]);
+    }
+}
+
+// fixed-order fp64 sum of the block partials (deterministic)
+__global__ void __launch_bounds__(256)
+lstm_loss_final_kernel(const float* __restrict__ part, int64_t nblocks, float* __restrict__ sums) {
+    __shared__ double s0[256], s1[256];
+    double a = 0.0, b = 0.0;
+    for (int64_t i = threadIdx.x; i < nblocks; i += 256) {
+        a += (double)part[2 * i];
+        b += (double)part[2 * i + 1];
+    }
+    s0[threadIdx.x] = a;
+    s1[threadIdx.x] = b;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            s0[threadIdx.x] += s0[threadIdx.x + o];
+            s1[threadIdx.x] += s1[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { sums[0] = (float)s0[0]; sums[1] = (float)s1[0]; }
+}
+
+struct EpiLstmDh {      // d_hidden = dpre . w_out^T
+    float* out;
+    int ld;
+    __device__ f32x2 pre(int64_t, int) const { return f32x2{0.f, 0.f}; }
+    __device__ void operator()(int64_t row, int col, float acc, f32x2) const { out[row * ld + col] = acc; }
+};
+
+// ---- weight gradients -------------------------------------------------------------------------------------
+
+struct EpiLstmPart {    // split-K partial tiles of gemm_tn, summed by lstm_sum_parts_kernel in a fixed order
+    float* P;
+    int ld;
+    size_t stride;
+    __device__ float pre(int, int, int) const { return 0.f; }
+    __device__ void operator()(int split, int m, int n, float acc, float) const {
+        P[split * stride + (size_t)m * ld + n] = acc;
+    }
+};
+
+// column sums over rows, per split (fixed order)
+__global__ void __launch_bounds__(256)
+lstm_colsum_kernel(const float* __restrict__ A, float* __restrict__ part, int64_t rows, int N, int64_t ld) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    const int sp = blockIdx.y, nsp = gridDim.y;
+    if (n >= N) return;
+    const int64_t per = (rows + nsp - 1) / nsp;
+    int64_t r1 = (sp + 1) * per;
+    if (r1 > rows) r1 = rows;
+    float s = 0.f;
+    for (int64_t r = sp * per; r < r1; ++r) s += A[r * ld + n];
+    part[(size_t)sp * N + n] = s;
+}
+
+// out [Mr][Nr] = sum over the splits (in order) of P[s][m][col]; H > 0: Nr = 4H Keras gate columns, col = the
+// packed column of (gate g, unit u) = (u / 8) 32 + 8 g + u % 8; H == 0: col = the output column itself
+__global__ void __launch_bounds__(256)
+lstm_sum_parts_kernel(const float* __restrict__ P, float* __restrict__ out, int Mr, int Nr, int ldp,
+                      size_t pstride, int splits, int H) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)Mr * Nr) return;
+    const int m = (int)(i / Nr), c = (int)(i % Nr);
+    int col = c;
+    if (H > 0) {
+        const int g = c / H, u = c % H;
+        col = (u >> 3) * 32 + g * 8 + (u & 7);
+    }
+    const float* p = P + (size_t)m * ldp + col;
+    float s = 0.f;
+    for (int k = 0; k < splits; ++k) s += p[(size_t)k * pstride];
+    out[i] = s;
+}
+
+// ---- BPTT -------------------------------------------------------------------------------------------------
+
+// Transposed stacked matrix of layer k in the operand order of lstm_bwd_step_kernel (the packing of
+// lstm_pack_step_kernel with 32-unit output tiles): contraction rows = packed gate columns of
+// kernel_{k+1} (k < K-1) then of recurrent_k; output column n = unit n of layer k.
+__global__ void __launch_bounds__(256)
+lstm_pack_bwd_kernel(const float* __restrict__ kern_next, const float* __restrict__ rec, float* __restrict__ Mt,
+                     int H, int NC, int NB, int rows) {
+    const int NBc = NB * 32;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)rows * NBc) return;
+    const int i = (int)(idx / NBc), n = (int)(idx % NBc);
+    const bool two = kern_next != nullptr;
+    const float* src = two && i < NC ? kern_next : rec;
+    const int p = two && i >= NC ? i - NC : i;
+    const int g = (p & 31) >> 3, u = (p >> 5) * LSTM_UNITS + (p & 7);
+    const float v = (u < H && n < H) ? src[(size_t)n * 4 * H + (size_t)g * H + u] : 0.f;
+    const int c = i >> 4, kk = i & 15, q = kk >> 2, s = kk & 3;
+    const int ab = n >> 5, pc = n & 31;
+    Mt[((size_t)c * NB + ab) * 512 + (pc >> 4) * 256 + (q * 16 + (pc & 15)) * 4 + s] = v;
+}
+
+__global__ void __launch_bounds__(256)
+lstm_bwd_init_kernel(float* __restrict__ ph, float* __restrict__ pc, int* ctr, size_t n, int d0) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) { ctr[0] = d0; ctr[16] = d0; }
+    if (i < n) { ph[i] = 0.f; pc[i] = 0.f; }
+}
+
+__device__ __forceinline__ float gate_grad(float v, int act) {    // d gate_act / dv
+    if (act == DRNMF_ACT_SIGMOID) {
+        const float s = 1.f / (1.f + expf(-v));
+        return s * (1.f - s);
+    }
+    const float p = 0.2f * v + 0.5f;
+    return (p >= 0.f && p <= 1.f) ? 0.2f : 0.f;
+}
+
+struct LstmBwdArgs {
+    const float* Mt;           // [K][2 NC rows][NBc] packed (lstm_pack_bwd_kernel)
+    float* Z;                  // [K][zk][NC]: z in, dz out (training layout)
+    const float* cst;          // [K][Bp (T+1)][Hc]
+    const unsigned char* valid;   // [B (T+1)]
+    const float* dh;           // [B][T][H]: d loss / d (last layer's output)
+    float* ph;                 // [K][2][Bp][NBc]: dh carried past a masked frame, slot t & 1 written by (k, t)
+    float* pc;                 // [K][2][Bp][NBc]: dc carried to t - 1
+    const int* d_rd;
+    int* d_wr;
+    size_t zk;
+    int B, T, H, K, Bp, Hc, NB, NC, act;
+};
+
+// One launch = one diagonal d (descending): workgroup (ab, mb, k) computes (k, t = d - k) for rows
+// 16 mb .. 16 mb + 15 and units 32 ab .. 32 ab + 31.  Contraction as lstm_step_kernel (exact-fp32 MFMA, split
+// over the waves, reduced through LDS in a fixed order); the A rows are dz rows of the stash.
+__global__ void __launch_bounds__(64 * LSTM_NW) lstm_bwd_step_kernel(const LstmBwdArgs a) {
+    __shared__ __attribute__((aligned(16))) float red[LSTM_NW * 16 * 32];
+    const int ab = blockIdx.x, mb = blockIdx.y, k = blockIdx.z;
+    const int d = *a.d_rd;
+    if (ab == 0 && mb == 0 && k == 0 && threadIdx.x == 0) *a.d_wr = d - 1;
+    const int t = d - k;
+    if (t < 0 || t >= a.T) return;
+    const int tid = threadIdx.x;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l = tid & 63, j = l & 15, q = l >> 4;
+    const bool top = k == a.K - 1;
+    const int nq = a.NC / 16, nch = top ? nq : 2 * nq;
+    const size_t T1 = (size_t)a.T + 1;
+    const size_t seq = (size_t)(mb * 16 + j) * T1;
+    const float* next = a.Z + ((size_t)k * a.zk + seq + t + 2) * a.NC + 4 * q;                 // dz_{k,t+1}
+    const float* above = top ? next : a.Z + ((size_t)(k + 1) * a.zk + seq + t + 1) * a.NC + 4 * q;  // dz_{k+1,t}
+    const float* brow = a.Mt + (size_t)k * 2 * a.NC * (a.NB * 32) + (size_t)ab * 512 + l * 4;
+    const size_t bstep = (size_t)a.NB * 512;
+
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    for (int c0 = w; c0 < nch; c0 += LSTM_NW * LSTM_G) {
+        f32x4 av[LSTM_G], b0[LSTM_G], b1[LSTM_G];
+#pragma unroll
+        for (int g = 0; g < LSTM_G; ++g) {
+            const int c = c0 + LSTM_NW * g;
+            const int cc = c < nch ? c : nch - 1;
+            const float* ap = top ? next + 16 * cc : (cc < nq ? above + 16 * cc : next + 16 * (cc - nq));
+            av[g] = *(const f32x4*)ap;
+            b0[g] = *(const f32x4*)(brow + (size_t)cc * bstep);
+            b1[g] = *(const f32x4*)(brow + (size_t)cc * bstep + 256);
+            if (c >= nch) av[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int g = 0; g < LSTM_G; ++g)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                acc0 = mfma16(av[g][s], b0[g][s], acc0);
+                acc1 = mfma16(av[g][s], b1[g][s], acc1);
+            }
+    }
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        red[(w * 16 + 4 * q + v) * 32 + j] = acc0[v];
+        red[(w * 16 + 4 * q + v) * 32 + 16 + j] = acc1[v];
+    }
+    __syncthreads();
+
+    // cell backward: thread = row r, units uu and uu + 16 of the tile
+    const int r = tid >> 4, b = mb * 16 + r;
+    const int NBc = a.NB * 32;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int uu = (tid & 15) + 16 * half, n = ab * 32 + uu;
+        float gh = 0.f;
+#pragma unroll
+        for (int ww = 0; ww < LSTM_NW; ++ww) gh += red[(ww * 16 + r) * 32 + uu];
+        const size_t e_next = (((size_t)k * 2 + ((t + 1) & 1)) * a.Bp + b) * NBc + n;
+        const size_t e_cur = (((size_t)k * 2 + (t & 1)) * a.Bp + b) * NBc + n;
+        gh += a.ph[e_next];
+        const float gc = a.pc[e_next];
+        const bool keep = b < a.B && n < a.H;
+        if (top && keep) gh += a.dh[((size_t)b * a.T + t) * a.H + n];
+        const size_t zrow = (size_t)k * a.zk + (size_t)b * T1 + t + 1;
+        float* zp = a.Z + zrow * a.NC + (n >> 3) * 32 + (n & 7);
+        if (keep && a.valid[(size_t)b * T1 + t + 1]) {
+            const float z0 = zp[0], z1 = zp[8], z2 = zp[16], z3 = zp[24];
+            const size_t srow = (size_t)k * a.Bp * T1 + (size_t)b * T1 + t + 1;
+            const float c = a.cst[srow * a.Hc + n], cp = a.cst[(srow - 1) * a.Hc + n];
+            const float ig = gate_act(z0, a.act), fg = gate_act(z1, a.act), og = gate_act(z3, a.act);
+            const float gt = tanhf(z2), tc = tanhf(c);
+            const float dc = gc + gh * og * (1.f - tc * tc);
+            zp[0] = dc * gt * gate_grad(z0, a.act);
+            zp[8] = dc * cp * gate_grad(z1, a.act);
+            zp[16] = dc * ig * (1.f - gt * gt);
+            zp[24] = gh * tc * gate_grad(z3, a.act);
+            a.ph[e_cur] = 0.f;
+            a.pc[e_cur] = dc * fg;
+        } else {
+            if (n < a.NC / 4) { zp[0] = 0.f; zp[8] = 0.f; zp[16] = 0.f; zp[24] = 0.f; }
+            a.ph[e_cur] = keep ? gh : 0.f;
+            a.pc[e_cur] = keep ? gc : 0.f;
+        }
+    }
+}
+
+int validate_train_call(drnmf_handle_t h, const drnmf_lstm_desc_t* d, void* workspace, size_t workspace_bytes,
+                        const char* what, LstmTrainLayout* W) {
+    int rc = validate_lstm_desc(h, d, true);
+    if (rc) return rc;
+    *W = lstm_train_layout(d);
+    if (!workspace) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: NULL workspace", what);
+    if (workspace_bytes < W->total)
+        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "%s: workspace %zu < required %zu", what, workspace_bytes, W->total);
+    if ((uintptr_t)workspace & 255) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "workspace must be 256-byte aligned");
+    return DRNMF_OK;
+}
+
+// C[M x N] = A^T B over `rows` rows (split-K partials in the workspace) -> out [Mr][Nr] (Keras gate order when
+// H > 0, see lstm_sum_parts_kernel)
+hipError_t lstm_tn_product(const LstmTrainLayout& W, char* ws, const float* A, int64_t lda, int M, const float* Bm,
+                           int64_t ldb, int N, int64_t rows, float* out, int Mr, int Nr, int H, hipStream_t stream) {
+    float* part = (float*)(ws + W.off_part);
+    int splits = gemm_tn::pick_splits(M, N, rows, LSTM_WG_SPLITS);
+    gemm_tn::Operands g{A, Bm, rows, M, N, lda, ldb};
+    hipError_t e = gemm_tn::launch(g, EpiLstmPart{part, N, (size_t)M * N}, splits, stream);
+    if (e != hipSuccess) return e;
+    const size_t n = (size_t)Mr * Nr;
+    hipLaunchKernelGGL(lstm_sum_parts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, part, out,
+                       Mr, Nr, N, (size_t)M * N, splits, H);
+    return hipGetLastError();
+}
+
+hipError_t lstm_colsum(const LstmTrainLayout& W, char* ws, const float* A, int64_t ld, int N, int64_t rows,
+                       float* out, int Nr, int H, hipStream_t stream) {
+    float* part = (float*)(ws + W.off_cpart);
+    int splits = LSTM_WG_SPLITS;
+    while (splits > 1 && rows / splits < 64) splits >>= 1;
+    hipLaunchKernelGGL(lstm_colsum_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)splits), dim3(256), 0,
+                       stream, A, part, rows, N, ld);
+    hipLaunchKernelGGL(lstm_sum_parts_kernel, dim3((unsigned)((Nr + 255) / 256)), dim3(256), 0, stream, part, out,
+                       1, Nr, N, (size_t)N, splits, H);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" size_t drnmf_lstm_train_workspace_bytes(const drnmf_lstm_desc_t* d) {
+    if (!d || d->B <= 0 || d->T <= 0 || d->F <= 0 || d->H <= 0 || d->K <= 0) return 0;
+    return lstm_train_layout(d).total;
+}
+
+extern "C" int32_t drnmf_lstm_train_forward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x,
+                                            float mask_value, const void* params, float* h_out, int32_t ld_h,
+                                            void* workspace, size_t workspace_bytes, void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    LstmTrainLayout W;
+    int rc = validate_train_call(h, d, workspace, workspace_bytes, "lstm_train_forward", &W);
+    if (rc) return rc;
+    ++h->call_seq;
+    if (!x || !params || !h_out) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_train_forward: NULL pointer argument");
+    if (ld_h < d->H) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_train_forward: ld_h %d < H %d", ld_h, d->H);
+    if ((uintptr_t)params & 255) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "params must be 256-byte aligned");
+    const LstmLayout& L = W.L;
+    hipStream_t stream = (hipStream_t)stream_;
+    char* ws = (char*)workspace;
+    const char* pb = (const char*)params;
+    float* xz = (float*)(ws + W.off_xz);
+    unsigned char* valid = (unsigned char*)(ws + W.off_valid);
+    float* xproj = (float*)(ws + W.off_xproj);
+    float* hring = (float*)(ws + W.off_h);
+    float* cring = (float*)(ws + W.off_c);
+    int* ctr = (int*)(ws + W.off_ctr);
+    float* zst = (float*)(ws + W.off_z);
+    float* cst = (float*)(ws + W.off_cst);
+    float* hst = (float*)(ws + W.off_hst);
+
+    hipLaunchKernelGGL(lstm_pack_x_train_kernel, dim3((unsigned)((W.R1 + 3) / 4)), dim3(256), 0, stream, x, xz,
+                       valid, mask_value, W.R1, d->T, d->F, L.Fq);
+    const size_t nring = (size_t)d->K * 2 * L.Bp * L.Hc;
+    hipLaunchKernelGGL(lstm_init_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream, hring,
+                       cring, ctr, nring);
+    hipLaunchKernelGGL(lstm_stash_init_kernel, dim3((unsigned)(L.Bp + 1), (unsigned)d->K), dim3(256), 0, stream,
+                       zst, cst, hst, L.Bp, d->T, W.zk, W.RS, L.NC, L.Hc, L.Hq);
+    DRNMF_HIP(h, hipGetLastError());
+    {
+        gemm::Operands g;
+        g.A = xz;
+        g.Bt = (const float*)(pb + L.off_k0t);
+        g.M = (int64_t)W.R1;
+        g.N = L.NC;
+        g.K = L.Fq;
+        g.lda = g.ldb = L.Fq;
+        DRNMF_HIP(h, gemm::launch(g, EpiLstmXproj{xproj, (const float*)(pb + L.off_bias), L.NC}, stream));
+    }
+    LstmStepArgs base;
+    base.M = (const float*)pb;
+    base.bias = (const float*)(pb + L.off_bias);
+    base.xproj = xproj;
+    base.valid = valid;
+    base.hring = hring;
+    base.cring = cring;
+    base.out = h_out;
+    base.B = d->B; base.T = d->T; base.H = d->H; base.K = d->K;
+    base.Bp = L.Bp; base.Hc = L.Hc; base.numU = L.numU; base.NC = L.NC;
+    base.act = d->recurrent_activation;
+    base.ld_h = ld_h;
+    base.zst = zst; base.cst = cst; base.hst = hst; base.zk = W.zk; base.Hq = L.Hq;
+    const dim3 grid((unsigned)L.numU, (unsigned)(L.Bp / 16), (unsigned)d->K);
+    auto frame = [&](Launcher& chain, int) -> int32_t {      // two diagonals, as drnmf_lstm_forward
+        for (int p = 0; p < 2; ++p) {
+            LstmStepArgs a = base;
+            a.d_rd = ctr + 16 * p;
+            a.d_wr = ctr + 16 * (1 - p);
+            void* kp[1] = {&a};
+            DRNMF_HIP(h, chain.add((const void*)&lstm_step_kernel<true>, grid, dim3(64 * LSTM_NW), kp));
+        }
+        return DRNMF_OK;
+    };
+    const int diagonals = d->T + d->K - 1, frames = (diagonals + 1) / 2;
+    const int fpg = frames < 64 ? frames : 64;
+    const std::vector<uint64_t> key = {
+        (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->H, (uint64_t)d->K,
+        (uint64_t)d->recurrent_activation, (uint64_t)(uintptr_t)params, (uint64_t)(uintptr_t)h_out, (uint64_t)ld_h,
+        (uint64_t)(uintptr_t)workspace};
+    return replay_frames(h, stream, GraphKind::LstmTrain, key, {fpg, 1}, 0, frames, frame);
+}
+
+extern "C" int32_t drnmf_lstm_loss_head_backward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* y,
+                                                 const float* w, const float* hidden, int32_t ld_h,
+                                                 const void* params, const float* w_out, float* sums,
+                                                 float* d_hidden, float* d_w_out, float* d_b_out, void* workspace,
+                                                 size_t workspace_bytes, void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    LstmTrainLayout W;
+    int rc = validate_train_call(h, d, workspace, workspace_bytes, "lstm_loss_head_backward", &W);
+    if (rc) return rc;
+    if (!y || !w || !hidden || !params || !w_out || !sums || !d_hidden || !d_w_out || !d_b_out)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_loss_head_backward: NULL pointer argument");
+    if (ld_h < d->H) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_loss_head_backward: ld_h %d < H %d", ld_h, d->H);
+    if ((uintptr_t)params & 255) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "params must be 256-byte aligned");
+    const LstmLayout& L = W.L;
+    hipStream_t stream = (hipStream_t)stream_;
+    char* ws = (char*)workspace;
+    const char* pb = (const char*)params;
+    const int64_t rows = (int64_t)d->B * d->T;
+    float* S = (float*)(ws + W.off_s);
+    float* dpre = (float*)(ws + W.off_dpre);
+    float* wop = (float*)(ws + W.off_wop);
+    float* lpart = (float*)(ws + W.off_lpart);
+    {   // sigmoid head (as drnmf_lstm_head_forward)
+        gemm::Operands g;
+        g.A = hidden;
+        g.Bt = (const float*)(pb + L.off_wo);
+        g.M = rows;
+        g.N = d->F;
+        g.K = ld_h >= L.Hq ? L.Hq : d->H;
+        g.lda = ld_h;
+        g.ldb = L.Hq;
+        DRNMF_HIP(h, gemm::launch(g, EpiLstmHead{S, (const float*)(pb + L.off_bo), d->F}, stream));
+    }
+    const int64_t nblocks = (rows + 3) / 4;
+    hipLaunchKernelGGL(lstm_loss_rows_kernel, dim3((unsigned)nblocks), dim3(256), 0, stream,
+                       (const float*)(ws + W.off_xz), S, y, w, dpre, lpart, (size_t)rows, d->T, d->F, L.Fq);
+    hipLaunchKernelGGL(lstm_loss_final_kernel, dim3(1), dim3(256), 0, stream, lpart, nblocks, sums);
+    const size_t nw = (size_t)d->H * L.Fq;
+    hipLaunchKernelGGL(lstm_pad_wo_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, stream, w_out, wop,
+                       d->F, L.Fq, nw);
+    DRNMF_HIP(h, hipGetLastError());
+    {   // d_hidden [B T][H] = dpre . w_out^T
+        gemm::Operands g;
+        g.A = dpre;
+        g.Bt = wop;
+        g.M = rows;
+        g.N = d->H;
+        g.K = L.Fq;
+        g.lda = g.ldb = L.Fq;
+        DRNMF_HIP(h, gemm::launch(g, EpiLstmDh{d_hidden, d->H}, stream));
+    }
+    const int Mh = ld_h >= L.Hq ? L.Hq : d->H;
+    DRNMF_HIP(h, lstm_tn_product(W, ws, hidden, ld_h, Mh, dpre, L.Fq, L.Fq, rows, d_w_out, d->H, d->F, 0, stream));
+    DRNMF_HIP(h, lstm_colsum(W, ws, dpre, L.Fq, L.Fq, rows, d_b_out, d->F, 0, stream));
+    return DRNMF_OK;
+}
+
+extern "C" int32_t drnmf_lstm_backward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* const* kernel,
+                                       const float* const* recurrent, const float* d_hidden,
+                                       float* const* d_kernel, float* const* d_recurrent, float* const* d_bias,
+                                       void* workspace, size_t workspace_bytes, void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    LstmTrainLayout W;
+    int rc = validate_train_call(h, d, workspace, workspace_bytes, "lstm_backward", &W);
+    if (rc) return rc;
+    ++h->call_seq;
+    if (!kernel || !recurrent || !d_hidden || !d_kernel || !d_recurrent || !d_bias)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_backward: NULL pointer argument");
+    for (int k = 0; k < d->K; ++k)
+        if ((k > 0 && !kernel[k]) || !recurrent[k] || !d_kernel[k] || !d_recurrent[k] || !d_bias[k])
+            DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_backward: NULL pointer in the arrays (layer %d)", k);
+    const LstmLayout& L = W.L;
+    hipStream_t stream = (hipStream_t)stream_;
+    char* ws = (char*)workspace;
+    float* Mt = (float*)(ws + W.off_mt);
+    float* Z = (float*)(ws + W.off_z);
+    float* ph = (float*)(ws + W.off_ph);
+    float* pc = (float*)(ws + W.off_pc);
+    int* ctr = (int*)(ws + W.off_bctr);
+    const size_t layer_mt = (size_t)2 * L.NC * W.NBc;
+    for (int k = 0; k < d->K; ++k) {
+        const int rows = k < d->K - 1 ? 2 * L.NC : L.NC;
+        const size_t tot = (size_t)rows * W.NBc;
+        hipLaunchKernelGGL(lstm_pack_bwd_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream,
+                           k < d->K - 1 ? kernel[k + 1] : nullptr, recurrent[k], Mt + (size_t)k * layer_mt, d->H,
+                           L.NC, W.NB, rows);
+    }
+    const size_t nring = (size_t)d->K * 2 * L.Bp * W.NBc;
+    hipLaunchKernelGGL(lstm_bwd_init_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream, ph, pc,
+                       ctr, nring, d->T + d->K - 2);
+    DRNMF_HIP(h, hipGetLastError());
+
+    LstmBwdArgs base;
+    base.Mt = Mt;
+    base.Z = Z;
+    base.cst = (const float*)(ws + W.off_cst);
+    base.valid = (const unsigned char*)(ws + W.off_valid);
+    base.dh = d_hidden;
+    base.ph = ph;
+    base.pc = pc;
+    base.zk = W.zk;
+    base.B = d->B; base.T = d->T; base.H = d->H; base.K = d->K;
+    base.Bp = L.Bp; base.Hc = L.Hc; base.NB = W.NB; base.NC = L.NC;
+    base.act = d->recurrent_activation;
+    const dim3 grid((unsigned)W.NB, (unsigned)(L.Bp / 16), (unsigned)d->K);
+    // two diagonals per graph frame, the counter going DOWN (lstm_bwd_step_kernel writes d - 1)
+    auto frame = [&](Launcher& chain, int) -> int32_t {
+        for (int p = 0; p < 2; ++p) {
+            LstmBwdArgs a = base;
+            a.d_rd = ctr + 16 * p;
+            a.d_wr = ctr + 16 * (1 - p);
+            void* kp[1] = {&a};
+            DRNMF_HIP(h, chain.add((const void*)&lstm_bwd_step_kernel, grid, dim3(64 * LSTM_NW), kp));
+        }
+        return DRNMF_OK;
+    };
+    const int diagonals = d->T + d->K - 1, frames = (diagonals + 1) / 2;
+    const int fpg = frames < 64 ? frames : 64;
+    const std::vector<uint64_t> key = {
+        (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->H, (uint64_t)d->K,
+        (uint64_t)d->recurrent_activation, (uint64_t)(uintptr_t)d_hidden, (uint64_t)(uintptr_t)workspace};
+    rc = replay_frames(h, stream, GraphKind::LstmBackward, key, {fpg, 1}, 0, frames, frame);
+    if (rc) return rc;
+
+    // time-batched weight gradients, unnormalised sums, Keras layouts
+    const int64_t rows = (int64_t)d->B * (d->T + 1);
+    const int H4 = 4 * d->H;
+    const float* hst = (const float*)(ws + W.off_hst);
+    for (int k = 0; k < d->K; ++k) {
+        const float* Zk = Z + (size_t)k * W.zk * L.NC;
+        // recurrent_k: sum over rows of h_{k}[row]^T dz_k[row + 1]
+        DRNMF_HIP(h, lstm_tn_product(W, ws, hst + (size_t)k * W.RS * L.Hq, L.Hq, L.Hq, Zk + L.NC, L.NC, L.NC, rows,
+                                     d_recurrent[k], d->H, H4, d->H, stream));
+        if (k == 0)
+            DRNMF_HIP(h, lstm_tn_product(W, ws, (const float*)(ws + W.off_xz), L.Fq, L.Fq, Zk, L.NC, L.NC, rows,
+                                         d_kernel[0], d->F, H4, d->H, stream));
+        else
+            DRNMF_HIP(h, lstm_tn_product(W, ws, hst + (size_t)(k - 1) * W.RS * L.Hq, L.Hq, L.Hq, Zk, L.NC, L.NC,
+                                         rows, d_kernel[k], d->H, H4, d->H, stream));
+        DRNMF_HIP(h, lstm_colsum(W, ws, Zk, L.NC, L.NC, rows, d_bias[k], H4, d->H, stream));
+    }
     return DRNMF_OK;
 }

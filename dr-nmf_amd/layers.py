@@ -1235,6 +1235,341 @@ class _SequenceModel(object):
             self._host_pool_obj = None
 
 
+    # -- the model-independent half of the trainer (loss 'mse' with temporal sample weights + the fused Adam,
+    #    enhance.py:1040-1073, 1152-1157, 1260-1312).  A subclass's compile() sets up the flat gradient buffer
+    #    (self._flat, _mflat, _vflat, _train_items, _step_dev, ...) and supplies the hooks loss_and_grads,
+    #    _validation_sums and _after_step; regularizers default to none.
+    N_SCALARS = 4      # tail of the flat buffer: [sum w*mse, #frames with w != 0, #frames, fault]
+    PENDING_STEPS = 8  # optimiser steps whose reports may be outstanding before the host looks at one
+
+    def loss_and_grads(self, x, y, sample_weight, live=True):
+        raise NotImplementedError
+
+    def _validation_sums(self, x, y, w):
+        raise NotImplementedError
+
+    def _after_step(self):
+        pass
+
+    def _regularized_items(self):
+        return []
+
+    def _drop_stale_fault(self):
+        """Stream-ordered read-and-clear of the handle's fault word into a scratch, at the START of a
+        training / test / validation step: a fault raised by an EARLIER asynchronous call on this device
+        (model.forward, cell.call, ops.cell_forward -- whose caller is told by ops.check_status after its own
+        synchronisation, or not at all) must not be charged to this step, which would then be skipped, or
+        raised, on every rank.  The count of dropped words stays readable in `self._stale_faults`."""
+        sf = getattr(self, '_stale_faults', None)
+        if sf is None or sf.device != torch.device(self._device()):
+            sf = self._stale_faults = torch.zeros(1, dtype=torch.float32, device=self._device())
+        ops.status_take(sf)
+
+    def _set_scalars(self, x, live=True):
+        # tail of the flat buffer: [sum w*mse, count] were written by the loss head (_grad_targets), then
+        # rows and the fault word.  (A step that is not live -- fit() on a rank whose shard has run out
+        # replays a batch with zero weights -- contributes no rows either: 'rows' feeds p = count / rows of
+        # loss_norm='keras204', which must be the GLOBAL batch's, not inflated by the replay)
+        # (fill_, a kernel: `tensor[i] = python_float` is a BLOCKING host-to-device copy of a CPU scalar --
+        # one hidden hipMemcpyWithStream per step in rounds 1-3, profiles/r04g_step_hip_api_delta.txt)
+        self._flat[-2:-1].fill_(float(x.shape[0] * x.shape[1]) if live else 0.0)
+        self._flat[-1:].fill_(0.0)
+        # fault word: 1.0 if a persistent chain of THIS step's forward / BPTT gave up (stream-ordered
+        # read-and-clear of the handle's flag; all-reduced with the gradients, so that every rank skips
+        # the update and reports the step -- ADVICE r3)
+        ops.status_take(self._flat[-1:])
+
+    def _regularization_loss(self):
+        tot = 0.0
+        for _, p, l1, l2 in self._regularized_items():
+            tot += l1 * float(p.abs().sum()) + l2 * float((p * p).sum())
+        return tot
+
+    def _add_regularizers(self, scale):
+        """Adds d/dw [l1 |w| + l2 w^2] of every regularized weight to the flat gradient -- divided
+        by `scale`, the factor the optimiser step applies to the DATA gradient sums (the penalty is
+        not a sum over frames; it enters once, after the all-reduce) -- and returns the penalty
+        (Keras: total_loss = loss + sum of layer.losses)."""
+        tot = 0.0
+        for n, p, l1, l2 in self._regularized_items():
+            self._gview[n].add_((l1 * torch.sign(p) + (2.0 * l2) * p) / scale)
+            tot += l1 * float(p.abs().sum()) + l2 * float((p * p).sum())
+        return tot
+
+    def _adam_blocks(self):
+        """Block table of the fused Adam launch, rebuilt if a weight tensor has been re-bound."""
+        ptrs = tuple(int(t.data_ptr()) for _, t in self._train_items)
+        if self._adam_table is None or self._adam_table[2] != ptrs:
+            table, nb = ops.adam_block_table(self._train_items, self._device())
+            self._adam_table = (table, nb, ptrs)
+        return self._adam_table[0], self._adam_table[1]
+
+    def apply_gradients(self, flat):
+        """Adam step from the (already all-reduced) flat buffer [gradients..., sum w*mse, count, frames,
+        fault]: ONE launch (csrc/train.hip adam_flat_kernel) that derives 1/count, the keras204 factor and
+        the clip scale from device memory and skips the update if the fault word is set.  Nothing here
+        waits for the device; returns the normalised loss as a DeviceLoss (float() it to wait)."""
+        o = self.opt
+        ns = self.N_SCALARS
+        keras204 = getattr(self, 'loss_norm', 'masked_mean') == 'keras204'
+        reg_loss = 0.0
+        if self._regularized_items():
+            # free-weight configurations with W_/U_/b_regularizer only (never build_alt's): the penalty's
+            # gradient enters scaled by the step's data-gradient scale, which the host must then know
+            sse, cnt, rows = (float(v) for v in flat[-ns:-1].tolist())
+            scale = 1.0 / max(cnt, 1.0)
+            if keras204:
+                scale *= rows / max(cnt, 1.0)
+            reg_loss = self._add_regularizers(scale)     # (before the clip: Keras clips the total gradient)
+        if o['clipnorm'] > 0:                           # global-norm clip [K2.0.4-memory]
+            ops.sumsq_partials(flat[:-ns], out=self._sumsq)
+        table, nb = self._adam_blocks()
+        ring, base = ops.host_report_ring(self._device())
+        slot, register = _claim_report_slot(ops._dev_of(self._device()), ring.shape[0])
+        j = self._step_no & 1
+        self._step_no += 1
+        # (lr_t -- decay and bias correction -- is evaluated by the launch from the device's own count of applied
+        # steps: a host-side count, corrected whenever a fault report happened to be read, made the ranks of a
+        # data-parallel group pass different lr_t for a few steps after a skipped one; ADVICE r5)
+        ops.adam_step_flat_counted(table, nb, flat, self._mflat, self._vflat, flat[-ns:], o['lr'], o['decay'],
+                                   self._step_dev[j:j + 1], self._step_dev[1 - j:2 - j], beta1=o['b1'],
+                                   beta2=o['b2'], eps=o['eps'], clipnorm=o['clipnorm'], keras204=keras204,
+                                   reg_loss=reg_loss, sumsq256=self._sumsq if o['clipnorm'] > 0 else None,
+                                   report=base + 16 * slot)
+        ev = torch.cuda.Event()
+        ev.record()
+        # opt['iterations'] is the host's MIRROR of that count (get_config, logging): steps enqueued minus the
+        # skipped ones it has been told about so far; nothing on the device depends on it
+        def uncount(o=o):
+            o['iterations'] = max(0, o['iterations'] - 1)
+        loss = DeviceLoss(ev, ring[slot], self._device(), on_fault=uncount)
+        register(loss)
+        o['iterations'] += 1
+        # the fused Adam wrote the weights through raw pointers (torch's _version did not move): whatever the
+        # model prepared from them is stale
+        self._after_step()
+        # Reports are consumed at most PENDING_STEPS late: a fault is then raised from THIS call (the
+        # wait is for a step that finished long ago; it never drains the queue), and a ring slot is
+        # never reused before it was read.
+        self._pending.append(loss)
+        while len(self._pending) > self.PENDING_STEPS or (self._pending and self._pending[0].ready()):
+            old = self._pending.pop(0)
+            if old._error is None:       # (a fault its reader has already been told about is not raised again)
+                old._get()
+        return loss
+
+    def train_on_batch(self, x, y, sample_weight=None, _live=True):
+        """One optimiser step.  x, y: (B,T,F); sample_weight: (B,T) (the data mask,
+        enhance.py:1148-1152).  Under torch.distributed the flat gradient + (sum, count, frames, fault)
+        are all-reduced (RCCL) before the update, so every rank applies the same step.  Returns the
+        loss as a DeviceLoss: the call enqueues the step and returns without waiting for it (float()
+        the result, as Keras' train_on_batch would have, to wait)."""
+        from . import dp
+        dev = self._device()
+        tt = lambda a: a if isinstance(a, torch.Tensor) else \
+            torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        x, y = tt(x), tt(y)
+        if sample_weight is None:
+            sample_weight = torch.ones(x.shape[:2], dtype=torch.float32, device=dev)
+        flat = self.loss_and_grads(x, y, tt(sample_weight), live=_live)
+        dp.allreduce_sum_(flat)
+        return self.apply_gradients(flat)
+
+    def test_on_batch(self, x, y, sample_weight=None):
+        from . import dp
+        dev = self._device()
+        tt = lambda a: a if isinstance(a, torch.Tensor) else \
+            torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        x, y = tt(x), tt(y)
+        w = tt(sample_weight) if sample_weight is not None else \
+            torch.ones(x.shape[:2], dtype=torch.float32, device=dev)
+        s3 = torch.empty(4, dtype=torch.float32, device=dev)
+        self._drop_stale_fault()
+        s3[:2].copy_(self._validation_sums(x, y, w))
+        s3[2:3].fill_(float(x.shape[0] * x.shape[1]))      # (fill_: no blocking scalar copy)
+        s3[3:].fill_(0.0)
+        ops.status_take(s3[3:])                 # fault word of this forward, all-reduced with the sums
+        dp.allreduce_sum_(s3)
+        sse, cnt, rows, fault = s3.tolist()
+        if fault != 0.0:
+            raise _capi.DrnmfError('test_on_batch: a persistent small-shape chain timed out on at least '
+                                   'one rank (DRNMF_ERR_TIMEOUT); rerun, or set DRNMF_PERSIST=0')
+        scale = 1.0 / max(cnt, 1.0)
+        if getattr(self, 'loss_norm', 'masked_mean') == 'keras204':
+            scale *= rows / max(cnt, 1.0)
+        return sse * scale + (self._regularization_loss() if hasattr(self, '_train_items') else 0.0)
+
+    def fit(self, x, y, sample_weight=None, batch_size=32, epochs=1, validation_data=None,
+            shuffle=True, seed=7654, verbose=0, callbacks=None, resident_bytes=64 << 30):
+        """Minimal keras.Model.fit: shuffled mini-batches (np.random.seed(7654), enhance.py:7),
+        Keras-style callbacks (callbacks.py: on_train_begin / on_batch_end / on_epoch_end with
+        logs {'loss', 'val_loss'}; a callback may set model.stop_training), returns {'loss': [...],
+        'val_loss': [...]} per epoch.  Under torch.distributed every rank passes ITS shard of the
+        data; batches are all-reduced per step and the ranks take the same number of steps
+        (a rank with fewer batches joins the remaining reductions with zero weights).
+        Host (numpy) data sets of up to `resident_bytes` (64 GiB: the reference's whole CHiME2 training
+        tensors are ~6 GB, the GPU has 288 GB) are uploaded ONCE and mini-batches gathered on the
+        device -- a per-batch host-to-device copy of x and y costs ~1 ms of the 10-ms step of the
+        shipped r = 100 configuration; larger sets (or resident_bytes=0) are copied batch by batch as
+        Keras does."""
+        from . import dp
+        dev = self._device()
+        # what may stay resident: at most `resident_bytes` and at most half of the device memory that is
+        # free right now (ADVICE r3: workspaces, other tenants of the GPU); a failed upload falls back to
+        # per-batch copies
+        try:
+            free_now = int(torch.cuda.mem_get_info(dev)[0])
+        except Exception:
+            free_now = 0
+        budget = min(int(resident_bytes), free_now // 2)
+
+        def upload(arrays):
+            """Device copies of the numpy members of `arrays` (one copy per distinct array: the
+            pretraining model passes y = x) if they fit the budget, else None."""
+            nonlocal budget
+            uniq = {}
+            for a in arrays:
+                if isinstance(a, np.ndarray):
+                    uniq.setdefault(id(a), a)
+            need = sum(a.size * 4 for a in uniq.values())
+            if not uniq or need > budget:
+                return None
+            try:
+                dev_of = {k: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+                          for k, a in uniq.items()}
+            except torch.cuda.OutOfMemoryError:
+                torch.cuda.empty_cache()
+                return None
+            budget -= need
+            return [dev_of[id(a)] if isinstance(a, np.ndarray) else a for a in arrays]
+        up = upload([x, y, sample_weight])
+        if up is not None:
+            x, y, sample_weight = up
+        if validation_data is not None:
+            up = upload(list(validation_data))
+            if up is not None:
+                validation_data = tuple(up)
+        take = lambda a, b: a.index_select(0, torch.as_tensor(b, dtype=torch.long, device=a.device)) \
+            if isinstance(a, torch.Tensor) else a[b]
+        n = x.shape[0]
+        rng = np.random.RandomState(seed)
+        hist = {'loss': [], 'val_loss': []}
+        # file-writing callbacks (rank0_only: ModelCheckpoint, LossHistory) run on rank 0 only --
+        # every rank holds the same weights and logs; the others (EarlyStopping) run everywhere so
+        # that all ranks stop together
+        callbacks = [cb for cb in (callbacks or [])
+                     if dp.rank() == 0 or not getattr(cb, 'rank0_only', False)]
+        self.stop_training = False
+        for cb in callbacks:
+            if hasattr(cb, 'set_model'):
+                cb.set_model(self)
+            else:
+                cb.model = self
+            if hasattr(cb, 'on_train_begin'):
+                cb.on_train_begin({})
+        # a callback that looks at every batch's loss needs the number: the step then waits for it, as
+        # Keras does; without one the losses of an epoch are read when the epoch ends
+        per_batch_cbs = [cb for cb in callbacks if hasattr(cb, 'on_batch_end')]
+        # every train_on_batch is a collective: all ranks must take the same number of steps even
+        # when their shards differ in size (dp.shard hands the remainder to the first ranks)
+        steps = dp.max_over_ranks(epoch_steps(n, batch_size))
+        # an empty shard has no batch to replay with zero weights; every rank must learn of it HERE
+        # (one that raised alone would leave the others waiting in the first all-reduce)
+        if dp.max_over_ranks(1 if n == 0 else 0):
+            raise ValueError("fit(): a rank holds no sequences (%d here); give every rank at least "
+                             "one (dp.shard of fewer sequences than ranks?)" % n)
+        for ep in range(epochs):
+            for cb in callbacks:
+                if hasattr(cb, 'on_epoch_begin'):
+                    cb.on_epoch_begin(ep, {})
+            idx = rng.permutation(n) if shuffle else np.arange(n)
+            ep_losses, cnt = [], 0
+            for b, live in epoch_batches(idx, batch_size, steps):
+                sw = None if sample_weight is None else take(sample_weight, b)
+                if not live:
+                    # this rank has run out of data: it joins the all-reduce with zero weights
+                    # (zero gradient, zero count) on a batch it has already used
+                    sw = np.zeros((len(b), x.shape[1]), np.float32)
+                loss = self.train_on_batch(take(x, b), take(y, b), sw, _live=live)
+                ep_losses.append(loss)
+                for cb in per_batch_cbs:
+                    cb.on_batch_end(cnt, {'batch': cnt, 'size': len(b), 'loss': float(loss)})
+                cnt += 1
+            logs = {'loss': sum(float(l) for l in ep_losses) / max(cnt, 1)}
+            hist['loss'].append(logs['loss'])
+            if validation_data is not None:
+                logs['val_loss'] = self._validate(validation_data, batch_size, take)
+                hist['val_loss'].append(logs['val_loss'])
+            if verbose and dp.rank() == 0:
+                print('epoch %d loss %.6f%s' % (ep + 1, logs['loss'],
+                      (' val_loss %.6f' % logs['val_loss']) if validation_data else ''))
+            for cb in callbacks:
+                if hasattr(cb, 'on_epoch_end'):
+                    cb.on_epoch_end(ep, logs)
+            if self.stop_training:
+                break
+        for cb in callbacks:
+            if hasattr(cb, 'on_train_end'):
+                cb.on_train_end({})
+        return hist
+
+
+    def _validate(self, validation_data, batch_size, take):
+        """Validation loss of fit(), evaluated in mini-batches of `batch_size` sequences as Keras'
+        test loop does (enhance.py:1152-1157: model.fit(..., validation_data=...)); the reference's
+        2 460-utterance CHiME2 validation set at N = 2000 would otherwise need a ~40 GB hidden tensor.
+        The sums [sum w*loss, count, frames, fault] are accumulated on the device over the batches and
+        all-reduced ONCE (every rank holds its shard), so the value is the loss of the whole set."""
+        from . import dp
+        dev = self._device()
+        tt = lambda a: a if isinstance(a, torch.Tensor) else \
+            torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        xv, yv = validation_data[0], validation_data[1]
+        wv = validation_data[2] if len(validation_data) > 2 else None
+        nv, Tv = xv.shape[0], xv.shape[1]
+        s4 = torch.zeros(4, dtype=torch.float32, device=dev)
+        self._drop_stale_fault()
+        # Length-aware, as predict(): a frame behind a sequence's last non-zero weight adds nothing to either
+        # sum (the reference's sample weights are the data mask, enhance.py:1148-1152) and nothing to the
+        # frames before it, so the sequences are taken in order of that length and every mini-batch runs at the
+        # longest one IN IT (rounded up to PREDICT_T_STEP frames).  The same terms are summed; only their
+        # grouping into mini-batches -- fp32 partial sums -- differs from the input-order pass.
+        order, lens = np.arange(nv), None
+        if wv is not None and not self._stateful() and Tv > self.PREDICT_T_STEP:
+            key = (id(wv), tuple(wv.shape))
+            cached = getattr(self, '_val_lens', None)
+            if cached is None or cached[0] != key:
+                wt = wv if isinstance(wv, torch.Tensor) else torch.from_numpy(np.asarray(wv))
+                pos = torch.arange(1, Tv + 1, device=wt.device).unsqueeze(0)
+                cached = (key, ((wt != 0) * pos).amax(dim=1).cpu().numpy())
+                self._val_lens = cached
+            lens = cached[1]
+            order = np.argsort(-lens, kind='stable')
+        for lo in range(0, nv, int(batch_size)):
+            b = order[lo:min(nv, lo + int(batch_size))]
+            Tb = Tv
+            if lens is not None:
+                step = self.PREDICT_T_STEP
+                Tb = int(min(Tv, max(1, -(-int(lens[b].max()) // step) * step)))
+            cut = (lambda a: a) if Tb == Tv else (lambda a: a[:, :Tb].contiguous() if isinstance(a, torch.Tensor)
+                                                  else np.ascontiguousarray(a[:, :Tb]))
+            xb, yb = tt(cut(take(xv, b))), tt(cut(take(yv, b)))
+            wb = tt(cut(take(wv, b))) if wv is not None else \
+                torch.ones(xb.shape[:2], dtype=torch.float32, device=dev)
+            s4[:2].add_(self._validation_sums(xb, yb, wb))
+            s4[2] += float(len(b) * Tv)          # (frames of the PADDED batch: loss_norm='keras204' divides by them)
+        ops.status_take(s4[3:])
+        dp.allreduce_sum_(s4)
+        sse, cnt, rows, fault = s4.tolist()
+        if fault != 0.0:
+            raise _capi.DrnmfError('fit(): a persistent small-shape chain timed out during validation on '
+                                   'at least one rank (DRNMF_ERR_TIMEOUT); rerun, or set DRNMF_PERSIST=0')
+        scale = 1.0 / max(cnt, 1.0)
+        if getattr(self, 'loss_norm', 'masked_mean') == 'keras204':
+            scale *= rows / max(cnt, 1.0)
+        return sse * scale + (self._regularization_loss() if hasattr(self, '_train_items') else 0.0)
+
+
 class UnfoldedSNMFModel(_SequenceModel):
     """Masking -> SimpleDeepRNN -> [:r]/[r:] -> DenseNonNegW x2 -> (square) -> A/(A+B).
     Exposes the slice of keras.Model that enhance.py uses: layers, get/set_weights,
@@ -1280,8 +1615,6 @@ class UnfoldedSNMFModel(_SequenceModel):
     __call__ = forward
 
     # -- training: loss 'mse_of_masked' + Adam (enhance.py:1040-1073, 1152) -----------------
-    N_SCALARS = 4      # tail of the flat buffer: [sum w*mse, #frames with w != 0, #frames, fault]
-    PENDING_STEPS = 8  # optimiser steps whose reports may be outstanding before the host looks at one
 
     def compile(self, loss='mse', optimizer='adam', lr=1e-3, clipnorm=0., decay=0., beta_1=0.9,
                 beta_2=0.999, epsilon=1e-8, sample_weight_mode='temporal',
@@ -1452,31 +1785,6 @@ class UnfoldedSNMFModel(_SequenceModel):
         self._set_scalars(x, live)
         return self._flat
 
-    def _drop_stale_fault(self):
-        """Stream-ordered read-and-clear of the handle's fault word into a scratch, at the START of a
-        training / test / validation step: a fault raised by an EARLIER asynchronous call on this device
-        (model.forward, cell.call, ops.cell_forward -- whose caller is told by ops.check_status after its own
-        synchronisation, or not at all) must not be charged to this step, which would then be skipped, or
-        raised, on every rank.  The count of dropped words stays readable in `self._stale_faults`."""
-        sf = getattr(self, '_stale_faults', None)
-        if sf is None or sf.device != torch.device(self.cell.device):
-            sf = self._stale_faults = torch.zeros(1, dtype=torch.float32, device=self.cell.device)
-        ops.status_take(sf)
-
-    def _set_scalars(self, x, live=True):
-        # tail of the flat buffer: [sum w*mse, count] were written by the loss head (_grad_targets), then
-        # rows and the fault word.  (A step that is not live -- fit() on a rank whose shard has run out
-        # replays a batch with zero weights -- contributes no rows either: 'rows' feeds p = count / rows of
-        # loss_norm='keras204', which must be the GLOBAL batch's, not inflated by the replay)
-        # (fill_, a kernel: `tensor[i] = python_float` is a BLOCKING host-to-device copy of a CPU scalar --
-        # one hidden hipMemcpyWithStream per step in rounds 1-3, profiles/r04g_step_hip_api_delta.txt)
-        self._flat[-2:-1].fill_(float(x.shape[0] * x.shape[1]) if live else 0.0)
-        self._flat[-1:].fill_(0.0)
-        # fault word: 1.0 if a persistent chain of THIS step's forward / BPTT gave up (stream-ordered
-        # read-and-clear of the handle's flag; all-reduced with the gradients, so that every rank skips
-        # the update and reports the step -- ADVICE r3)
-        ops.status_take(self._flat[-1:])
-
     @staticmethod
     def _reg_coeffs(reg):
         """(l1, l2) of a Keras-style regularizer: an object with .l1 / .l2 (keras.regularizers.L1L2),
@@ -1501,72 +1809,7 @@ class UnfoldedSNMFModel(_SequenceModel):
                     out.append((n, p, l1, l2))
         return out
 
-    def _regularization_loss(self):
-        tot = 0.0
-        for _, p, l1, l2 in self._regularized_items():
-            tot += l1 * float(p.abs().sum()) + l2 * float((p * p).sum())
-        return tot
-
-    def _add_regularizers(self, scale):
-        """Adds d/dw [l1 |w| + l2 w^2] of every regularized weight to the flat gradient -- divided
-        by `scale`, the factor the optimiser step applies to the DATA gradient sums (the penalty is
-        not a sum over frames; it enters once, after the all-reduce) -- and returns the penalty
-        (Keras: total_loss = loss + sum of layer.losses)."""
-        tot = 0.0
-        for n, p, l1, l2 in self._regularized_items():
-            self._gview[n].add_((l1 * torch.sign(p) + (2.0 * l2) * p) / scale)
-            tot += l1 * float(p.abs().sum()) + l2 * float((p * p).sum())
-        return tot
-
-    def _adam_blocks(self):
-        """Block table of the fused Adam launch, rebuilt if a weight tensor has been re-bound."""
-        ptrs = tuple(int(t.data_ptr()) for _, t in self._train_items)
-        if self._adam_table is None or self._adam_table[2] != ptrs:
-            table, nb = ops.adam_block_table(self._train_items, self.cell.device)
-            self._adam_table = (table, nb, ptrs)
-        return self._adam_table[0], self._adam_table[1]
-
-    def apply_gradients(self, flat):
-        """Adam step from the (already all-reduced) flat buffer [gradients..., sum w*mse, count, frames,
-        fault]: ONE launch (csrc/train.hip adam_flat_kernel) that derives 1/count, the keras204 factor and
-        the clip scale from device memory and skips the update if the fault word is set.  Nothing here
-        waits for the device; returns the normalised loss as a DeviceLoss (float() it to wait)."""
-        o = self.opt
-        ns = self.N_SCALARS
-        keras204 = getattr(self, 'loss_norm', 'masked_mean') == 'keras204'
-        reg_loss = 0.0
-        if self._regularized_items():
-            # free-weight configurations with W_/U_/b_regularizer only (never build_alt's): the penalty's
-            # gradient enters scaled by the step's data-gradient scale, which the host must then know
-            sse, cnt, rows = (float(v) for v in flat[-ns:-1].tolist())
-            scale = 1.0 / max(cnt, 1.0)
-            if keras204:
-                scale *= rows / max(cnt, 1.0)
-            reg_loss = self._add_regularizers(scale)     # (before the clip: Keras clips the total gradient)
-        if o['clipnorm'] > 0:                           # global-norm clip [K2.0.4-memory]
-            ops.sumsq_partials(flat[:-ns], out=self._sumsq)
-        table, nb = self._adam_blocks()
-        ring, base = ops.host_report_ring(self.cell.device)
-        slot, register = _claim_report_slot(ops._dev_of(self.cell.device), ring.shape[0])
-        j = self._step_no & 1
-        self._step_no += 1
-        # (lr_t -- decay and bias correction -- is evaluated by the launch from the device's own count of applied
-        # steps: a host-side count, corrected whenever a fault report happened to be read, made the ranks of a
-        # data-parallel group pass different lr_t for a few steps after a skipped one; ADVICE r5)
-        ops.adam_step_flat_counted(table, nb, flat, self._mflat, self._vflat, flat[-ns:], o['lr'], o['decay'],
-                                   self._step_dev[j:j + 1], self._step_dev[1 - j:2 - j], beta1=o['b1'],
-                                   beta2=o['b2'], eps=o['eps'], clipnorm=o['clipnorm'], keras204=keras204,
-                                   reg_loss=reg_loss, sumsq256=self._sumsq if o['clipnorm'] > 0 else None,
-                                   report=base + 16 * slot)
-        ev = torch.cuda.Event()
-        ev.record()
-        # opt['iterations'] is the host's MIRROR of that count (get_config, logging): steps enqueued minus the
-        # skipped ones it has been told about so far; nothing on the device depends on it
-        def uncount(o=o):
-            o['iterations'] = max(0, o['iterations'] - 1)
-        loss = DeviceLoss(ev, ring[slot], self.cell.device, on_fault=uncount)
-        register(loss)
-        o['iterations'] += 1
+    def _after_step(self):
         # the prepared parameter block is stale; the (u0_diag, u0_off, uk_off) scalars are derived
         # from log_U1 / log_Uk, which compile() refuses to train: re-deriving them here would cost
         # two N x N device-to-host copies and a host pass per step
@@ -1576,229 +1819,10 @@ class UnfoldedSNMFModel(_SequenceModel):
             # round trip to re-examine U's structure after every step)
             self.cell._dense_now = True
             self.cell._dense_block_valid = False
-        # Reports are consumed at most PENDING_STEPS late: a fault is then raised from THIS call (the
-        # wait is for a step that finished long ago; it never drains the queue), and a ring slot is
-        # never reused before it was read.
-        self._pending.append(loss)
-        while len(self._pending) > self.PENDING_STEPS or (self._pending and self._pending[0].ready()):
-            old = self._pending.pop(0)
-            if old._error is None:       # (a fault its reader has already been told about is not raised again)
-                old._get()
-        return loss
-
-    def train_on_batch(self, x, y, sample_weight=None, _live=True):
-        """One optimiser step.  x, y: (B,T,F); sample_weight: (B,T) (the data mask,
-        enhance.py:1148-1152).  Under torch.distributed the flat gradient + (sum, count, frames, fault)
-        are all-reduced (RCCL) before the update, so every rank applies the same step.  Returns the
-        loss as a DeviceLoss: the call enqueues the step and returns without waiting for it (float()
-        the result, as Keras' train_on_batch would have, to wait)."""
-        from . import dp
-        dev = self.cell.device
-        tt = lambda a: a if isinstance(a, torch.Tensor) else \
-            torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-        x, y = tt(x), tt(y)
-        if sample_weight is None:
-            sample_weight = torch.ones(x.shape[:2], dtype=torch.float32, device=dev)
-        flat = self.loss_and_grads(x, y, tt(sample_weight), live=_live)
-        dp.allreduce_sum_(flat)
-        return self.apply_gradients(flat)
-
-    def test_on_batch(self, x, y, sample_weight=None):
-        from . import dp
-        dev = self.cell.device
-        tt = lambda a: a if isinstance(a, torch.Tensor) else \
-            torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-        x, y = tt(x), tt(y)
-        w = tt(sample_weight) if sample_weight is not None else \
-            torch.ones(x.shape[:2], dtype=torch.float32, device=dev)
-        s3 = torch.empty(4, dtype=torch.float32, device=dev)
-        self._drop_stale_fault()
-        s3[:2].copy_(ops.loss_forward(y, w, x_raw=x, mask=self.forward(x)))
-        s3[2:3].fill_(float(x.shape[0] * x.shape[1]))      # (fill_: no blocking scalar copy)
-        s3[3:].fill_(0.0)
-        ops.status_take(s3[3:])                 # fault word of this forward, all-reduced with the sums
-        dp.allreduce_sum_(s3)
-        sse, cnt, rows, fault = s3.tolist()
-        if fault != 0.0:
-            raise _capi.DrnmfError('test_on_batch: a persistent small-shape chain timed out on at least '
-                                   'one rank (DRNMF_ERR_TIMEOUT); rerun, or set DRNMF_PERSIST=0')
-        scale = 1.0 / max(cnt, 1.0)
-        if getattr(self, 'loss_norm', 'masked_mean') == 'keras204':
-            scale *= rows / max(cnt, 1.0)
-        return sse * scale + (self._regularization_loss() if hasattr(self, '_train_items') else 0.0)
-
-    def fit(self, x, y, sample_weight=None, batch_size=32, epochs=1, validation_data=None,
-            shuffle=True, seed=7654, verbose=0, callbacks=None, resident_bytes=64 << 30):
-        """Minimal keras.Model.fit: shuffled mini-batches (np.random.seed(7654), enhance.py:7),
-        Keras-style callbacks (callbacks.py: on_train_begin / on_batch_end / on_epoch_end with
-        logs {'loss', 'val_loss'}; a callback may set model.stop_training), returns {'loss': [...],
-        'val_loss': [...]} per epoch.  Under torch.distributed every rank passes ITS shard of the
-        data; batches are all-reduced per step and the ranks take the same number of steps
-        (a rank with fewer batches joins the remaining reductions with zero weights).
-        Host (numpy) data sets of up to `resident_bytes` (64 GiB: the reference's whole CHiME2 training
-        tensors are ~6 GB, the GPU has 288 GB) are uploaded ONCE and mini-batches gathered on the
-        device -- a per-batch host-to-device copy of x and y costs ~1 ms of the 10-ms step of the
-        shipped r = 100 configuration; larger sets (or resident_bytes=0) are copied batch by batch as
-        Keras does."""
-        from . import dp
-        dev = self.cell.device
-        # what may stay resident: at most `resident_bytes` and at most half of the device memory that is
-        # free right now (ADVICE r3: workspaces, other tenants of the GPU); a failed upload falls back to
-        # per-batch copies
-        try:
-            free_now = int(torch.cuda.mem_get_info(dev)[0])
-        except Exception:
-            free_now = 0
-        budget = min(int(resident_bytes), free_now // 2)
-
-        def upload(arrays):
-            """Device copies of the numpy members of `arrays` (one copy per distinct array: the
-            pretraining model passes y = x) if they fit the budget, else None."""
-            nonlocal budget
-            uniq = {}
-            for a in arrays:
-                if isinstance(a, np.ndarray):
-                    uniq.setdefault(id(a), a)
-            need = sum(a.size * 4 for a in uniq.values())
-            if not uniq or need > budget:
-                return None
-            try:
-                dev_of = {k: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-                          for k, a in uniq.items()}
-            except torch.cuda.OutOfMemoryError:
-                torch.cuda.empty_cache()
-                return None
-            budget -= need
-            return [dev_of[id(a)] if isinstance(a, np.ndarray) else a for a in arrays]
-        up = upload([x, y, sample_weight])
-        if up is not None:
-            x, y, sample_weight = up
-        if validation_data is not None:
-            up = upload(list(validation_data))
-            if up is not None:
-                validation_data = tuple(up)
-        take = lambda a, b: a.index_select(0, torch.as_tensor(b, dtype=torch.long, device=a.device)) \
-            if isinstance(a, torch.Tensor) else a[b]
-        n = x.shape[0]
-        rng = np.random.RandomState(seed)
-        hist = {'loss': [], 'val_loss': []}
-        # file-writing callbacks (rank0_only: ModelCheckpoint, LossHistory) run on rank 0 only --
-        # every rank holds the same weights and logs; the others (EarlyStopping) run everywhere so
-        # that all ranks stop together
-        callbacks = [cb for cb in (callbacks or [])
-                     if dp.rank() == 0 or not getattr(cb, 'rank0_only', False)]
-        self.stop_training = False
-        for cb in callbacks:
-            if hasattr(cb, 'set_model'):
-                cb.set_model(self)
-            else:
-                cb.model = self
-            if hasattr(cb, 'on_train_begin'):
-                cb.on_train_begin({})
-        # a callback that looks at every batch's loss needs the number: the step then waits for it, as
-        # Keras does; without one the losses of an epoch are read when the epoch ends
-        per_batch_cbs = [cb for cb in callbacks if hasattr(cb, 'on_batch_end')]
-        # every train_on_batch is a collective: all ranks must take the same number of steps even
-        # when their shards differ in size (dp.shard hands the remainder to the first ranks)
-        steps = dp.max_over_ranks(epoch_steps(n, batch_size))
-        # an empty shard has no batch to replay with zero weights; every rank must learn of it HERE
-        # (one that raised alone would leave the others waiting in the first all-reduce)
-        if dp.max_over_ranks(1 if n == 0 else 0):
-            raise ValueError("fit(): a rank holds no sequences (%d here); give every rank at least "
-                             "one (dp.shard of fewer sequences than ranks?)" % n)
-        for ep in range(epochs):
-            for cb in callbacks:
-                if hasattr(cb, 'on_epoch_begin'):
-                    cb.on_epoch_begin(ep, {})
-            idx = rng.permutation(n) if shuffle else np.arange(n)
-            ep_losses, cnt = [], 0
-            for b, live in epoch_batches(idx, batch_size, steps):
-                sw = None if sample_weight is None else take(sample_weight, b)
-                if not live:
-                    # this rank has run out of data: it joins the all-reduce with zero weights
-                    # (zero gradient, zero count) on a batch it has already used
-                    sw = np.zeros((len(b), x.shape[1]), np.float32)
-                loss = self.train_on_batch(take(x, b), take(y, b), sw, _live=live)
-                ep_losses.append(loss)
-                for cb in per_batch_cbs:
-                    cb.on_batch_end(cnt, {'batch': cnt, 'size': len(b), 'loss': float(loss)})
-                cnt += 1
-            logs = {'loss': sum(float(l) for l in ep_losses) / max(cnt, 1)}
-            hist['loss'].append(logs['loss'])
-            if validation_data is not None:
-                logs['val_loss'] = self._validate(validation_data, batch_size, take)
-                hist['val_loss'].append(logs['val_loss'])
-            if verbose and dp.rank() == 0:
-                print('epoch %d loss %.6f%s' % (ep + 1, logs['loss'],
-                      (' val_loss %.6f' % logs['val_loss']) if validation_data else ''))
-            for cb in callbacks:
-                if hasattr(cb, 'on_epoch_end'):
-                    cb.on_epoch_end(ep, logs)
-            if self.stop_training:
-                break
-        for cb in callbacks:
-            if hasattr(cb, 'on_train_end'):
-                cb.on_train_end({})
-        return hist
 
     def _validation_sums(self, x, y, w):
         """[sum w*loss, #frames with w != 0] of one validation batch as a device tensor of 2 floats."""
         return ops.loss_forward(y, w, x_raw=x, mask=self.forward(x))
-
-    def _validate(self, validation_data, batch_size, take):
-        """Validation loss of fit(), evaluated in mini-batches of `batch_size` sequences as Keras'
-        test loop does (enhance.py:1152-1157: model.fit(..., validation_data=...)); the reference's
-        2 460-utterance CHiME2 validation set at N = 2000 would otherwise need a ~40 GB hidden tensor.
-        The sums [sum w*loss, count, frames, fault] are accumulated on the device over the batches and
-        all-reduced ONCE (every rank holds its shard), so the value is the loss of the whole set."""
-        from . import dp
-        dev = self.cell.device
-        tt = lambda a: a if isinstance(a, torch.Tensor) else \
-            torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-        xv, yv = validation_data[0], validation_data[1]
-        wv = validation_data[2] if len(validation_data) > 2 else None
-        nv, Tv = xv.shape[0], xv.shape[1]
-        s4 = torch.zeros(4, dtype=torch.float32, device=dev)
-        self._drop_stale_fault()
-        # Length-aware, as predict(): a frame behind a sequence's last non-zero weight adds nothing to either
-        # sum (the reference's sample weights are the data mask, enhance.py:1148-1152) and nothing to the
-        # frames before it, so the sequences are taken in order of that length and every mini-batch runs at the
-        # longest one IN IT (rounded up to PREDICT_T_STEP frames).  The same terms are summed; only their
-        # grouping into mini-batches -- fp32 partial sums -- differs from the input-order pass.
-        order, lens = np.arange(nv), None
-        if wv is not None and not bool(getattr(self.cell, 'stateful', False)) and Tv > self.PREDICT_T_STEP:
-            key = (id(wv), tuple(wv.shape))
-            cached = getattr(self, '_val_lens', None)
-            if cached is None or cached[0] != key:
-                wt = wv if isinstance(wv, torch.Tensor) else torch.from_numpy(np.asarray(wv))
-                pos = torch.arange(1, Tv + 1, device=wt.device).unsqueeze(0)
-                cached = (key, ((wt != 0) * pos).amax(dim=1).cpu().numpy())
-                self._val_lens = cached
-            lens = cached[1]
-            order = np.argsort(-lens, kind='stable')
-        for lo in range(0, nv, int(batch_size)):
-            b = order[lo:min(nv, lo + int(batch_size))]
-            Tb = Tv
-            if lens is not None:
-                step = self.PREDICT_T_STEP
-                Tb = int(min(Tv, max(1, -(-int(lens[b].max()) // step) * step)))
-            cut = (lambda a: a) if Tb == Tv else (lambda a: a[:, :Tb].contiguous() if isinstance(a, torch.Tensor)
-                                                  else np.ascontiguousarray(a[:, :Tb]))
-            xb, yb = tt(cut(take(xv, b))), tt(cut(take(yv, b)))
-            wb = tt(cut(take(wv, b))) if wv is not None else \
-                torch.ones(xb.shape[:2], dtype=torch.float32, device=dev)
-            s4[:2].add_(self._validation_sums(xb, yb, wb))
-            s4[2] += float(len(b) * Tv)          # (frames of the PADDED batch: loss_norm='keras204' divides by them)
-        ops.status_take(s4[3:])
-        dp.allreduce_sum_(s4)
-        sse, cnt, rows, fault = s4.tolist()
-        if fault != 0.0:
-            raise _capi.DrnmfError('fit(): a persistent small-shape chain timed out during validation on '
-                                   'at least one rank (DRNMF_ERR_TIMEOUT); rerun, or set DRNMF_PERSIST=0')
-        scale = 1.0 / max(cnt, 1.0)
-        if getattr(self, 'loss_norm', 'masked_mean') == 'keras204':
-            scale *= rows / max(cnt, 1.0)
-        return sse * scale + (self._regularization_loss() if hasattr(self, '_train_items') else 0.0)
 
 
 def epoch_steps(n_local, batch_size):
@@ -2132,9 +2156,109 @@ class LSTMModel(_SequenceModel):
     def _output_width(self):
         return self.dense.units
 
-    def compile(self, *args, **kwargs):
-        raise NotImplementedError('LSTMModel: training (compile / fit / train_on_batch) is not implemented; '
-                                  'the LSTM baseline runs inference only')
+    # -- training (enhance.py:1260-1312): loss 'mse_of_masked' = mse(Masking output * sigmoid output, y) with
+    #    temporal sample weights, Adam; the trainer itself is _SequenceModel's ------------------------------------
+    def compile(self, loss='mse', optimizer='adam', lr=1e-3, clipnorm=0., decay=0., beta_1=0.9,
+                beta_2=0.999, epsilon=1e-8, sample_weight_mode='temporal', loss_norm='masked_mean'):
+        """model.compile(loss='mse', optimizer=Adam(lr, clipnorm, decay), sample_weight_mode='temporal') on
+        output_masked = Masking output * sigmoid output; same arguments and refusals as
+        UnfoldedSNMFModel.compile.  The gradients come from csrc/lstm.hip (training forward, loss head, BPTT);
+        there is no host fallback, so a model whose device is not a GPU cannot be trained."""
+        if self.device.type != 'cuda':
+            raise NotImplementedError('LSTMModel: training runs on the GPU kernels only (device %s)' % self.device)
+        if loss != 'mse' or optimizer != 'adam' or sample_weight_mode != 'temporal':
+            raise NotImplementedError("only loss='mse', optimizer='adam', temporal sample weights "
+                                      "(the reference's training configuration)")
+        if loss_norm not in ('masked_mean', 'keras204'):
+            raise ValueError("loss_norm must be 'masked_mean' or 'keras204'")
+        self.loss_norm = loss_norm
+        self.opt = dict(lr=float(lr), clipnorm=float(clipnorm), decay=float(decay),
+                        b1=float(beta_1), b2=float(beta_2), eps=float(epsilon), iterations=0)
+        self._train_items = self.flat_layout_items()
+        total = sum(int(t.numel()) for _, t in self._train_items)
+        dev = self.device
+        # the kernels write their gradients straight into views of the flat buffer (Keras weight order, then the
+        # 4-float tail [sum w*mse, count, frames, fault])
+        self._flat = torch.zeros(total + self.N_SCALARS, dtype=torch.float32, device=dev)
+        self._mflat = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._vflat = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._gview, self._opt_state, o = {}, {}, 0
+        for n, t in self._train_items:
+            self._gview[n] = self._flat[o:o + t.numel()].view(t.shape)
+            self._opt_state[n] = (self._mflat[o:o + t.numel()].view(t.shape),
+                                  self._vflat[o:o + t.numel()].view(t.shape))
+            o += t.numel()
+        self._adam_table = None
+        self._sumsq = torch.zeros(256, dtype=torch.float32, device=dev)
+        self._pending = []
+        self._step_no = 0
+        self._step_dev = torch.zeros((2,), dtype=torch.float32, device=dev)
+        self._train_ws = None
+        self._d_hidden = None
+        self.sync_replicas()
+        return self
+
+    def flat_layout_items(self):
+        """[(name, weight tensor)] in flat-buffer order = Keras weight order: per LSTM layer kernel,
+        recurrent_kernel, bias; then the Dense kernel and bias (names as in the weight files)."""
+        items = []
+        for l in self.lstms:
+            items += list(zip(l.weight_names, l.weights))
+        items += list(zip(self.dense.weight_names, self.dense.weights))
+        return items
+
+    def sync_replicas(self, root=0):
+        """Data parallelism: rank `root`'s weights everywhere (one broadcast); no-op for a single rank."""
+        from . import dp
+        if dp.world_size() <= 1:
+            return
+        ws = self.weights
+        flat = torch.cat([w.reshape(-1) for w in ws]).contiguous()
+        dp.broadcast_(flat, root)
+        o = 0
+        for w in ws:
+            w.copy_(flat[o:o + w.numel()].view(w.shape))
+            o += w.numel()
+        self._prepared = None
+
+    def loss_and_grads(self, x, y, sample_weight, live=True):
+        """Unnormalised loss and gradients of one (local) batch into the flat buffer, which is returned:
+        training forward, loss head + its backward, BPTT with the weight gradients -- all on the device."""
+        if not hasattr(self, '_flat'):
+            raise RuntimeError('LSTMModel: compile() before training')
+        self._drop_stale_fault()
+        x = x.float().contiguous()
+        B, T = int(x.shape[0]), int(x.shape[1])
+        desc = self._desc(B, T)
+        params = self._params(desc)
+        need = _capi.lib().drnmf_lstm_train_workspace_bytes(ctypes.byref(desc))
+        if self._train_ws is None or self._train_ws.numel() < need:
+            self._train_ws = None
+            self._train_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if self._d_hidden is None or tuple(self._d_hidden.shape) != (B, T, desc.H):
+            self._d_hidden = torch.empty((B, T, desc.H), dtype=torch.float32, device=self.device)
+        ws, gv, ns = self._train_ws, self._gview, self.N_SCALARS
+        h = ops.lstm_train_forward(x, self.mask_value, params, desc, ws)
+        d = self.dense
+        ops.lstm_loss_head_backward(y, sample_weight, h, params, d.kernel, desc, ws, self._flat[-ns:-ns + 2],
+                                    self._d_hidden, gv[d.weight_names[0]], gv[d.weight_names[1]])
+        ls = self.lstms
+        ops.lstm_backward([l.kernel for l in ls], [l.recurrent_kernel for l in ls], self._d_hidden,
+                          [gv[l.weight_names[0]] for l in ls], [gv[l.weight_names[1]] for l in ls],
+                          [gv[l.weight_names[2]] for l in ls], desc, ws)
+        self._set_scalars(x, live)
+        return self._flat
+
+    def _after_step(self):
+        self._prepared = None       # Adam moved the weights behind torch's back: repack before the next use
+
+    def _validation_sums(self, x, y, w):
+        """[sum w * mean_F (xm * s - y)^2, #frames with w != 0]: xm = the Masking layer's output (x with masked
+        frames zeroed), as the training loss."""
+        x = x.float().contiguous()
+        xm = x if self.mask_value is None else \
+            torch.where((x != self.mask_value).any(dim=-1, keepdim=True), x, torch.zeros_like(x))
+        return ops.loss_forward(y, w, x_raw=xm, mask=self.forward(x))
 
     def _desc(self, B, T):
         l0 = self.lstms[0]

@@ -1084,3 +1084,77 @@ def lstm_head_forward(hidden, params, desc, out=None):
                                    _stream())
     _capi.check(rc, h, "drnmf_lstm_head_forward")
     return out
+
+
+# ---- LSTM training (include/drnmf_lstm.h: drnmf_lstm_train_* / loss_head_backward / backward) ------------------
+def lstm_train_workspace(desc, device):
+    """The workspace the three training calls share (its size grows with B and T)."""
+    nbytes = _capi.lib().drnmf_lstm_train_workspace_bytes(C.byref(desc))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def lstm_train_forward(x, mask_value, params, desc, workspace, out=None):
+    """lstm_forward (the same hidden states, bit for bit) that also keeps in `workspace` what
+    lstm_loss_head_backward and lstm_backward need."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(x))
+    x = _f32c(x, "x")
+    if tuple(x.shape) != (desc.B, desc.T, desc.F):
+        raise ValueError("x has shape %s, descriptor says (%d,%d,%d)" % (tuple(x.shape), desc.B, desc.T, desc.F))
+    if out is None:
+        ld = lstm_hidden_ld(desc.H)
+        out = torch.empty((desc.B, desc.T, ld), dtype=torch.float32, device=x.device)[..., :desc.H]
+    else:
+        ld = _hidden_ld(out, desc, "out")
+    mv = float("nan") if mask_value is None else float(mask_value)
+    rc = L.drnmf_lstm_train_forward(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), _capi.ptr(out), ld,
+                                    _capi.ptr(workspace), workspace.numel(), _stream())
+    _capi.check(rc, h, "drnmf_lstm_train_forward")
+    return out
+
+
+def lstm_loss_head_backward(y, w, hidden, params, w_out, desc, workspace, sums, d_hidden, d_w_out, d_b_out):
+    """Loss 'mse_of_masked' and the head's backward after lstm_train_forward on the same workspace: writes
+    sums [2] = {sum w * mean_F (xm*s - y)^2, #frames with w != 0} (unnormalised), d_hidden [B,T,H], d_w_out [H,F],
+    d_b_out [F] (device tensors, overwritten)."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(hidden))
+    y, w, w_out = _f32c(y, "y"), _f32c(w, "sample_weight"), _f32c(w_out, "w_out")
+    if tuple(y.shape) != (desc.B, desc.T, desc.F) or tuple(w.shape) != (desc.B, desc.T):
+        raise ValueError("y / sample_weight must have shapes (B,T,F) / (B,T)")
+    ld = _hidden_ld(hidden, desc, "hidden")
+    for t, shp, what in ((sums, (2,), "sums"), (d_hidden, (desc.B, desc.T, desc.H), "d_hidden"),
+                         (d_w_out, (desc.H, desc.F), "d_w_out"), (d_b_out, (desc.F,), "d_b_out")):
+        if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 tensor of shape %s" % (what, shp))
+    rc = L.drnmf_lstm_loss_head_backward(h, C.byref(desc), _capi.ptr(y), _capi.ptr(w), _capi.ptr(hidden), ld,
+                                         _capi.ptr(params), _capi.ptr(w_out), _capi.ptr(sums), _capi.ptr(d_hidden),
+                                         _capi.ptr(d_w_out), _capi.ptr(d_b_out), _capi.ptr(workspace),
+                                         workspace.numel(), _stream())
+    _capi.check(rc, h, "drnmf_lstm_loss_head_backward")
+
+
+def _ptr_array(ts):
+    return (C.c_void_p * len(ts))(*[t.data_ptr() if t is not None else None for t in ts])
+
+
+def lstm_backward(kernels, recurrents, d_hidden, d_kernels, d_recurrents, d_biases, desc, workspace):
+    """BPTT after lstm_loss_head_backward on the same workspace: the unnormalised gradients of every layer's
+    kernel, recurrent_kernel and bias, written in Keras layout into the given (contiguous float32) tensors."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(d_hidden))
+    K, H, F = desc.K, desc.H, desc.F
+    if not (len(kernels) == len(recurrents) == len(d_kernels) == len(d_recurrents) == len(d_biases) == K):
+        raise ValueError("lstm_backward: K = %d tensors per list expected" % K)
+    for k in range(K):
+        fin = F if k == 0 else H
+        for t, shp in ((kernels[k], (fin, 4 * H)), (recurrents[k], (H, 4 * H)), (d_kernels[k], (fin, 4 * H)),
+                       (d_recurrents[k], (H, 4 * H)), (d_biases[k], (4 * H,))):
+            if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("lstm_backward: layer %d expects contiguous float32 %s" % (k, shp))
+    if tuple(d_hidden.shape) != (desc.B, desc.T, H) or not d_hidden.is_contiguous():
+        raise ValueError("d_hidden must be a contiguous (B,T,H) tensor")
+    rc = L.drnmf_lstm_backward(h, C.byref(desc), _ptr_array(kernels), _ptr_array(recurrents), _capi.ptr(d_hidden),
+                               _ptr_array(d_kernels), _ptr_array(d_recurrents), _ptr_array(d_biases),
+                               _capi.ptr(workspace), workspace.numel(), _stream())
+    _capi.check(rc, h, "drnmf_lstm_backward")

@@ -3,7 +3,7 @@
  * comparison model,
  *     Masking(mask_value) -> LSTM(H, return_sequences=True) x K -> TimeDistributed(Dense(F))
  *                         -> TimeDistributed(Activation('sigmoid')),
- * inference path.  Conventions as in drnmf.h: device pointers, caller-owned memory (nothing is allocated
+ * inference and training.  Conventions as in drnmf.h: device pointers, caller-owned memory (nothing is allocated
  * inside an enqueue call), the caller's stream, the handle's mutex, never a synchronisation, status codes.
  *
  * Keras 2.0.4 LSTM semantics [K2.0.4-memory] -- Keras is not part of the reference repository:
@@ -55,6 +55,39 @@ int32_t drnmf_lstm_forward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const f
  * (drnmf_lstm_forward writes zeros there). */
 int32_t drnmf_lstm_head_forward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* hidden, int32_t ld_h,
                                 const void* params, float* out, void* stream);
+
+/* ---- training (enhance.py:1260-1312: loss 'mse_of_masked', Adam) ----------------------------------------------
+ * Three calls on ONE training workspace (256-byte aligned, >= drnmf_lstm_train_workspace_bytes(d), else
+ * DRNMF_ERR_WORKSPACE), in this order:
+ *
+ * drnmf_lstm_train_forward: drnmf_lstm_forward (same arguments, same h_out bit for bit) that also keeps, in the
+ *   workspace, the masked input and every layer's gate pre-activations, c_t and h_t for the backward.
+ *
+ * drnmf_lstm_loss_head_backward: sigmoid head, loss and its gradient.  xm = the Masking layer's output (x with
+ *   masked frames zeroed, from the forward's workspace), s = sigmoid(hidden . w_out + b_out):
+ *     per frame  loss = w * mean_F (xm * s - y)^2
+ *   y [B][T][F]; w [B][T] (temporal sample weights); hidden [B][T][ld_h] = the forward's h_out; w_out [H][F]
+ *   (Keras layout; the weights params was prepared from).  Outputs (overwritten, UNNORMALISED sums as
+ *   drnmf_loss_head_backward): sums [2] = {sum w*loss, #frames with w != 0}; d_hidden [B][T][H];
+ *   d_w_out [H][F]; d_b_out [F].
+ *
+ * drnmf_lstm_backward: BPTT through the K layers from d_hidden (masked frames follow K.rnn: no gradient enters
+ *   them, both state gradients pass to the frame before).  kernel / recurrent: host arrays of K device pointers
+ *   to the Keras weights (kernel[0] is not read); d_kernel [K] (d_kernel[0] -> [F][4H], others [H][4H]),
+ *   d_recurrent [K] ([H][4H]), d_bias [K] ([4H]): host arrays of device pointers, overwritten in Keras layout with
+ *   the unnormalised gradient sums. */
+size_t drnmf_lstm_train_workspace_bytes(const drnmf_lstm_desc_t* d);
+int32_t drnmf_lstm_train_forward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x, float mask_value,
+                                 const void* params, float* h_out, int32_t ld_h, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+int32_t drnmf_lstm_loss_head_backward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* y, const float* w,
+                                      const float* hidden, int32_t ld_h, const void* params, const float* w_out,
+                                      float* sums, float* d_hidden, float* d_w_out, float* d_b_out, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+int32_t drnmf_lstm_backward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* const* kernel,
+                            const float* const* recurrent, const float* d_hidden, float* const* d_kernel,
+                            float* const* d_recurrent, float* const* d_bias, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

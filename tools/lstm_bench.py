@@ -10,7 +10,10 @@ params_lstm_*.yaml: K_layers / hidden_dim = 5/250, 2/54, 5/70, 2/244) at F = 513
   hip_forward_ms_b32        LSTMModel.forward at B = 32 (the training batch size)
   torch_lstm_ms_b{250,32}   torch.nn.LSTM(F, H, K, batch_first) forward at the same shapes -- a YARDSTICK, a
                             different model: sigmoid gates, no masking, full-length sequences, no head
-  train_step_ms_b32         null: training of the LSTM baseline is not implemented
+  train_step_ms_b32         LSTMModel.train_on_batch at B = 32 with the reference's Adam(lr=1e-4, clipnorm=1.0):
+                            training forward, loss head, BPTT, weight gradients and the fused Adam
+  torch_train_step_ms_b32   torch.nn.LSTM + Linear + sigmoid, mse loss, autograd and torch.optim.Adam at the same
+                            shapes -- the training YARDSTICK (sigmoid gates, no masking, no gradient clipping)
 Medians of --reps timed calls (CUDA events; wall clock for predict, which synchronises) after two warm-up calls.
 JSON lines go to stdout, nothing else does.
 """
@@ -80,7 +83,25 @@ def main():
             line["torch_lstm_ms_b%d" % B] = round(ref, 3)
             line["hip_over_torch_b%d" % B] = round(hip / ref, 3)
             del x
-        line["train_step_ms_b32"] = None
+        B = 32
+        x = rng.random((B, T, F), dtype=np.float32)
+        y = rng.random((B, T, F), dtype=np.float32)
+        xd, yd = torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev)
+        wd = torch.ones((B, T), dtype=torch.float32, device=dev)
+        m.compile(lr=1e-4, clipnorm=1.0)
+        line["train_step_ms_b32"] = round(_time(lambda: m.train_on_batch(xd, yd, wd), args.reps), 3)
+        lin = torch.nn.Linear(H, F).to(dev)
+        opt = torch.optim.Adam(list(net.parameters()) + list(lin.parameters()), lr=1e-4)
+
+        def torch_step():
+            opt.zero_grad(set_to_none=True)
+            out = torch.sigmoid(lin(net(xd)[0]))
+            loss = ((xd * out - yd) ** 2).mean()
+            loss.backward()
+            opt.step()
+        line["torch_train_step_ms_b32"] = round(_time(torch_step, args.reps), 3)
+        line["train_hip_over_torch_b32"] = round(line["train_step_ms_b32"] / line["torch_train_step_ms_b32"], 3)
+        del xd, yd, wd, lin, opt
         line["yardstick"] = "torch.nn.LSTM: sigmoid gates, unmasked full-length input, no head (a different model)"
         print(json.dumps(line), flush=True)
         m.free_predict_buffers()
