@@ -1,4 +1,5 @@
-"""ctypes binding of libdrnmf.so (C ABI in include/drnmf.h; the LSTM baseline's in include/drnmf_lstm.h).
+"""ctypes binding of libdrnmf.so (C ABI in include/drnmf.h; the LSTM baseline's in include/drnmf_lstm.h; the
+STOI score's in include/drnmf_score.h).
 
 The library is the product path: there is NO fallback.  If the shared object is missing or a
 call fails, an exception is raised.
@@ -157,6 +158,13 @@ LSTM_SIGNATURES = {
     "drnmf_lstm_backward": (_i32, [_vp, _LDP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/drnmf_score.h one to one (a table of its own, like LSTM_SIGNATURES)
+SCORE_SIGNATURES = {
+    "drnmf_stoi_vad_frames": (_i32, [_i64, _i32]),
+    "drnmf_stoi_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "drnmf_stoi": (_i32, [_vp, _i32, _i64, C.POINTER(_i64), _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 _handles = {}
 
@@ -178,7 +186,8 @@ def lib():
         # to initialise reports "no ROCm-capable device".
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(LSTM_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(LSTM_SIGNATURES.items()) +
+                                  list(SCORE_SIGNATURES.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

@@ -1,0 +1,515 @@
+// STOI of compute_scores (score_audio.m:231, `stoi(xref, xest, fs_est)`) for a ragged batch on gfx950.
+//
+// The STOI toolbox (Taal et al., IEEE TASLP 19(7), 2011) is a third-party download of the reference
+// (download_toolboxes.sh) and not in its tree: parity is pinned to the published algorithm only, as restated in
+// include/drnmf_score.h and tests/stoi_ref.py [STOI-memory].  x = reference, y = estimate.  Six stages, each a
+// kernel over the whole batch; every row is computed from its own samples alone, every sum in a fixed order, so
+// a row's score is bitwise the same in any batch and in every run:
+//   stoi_taps      Matlab resample's filter for p/q = 10000/fs reduced (L = 20 max(p,q) + 1 Kaiser(5)-windowed
+//                  sinc taps, p h / sum h), fp64, one workgroup.
+//   stoi_resample  y[m] = sum_k x[k] h[q m + (L-1)/2 - p k] for m < ceil(len p / q): one lane per output sample,
+//                  all L taps in LDS (a lane reads every p-th: ~L/p = 32 taps at 16 kHz), fp64 fma in k order,
+//                  stored as fp64.  Skipped at 10 kHz (the stages below then read the float32 input).
+//   stoi_vad       one workgroup per signal: the energies of x's frames (hop 128, hanning(256), fp64, one wave
+//                  per frame), their max, the keep mask e - max + 40 > 0 and the compaction index (kept frame c
+//                  -> its frame of x) by a chunked exclusive scan in thread order.
+//   stoi_band      one wave per band frame, 4 per workgroup.  Band frame i of the compacted signal is built on
+//                  load from kept frames i-1, i, i+1 through the compaction index (the compacted signal is never
+//                  written), windowed again and transformed as ONE 256-point complex FFT of its sample pairs
+//                  (the real-input split and the radix-4 Stockham passes of csrc/stft.hip's fast path, in a
+//                  wave-private LDS slice with no workgroup barrier) -- in fp64, as the resampled signal is
+//                  kept: a band 80 dB below its frame's loudest keeps full relative precision, where fp32
+//                  rounding of the samples or of the transform (~-140 dB of the frame) would cost it ~1e-3.  The
+//                  epilogue sums |X_k|^2 over the 15 one-third-octave bands and stores sqrt as float32.
+//   stoi_segment   one lane per (30-frame segment, band), fp64: alpha, the clipped Y', the centred correlation.
+//   stoi_mean      one workgroup per signal: the fp64 mean of its segment scores in a fixed order.
+// Matlab edge semantics (not pystoi's): fewer than 30 band frames -> NaN; fmin ignores NaN, so a segment with
+// sum Y^2 = 0 (alpha = inf, inf * 0 = NaN) takes Y' = X (1 + c) and scores 1; a zero-variance vector divides
+// 0 by 0 and the NaN reaches the mean.
+#include "common.h"
+#include "../../include/drnmf_score.h"
+
+namespace {
+
+constexpr int ST_FS = 10000, ST_N = 256, ST_HOP = 128, ST_J = 15, ST_SEG = 30;
+constexpr int ST_MAX_PQ = 160;                     // L <= 3201 taps in LDS
+constexpr int ST_LEN_CHUNK = 224;                  // lengths per upload launch (kernel-argument bytes)
+constexpr double ST_CLIP = 1.0 + 5.6234132519034908;   // 1 + 10^(-beta/20), beta = -15 dB
+
+// one-third-octave bands (fs 10 kHz, 512-point FFT, 150 Hz lowest centre): bins [lo, hi)
+__constant__ int k_band_lo[ST_J] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174};
+__constant__ int k_band_hi[ST_J] = {9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219};
+constexpr int ST_K0 = 7, ST_K1 = 219;              // bins read by the bands
+
+struct LenChunk {
+    int64_t len[ST_LEN_CHUNK];
+};
+
+__device__ __forceinline__ int64_t resampled_len(int64_t len, int p, int q) {
+    return (len * p + q - 1) / q;
+}
+__device__ __forceinline__ int vad_frames_dev(int64_t rlen) {
+    return rlen >= ST_N + 1 ? (int)((rlen - ST_N - 1) / ST_HOP) + 1 : 0;
+}
+__device__ __forceinline__ double hanning256(int n) {      // Matlab hanning(256): 0.5 (1 - cos(2 pi (n+1) / 257))
+    return 0.5 - 0.5 * cospi(2.0 * (double)(n + 1) / (double)(ST_N + 1));
+}
+
+// the caller's host lengths reach the device as kernel arguments: enqueued, no copy from pageable memory
+__global__ void __launch_bounds__(256) stoi_lengths_kernel(LenChunk c, int n, int64_t* __restrict__ out) {
+    const int i = threadIdx.x;
+    if (i < n) out[i] = c.len[i];
+}
+
+__device__ double bessel_i0(double x) {
+    double term = 1.0, sum = 1.0;
+    const double q = 0.25 * x * x;
+    for (int k = 1; k < 64; ++k) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < 1e-18 * sum) break;
+    }
+    return sum;
+}
+
+__device__ double resample_tap(int i, int L, int mpq) {
+    const int half = (L - 1) / 2;
+    const double r = (double)(i - half) / (double)half;
+    const double kw = bessel_i0(5.0 * sqrt(fmax(0.0, 1.0 - r * r))) / bessel_i0(5.0);
+    const double x = (double)(i - half) / (double)mpq;
+    const double s = i == half ? 1.0 : sinpi(x) / (M_PI * x);
+    return kw * s / (double)mpq;
+}
+
+__global__ void __launch_bounds__(256) stoi_taps_kernel(int p, int mpq, int L, double* __restrict__ taps) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    for (int i = tid; i < L; i += 256) s += resample_tap(i, L, mpq);
+    red[tid] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    const double scale = (double)p / red[0];
+    for (int i = tid; i < L; i += 256) taps[i] = resample_tap(i, L, mpq) * scale;
+}
+
+// grid (ceil(max resampled length / 256), n_sig, 2): z = 0 the reference, 1 the estimate
+__global__ void __launch_bounds__(256)
+stoi_resample_kernel(const float* __restrict__ ref, const float* __restrict__ est, int64_t ld_in,
+                     const int64_t* __restrict__ lens, int p, int q, int L, const double* __restrict__ taps,
+                     double* __restrict__ xr, double* __restrict__ yr, int64_t ld_out) {
+    extern __shared__ double h[];
+    for (int i = threadIdx.x; i < L; i += 256) h[i] = taps[i];
+    __syncthreads();
+    const int sig = blockIdx.y;
+    const int64_t len = lens[sig];
+    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (m >= resampled_len(len, p, q)) return;
+    const float* __restrict__ x = (blockIdx.z ? est : ref) + (size_t)sig * ld_in;
+    double* __restrict__ y = (blockIdx.z ? yr : xr) + (size_t)sig * ld_out;
+    const int64_t t0 = (int64_t)q * m + (L - 1) / 2;
+    int64_t k1 = t0 / p;
+    if (k1 > len - 1) k1 = len - 1;
+    const int64_t lo = t0 - (L - 1);
+    const int64_t k0 = lo <= 0 ? 0 : (lo + p - 1) / p;
+    double acc = 0.0;
+    for (int64_t k = k0; k <= k1; ++k) acc = fma((double)x[k], h[t0 - p * k], acc);
+    y[m] = acc;
+}
+
+// one workgroup per signal; e [n_sig][V] fp64 frame energies (workspace), kidx [n_sig][V], nkept [n_sig].
+// T: float (the input at 10 kHz) or double (resampled)
+template <typename T>
+__global__ void __launch_bounds__(256)
+stoi_vad_kernel(const T* __restrict__ xr, int64_t ld, const int64_t* __restrict__ lens, int p, int q, int V,
+                double* __restrict__ e, int* __restrict__ kidx, int* __restrict__ nkept,
+                uint8_t* __restrict__ keep_out) {
+    __shared__ double win[ST_N];
+    __shared__ double red[256];
+    __shared__ int cnt[256];
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const int sig = blockIdx.x;
+    const int nv = vad_frames_dev(resampled_len(lens[sig], p, q));
+    const T* __restrict__ x = xr + (size_t)sig * ld;
+    double* __restrict__ es = e + (size_t)sig * V;
+    win[tid] = hanning256(tid);
+    __syncthreads();
+    for (int j = wv; j < nv; j += 4) {
+        const T* f = x + (int64_t)j * ST_HOP;
+        double s = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double v = (double)f[lane + 64 * r] * win[lane + 64 * r];
+            s = fma(v, v, s);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        if (lane == 0) es[j] = 20.0 * log10(sqrt(s) / 16.0);     // 16 = sqrt(256)
+    }
+    __syncthreads();
+    double mx = -INFINITY;
+    for (int j = tid; j < nv; j += 256) mx = fmax(mx, es[j]);
+    red[tid] = mx;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] = fmax(red[tid], red[tid + o]);
+        __syncthreads();
+    }
+    const double emax = red[0];
+    const int per = (nv + 255) / 256;
+    const int j0 = tid * per < nv ? tid * per : nv;
+    const int j1 = j0 + per < nv ? j0 + per : nv;
+    int c = 0;
+    for (int j = j0; j < j1; ++j) c += (es[j] - emax + 40.0) > 0.0;
+    cnt[tid] = c;
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0;
+        for (int t = 0; t < 256; ++t) {
+            const int v = cnt[t];
+            cnt[t] = run;
+            run += v;
+        }
+        nkept[sig] = run;
+    }
+    __syncthreads();
+    int pos = cnt[tid];
+    int* __restrict__ ki = kidx + (size_t)sig * V;
+    for (int j = j0; j < j1; ++j) {
+        const bool keep = (es[j] - emax + 40.0) > 0.0;
+        if (keep) ki[pos++] = j;
+        if (keep_out) keep_out[(size_t)sig * V + j] = keep;
+    }
+    if (keep_out)
+        for (int j = nv + tid; j < V; j += 256) keep_out[(size_t)sig * V + j] = 0;
+}
+
+__device__ __forceinline__ double2 zmul(double2 a, double2 w) {
+    return make_double2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
+}
+
+__device__ __forceinline__ void dft4(double2 (&v)[4]) {
+    const double2 a = make_double2(v[0].x + v[2].x, v[0].y + v[2].y);
+    const double2 b = make_double2(v[0].x - v[2].x, v[0].y - v[2].y);
+    const double2 c = make_double2(v[1].x + v[3].x, v[1].y + v[3].y);
+    const double2 d = make_double2(v[1].x - v[3].x, v[1].y - v[3].y);
+    v[0] = make_double2(a.x + c.x, a.y + c.y);
+    v[2] = make_double2(a.x - c.x, a.y - c.y);
+    v[1] = make_double2(b.x + d.y, b.y - d.x);      // b - i d
+    v[3] = make_double2(b.x - d.y, b.y + d.x);      // b + i d
+}
+
+// grid (ceil(F / 4), n_sig), one wave per band frame; env [n_sig][F][15]
+template <typename T>
+__global__ void __launch_bounds__(256)
+stoi_band_kernel(const T* __restrict__ xr, const T* __restrict__ yr, int64_t ld,
+                 const int* __restrict__ kidx, const int* __restrict__ nkept, int V, int F,
+                 float* __restrict__ env_x, float* __restrict__ env_y) {
+    constexpr int M = 256, N = 512, R = 4, P = 4, MP = M + M / 8;
+    __shared__ double2 tw[N / 2];              // e^{-2 pi i k / N}, k < N/2
+    __shared__ double win[ST_N];
+    __shared__ double2 bufs[4][MP];            // per wave; index i lives at i + i/8 (bank spread)
+    __shared__ double pw[4][ST_K1 - ST_K0];    // per wave: |X_k|^2 of the band bins
+    auto pad = [](int i) { return i + (i >> 3); };
+    const int tid = threadIdx.x, wv = tid >> 6, j = tid & 63;
+    const int frame = blockIdx.x * 4 + wv, sig = blockIdx.y;
+    {
+        double sn, cs;
+        sincospi(-2.0 * (double)tid / (double)N, &sn, &cs);
+        tw[tid] = make_double2(cs, sn);
+        win[tid] = hanning256(tid);
+    }
+    __syncthreads();
+    if (frame >= nkept[sig] - 1) return;       // (whole waves: no barrier below)
+    const int* __restrict__ ki = kidx + (size_t)sig * V;
+    const int64_t s0 = (int64_t)ki[frame] * ST_HOP;                        // kept frame i
+    const int64_t sp = frame > 0 ? (int64_t)ki[frame - 1] * ST_HOP : 0;    // kept frame i - 1
+    const int64_t sn = (int64_t)ki[frame + 1] * ST_HOP;                    // kept frame i + 1 (i < n_kept - 1)
+    double2* buf = bufs[wv];
+    for (int which = 0; which < 2; ++which) {
+        const T* __restrict__ src = (which ? yr : xr) + (size_t)sig * ld;
+        // sample t of compacted frame i: the overlap-add of kept frames i and i -+ 1, windowed again
+        auto samp = [&](int t) {
+            const double a = (double)src[s0 + t] * win[t];
+            double b = 0.0;
+            if (t < ST_HOP) {
+                if (frame > 0) b = (double)src[sp + t + ST_HOP] * win[t + ST_HOP];
+            } else {
+                b = (double)src[sn + t - ST_HOP] * win[t - ST_HOP];
+            }
+            return (a + b) * win[t];
+        };
+        // pass-0 input z[n] = (s[2n], s[2n+1]), n = j + 64 r; zero padding from n = 128 on
+        double2 v[R];
+        v[0] = make_double2(samp(2 * j), samp(2 * j + 1));
+        v[1] = make_double2(samp(2 * j + 128), samp(2 * j + 129));
+        v[2] = make_double2(0.0, 0.0);
+        v[3] = make_double2(0.0, 0.0);
+        int Ns = 1;
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            if (p > 0) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) v[r] = buf[pad(j + r * (M / R))];
+            }
+            const int k = j & (Ns - 1);
+            if (p > 0) {                       // twiddles e^{-2 pi i k r / (Ns R)}
+                const int step = k * (N / (Ns * R));
+#pragma unroll
+                for (int r = 1; r < R; ++r) {
+                    const int idx = step * r;
+                    const double2 t = tw[idx & (N / 2 - 1)];
+                    v[r] = zmul(v[r], idx >= N / 2 ? make_double2(-t.x, -t.y) : t);
+                }
+            }
+            dft4(v);
+            const int j0 = (j - k) * R + k;
+#pragma unroll
+            for (int r = 0; r < R; ++r) buf[pad(j0 + r * Ns)] = v[r];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            Ns *= R;
+        }
+        // split the real spectrum X[k] = a - i w b of the band bins; |X_k|^2 to LDS
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int k = ST_K0 + j + 64 * i;
+            if (k < ST_K1) {
+                const double2 zk = buf[pad(k)];
+                const double2 zc = buf[pad(M - k)];
+                const double2 a = make_double2(0.5 * (zk.x + zc.x), 0.5 * (zk.y - zc.y));
+                const double2 b = make_double2(0.5 * (zk.x - zc.x), 0.5 * (zk.y + zc.y));
+                const double2 wb = zmul(b, tw[k]);
+                const double re = a.x + wb.y, im = a.y - wb.x;
+                pw[wv][k - ST_K0] = re * re + im * im;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (j < ST_J) {
+            double acc = 0.0;
+            for (int k = k_band_lo[j]; k < k_band_hi[j]; ++k) acc += pw[wv][k - ST_K0];
+            float* __restrict__ env = which ? env_y : env_x;
+            env[((size_t)sig * F + frame) * ST_J + j] = (float)sqrt(acc);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// grid (ceil(S * 15 / 256), n_sig): lane g = segment * 15 + band; d [n_sig][S][15]
+__global__ void __launch_bounds__(256)
+stoi_segment_kernel(const float* __restrict__ env_x, const float* __restrict__ env_y,
+                    const int* __restrict__ nkept, int F, int S, double* __restrict__ d) {
+    const int sig = blockIdx.y;
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    const int seg = g / ST_J, band = g - seg * ST_J;
+    if (seg >= nkept[sig] - 1 - (ST_SEG - 1)) return;
+    const float* __restrict__ ex = env_x + ((size_t)sig * F + seg) * ST_J + band;
+    const float* __restrict__ ey = env_y + ((size_t)sig * F + seg) * ST_J + band;
+    double X[ST_SEG], Y[ST_SEG];
+#pragma unroll
+    for (int f = 0; f < ST_SEG; ++f) {
+        X[f] = (double)ex[f * ST_J];
+        Y[f] = (double)ey[f * ST_J];
+    }
+    double sx = 0.0, sy = 0.0;
+#pragma unroll
+    for (int f = 0; f < ST_SEG; ++f) {
+        sx = fma(X[f], X[f], sx);
+        sy = fma(Y[f], Y[f], sy);
+    }
+    const double alpha = sqrt(sx / sy);
+    double mx = 0.0, my = 0.0;
+#pragma unroll
+    for (int f = 0; f < ST_SEG; ++f) {
+        Y[f] = fmin(alpha * Y[f], X[f] * ST_CLIP);    // fmin: a NaN operand yields the other (Matlab min)
+        mx += X[f];
+        my += Y[f];
+    }
+    mx /= ST_SEG;
+    my /= ST_SEG;
+    double nx = 0.0, ny = 0.0;
+#pragma unroll
+    for (int f = 0; f < ST_SEG; ++f) {
+        X[f] -= mx;
+        Y[f] -= my;
+        nx = fma(X[f], X[f], nx);
+        ny = fma(Y[f], Y[f], ny);
+    }
+    nx = sqrt(nx);
+    ny = sqrt(ny);
+    double rho = 0.0;
+#pragma unroll
+    for (int f = 0; f < ST_SEG; ++f) rho = fma(X[f] / nx, Y[f] / ny, rho);
+    d[(size_t)sig * S * ST_J + g] = rho;
+}
+
+__global__ void __launch_bounds__(256)
+stoi_mean_kernel(const double* __restrict__ d, const int* __restrict__ nkept, int S, float* __restrict__ out) {
+    __shared__ double red[256];
+    const int sig = blockIdx.x, tid = threadIdx.x;
+    const int nseg = nkept[sig] - 1 - (ST_SEG - 1);
+    if (nseg <= 0) {                           // Matlab's mean of an empty set
+        if (tid == 0) out[sig] = __int_as_float(0x7fc00000);
+        return;
+    }
+    const int cnt = nseg * ST_J;
+    const double* __restrict__ ds = d + (size_t)sig * S * ST_J;
+    double s = 0.0;
+    for (int g = tid; g < cnt; g += 256) s += ds[g];
+    red[tid] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) out[sig] = (float)(red[0] / (double)cnt);
+}
+
+int gcd_i(int a, int b) {
+    while (b) {
+        const int t = a % b;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+
+// p / q = 10000 / fs reduced; false when unsupported
+bool stoi_rate(int32_t fs, int& p, int& q) {
+    if (fs <= 0) return false;
+    const int g = gcd_i(ST_FS, fs);
+    p = ST_FS / g;
+    q = fs / g;
+    return (p > q ? p : q) <= ST_MAX_PQ;
+}
+
+int64_t resampled_len_h(int64_t len, int p, int q) { return (len * p + q - 1) / q; }
+int vad_frames_h(int64_t rlen) { return rlen >= ST_N + 1 ? (int)((rlen - ST_N - 1) / ST_HOP) + 1 : 0; }
+
+struct StoiLayout {
+    int p, q, mpq, L;
+    bool rs;                 // resample (fs != 10 kHz)
+    int64_t rstride;         // row stride of the resampled signals
+    int V, F, S;             // VAD frames, band frames (>= 1), segments (>= 1) bounds
+    size_t off_len, off_taps, off_xr, off_yr, off_e, off_kidx, off_nk, off_envx, off_envy, off_d, total;
+};
+
+constexpr int64_t ST_MAX_LEN = (int64_t)1 << 30;
+
+bool stoi_layout(int32_t n_sig, int64_t max_len, int32_t fs, StoiLayout& Lo) {
+    if (n_sig <= 0 || max_len < 0 || max_len > ST_MAX_LEN || !stoi_rate(fs, Lo.p, Lo.q)) return false;
+    Lo.mpq = Lo.p > Lo.q ? Lo.p : Lo.q;
+    Lo.rs = Lo.p != Lo.q;
+    Lo.L = 20 * Lo.mpq + 1;
+    const int64_t rmax = resampled_len_h(max_len, Lo.p, Lo.q);
+    Lo.rstride = rmax < 64 ? 64 : (int64_t)round_up_sz((size_t)rmax, 64);
+    Lo.V = vad_frames_h(rmax);
+    Lo.F = Lo.V > 1 ? Lo.V - 1 : 1;
+    Lo.S = Lo.F > ST_SEG - 1 ? Lo.F - (ST_SEG - 1) : 1;
+    const size_t n = (size_t)n_sig;
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = o;
+        o += round_up_sz(bytes, 256);
+        return at;
+    };
+    Lo.off_len = take(n * sizeof(int64_t));
+    Lo.off_taps = take(Lo.rs ? (size_t)Lo.L * sizeof(double) : 0);
+    Lo.off_xr = take(Lo.rs ? n * Lo.rstride * sizeof(double) : 0);
+    Lo.off_yr = take(Lo.rs ? n * Lo.rstride * sizeof(double) : 0);
+    Lo.off_e = take(n * (Lo.V > 0 ? Lo.V : 1) * sizeof(double));
+    Lo.off_kidx = take(n * (Lo.V > 0 ? Lo.V : 1) * sizeof(int));
+    Lo.off_nk = take(n * sizeof(int));
+    Lo.off_envx = take(n * Lo.F * ST_J * sizeof(float));
+    Lo.off_envy = take(n * Lo.F * ST_J * sizeof(float));
+    Lo.off_d = take(n * Lo.S * ST_J * sizeof(double));
+    Lo.total = o;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int32_t drnmf_stoi_vad_frames(int64_t len, int32_t fs) {
+    int p, q;
+    if (len < 0 || len > ST_MAX_LEN || !stoi_rate(fs, p, q)) return -1;
+    return vad_frames_h(resampled_len_h(len, p, q));
+}
+
+extern "C" size_t drnmf_stoi_workspace_bytes(int32_t n_sig, int64_t max_len, int32_t fs) {
+    StoiLayout Lo;
+    return stoi_layout(n_sig, max_len, fs, Lo) ? Lo.total : 0;
+}
+
+extern "C" int32_t drnmf_stoi(drnmf_handle_t h, int32_t n_sig, int64_t stride, const int64_t* lengths_host,
+                              int32_t fs, const float* est, const float* ref, float* stoi_out, uint8_t* keep_out,
+                              float* env_ref_out, float* env_est_out, void* workspace, size_t workspace_bytes,
+                              void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    if (n_sig <= 0 || n_sig > 65535 || stride <= 0 || !lengths_host || !est || !ref || !stoi_out || !workspace)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stoi: bad argument (n_sig in [1, 65535], stride > 0, non-NULL)");
+    int64_t max_len = 0;
+    for (int i = 0; i < n_sig; ++i) {
+        const int64_t l = lengths_host[i];
+        if (l < 0 || l > stride || l > ST_MAX_LEN)
+            DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stoi: lengths[%d] = %lld outside [0, min(stride, 2^30)]", i,
+                       (long long)l);
+        if (l > max_len) max_len = l;
+    }
+    StoiLayout Lo;
+    if (!stoi_layout(n_sig, max_len, fs, Lo))
+        DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED,
+                   "stoi: fs = %d unsupported (10000/fs reduced to p/q must have max(p, q) <= 160)", fs);
+    if (workspace_bytes < Lo.total)
+        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "stoi: workspace too small (%zu < %zu bytes)", workspace_bytes,
+                   Lo.total);
+    hipStream_t stream = (hipStream_t)stream_;
+    char* ws = (char*)workspace;
+    int64_t* lens = (int64_t*)(ws + Lo.off_len);
+    for (int base = 0; base < n_sig; base += ST_LEN_CHUNK) {
+        LenChunk c;
+        const int n = n_sig - base < ST_LEN_CHUNK ? n_sig - base : ST_LEN_CHUNK;
+        for (int i = 0; i < ST_LEN_CHUNK; ++i) c.len[i] = i < n ? lengths_host[base + i] : 0;
+        hipLaunchKernelGGL(stoi_lengths_kernel, dim3(1), dim3(256), 0, stream, c, n, lens + base);
+    }
+    double* e = (double*)(ws + Lo.off_e);
+    int* kidx = (int*)(ws + Lo.off_kidx);
+    int* nk = (int*)(ws + Lo.off_nk);
+    float* envx = env_ref_out ? env_ref_out : (float*)(ws + Lo.off_envx);
+    float* envy = env_est_out ? env_est_out : (float*)(ws + Lo.off_envy);
+    double* d = (double*)(ws + Lo.off_d);
+    const int V = Lo.V > 0 ? Lo.V : 1;
+    uint8_t* keep = Lo.V > 0 ? keep_out : nullptr;
+    const dim3 band_grid((unsigned)((Lo.F + 3) / 4), (unsigned)n_sig);
+    if (Lo.rs) {
+        double* taps = (double*)(ws + Lo.off_taps);
+        double* xr = (double*)(ws + Lo.off_xr);
+        double* yr = (double*)(ws + Lo.off_yr);
+        hipLaunchKernelGGL(stoi_taps_kernel, dim3(1), dim3(256), 0, stream, Lo.p, Lo.mpq, Lo.L, taps);
+        const unsigned nb = (unsigned)((resampled_len_h(max_len, Lo.p, Lo.q) + 255) / 256);
+        hipLaunchKernelGGL(stoi_resample_kernel, dim3(nb > 0 ? nb : 1, (unsigned)n_sig, 2), dim3(256),
+                           (size_t)Lo.L * sizeof(double), stream, ref, est, stride, (const int64_t*)lens, Lo.p,
+                           Lo.q, Lo.L, (const double*)taps, xr, yr, Lo.rstride);
+        hipLaunchKernelGGL(stoi_vad_kernel<double>, dim3((unsigned)n_sig), dim3(256), 0, stream,
+                           (const double*)xr, Lo.rstride, (const int64_t*)lens, Lo.p, Lo.q, V, e, kidx, nk, keep);
+        hipLaunchKernelGGL(stoi_band_kernel<double>, band_grid, dim3(256), 0, stream, (const double*)xr,
+                           (const double*)yr, Lo.rstride, (const int*)kidx, (const int*)nk, V, Lo.F, envx, envy);
+    } else {
+        hipLaunchKernelGGL(stoi_vad_kernel<float>, dim3((unsigned)n_sig), dim3(256), 0, stream, ref, stride,
+                           (const int64_t*)lens, Lo.p, Lo.q, V, e, kidx, nk, keep);
+        hipLaunchKernelGGL(stoi_band_kernel<float>, band_grid, dim3(256), 0, stream, ref, est, stride,
+                           (const int*)kidx, (const int*)nk, V, Lo.F, envx, envy);
+    }
+    hipLaunchKernelGGL(stoi_segment_kernel, dim3((unsigned)((Lo.S * ST_J + 255) / 256), (unsigned)n_sig),
+                       dim3(256), 0, stream, (const float*)envx, (const float*)envy, (const int*)nk, Lo.F, Lo.S,
+                       d);
+    hipLaunchKernelGGL(stoi_mean_kernel, dim3((unsigned)n_sig), dim3(256), 0, stream, (const double*)d,
+                       (const int*)nk, Lo.S, stoi_out);
+    DRNMF_HIP(h, hipGetLastError());
+    return DRNMF_OK;
+}

@@ -984,6 +984,111 @@ def to_int16_wav(x):
     return out
 
 
+# ---- STOI and the compute_scores row (score_audio.m:177-238; C ABI in include/drnmf_score.h) ---------------
+STOI_BANDS = 15
+SCORE_LABELS = ['SDR', 'SNR', 'SegSNR local', 'SegSNR global', 'PESQ', 'STOI']
+
+
+def stoi_vad_frames(nsampl, fs):
+    """Silence-detector frames of a signal of nsampl samples at fs (after resampling to 10 kHz)."""
+    n = int(_capi.lib().drnmf_stoi_vad_frames(int(nsampl), int(fs)))
+    if n < 0:
+        raise ValueError("stoi: fs = %d is not supported (10000/fs reduced to p/q needs max(p, q) <= 160)" % fs)
+    return n
+
+
+def _host_lengths(lengths, n_sig, n):
+    if lengths is None:
+        return np.full(n_sig, n, dtype=np.int64)
+    if isinstance(lengths, torch.Tensor):
+        lengths = lengths.cpu().numpy()
+    lh = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+    if lh.shape[0] != n_sig:
+        raise ValueError("lengths has %d entries for %d signals" % (lh.shape[0], n_sig))
+    return lh
+
+
+def stoi(est, ref, fs=16000, lengths=None, return_parts=False):
+    """STOI per signal, as `stoi(xref, xest, fs)` of compute_scores (score_audio.m:231) [STOI-memory]:
+    short-time objective intelligibility (Taal et al., 2011), restated in include/drnmf_score.h and
+    tests/stoi_ref.py.  est, ref: device float32 [n_sig, n] (or 1-D); lengths: per-row valid samples (host
+    ints or a tensor; default n).  Returns a float32 [n_sig] device tensor -- NaN for a row with fewer than 30
+    band frames, as Matlab's mean of an empty set.  return_parts=True returns (stoi, parts), parts = dict(
+    keep=[n_sig, V] bool silence decision on ref, env_ref / env_est=[n_sig, max(V-1, 1), 15] band envelopes
+    (rows past a signal's own n_kept - 1 band frames are unspecified), n_kept=[n_sig] int64)."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(est))
+    est, ref = _f32c(est, "est"), _f32c(ref, "ref")
+    if est.dim() == 1:
+        est, ref = est[None], ref[None]
+    if est.dim() != 2 or est.shape != ref.shape:
+        raise ValueError("est and ref must have the same shape [n_sig, n] (got %s and %s)" %
+                         (tuple(est.shape), tuple(ref.shape)))
+    if ref.device != est.device:
+        raise ValueError("est and ref must be on one device")
+    n_sig, n = est.shape
+    lh = _host_lengths(lengths, n_sig, n)
+    max_len = int(lh.max()) if n_sig else 0
+    V = stoi_vad_frames(max_len, fs)
+    dev = est.device
+    nbytes = L.drnmf_stoi_workspace_bytes(n_sig, max_len, int(fs))
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    out = torch.empty(n_sig, dtype=torch.float32, device=dev)
+    keep = env_r = env_e = None
+    if return_parts:
+        keep = torch.zeros((n_sig, V), dtype=torch.uint8, device=dev)
+        env_r = torch.zeros((n_sig, max(V - 1, 1), STOI_BANDS), dtype=torch.float32, device=dev)
+        env_e = torch.zeros_like(env_r)
+    rc = L.drnmf_stoi(h, n_sig, n, lh.ctypes.data_as(C.POINTER(C.c_int64)), int(fs), _capi.ptr(est),
+                      _capi.ptr(ref), _capi.ptr(out), _capi.ptr(keep if V > 0 else None), _capi.ptr(env_r),
+                      _capi.ptr(env_e), _capi.ptr(ws), ws.numel(), _stream())
+    _capi.check(rc, h, "drnmf_stoi")
+    if not return_parts:
+        return out
+    kb = keep.bool()
+    return out, dict(keep=kb, env_ref=env_r, env_est=env_e, n_kept=kb.sum(dim=1))
+
+
+def compute_scores(est, ref, fs, lengths_est=None, lengths_ref=None, flen=512):
+    """One row per file as compute_scores (score_audio.m:177-238) returns it:
+        S = [SDR, SNR, SegSNR local, SegSNR global, PESQ, STOI]        (score_audio.m:233-236)
+    est [n_sig, n_est], ref [n_sig, n_ref]: device float32 (or 1-D), each row valid up to its length
+    (default: the row width).  Each pair is truncated to min(len_est, len_ref); SDR (`sdr_db`, 512-tap BSS Eval)
+    and SNR (`snr_db`) see the pairs zero-padded to a common width, to which both are neutral; STOI (`stoi`) runs
+    at fs on the truncated pairs.  Returns (S, labels): S float64 numpy [n_sig, 6], labels SCORE_LABELS.
+
+    SegSNR and PESQ are NaN.  SegSNR is voicebox `snrseg` (score_audio.m:212), whose default mode runs a P.56
+    speech-activity detector and a sub-sample delay search whose exact definitions are not available to this
+    project; PESQ is ITU-T P.862, large, table-driven and licensed.  A restatement from memory would be a number
+    labelled as the reference's that is probably not the reference's, so neither column is computed."""
+    if est.dim() == 1:
+        est, ref = est[None], ref[None]
+    if est.dim() != 2 or ref.dim() != 2 or est.shape[0] != ref.shape[0]:
+        raise ValueError("est and ref must be [n_sig, n] with the same n_sig (got %s and %s)" %
+                         (tuple(est.shape), tuple(ref.shape)))
+    n_sig = est.shape[0]
+    le = _host_lengths(lengths_est, n_sig, est.shape[1])
+    lr = _host_lengths(lengths_ref, n_sig, ref.shape[1])
+    if np.any(le > est.shape[1]) or np.any(lr > ref.shape[1]) or np.any(le < 0) or np.any(lr < 0):
+        raise ValueError("lengths outside [0, row width]")
+    ln = np.minimum(le, lr)
+    width = max(int(ln.max()) if n_sig else 0, 1)
+    col = torch.arange(width, device=est.device)[None, :]
+    valid = col < torch.from_numpy(ln).to(est.device)[:, None]
+    e = torch.zeros((n_sig, width), dtype=torch.float32, device=est.device)
+    r = torch.zeros_like(e)
+    we, wr = min(width, est.shape[1]), min(width, ref.shape[1])
+    e[:, :we] = _f32c(est, "est")[:, :we]
+    r[:, :wr] = _f32c(ref, "ref")[:, :wr]
+    e = torch.where(valid, e, torch.zeros_like(e))
+    r = torch.where(valid, r, torch.zeros_like(r))
+    S = np.full((n_sig, len(SCORE_LABELS)), np.nan, dtype=np.float64)
+    S[:, 0] = sdr_db(e, r, flen=flen).cpu().numpy()
+    S[:, 1] = snr_db(e, r).cpu().numpy()
+    S[:, 5] = stoi(e, r, fs=fs, lengths=ln).cpu().numpy()
+    return S, list(SCORE_LABELS)
+
+
 # ---- LSTM baseline (build_lstm, enhance.py:321-345; C ABI in include/drnmf_lstm.h) -----------------------
 LSTM_ACTIVATIONS = {"hard_sigmoid": _capi.ACTIVATIONS["hard_sigmoid"], "sigmoid": _capi.ACTIVATIONS["sigmoid"]}
 
