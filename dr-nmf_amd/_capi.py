@@ -1,5 +1,5 @@
 """ctypes binding of libdrnmf.so (C ABI in include/drnmf.h; the LSTM baseline's in include/drnmf_lstm.h; the
-STOI score's in include/drnmf_score.h).
+STOI score's in include/drnmf_score.h; the ragged STFT / iSTFT / int16 stages' in include/drnmf_enhance.h).
 
 The library is the product path: there is NO fallback.  If the shared object is missing or a
 call fails, an exception is raised.
@@ -165,6 +165,17 @@ SCORE_SIGNATURES = {
     "drnmf_stoi": (_i32, [_vp, _i32, _i64, C.POINTER(_i64), _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/drnmf_enhance.h one to one (a table of its own, like the two above)
+ENHANCE_SIGNATURES = {
+    "drnmf_stft_ragged": (_i32, [_vp, _i32, _i64, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp,
+                                 _vp]),
+    "drnmf_istft_ragged_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "drnmf_istft_ragged": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32,
+                                  _vp, _sz, _vp]),
+    "drnmf_wav_int16_rows_workspace_bytes": (_sz, [_i32]),
+    "drnmf_wav_int16_rows": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 _handles = {}
 
@@ -187,7 +198,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(LSTM_SIGNATURES.items()) +
-                                  list(SCORE_SIGNATURES.items())):
+                                  list(SCORE_SIGNATURES.items()) + list(ENHANCE_SIGNATURES.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

@@ -6,6 +6,7 @@
 //   drnmf_loss_forward        validation loss of fit()/evaluate (enhance.py:1152-1157) without gradients
 //   drnmf_wav_int16           util.wavwrite's float32 -> int16 conversion (util.py:37-45)
 #include "common.h"
+#include "../../include/drnmf_enhance.h"
 
 namespace {
 
@@ -123,6 +124,40 @@ to_int16_kernel(const float* __restrict__ x, const float* __restrict__ amax,
     out[i] = (int16_t)(int)(v * 32767.0f);
 }
 
+// util.wavwrite per row of a ragged batch (include/drnmf_enhance.h): one peak per row, then to_int16_kernel's
+// arithmetic with the row's own peak; zeros behind the row's length
+__global__ void __launch_bounds__(256)
+absmax_rows_kernel(const float* __restrict__ y, int64_t stride, const int64_t* __restrict__ lengths,
+                   float* __restrict__ peak) {
+    __shared__ float sm[4];
+    const int k = blockIdx.x;
+    int64_t len = lengths[k];
+    len = len < 0 ? 0 : (len > stride ? stride : len);
+    const float* __restrict__ row = y + (size_t)k * stride;
+    float m = 0.f;
+    for (int64_t i = threadIdx.x; i < len; i += 256) m = fmaxf(m, fabsf(row[i]));
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) peak[k] = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+}
+
+__global__ void __launch_bounds__(256)
+to_int16_rows_kernel(const float* __restrict__ y, int64_t stride, const int64_t* __restrict__ lengths,
+                     const float* __restrict__ peak, int16_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int k = blockIdx.y;
+    if (i >= stride) return;
+    int16_t q = 0;
+    if (i < lengths[k]) {
+        const float m = peak[k];
+        float v = y[(size_t)k * stride + i];
+        if (m > 1.f) v = v / m;
+        q = (int16_t)(int)(v * 32767.0f);
+    }
+    out[(size_t)k * stride + i] = q;
+}
+
 }  // namespace
 
 extern "C" int32_t drnmf_divide_a_by_aplusb(drnmf_handle_t h, int64_t n, const float* A,
@@ -198,6 +233,33 @@ extern "C" int32_t drnmf_wav_int16(drnmf_handle_t h, int64_t n, const float* x, 
     hipLaunchKernelGGL(absmax_final_kernel, dim3(1), dim3(256), 0, stream, part, nb);
     hipLaunchKernelGGL(to_int16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x,
                        part + nb, out, n);
+    DRNMF_HIP(h, hipGetLastError());
+    return DRNMF_OK;
+}
+
+extern "C" size_t drnmf_wav_int16_rows_workspace_bytes(int32_t n_sig) {
+    if (n_sig <= 0) return 0;
+    return round_up_sz((size_t)n_sig * sizeof(float), 256);
+}
+
+extern "C" int32_t drnmf_wav_int16_rows(drnmf_handle_t h, int32_t n_sig, int64_t stride,
+                                        const int64_t* lengths, const float* y, int16_t* out,
+                                        void* workspace, size_t workspace_bytes, void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    if (n_sig <= 0 || n_sig > 65535 || stride <= 0)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "wav_int16_rows: bad shape n_sig=%d (1..65535) stride=%lld",
+                   n_sig, (long long)stride);
+    if (!lengths || !y || !out || !workspace)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "wav_int16_rows: NULL pointer argument");
+    if (workspace_bytes < drnmf_wav_int16_rows_workspace_bytes(n_sig))
+        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "wav_int16_rows: workspace too small");
+    hipStream_t stream = (hipStream_t)stream_;
+    float* peak = (float*)workspace;
+    hipLaunchKernelGGL(absmax_rows_kernel, dim3((unsigned)n_sig), dim3(256), 0, stream, y, stride, lengths,
+                       peak);
+    hipLaunchKernelGGL(to_int16_rows_kernel, dim3((unsigned)((stride + 255) / 256), (unsigned)n_sig),
+                       dim3(256), 0, stream, y, stride, lengths, peak, out);
     DRNMF_HIP(h, hipGetLastError());
     return DRNMF_OK;
 }

@@ -13,6 +13,7 @@
 // LDS-latency / barrier bound (two radix-2 stages per pass: 293 -> 217 us together with the tables),
 // not memory bound; the front end is ~600x faster than the recurrent cell consumes frames.
 #include "common.h"
+#include "../../include/drnmf_enhance.h"
 
 namespace {
 
@@ -84,14 +85,12 @@ __global__ void __launch_bounds__(256) fft_tables_kernel(int N, int logN) {
     }
 }
 
-__global__ void __launch_bounds__(256)
-stft_kernel(const void* __restrict__ pcm, int is_int16, int64_t nsampl, int N, int logN, int hop,
-            int nf, float* __restrict__ mag, float* __restrict__ re, float* __restrict__ im) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float2* buf = (float2*)smem;            // N complex points
-    float2* tw = buf + N;                   // N/2 twiddles e^{-2 pi i k / N}
-    const int tid = threadIdx.x;
-    const int frame = blockIdx.x, sig = blockIdx.y;
+// one frame of one signal by the whole workgroup: row0 = element offset of the signal's first sample in pcm,
+// nsampl its length, o = element offset of the frame's output row (shared by the batched and the ragged kernel)
+__device__ __forceinline__ void stft_frame(const void* __restrict__ pcm, int is_int16, size_t row0,
+                                           int64_t nsampl, int N, int logN, int hop, int frame, size_t o,
+                                           float* __restrict__ mag, float* __restrict__ re,
+                                           float* __restrict__ im, float2* buf, float2* tw, int tid) {
     const int64_t base = (int64_t)frame * hop - N;   // first sample of the frame (N leading zeros)
 
     const float* __restrict__ win = g_window[logN - TAB_LOG_MIN];
@@ -100,8 +99,8 @@ stft_kernel(const void* __restrict__ pcm, int is_int16, int64_t nsampl, int N, i
         const int64_t idx = base + i;
         float v = 0.f;
         if (idx >= 0 && idx < nsampl) {
-            v = is_int16 ? (float)((const short*)pcm)[(size_t)sig * nsampl + idx] / 32768.0f
-                         : ((const float*)pcm)[(size_t)sig * nsampl + idx];
+            v = is_int16 ? (float)((const short*)pcm)[row0 + idx] / 32768.0f
+                         : ((const float*)pcm)[row0 + idx];
         }
         v *= win[i];
         const unsigned rev = __brev((unsigned)i) >> (32 - logN);
@@ -109,13 +108,23 @@ stft_kernel(const void* __restrict__ pcm, int is_int16, int64_t nsampl, int N, i
     }
     __syncthreads();
     fft_lds(buf, tw, N, logN, tid);
-    const size_t o = ((size_t)sig * nf + frame) * (N / 2 + 1);
     for (int k = tid; k <= N / 2; k += 256) {
         const float2 z = buf[k];
         if (mag) mag[o + k] = sqrtf(z.x * z.x + z.y * z.y);
         if (re) re[o + k] = z.x;
         if (im) im[o + k] = -z.y;    // librosa 0.5.1 conjugates the spectrum (util.py:195 via stft)
     }
+}
+
+__global__ void __launch_bounds__(256)
+stft_kernel(const void* __restrict__ pcm, int is_int16, int64_t nsampl, int N, int logN, int hop,
+            int nf, float* __restrict__ mag, float* __restrict__ re, float* __restrict__ im) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float2* buf = (float2*)smem;            // N complex points
+    float2* tw = buf + N;                   // N/2 twiddles e^{-2 pi i k / N}
+    const int frame = blockIdx.x, sig = blockIdx.y;
+    stft_frame(pcm, is_int16, (size_t)sig * nsampl, nsampl, N, logN, hop, frame,
+               ((size_t)sig * nf + frame) * (N / 2 + 1), mag, re, im, buf, tw, threadIdx.x);
 }
 
 
@@ -160,37 +169,69 @@ __device__ __forceinline__ void dft_r<8>(float2 (&v)[8]) {
     }
 }
 
-template <int R, int P>       // M = R^P complex points, N = 2M real samples
-__global__ void __launch_bounds__(256)
-stft_real_kernel(const void* __restrict__ pcm, int is_int16, int64_t nsampl, int logN, int hop,
-                 int nf, float* __restrict__ mag, float* __restrict__ re, float* __restrict__ im) {
-    constexpr int M = (R == 8 ? (P == 3 ? 512 : 64) : (P == 4 ? 256 : 64)), N = 2 * M;
-    __shared__ float2 tw[N / 2];              // e^{-2 pi i k / N}, k < N/2
+template <int R, int P>
+struct RealFft {                          // M = R^P complex points, N = 2M real samples
+    static constexpr int M = (R == 8 ? (P == 3 ? 512 : 64) : (P == 4 ? 256 : 64)), N = 2 * M;
     // per wave: ONE buffer, rewritten in place by every pass -- a wave executes its LDS reads of a
     // pass (all 64 lanes, into registers) before that pass's writes are issued, and LDS serves one
     // wave's requests in order, so the Stockham reorder needs no second buffer (the ping-pong pair
     // it replaced held the kernel to 3 workgroups per CU; 7 now).  Index i lives at i + i/8: the
     // scatter of the early passes (stride R, then R*R) would otherwise put 8-16 lanes on one bank
-    constexpr int MP = M + M / 8;
-    __shared__ float2 bufs[4][MP];
-    auto pad = [](int i) { return i + (i >> 3); };
-    const int tid = threadIdx.x, wv = tid >> 6, j = tid & 63;
-    const int frame = blockIdx.x * 4 + wv, sig = blockIdx.y;
-    for (int k = tid; k < N / 2; k += 256) tw[k] = g_twiddle[logN - TAB_LOG_MIN][k];
-    __syncthreads();
-    if (frame >= nf) return;                  // (whole waves: no barrier below)
-    const float* __restrict__ win = g_window[logN - TAB_LOG_MIN];
+    static constexpr int MP = M + M / 8;
+    static __device__ __forceinline__ int pad(int i) { return i + (i >> 3); }
+};
+
+// The P radix-R Stockham passes of one wave (lane j): v[r] = z[j + r M/R] on entry, Z[k] = sum_n z[n]
+// e^{-2 pi i k n / M} at cur[pad(k)] on return; tw = e^{-2 pi i k / N}, k < N/2, in LDS.
+template <int R, int P>
+__device__ __forceinline__ void stockham_passes(float2 (&v)[R], float2* cur, const float2* tw, int j) {
+    constexpr int M = RealFft<R, P>::M, N = 2 * M;
+    auto pad = [](int i) { return RealFft<R, P>::pad(i); };
     auto twid = [&](int idx) {                // e^{-2 pi i idx / N}, 0 <= idx < N
         const float2 t = tw[idx & (N / 2 - 1)];
         return idx >= N / 2 ? make_float2(-t.x, -t.y) : t;
     };
+    float2* nxt = cur;
+    int Ns = 1;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        if (p > 0) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) v[r] = cur[pad(j + r * (M / R))];
+        }
+        const int k = j & (Ns - 1);
+        if (p > 0) {                          // twiddles e^{-2 pi i k r / (Ns R)} (pass 0: k = 0)
+            const int step = k * (N / (Ns * R));
+#pragma unroll
+            for (int r = 1; r < R; ++r) v[r] = cmul(v[r], twid(step * r));
+        }
+        dft_r<R>(v);
+        const int j0 = (j - k) * R + k;
+#pragma unroll
+        for (int r = 0; r < R; ++r) nxt[pad(j0 + r * Ns)] = v[r];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        Ns *= R;
+    }
+}
+
+// one frame of one signal by ONE WAVE (lane j): row0 = element offset of the signal's first sample in pcm,
+// nsampl its length, o = element offset of the frame's output row (shared by the batched and the ragged kernel)
+template <int R, int P>
+__device__ __forceinline__ void stft_real_frame(const void* __restrict__ pcm, int is_int16, size_t row0,
+                                                int64_t nsampl, int logN, int hop, int frame, size_t o,
+                                                float* __restrict__ mag, float* __restrict__ re,
+                                                float* __restrict__ im, const float2* tw, float2* cur, int j) {
+    constexpr int M = RealFft<R, P>::M, N = 2 * M;
+    auto pad = [](int i) { return RealFft<R, P>::pad(i); };
+    const float* __restrict__ win = g_window[logN - TAB_LOG_MIN];
     // pass 0 input straight from the signal: z[n] = (x[2n] w[2n], x[2n+1] w[2n+1]), n = j + r M/R
     const int64_t base = (int64_t)frame * hop - N;       // first sample of the frame (N leading zeros)
     float2 v[R];
     // interior frames (all but the first N/hop and the last few): no bounds tests, one 8-byte load
     // per sample pair -- this kernel is VALU-issue bound (~1000 instructions per lane and frame),
     // the 16 64-bit range tests were a tenth of them
-    const size_t e0 = (size_t)sig * nsampl + (size_t)(base > 0 ? base : 0);   // first element
+    const size_t e0 = row0 + (size_t)(base > 0 ? base : 0);   // first element
     const bool interior = base >= 0 && base + N <= nsampl &&
                           ((((uintptr_t)pcm >> (is_int16 ? 1 : 2)) + e0) & 1) == 0;
     if (interior && is_int16) {
@@ -218,42 +259,19 @@ stft_real_kernel(const void* __restrict__ pcm, int is_int16, int64_t nsampl, int
         const int64_t i0 = base + 2 * n;
         float x0 = 0.f, x1 = 0.f;
         if (is_int16) {
-            const short* p = (const short*)pcm + (size_t)sig * nsampl;
+            const short* p = (const short*)pcm + row0;
             if (i0 >= 0 && i0 < nsampl) x0 = (float)p[i0] / 32768.0f;
             if (i0 + 1 >= 0 && i0 + 1 < nsampl) x1 = (float)p[i0 + 1] / 32768.0f;
         } else {
-            const float* p = (const float*)pcm + (size_t)sig * nsampl;
+            const float* p = (const float*)pcm + row0;
             if (i0 >= 0 && i0 < nsampl) x0 = p[i0];
             if (i0 + 1 >= 0 && i0 + 1 < nsampl) x1 = p[i0 + 1];
         }
         const float2 w2 = *(const float2*)(win + 2 * n);
         v[r] = make_float2(x0 * w2.x, x1 * w2.y);
     }
-    float2* cur = bufs[wv];
-    float2* nxt = bufs[wv];
-    int Ns = 1;
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        if (p > 0) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) v[r] = cur[pad(j + r * (M / R))];
-        }
-        const int k = j & (Ns - 1);
-        if (p > 0) {                          // twiddles e^{-2 pi i k r / (Ns R)} (pass 0: k = 0)
-            const int step = k * (N / (Ns * R));
-#pragma unroll
-            for (int r = 1; r < R; ++r) v[r] = cmul(v[r], twid(step * r));
-        }
-        dft_r<R>(v);
-        const int j0 = (j - k) * R + k;
-#pragma unroll
-        for (int r = 0; r < R; ++r) nxt[pad(j0 + r * Ns)] = v[r];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        Ns *= R;
-    }
+    stockham_passes<R, P>(v, cur, tw, j);
     // split + output: k = j + 64 i, i < M/64, and k = M
-    const size_t o = ((size_t)sig * nf + frame) * (M + 1);
     auto emit = [&](int k) {
         const float2 zk = cur[pad(k & (M - 1))];
         const float2 zc = cur[pad((M - k) & (M - 1))];     // Z[M-k] (Z[M] = Z[0])
@@ -269,6 +287,23 @@ stft_real_kernel(const void* __restrict__ pcm, int is_int16, int64_t nsampl, int
 #pragma unroll
     for (int i = 0; i < M / 64; ++i) emit(j + 64 * i);
     if (j == 0) emit(M);
+}
+
+
+template <int R, int P>
+__global__ void __launch_bounds__(256)
+stft_real_kernel(const void* __restrict__ pcm, int is_int16, int64_t nsampl, int logN, int hop,
+                 int nf, float* __restrict__ mag, float* __restrict__ re, float* __restrict__ im) {
+    constexpr int N = RealFft<R, P>::N;
+    __shared__ float2 tw[N / 2];              // e^{-2 pi i k / N}, k < N/2
+    __shared__ float2 bufs[4][RealFft<R, P>::MP];
+    const int tid = threadIdx.x, wv = tid >> 6, j = tid & 63;
+    const int frame = blockIdx.x * 4 + wv, sig = blockIdx.y;
+    for (int k = tid; k < N / 2; k += 256) tw[k] = g_twiddle[logN - TAB_LOG_MIN][k];
+    __syncthreads();
+    if (frame >= nf) return;                  // (whole waves: no barrier below)
+    stft_real_frame<R, P>(pcm, is_int16, (size_t)sig * nsampl, nsampl, logN, hop, frame,
+                          ((size_t)sig * nf + frame) * (N / 2 + 1), mag, re, im, tw, bufs[wv], j);
 }
 
 static bool stft_fast(int N) { return N == 512 || N == 1024; }
@@ -301,25 +336,19 @@ static void launch_stft_real(int N, int logN, const void* pcm, int is_int16, int
 }
 
 // one workgroup per (signal, frame): masked spectrum -> Hermitian extension -> inverse FFT -> real
-// part * window * 2/(N/hop)  (util.py:48-169 istft_noDiv with center=False)
-__global__ void __launch_bounds__(256)
-istft_frames_kernel(const float* __restrict__ re, const float* __restrict__ im,
-                    const float* __restrict__ mask, int N, int logN, int hop, int nf,
-                    float* __restrict__ frames) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float2* buf = (float2*)smem;
-    float2* tw = buf + N;
-    const int tid = threadIdx.x;
-    const int frame = blockIdx.x, sig = blockIdx.y;
-    const int F = N / 2 + 1;
+// part * window * 2/(N/hop)  (util.py:48-169 istft_noDiv with center=False).  o, om = element offsets of the
+// frame's spectrum and mask rows, out = its N output samples (shared by the batched and the ragged kernel)
+__device__ __forceinline__ void istft_frame(const float* __restrict__ re, const float* __restrict__ im,
+                                            const float* __restrict__ mask, size_t o, size_t om, int N,
+                                            int logN, int hop, float* __restrict__ out, float2* buf,
+                                            float2* tw, int tid) {
     const float* __restrict__ win = g_window[logN - TAB_LOG_MIN];
     for (int k = tid; k < N / 2; k += 256) tw[k] = g_twiddle[logN - TAB_LOG_MIN][k];
     // ifft(z) = conj(fft(conj(z)))/N.  With S the stored (conjugated) spectrum the reference
     // builds z = [conj(S_0..S_{N/2}), S_{N/2-1}..S_1], so conj(z) = [S_k ; conj(S_{N-k})].
-    const size_t o = ((size_t)sig * nf + frame) * F;
     for (int k = tid; k < N; k += 256) {
         const int kk = k <= N / 2 ? k : N - k;
-        const float m = mask ? mask[o + kk] : 1.f;
+        const float m = mask ? mask[om + kk] : 1.f;
         float2 z = make_float2(m * re[o + kk], m * im[o + kk]);
         if (k > N / 2) z.y = -z.y;
         const unsigned rev = __brev((unsigned)k) >> (32 - logN);
@@ -328,8 +357,20 @@ istft_frames_kernel(const float* __restrict__ re, const float* __restrict__ im,
     __syncthreads();
     fft_lds(buf, tw, N, logN, tid);
     const float scale = (2.0f / ((float)N / (float)hop)) / (float)N;
-    float* out = frames + ((size_t)sig * nf + frame) * N;
     for (int i = tid; i < N; i += 256) out[i] = buf[i].x * scale * win[i];
+}
+
+__global__ void __launch_bounds__(256)
+istft_frames_kernel(const float* __restrict__ re, const float* __restrict__ im,
+                    const float* __restrict__ mask, int N, int logN, int hop, int nf,
+                    float* __restrict__ frames) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float2* buf = (float2*)smem;
+    float2* tw = buf + N;
+    const int frame = blockIdx.x, sig = blockIdx.y;
+    const size_t o = ((size_t)sig * nf + frame) * (N / 2 + 1);
+    istft_frame(re, im, mask, o, o, N, logN, hop, frames + ((size_t)sig * nf + frame) * N, buf, tw,
+                threadIdx.x);
 }
 
 // overlap-add by gathering (deterministic), with istft_mc's trimming of the N padding samples on
@@ -377,6 +418,237 @@ snr_kernel(const float* __restrict__ est, const float* __restrict__ ref, int64_t
         __syncthreads();
     }
     if (threadIdx.x == 0) out_db[sig] = (float)(10.0 * log10(s0[0] / s1[0]));
+}
+
+
+// ---------------------------------------------------------------------------------------------
+// Ragged batches (include/drnmf_enhance.h): the signals of a slab have their own lengths, read on the device;
+// slab row k = signal sig_index[k].  What a row computes depends on its own signal only.
+struct RaggedRow {
+    int sig;              // -1: sig_index[k] outside [0, n_sig)
+    int64_t len;          // lengths[sig] taken into [0, cap]
+    int64_t nf;           // drnmf_stft_frames(len, N, hop)
+};
+
+__device__ __forceinline__ RaggedRow ragged_row(const int64_t* __restrict__ lengths,
+                                                const int* __restrict__ sig_index, int n_sig, int k,
+                                                int64_t cap, int N, int hop) {
+    RaggedRow r;
+    r.sig = sig_index[k];
+    if (r.sig < 0 || r.sig >= n_sig) {
+        r.sig = -1;
+        r.len = 0;
+        r.nf = 0;
+        return r;
+    }
+    int64_t len = lengths[r.sig];
+    len = len < 0 ? 0 : (len > cap ? cap : len);
+    r.len = len;
+    const int64_t nfram = (len + hop - 1) / hop;                 // as drnmf_stft_frames
+    r.nf = 1 + (nfram * hop + (int64_t)N) / hop;
+    return r;
+}
+
+// samples a row's reconstruction has: istft_mc trims N on both sides of N + hop (nf - 1) (util.py:203-226)
+__device__ __forceinline__ int64_t ragged_nout(const RaggedRow& r, int N, int hop, int crop,
+                                               int64_t stride_y) {
+    int64_t n = (int64_t)hop * (r.nf - 1) - N;
+    if (n < 0) n = 0;
+    if (crop && r.len < n) n = r.len;
+    return n < stride_y ? n : stride_y;
+}
+
+template <int R, int P>
+__global__ void __launch_bounds__(256)
+stft_real_ragged_kernel(const void* __restrict__ pcm, int is_int16, int64_t stride,
+                        const int64_t* __restrict__ lengths, const int* __restrict__ sig_index, int n_sig,
+                        int T, int logN, int hop, float mask_value, float* __restrict__ x,
+                        float* __restrict__ re, float* __restrict__ im) {
+    constexpr int N = RealFft<R, P>::N, F = N / 2 + 1;
+    __shared__ float2 tw[N / 2];
+    __shared__ float2 bufs[4][RealFft<R, P>::MP];
+    const int tid = threadIdx.x, wv = tid >> 6, j = tid & 63;
+    const int frame = blockIdx.x * 4 + wv, k = blockIdx.y;
+    for (int i = tid; i < N / 2; i += 256) tw[i] = g_twiddle[logN - TAB_LOG_MIN][i];
+    __syncthreads();
+    if (frame >= T) return;                   // (whole waves: no barrier below)
+    const RaggedRow row = ragged_row(lengths, sig_index, n_sig, k, stride, N, hop);
+    const size_t o = ((size_t)k * T + frame) * F;
+    if (frame >= row.nf) {                    // padding frame: Masking's value in every bin
+        for (int i = j; i < F; i += 64) x[o + i] = mask_value;
+        return;
+    }
+    stft_real_frame<R, P>(pcm, is_int16, (size_t)row.sig * stride, row.len, logN, hop, frame, o, x, re, im,
+                          tw, bufs[wv], j);
+}
+
+__global__ void __launch_bounds__(256)
+stft_ragged_kernel(const void* __restrict__ pcm, int is_int16, int64_t stride,
+                   const int64_t* __restrict__ lengths, const int* __restrict__ sig_index, int n_sig, int T,
+                   int N, int logN, int hop, float mask_value, float* __restrict__ x,
+                   float* __restrict__ re, float* __restrict__ im) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float2* buf = (float2*)smem;
+    float2* tw = buf + N;
+    const int frame = blockIdx.x, k = blockIdx.y, F = N / 2 + 1;
+    const RaggedRow row = ragged_row(lengths, sig_index, n_sig, k, stride, N, hop);
+    const size_t o = ((size_t)k * T + frame) * F;
+    if (frame >= row.nf) {                    // (the whole workgroup: no barrier is skipped by a part of it)
+        for (int i = threadIdx.x; i < F; i += 256) x[o + i] = mask_value;
+        return;
+    }
+    stft_frame(pcm, is_int16, (size_t)row.sig * stride, row.len, N, logN, hop, frame, o, x, re, im, buf, tw,
+               threadIdx.x);
+}
+
+// Masked inverse for N = 512 / 1024, the mirror of stft_real_kernel.  The frame is real, so its N samples are
+// ONE complex transform of M = N/2 points: with W_k = mask_k S_k (Hermitian, the imaginary parts of W_0 and
+// W_M dropped as the real part of the full transform drops them) and x[n] = sum_{k<N} W_k e^{-2 pi i k n / N},
+//   z[n] = x[2n] + i x[2n+1] = sum_{k<M} Z_k e^{-2 pi i k n / M},
+//   Z_k = (W_k + conj W_{M-k}) + i e^{-2 pi i k / N} (W_k - conj W_{M-k}),
+// the inverse of the forward kernel's split.  One wave per frame runs the same Stockham passes and leaves
+// x * window * 2 / (N / hop) / N in its LDS slice.
+//
+// A workgroup owns a run of `run` = C hop consecutive output samples of one signal (<= 2048: 8 per thread, in
+// registers) and computes EVERY frame that overlaps the run, four at a time in ascending order; after each
+// group of four, thread i adds the frames covering its samples, again ascending.  A sample is therefore the
+// sum of its frames in ascending frame order starting from 0, whatever the run, slab or batch: bitwise
+// reproducible, no atomics, no frames workspace, every sample of y written once (zeros behind the row's own
+// length included).  The N/hop - 1 frames a run shares with each neighbour are recomputed, not exchanged.
+template <int R, int P>
+__global__ void __launch_bounds__(256)
+istft_real_ragged_kernel(const float* __restrict__ re, const float* __restrict__ im,
+                         const float* __restrict__ mask, int64_t ld_mask,
+                         const int64_t* __restrict__ lengths, const int* __restrict__ sig_index, int n_sig,
+                         int T, int logN, int hop, int run, int crop, float* __restrict__ y,
+                         int64_t stride_y) {
+    constexpr int M = RealFft<R, P>::M, N = 2 * M, F = M + 1, MP = RealFft<R, P>::MP;
+    constexpr int SPT = 8;                    // samples per thread: run <= 256 SPT
+    __shared__ float2 tw[N / 2];
+    __shared__ float2 bufs[4][MP];
+    auto pad = [](int i) { return RealFft<R, P>::pad(i); };
+    const int tid = threadIdx.x, wv = tid >> 6, j = tid & 63;
+    const int k = blockIdx.y;
+    const RaggedRow row = ragged_row(lengths, sig_index, n_sig, k, (int64_t)1 << 40, N, hop);
+    if (row.sig < 0) return;                  // (uniform over the workgroup, as every exit below)
+    const int64_t nout = ragged_nout(row, N, hop, crop, stride_y);
+    const int64_t s0 = (int64_t)blockIdx.x * run;
+    float* __restrict__ yrow = y + (size_t)row.sig * stride_y;
+    if (s0 >= nout) {                         // behind the row's samples: zeros
+#pragma unroll
+        for (int q = 0; q < SPT; ++q) {
+            const int i = tid + 256 * q;
+            if (i < run && s0 + i < stride_y) yrow[s0 + i] = 0.f;
+        }
+        return;
+    }
+    for (int i = tid; i < N / 2; i += 256) tw[i] = g_twiddle[logN - TAB_LOG_MIN][i];
+    __syncthreads();
+    const float* __restrict__ win = g_window[logN - TAB_LOG_MIN];
+    const float scale = (2.0f / ((float)N / (float)hop)) / (float)N;
+    // sample s is position p = s + N of the untrimmed signal; frame f covers [f hop, f hop + N)
+    const int64_t s1 = s0 + run < nout ? s0 + run : nout;          // samples [s0, s1) are summed
+    const int64_t nfe = row.nf < T ? row.nf : T;                   // frames at or behind T are dropped
+    const int64_t f_lo = s0 / hop + 1;                             // first f with f hop + N - 1 >= s0 + N
+    int64_t f_hi = (s1 - 1 + N) / hop;                             // last f with f hop <= s1 - 1 + N
+    if (f_hi > nfe - 1) f_hi = nfe - 1;
+    float acc[SPT];
+#pragma unroll
+    for (int q = 0; q < SPT; ++q) acc[q] = 0.f;
+    float2* cur = bufs[wv];
+    for (int64_t fb = f_lo; fb <= f_hi; fb += 4) {
+        const int64_t f = fb + wv;
+        if (f <= f_hi) {
+            const size_t o = ((size_t)k * T + (size_t)f) * F;
+            const size_t om = ((size_t)k * T + (size_t)f) * (size_t)ld_mask;
+            float2 v[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int ka = j + r * (M / R), kc = M - ka;       // 0 <= ka < M, 1 <= kc <= M
+                const float ma = mask ? mask[om + ka] : 1.f, mc = mask ? mask[om + kc] : 1.f;
+                float2 a = make_float2(ma * re[o + ka], ma * im[o + ka]);
+                float2 c = make_float2(mc * re[o + kc], mc * im[o + kc]);
+                if (ka == 0) {
+                    a.y = 0.f;
+                    c.y = 0.f;
+                }
+                const float2 A = make_float2(a.x + c.x, a.y - c.y);   // W_k + conj W_{M-k}
+                const float2 B = make_float2(a.x - c.x, a.y + c.y);   // W_k - conj W_{M-k}
+                const float2 wB = cmul(B, tw[ka]);
+                v[r] = make_float2(A.x - wB.y, A.y + wB.x);           // A + i w B
+            }
+            stockham_passes<R, P>(v, cur, tw, j);
+#pragma unroll
+            for (int i = 0; i < M / 64; ++i) {
+                const int n = j + 64 * i;
+                const float2 z = cur[pad(n)];
+                const float2 w2 = *(const float2*)(win + 2 * n);
+                cur[pad(n)] = make_float2(z.x * scale * w2.x, z.y * scale * w2.y);
+            }
+        }
+        __syncthreads();
+        // sample i of the run sits at n = s0 + i + N - f hop of frame f (|s0 - f hop| < run + N + hop: int)
+        const int nb = (int)(s0 + N - fb * hop), wmax = (int)(f_hi - fb);
+#pragma unroll
+        for (int q = 0; q < SPT; ++q) {
+            const int i = tid + 256 * q;
+            if (i < run) {
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const int n = nb + i - w * hop;
+                    if (w <= wmax && n >= 0 && n < N) {
+                        const float2 z = bufs[w][pad(n >> 1)];
+                        acc[q] += (n & 1) ? z.y : z.x;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < SPT; ++q) {
+        const int i = tid + 256 * q;
+        const int64_t s = s0 + i;
+        if (i < run && s < stride_y) yrow[s] = s < nout ? acc[q] : 0.f;
+    }
+}
+
+// other sizes: the two-stage scheme of drnmf_istft_masked on a [b][T][N] frames buffer
+__global__ void __launch_bounds__(256)
+istft_frames_ragged_kernel(const float* __restrict__ re, const float* __restrict__ im,
+                           const float* __restrict__ mask, int64_t ld_mask,
+                           const int64_t* __restrict__ lengths, const int* __restrict__ sig_index, int n_sig,
+                           int T, int N, int logN, int hop, float* __restrict__ frames) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float2* buf = (float2*)smem;
+    float2* tw = buf + N;
+    const int frame = blockIdx.x, k = blockIdx.y;
+    const RaggedRow row = ragged_row(lengths, sig_index, n_sig, k, (int64_t)1 << 40, N, hop);
+    if (frame >= row.nf) return;              // (the whole workgroup)
+    const size_t fr = (size_t)k * T + frame;
+    istft_frame(re, im, mask, fr * (N / 2 + 1), fr * (size_t)ld_mask, N, logN, hop, frames + fr * N, buf, tw,
+                threadIdx.x);
+}
+
+__global__ void __launch_bounds__(256)
+overlap_add_ragged_kernel(const float* __restrict__ frames, const int64_t* __restrict__ lengths,
+                          const int* __restrict__ sig_index, int n_sig, int T, int N, int hop, int crop,
+                          float* __restrict__ y, int64_t stride_y) {
+    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int k = blockIdx.y;
+    const RaggedRow row = ragged_row(lengths, sig_index, n_sig, k, (int64_t)1 << 40, N, hop);
+    if (row.sig < 0 || s >= stride_y) return;
+    const int64_t nout = ragged_nout(row, N, hop, crop, stride_y);
+    const int64_t nfe = row.nf < T ? row.nf : T;
+    float acc = 0.f;
+    if (s < nout) {
+        const int64_t p = s + N;                                  // index in the untrimmed signal
+        int64_t j0 = (p - N + hop) / hop;                         // ceil((p - N + 1) / hop)
+        int64_t j1 = p / hop;
+        if (j1 > nfe - 1) j1 = nfe - 1;
+        for (int64_t j = j0; j <= j1; ++j) acc += frames[((size_t)k * T + j) * N + (p - j * hop)];
+    }
+    y[(size_t)row.sig * stride_y + s] = acc;
 }
 
 }  // namespace
@@ -494,6 +766,109 @@ extern "C" int32_t drnmf_snr(drnmf_handle_t h, int32_t n_sig, int64_t nsampl, co
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snr: bad argument");
     hipLaunchKernelGGL(snr_kernel, dim3((unsigned)n_sig), dim3(256), 0, (hipStream_t)stream_, est,
                        ref, nsampl, out_db);
+    DRNMF_HIP(h, hipGetLastError());
+    return DRNMF_OK;
+}
+
+// ---- ragged batches (include/drnmf_enhance.h) ------------------------------------------------------------
+static bool istft_ragged_fused(int N, int hop) { return stft_fast(N) && hop <= N; }
+
+static int ragged_run(int hop) {              // samples per workgroup of the fused inverse: C hop <= 2048
+    const int C = 2048 / hop;
+    return (C < 1 ? 1 : C) * hop;
+}
+
+extern "C" int32_t drnmf_stft_ragged(drnmf_handle_t h, int32_t n_sig, int64_t stride, const int64_t* lengths,
+                                     int32_t b, const int32_t* sig_index, int32_t T, int32_t N, int32_t hop,
+                                     int32_t is_int16, float mask_value, const void* pcm, float* x, float* re,
+                                     float* im, void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    if (n_sig <= 0 || stride <= 0 || b <= 0 || b > 65535 || T <= 0 || hop <= 0)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG,
+                   "stft_ragged: bad shape n_sig=%d stride=%lld b=%d (1..65535) T=%d hop=%d", n_sig,
+                   (long long)stride, b, T, hop);
+    if (N < 64 || N > 4096 || (N & (N - 1)))
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stft_ragged: N=%d must be a power of two in [64,4096]", N);
+    if (!lengths || !sig_index || !pcm || !x || !re || !im)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stft_ragged: NULL pointer argument");
+    int logN = 0;
+    while ((1 << logN) < N) ++logN;
+    hipStream_t stream = (hipStream_t)stream_;
+    {
+        const int32_t trc = ensure_fft_tables(h, N, logN, stream);
+        if (trc) return trc;
+    }
+    if (stft_fast(N)) {
+        const dim3 grid((unsigned)((T + 3) / 4), (unsigned)b);
+        if (N == 1024)
+            hipLaunchKernelGGL((stft_real_ragged_kernel<8, 3>), grid, dim3(256), 0, stream, pcm, is_int16,
+                               stride, lengths, sig_index, n_sig, T, logN, hop, mask_value, x, re, im);
+        else
+            hipLaunchKernelGGL((stft_real_ragged_kernel<4, 4>), grid, dim3(256), 0, stream, pcm, is_int16,
+                               stride, lengths, sig_index, n_sig, T, logN, hop, mask_value, x, re, im);
+    } else {
+        const size_t shmem = (size_t)(N + N / 2) * sizeof(float2);
+        hipLaunchKernelGGL(stft_ragged_kernel, dim3((unsigned)T, (unsigned)b), dim3(256), shmem, stream, pcm,
+                           is_int16, stride, lengths, sig_index, n_sig, T, N, logN, hop, mask_value, x, re,
+                           im);
+    }
+    DRNMF_HIP(h, hipGetLastError());
+    return DRNMF_OK;
+}
+
+extern "C" size_t drnmf_istft_ragged_workspace_bytes(int32_t b, int32_t T, int32_t N, int32_t hop) {
+    if (b <= 0 || T <= 0 || N <= 0 || hop <= 0 || istft_ragged_fused(N, hop)) return 0;
+    return round_up_sz((size_t)b * T * N * sizeof(float), 256);
+}
+
+extern "C" int32_t drnmf_istft_ragged(drnmf_handle_t h, int32_t n_sig, int32_t b, int32_t T, int32_t N,
+                                      int32_t hop, const int64_t* lengths, const int32_t* sig_index,
+                                      const float* re, const float* im, const float* mask, int64_t ld_mask,
+                                      float* y, int64_t stride_y, int32_t crop, void* workspace,
+                                      size_t workspace_bytes, void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    if (n_sig <= 0 || b <= 0 || b > 65535 || T <= 0 || hop <= 0 || stride_y <= 0 || (crop != 0 && crop != 1))
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG,
+                   "istft_ragged: bad shape n_sig=%d b=%d (1..65535) T=%d hop=%d stride_y=%lld crop=%d", n_sig,
+                   b, T, hop, (long long)stride_y, crop);
+    if (N < 64 || N > 4096 || (N & (N - 1)))
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "istft_ragged: N=%d must be a power of two in [64,4096]", N);
+    if (!lengths || !sig_index || !re || !im || !y)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "istft_ragged: NULL pointer argument");
+    if (mask && ld_mask < N / 2 + 1)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "istft_ragged: ld_mask=%lld is below N/2+1=%d",
+                   (long long)ld_mask, N / 2 + 1);
+    const size_t need = drnmf_istft_ragged_workspace_bytes(b, T, N, hop);
+    if (need && (!workspace || workspace_bytes < need))
+        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "istft_ragged: workspace too small (%zu < %zu bytes)",
+                   workspace ? workspace_bytes : (size_t)0, need);
+    int logN = 0;
+    while ((1 << logN) < N) ++logN;
+    hipStream_t stream = (hipStream_t)stream_;
+    {
+        const int32_t trc = ensure_fft_tables(h, N, logN, stream);
+        if (trc) return trc;
+    }
+    if (istft_ragged_fused(N, hop)) {
+        const int run = ragged_run(hop);
+        const dim3 grid((unsigned)((stride_y + run - 1) / run), (unsigned)b);
+        if (N == 1024)
+            hipLaunchKernelGGL((istft_real_ragged_kernel<8, 3>), grid, dim3(256), 0, stream, re, im, mask,
+                               ld_mask, lengths, sig_index, n_sig, T, logN, hop, run, crop, y, stride_y);
+        else
+            hipLaunchKernelGGL((istft_real_ragged_kernel<4, 4>), grid, dim3(256), 0, stream, re, im, mask,
+                               ld_mask, lengths, sig_index, n_sig, T, logN, hop, run, crop, y, stride_y);
+    } else {
+        float* frames = (float*)workspace;
+        const size_t shmem = (size_t)(N + N / 2) * sizeof(float2);
+        hipLaunchKernelGGL(istft_frames_ragged_kernel, dim3((unsigned)T, (unsigned)b), dim3(256), shmem,
+                           stream, re, im, mask, ld_mask, lengths, sig_index, n_sig, T, N, logN, hop, frames);
+        hipLaunchKernelGGL(overlap_add_ragged_kernel, dim3((unsigned)((stride_y + 255) / 256), (unsigned)b),
+                           dim3(256), 0, stream, frames, lengths, sig_index, n_sig, T, N, hop, crop, y,
+                           stride_y);
+    }
     DRNMF_HIP(h, hipGetLastError());
     return DRNMF_OK;
 }

@@ -1076,6 +1076,22 @@ class _SequenceModel(object):
     PREDICT_T_STEP = 32     # slab lengths are rounded up to a multiple of this many frames (graph reuse)
     HOST_COPY_THREADS = 8   # worker threads of predict's host-side staging copies
 
+    @classmethod
+    def length_sorted_slabs(cls, lens, batch_size, T_cap=None):
+        """The slabs of a length-aware run: a stable sort by length, longest first (the largest buffers come
+        first), batch_size neighbours per slab, each slab's T its longest length rounded up to PREDICT_T_STEP
+        (at least 1, at most T_cap).  Returns [(indices, T), ...]; `predict` and `enhance` both form their slabs
+        here."""
+        lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+        order = np.argsort(-lens, kind='stable')
+        step = cls.PREDICT_T_STEP
+        slabs = []
+        for lo in range(0, lens.shape[0], int(batch_size)):
+            idx = order[lo:lo + int(batch_size)]
+            Ts = max(1, -(-int(lens[idx].max()) // step) * step)
+            slabs.append((idx, int(Ts if T_cap is None else min(int(T_cap), Ts))))
+        return slabs
+
     def _host_pool(self):
         pool = getattr(self, '_host_pool_obj', None)
         if pool is None:
@@ -1125,13 +1141,7 @@ class _SequenceModel(object):
                 lens = np.asarray(lengths, dtype=np.int64).reshape(-1)
                 if lens.shape[0] != n or (lens < 0).any() or (lens > T).any():
                     raise ValueError('predict: lengths must be %d values in [0, %d]' % (n, T))
-            order = np.argsort(-lens, kind='stable')          # longest first: the largest buffers come first
-            step = self.PREDICT_T_STEP
-            slabs = []
-            for lo in range(0, n, bs):
-                idx = order[lo:lo + bs]
-                Ts = int(min(T, max(1, -(-int(lens[idx].max()) // step) * step)))
-                slabs.append((idx, Ts))
+            slabs = self.length_sorted_slabs(lens, bs, T)
         else:
             # (a stateful layer carries row i's state to row i of the next batch: order and length stay)
             slabs = [(np.arange(lo, min(lo + bs, n)), T) for lo in range(0, n, bs)]
@@ -1224,6 +1234,161 @@ class _SequenceModel(object):
             main.synchronize()
         ops.check_status(dev)
         return out
+
+    def _input_width(self):
+        raise NotImplementedError
+
+    @staticmethod
+    def _pack_waveforms(wavs, lengths, what):
+        """(list of 1-D arrays | 2-D array + lengths | 2-D tensor + lengths) -> (rows, host lengths, dtype): rows
+        is a list of 1-D numpy arrays, or a 2-D device tensor."""
+        if isinstance(wavs, torch.Tensor):
+            if wavs.dim() != 2 or wavs.dtype not in (torch.int16, torch.float32) or lengths is None:
+                raise ValueError('enhance: a %s tensor must be 2-D int16 / float32 and come with lengths=' % what)
+            lens = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths,
+                              dtype=np.int64).reshape(-1)
+            if lens.shape[0] != wavs.shape[0] or (len(lens) and (lens.min() < 1 or lens.max() > wavs.shape[1])):
+                raise ValueError('enhance: lengths must be %d values in [1, %d]' % tuple(wavs.shape))
+            return wavs, lens, np.dtype('int16' if wavs.dtype == torch.int16 else 'float32')
+        if isinstance(wavs, np.ndarray) and wavs.ndim == 2:
+            if lengths is None:
+                raise ValueError('enhance: a 2-D %s array comes with lengths=' % what)
+            lens = np.asarray(lengths, dtype=np.int64).reshape(-1)
+            if lens.shape[0] != wavs.shape[0] or (len(lens) and (lens.min() < 1 or lens.max() > wavs.shape[1])):
+                raise ValueError('enhance: lengths must be %d values in [1, %d]' % wavs.shape)
+            rows = [wavs[i, :int(lens[i])] for i in range(wavs.shape[0])]
+        else:
+            if lengths is not None:
+                raise ValueError('enhance: lengths= goes with a 2-D array, not with a list')
+            rows = [np.asarray(w) for w in wavs]
+        if not rows:
+            raise ValueError('enhance: no %s waveforms' % what)
+        dt = rows[0].dtype
+        if dt not in (np.dtype('int16'), np.dtype('float32')):
+            raise ValueError('enhance: %s waveforms must be int16 or float32 (got %s)' % (what, dt))
+        for w in rows:
+            if w.ndim != 1 or w.dtype != dt or w.shape[0] < 1:
+                raise ValueError('enhance: every %s waveform must be a non-empty 1-D %s array' % (what, dt))
+        return rows, np.array([w.shape[0] for w in rows], dtype=np.int64), dt
+
+    def enhance(self, wavs, N=512, hop=128, batch_size=250, crop=False, dtype='int16', ref=None, fs=16000,
+                return_masks=False, lengths=None, ref_lengths=None):
+        """The reference's enhancement loop (enhance.py:1181-1203; audio_dataset.py:267-339: STFT, padding, the
+        model, reconstruct_x, wavwrite) as ONE call, on the device from the samples to the samples.  wavs: a list
+        of 1-D int16 (scaled by 1/32768, util.py:29-35) or float32 numpy arrays, or a 2-D array / device tensor
+        with lengths=.  Returns a list of 1-D numpy arrays in the caller's order: int16 as util.wavwrite writes
+        them (each utterance normalised by its own peak if that exceeds 1), or, dtype='float32', the
+        reconstruction itself.  Utterance i has ceil(len_i / hop) * hop samples (what reconstruct_x returns), or
+        len_i with crop=True.
+
+        The packed samples, lengths and slab lists go up in one pinned copy and the result comes down in one;
+        in between, per slab (formed as `predict` forms them, by frame count): ops.stft_ragged gathers the slab's
+        rows into [b, T, F] with the padding the model's Masking expects, self.forward runs, ops.istft_ragged
+        scatters the masked inverse into the caller's order; one ops.to_int16_wav_rows at the end.  A stateful
+        model raises NotImplementedError (its rows must keep their order and length).
+
+        ref= (the clean waveforms, same container types; ref_lengths= with a 2-D array): returns (wavs_out, S,
+        labels) with S = ops.compute_scores(int16 output / 32768, ref, fs, ...): the rows the reference gets for
+        the files it wrote and read back (audio_dataset.py:399-435, score_audio.m:184-203); SegSNR / PESQ stay
+        NaN.  return_masks=True appends the list of (n_frames_i, F) masks.  No file IO, no resampling."""
+        if dtype not in ('int16', 'float32'):
+            raise ValueError("enhance: dtype must be 'int16' or 'float32'")
+        N, hop, bs = int(N), int(hop), int(batch_size)
+        if bs <= 0 or hop <= 0:
+            raise ValueError('enhance: batch_size and hop must be positive')
+        F = N // 2 + 1
+        if F != self._input_width():
+            raise ValueError('enhance: N = %d gives %d bins, the model takes %d' % (N, F, self._input_width()))
+        if self._stateful():
+            raise NotImplementedError('enhance: a stateful model needs its rows in order and at one length; '
+                                      'use predict_on_batch')
+        dev = torch.device(self._device())
+        rows, lens, dt = self._pack_waveforms(wavs, lengths, 'noisy')
+        n = lens.shape[0]
+        if n > 65535:
+            raise ValueError('enhance: at most 65535 utterances per call')
+        stride = int(lens.max())
+        nf = np.array([ops.stft_frames(int(l), N, hop) for l in lens], dtype=np.int64)
+        slabs = self.length_sorted_slabs(nf, min(bs, n))
+        n_out = ops.ragged_out_lengths(lens, N, hop, crop)
+        stride_y = max(1, int(n_out.max()))
+
+        # one pinned upload: lengths [n] int64 | output lengths [n] int64 | slab lists [n] int32 | samples
+        off_idx, off_pcm = 16 * n, -(-(20 * n) // 16) * 16
+        on_dev = isinstance(rows, torch.Tensor)
+        pcm_bytes = 0 if on_dev else n * stride * dt.itemsize
+        host = torch.empty(off_pcm + pcm_bytes, dtype=torch.uint8, pin_memory=True)
+        hn = host.numpy()
+        hn[:8 * n].view(np.int64)[:] = lens
+        hn[8 * n:16 * n].view(np.int64)[:] = n_out
+        hn[off_idx:off_idx + 4 * n].view(np.int32)[:] = np.concatenate([idx for idx, _ in slabs])
+        if not on_dev:
+            pk = hn[off_pcm:].view(dt).reshape(n, stride)
+            for i, w in enumerate(rows):
+                pk[i, :w.shape[0]] = w
+                pk[i, w.shape[0]:] = 0
+        packed = host.to(dev, non_blocking=True)
+        lens_d, nout_d = packed[:8 * n].view(torch.int64), packed[8 * n:16 * n].view(torch.int64)
+        idx_d = packed[off_idx:off_idx + 4 * n].view(torch.int32)
+        if on_dev:
+            pcm = rows.to(dev).contiguous()
+            stride = pcm.shape[1]
+        else:
+            pcm = packed[off_pcm:].view(torch.int16 if dt == np.dtype('int16') else torch.float32).view(n, stride)
+
+        b0, T0 = len(slabs[0][0]), max(Ts for _, Ts in slabs)
+        cap = max(len(idx) * Ts for idx, Ts in slabs) * F
+        bufs = [torch.empty(cap, dtype=torch.float32, device=dev) for _ in range(3)]
+        y = torch.empty((n, stride_y), dtype=torch.float32, device=dev)
+        ws_bytes = max(_capi.lib().drnmf_istft_ragged_workspace_bytes(len(idx), Ts, N, hop) for idx, Ts in slabs)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        masks = [None] * n if return_masks else None
+        lo = 0
+        try:
+            for idx, Ts in slabs:
+                b = len(idx)
+                x, re, im = (t[:b * Ts * F].view(b, Ts, F) for t in bufs)
+                sl = idx_d[lo:lo + b]
+                lo += b
+                ops.stft_ragged_enqueue(pcm, lens_d, sl, Ts, N, hop, self.mask_value, x, re, im)
+                mask = self.forward(x)
+                if mask.shape[-1] != F:
+                    raise ValueError('enhance: the model returns %d bins for %d' % (mask.shape[-1], F))
+                ops.istft_ragged_enqueue(re, im, mask, lens_d, sl, N, hop, y, crop, workspace=ws)
+                if return_masks:
+                    mh = mask.cpu().numpy()
+                    for k, i in enumerate(idx):
+                        masks[int(i)] = mh[k, :int(nf[i])].copy()
+            q = None
+            if dtype == 'int16' or ref is not None:
+                q = torch.empty((n, stride_y), dtype=torch.int16, device=dev)
+                ops.to_int16_wav_rows_enqueue(y, nout_d, q)
+            res = q if dtype == 'int16' else y
+            back = torch.empty(res.shape, dtype=res.dtype, pin_memory=True)
+            back.copy_(res, non_blocking=True)
+        finally:
+            torch.cuda.current_stream(dev).synchronize()
+        ops.check_status(dev)
+        bn = back.numpy()
+        out = [bn[i, :int(n_out[i])].copy() for i in range(n)]
+        ret = [out]
+        if ref is not None:
+            rrows, rlens, rdt = self._pack_waveforms(ref, ref_lengths, 'clean')
+            if rlens.shape[0] != n:
+                raise ValueError('enhance: %d clean waveforms for %d noisy ones' % (rlens.shape[0], n))
+            if isinstance(rrows, torch.Tensor):
+                rd = rrows.to(dev)
+            else:
+                rp = np.zeros((n, int(rlens.max())), dtype=rdt)
+                for i, w in enumerate(rrows):
+                    rp[i, :w.shape[0]] = w
+                rd = torch.from_numpy(rp).to(dev)
+            rd = rd.to(torch.float32) / 32768.0 if rd.dtype == torch.int16 else rd
+            S, labels = ops.compute_scores(q.to(torch.float32) / 32768.0, rd, fs, n_out, rlens)
+            ret += [S, labels]
+        if return_masks:
+            ret.append(masks)
+        return ret[0] if len(ret) == 1 else tuple(ret)
 
     def free_predict_buffers(self):
         """Drop the pinned staging buffers, device slabs and copy streams `predict` / `predict_on_batch` keep
@@ -1598,6 +1763,9 @@ class UnfoldedSNMFModel(_SequenceModel):
 
     def _output_width(self):
         return int(self.clean.kernel.shape[1])
+
+    def _input_width(self):
+        return int(self.cell.input_dim)
 
     def _stateful(self):
         return bool(getattr(self.cell, 'stateful', False))
@@ -2154,6 +2322,9 @@ class LSTMModel(_SequenceModel):
         return self.device
 
     def _output_width(self):
+        return self.dense.units
+
+    def _input_width(self):
         return self.dense.units
 
     # -- training (enhance.py:1260-1312): loss 'mse_of_masked' = mse(Masking output * sigmoid output, y) with

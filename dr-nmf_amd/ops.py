@@ -984,6 +984,177 @@ def to_int16_wav(x):
     return out
 
 
+# ---- ragged batches: STFT into the model's layout, masked inverse, int16 per row (include/drnmf_enhance.h) ----
+def _ragged_lengths(lengths, n_sig, width, dev, what):
+    """lengths (host ints, numpy or a tensor on any device) -> (host int64 numpy, device int64 tensor); every
+    length must lie in [1, width]."""
+    if isinstance(lengths, torch.Tensor):
+        ld = lengths.to(device=dev, dtype=torch.int64).contiguous().reshape(-1) if lengths.is_cuda else None
+        lh = lengths.detach().cpu().numpy()
+    else:
+        ld, lh = None, lengths
+    lh = np.ascontiguousarray(np.asarray(lh, dtype=np.int64).reshape(-1))
+    if lh.shape[0] != n_sig:
+        raise ValueError("%s: lengths has %d entries for %d signals" % (what, lh.shape[0], n_sig))
+    if n_sig and (lh.min() < 1 or lh.max() > width):
+        raise ValueError("%s: every length must lie in [1, %d] (got %d .. %d)" % (what, width, lh.min(), lh.max()))
+    if ld is None:
+        ld = torch.from_numpy(lh).to(dev)
+    return lh, ld
+
+
+def _ragged_index(sig_index, n_sig, dev, what):
+    if sig_index is None:
+        return torch.arange(n_sig, dtype=torch.int32, device=dev)
+    if isinstance(sig_index, torch.Tensor):
+        ih = sig_index.detach().cpu().numpy()
+    else:
+        ih = sig_index
+    ih = np.ascontiguousarray(np.asarray(ih, dtype=np.int64).reshape(-1))
+    if ih.shape[0] < 1 or ih.min() < 0 or ih.max() >= n_sig:
+        raise ValueError("%s: sig_index must hold at least one index, all in [0, %d)" % (what, n_sig))
+    if isinstance(sig_index, torch.Tensor) and sig_index.is_cuda and sig_index.dtype == torch.int32:
+        return sig_index.contiguous().reshape(-1)
+    return torch.from_numpy(ih.astype(np.int32)).to(dev)
+
+
+def ragged_out_lengths(lengths, N, hop, crop=False):
+    """Samples of each row's reconstruction: hop * (n_frames - 1) - N, which is ceil(len / hop) * hop when hop
+    divides N (what reconstruct_x returns); crop=True: at most the row's own length."""
+    lh = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    nf = 1 + (-(-lh // hop) * hop + N) // hop
+    n = np.maximum(hop * (nf - 1) - N, 0)
+    return np.minimum(n, lh) if crop else n
+
+
+def stft_ragged_enqueue(pcm, lengths_dev, sig_index_dev, T, N, hop, mask_value, x, re, im):
+    """drnmf_stft_ragged on tensors the caller owns and has checked: enqueues, reads nothing back."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(pcm))
+    n_sig, stride = pcm.shape
+    rc = L.drnmf_stft_ragged(h, n_sig, stride, _capi.ptr(lengths_dev), sig_index_dev.numel(),
+                             _capi.ptr(sig_index_dev), int(T), int(N), int(hop), int(pcm.dtype == torch.int16),
+                             float(mask_value), _capi.ptr(pcm), _capi.ptr(x), _capi.ptr(re), _capi.ptr(im),
+                             _stream())
+    _capi.check(rc, h, "drnmf_stft_ragged")
+
+
+def stft_ragged(pcm, lengths, sig_index=None, T=None, N=512, hop=None, mask_value=-1.0):
+    """STFT of a ragged batch straight into the model's layout.  pcm [n_sig, stride] int16 (scaled by 1/32768) or
+    float32 on the device, row i valid up to lengths[i] (host ints or a tensor, each in [1, stride]); sig_index [b]
+    (default: every row in order): slab row k is signal sig_index[k]; T: the slab's frame capacity (default: the
+    longest of the slab).  Returns (x, re, im, n_frames): x [b, T, N/2+1] the magnitude with mask_value in every
+    bin of the frames behind a row's own n_frames[k] (audio_dataset.py:144-146); re, im as `stft` returns them,
+    rows behind n_frames[k] unspecified; n_frames int64 numpy [b] = stft_frames(length, N, hop)."""
+    if hop is None:
+        hop = N // 2
+    if pcm.dim() == 1:
+        pcm = pcm[None]
+    if pcm.dim() != 2 or pcm.dtype not in (torch.int16, torch.float32):
+        raise ValueError("stft_ragged: pcm must be [n_sig, stride] int16 or float32")
+    dev = pcm.device
+    _dev_index(pcm)
+    pcm = pcm.contiguous()
+    n_sig, stride = pcm.shape
+    if n_sig < 1 or stride < 1 or int(hop) < 1:
+        raise ValueError("stft_ragged: empty batch or hop < 1")
+    lh, ld = _ragged_lengths(lengths, n_sig, stride, dev, "stft_ragged")
+    idx = _ragged_index(sig_index, n_sig, dev, "stft_ragged")
+    ih = np.arange(n_sig) if sig_index is None else idx.cpu().numpy()
+    nf = np.array([stft_frames(int(lh[i]), N, hop) for i in ih], dtype=np.int64)
+    if T is None:
+        T = int(nf.max())
+    if int(T) < int(nf.max()):
+        raise ValueError("stft_ragged: T = %d is below the slab's longest row (%d frames)" % (T, nf.max()))
+    shape = (idx.numel(), int(T), N // 2 + 1)
+    x = torch.empty(shape, dtype=torch.float32, device=dev)
+    re, im = torch.empty_like(x), torch.empty_like(x)
+    stft_ragged_enqueue(pcm, ld, idx, T, N, hop, mask_value, x, re, im)
+    return x, re, im, nf
+
+
+def istft_ragged_enqueue(re, im, mask, lengths_dev, sig_index_dev, N, hop, y, crop, workspace=None):
+    """drnmf_istft_ragged on tensors the caller owns and has checked: enqueues, reads nothing back."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(re))
+    b, T, F = re.shape
+    nbytes = L.drnmf_istft_ragged_workspace_bytes(b, T, int(N), int(hop))
+    if nbytes and (workspace is None or workspace.numel() < nbytes):
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=re.device)
+    rc = L.drnmf_istft_ragged(h, y.shape[0], b, T, int(N), int(hop), _capi.ptr(lengths_dev),
+                              _capi.ptr(sig_index_dev), _capi.ptr(re), _capi.ptr(im), _capi.ptr(mask),
+                              0 if mask is None else mask.stride(1), _capi.ptr(y), y.shape[1], int(bool(crop)),
+                              _capi.ptr(workspace), 0 if workspace is None else workspace.numel(), _stream())
+    _capi.check(rc, h, "drnmf_istft_ragged")
+
+
+def istft_ragged(re, im, mask, lengths, N, hop, sig_index=None, out=None, crop=False):
+    """Masked inverse of a slab: y[sig_index[k], :n_k] = istft_noDiv(mask[k] * (re[k] + i im[k])) (`istft_masked`
+    per row), zeros behind n_k = ragged_out_lengths(lengths, N, hop, crop)[sig_index[k]].  re, im, mask [b, T,
+    N/2+1] device float32 (mask may be None, or the model's output with a padded last stride); lengths [n_sig]
+    host ints or a tensor; out [n_sig, width] float32 (default: zeros of the widest row).  Rows of `out` that
+    sig_index does not name are left as they are.  A row's samples are bitwise the same in any batch."""
+    if re.dim() != 3 or re.shape != im.shape or re.shape[2] != N // 2 + 1:
+        raise ValueError("istft_ragged: re, im must be [b, T, %d] (got %s, %s)" % (N // 2 + 1, tuple(re.shape),
+                                                                                  tuple(im.shape)))
+    dev = re.device
+    _dev_index(re)
+    re, im = _f32c(re, "re"), _f32c(im, "im")
+    if im.device != dev:
+        raise ValueError("istft_ragged: re and im must be on one device")
+    b, T, F = re.shape
+    if mask is not None:
+        if mask.dtype != torch.float32 or mask.device != dev or tuple(mask.shape) != (b, T, F):
+            raise ValueError("istft_ragged: mask must be float32 %s on %s" % ((b, T, F), dev))
+        if mask.stride(2) != 1 or mask.stride(1) < F or mask.stride(0) != T * mask.stride(1):
+            mask = mask.contiguous()
+    if int(hop) < 1:
+        raise ValueError("istft_ragged: hop < 1")
+    if out is not None:
+        if out.dim() != 2 or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+            raise ValueError("istft_ragged: out must be a contiguous float32 [n_sig, width] tensor on %s" % dev)
+        n_sig = out.shape[0]
+    else:
+        n_sig = lengths.numel() if isinstance(lengths, torch.Tensor) else np.asarray(lengths).size
+    lh, ld = _ragged_lengths(lengths, n_sig, 1 << 40, dev, "istft_ragged")
+    idx = _ragged_index(sig_index, n_sig, dev, "istft_ragged")
+    if idx.numel() != b:
+        raise ValueError("istft_ragged: %d slab rows but sig_index names %d" % (b, idx.numel()))
+    if out is None:
+        out = torch.zeros((n_sig, max(1, int(ragged_out_lengths(lh, N, hop, crop).max()))), dtype=torch.float32,
+                          device=dev)
+    istft_ragged_enqueue(re, im, mask, ld, idx, N, hop, out, crop)
+    return out
+
+
+def to_int16_wav_rows_enqueue(y, lengths_dev, out, workspace=None):
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(y))
+    n_sig, stride = y.shape
+    nbytes = L.drnmf_wav_int16_rows_workspace_bytes(n_sig)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=y.device)
+    rc = L.drnmf_wav_int16_rows(h, n_sig, stride, _capi.ptr(lengths_dev), _capi.ptr(y), _capi.ptr(out),
+                                _capi.ptr(workspace), workspace.numel(), _stream())
+    _capi.check(rc, h, "drnmf_wav_int16_rows")
+
+
+def to_int16_wav_rows(y, lengths):
+    """`to_int16_wav` per row (util.wavwrite, util.py:37-45, one file per row): y [n_sig, stride] float32, row k
+    valid up to lengths[k]; row k of the int16 result equals to_int16_wav(y[k, :lengths[k]]) and is 0 behind it."""
+    if y.dim() != 2:
+        raise ValueError("to_int16_wav_rows: y must be [n_sig, stride]")
+    _dev_index(y)
+    y = _f32c(y, "y")
+    n_sig, stride = y.shape
+    if n_sig < 1 or stride < 1:
+        raise ValueError("to_int16_wav_rows: empty batch")
+    _, ld = _ragged_lengths(lengths, n_sig, stride, y.device, "to_int16_wav_rows")
+    out = torch.empty((n_sig, stride), dtype=torch.int16, device=y.device)
+    to_int16_wav_rows_enqueue(y, ld, out)
+    return out
+
+
 # ---- STOI and the compute_scores row (score_audio.m:177-238; C ABI in include/drnmf_score.h) ---------------
 STOI_BANDS = 15
 SCORE_LABELS = ['SDR', 'SNR', 'SegSNR local', 'SegSNR global', 'PESQ', 'STOI']
