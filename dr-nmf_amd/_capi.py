@@ -1,5 +1,6 @@
 """ctypes binding of libdrnmf.so (C ABI in include/drnmf.h; the LSTM baseline's in include/drnmf_lstm.h; the
-STOI score's in include/drnmf_score.h; the ragged STFT / iSTFT / int16 stages' in include/drnmf_enhance.h).
+STOI score's in include/drnmf_score.h; the ragged STFT / iSTFT / int16 stages' in include/drnmf_enhance.h; the
+device-side SDR's in include/drnmf_sdr.h).
 
 The library is the product path: there is NO fallback.  If the shared object is missing or a
 call fails, an exception is raised.
@@ -176,6 +177,13 @@ ENHANCE_SIGNATURES = {
     "drnmf_wav_int16_rows": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/drnmf_sdr.h one to one (a table of its own, like the three above)
+SDR_SIGNATURES = {
+    "drnmf_toeplitz_solve": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "drnmf_sdr_ragged_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "drnmf_sdr_ragged": (_i32, [_vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 _handles = {}
 
@@ -198,7 +206,8 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(LSTM_SIGNATURES.items()) +
-                                  list(SCORE_SIGNATURES.items()) + list(ENHANCE_SIGNATURES.items())):
+                                  list(SCORE_SIGNATURES.items()) + list(ENHANCE_SIGNATURES.items()) +
+                                  list(SDR_SIGNATURES.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

@@ -931,11 +931,79 @@ def snr_db(est, ref):
     return out
 
 
-def sdr_db(est, ref, flen=512, return_parts=False):
+def toeplitz_solve(r, d):
+    """Solve the symmetric Toeplitz systems Toeplitz(r[k]) c[k] = d[k] on the device (Levinson-Durbin, fp64;
+    include/drnmf_sdr.h).  r, d: device float64 [n_sys, n] (or 1-D), n <= 2048.  Returns (c, info): c like r,
+    info int32 [n_sys] -- 0 solved, 1 r[0] <= 0 or not finite (c = 0), 2 + k the recursion stopped at step k."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(r))
+    if r.dtype != torch.float64 or d.dtype != torch.float64 or r.shape != d.shape or r.device != d.device:
+        raise ValueError("toeplitz_solve: r and d must be float64 tensors of one shape on one device")
+    one = r.dim() == 1
+    r2, d2 = (r[None], d[None]) if one else (r, d)
+    if r2.dim() != 2 or r2.shape[0] < 1:
+        raise ValueError("toeplitz_solve: r and d must be [n_sys, n] with n_sys >= 1")
+    r2, d2 = r2.contiguous(), d2.contiguous()
+    n_sys, n = r2.shape
+    c = torch.empty_like(r2)
+    info = torch.empty(n_sys, dtype=torch.int32, device=r2.device)
+    rc = L.drnmf_toeplitz_solve(h, n_sys, n, _capi.ptr(r2), _capi.ptr(d2), _capi.ptr(c), _capi.ptr(info), _stream())
+    _capi.check(rc, h, "drnmf_toeplitz_solve")
+    return (c[0] if one else c), info
+
+
+SDR_SOLVERS = ("host", "device")
+
+
+def _sdr_lengths(lengths, n_sig, width, dev):
+    """As _ragged_lengths, with 0 allowed (a row of length 0 is a silent pair).  A device tensor is not read
+    back: the kernels clamp it into [0, width]."""
+    if lengths is None:
+        return None
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        ld = lengths.to(device=dev, dtype=torch.int64).contiguous().reshape(-1)
+        if ld.numel() != n_sig:
+            raise ValueError("sdr_db: lengths has %d entries for %d signals" % (ld.numel(), n_sig))
+        return ld
+    lh = lengths.detach().cpu().numpy() if isinstance(lengths, torch.Tensor) else lengths
+    lh = np.ascontiguousarray(np.asarray(lh, dtype=np.int64).reshape(-1))
+    if lh.shape[0] != n_sig:
+        raise ValueError("sdr_db: lengths has %d entries for %d signals" % (lh.shape[0], n_sig))
+    if n_sig and (lh.min() < 0 or lh.max() > width):
+        raise ValueError("sdr_db: every length must lie in [0, %d] (got %d .. %d)" % (width, lh.min(), lh.max()))
+    return torch.from_numpy(lh).to(dev)
+
+
+def sdr_ragged_enqueue(est, ref, lengths_dev, flen, out, coef=None, energies=None, r=None, d=None, info=None,
+                       workspace=None):
+    """drnmf_sdr_ragged on tensors the caller owns and has checked: enqueues, reads nothing back."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(est))
+    n_sig, stride = est.shape
+    nbytes = L.drnmf_sdr_ragged_workspace_bytes(n_sig, stride, int(flen))
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=est.device)
+    rc = L.drnmf_sdr_ragged(h, n_sig, stride, _capi.ptr(lengths_dev), int(flen), _capi.ptr(est), _capi.ptr(ref),
+                            _capi.ptr(out), _capi.ptr(coef), _capi.ptr(energies), _capi.ptr(r), _capi.ptr(d),
+                            _capi.ptr(info), _capi.ptr(workspace), workspace.numel(), _stream())
+    _capi.check(rc, h, "drnmf_sdr_ragged")
+
+
+def sdr_db(est, ref, flen=512, return_parts=False, lengths=None, solver="host"):
     """SDR per signal as `bss_eval_sources(xest', xref')` computes it for one source
     (score_audio.m:206; BSS Eval 3.0, 512-tap time-invariant filters).  Correlations, the
     projection and the energies run on the device in fp64; the flen x flen Toeplitz normal
-    equations are solved on the host (numpy fp64), one system per signal."""
+    equations are solved on the host (numpy fp64), one system per signal.
+
+    solver="device" (include/drnmf_sdr.h): the systems are solved on the device too (Levinson-Durbin) and the
+    whole score is only enqueued -- no host round trip.  lengths (host ints or a tensor, each in [0, width]; device
+    solver only): row i is scored over its first lengths[i] samples, whatever lies behind them; a row's numbers
+    are bitwise the same in any batch.  return_parts=True then returns (sdr, coef, energies, info), info as
+    `toeplitz_solve` returns it."""
+    if solver not in SDR_SOLVERS:
+        raise ValueError("sdr_db: solver must be one of %s (got %r)" % (SDR_SOLVERS, solver))
+    if lengths is not None and solver == "host":
+        raise ValueError("sdr_db: lengths= needs solver='device' (the host solver scores whole rows)")
     L = _capi.lib()
     h = _capi.handle(_dev_index(est))
     est, ref = _f32c(est, "est"), _f32c(ref, "ref")
@@ -944,6 +1012,19 @@ def sdr_db(est, ref, flen=512, return_parts=False):
     if est.shape != ref.shape:
         raise ValueError("est and ref must have the same shape")
     n_sig, nsampl = est.shape
+    if solver == "device":
+        if est.dim() != 2 or n_sig < 1 or nsampl < 1 or ref.device != est.device:
+            raise ValueError("sdr_db: est and ref must be non-empty [n_sig, n] tensors on one device")
+        dev = est.device
+        ld = _sdr_lengths(lengths, n_sig, nsampl, dev)
+        out = torch.empty(n_sig, dtype=torch.float32, device=dev)
+        coef = en = info = None
+        if return_parts:
+            coef = torch.empty((n_sig, int(flen)), dtype=torch.float64, device=dev)
+            en = torch.empty((n_sig, 2), dtype=torch.float64, device=dev)
+            info = torch.empty(n_sig, dtype=torch.int32, device=dev)
+        sdr_ragged_enqueue(est, ref, ld, flen, out, coef=coef, energies=en, info=info)
+        return (out, coef, en, info) if return_parts else out
     dev = est.device
     f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
     r, d, coef, en = f64(n_sig, flen), f64(n_sig, flen), f64(n_sig, flen), f64(n_sig, 2)
@@ -1220,18 +1301,23 @@ def stoi(est, ref, fs=16000, lengths=None, return_parts=False):
     return out, dict(keep=kb, env_ref=env_r, env_est=env_e, n_kept=kb.sum(dim=1))
 
 
-def compute_scores(est, ref, fs, lengths_est=None, lengths_ref=None, flen=512):
+def compute_scores(est, ref, fs, lengths_est=None, lengths_ref=None, flen=512, sdr_solver="host"):
     """One row per file as compute_scores (score_audio.m:177-238) returns it:
         S = [SDR, SNR, SegSNR local, SegSNR global, PESQ, STOI]        (score_audio.m:233-236)
     est [n_sig, n_est], ref [n_sig, n_ref]: device float32 (or 1-D), each row valid up to its length
     (default: the row width).  Each pair is truncated to min(len_est, len_ref); SDR (`sdr_db`, 512-tap BSS Eval)
     and SNR (`snr_db`) see the pairs zero-padded to a common width, to which both are neutral; STOI (`stoi`) runs
     at fs on the truncated pairs.  Returns (S, labels): S float64 numpy [n_sig, 6], labels SCORE_LABELS.
+    sdr_solver="device": SDR runs over each pair's own length with the normal equations solved on the device
+    (`sdr_db(..., lengths=, solver="device")`), nothing waits for the host between the three scores, and all
+    columns come down in one copy.
 
     SegSNR and PESQ are NaN.  SegSNR is voicebox `snrseg` (score_audio.m:212), whose default mode runs a P.56
     speech-activity detector and a sub-sample delay search whose exact definitions are not available to this
     project; PESQ is ITU-T P.862, large, table-driven and licensed.  A restatement from memory would be a number
     labelled as the reference's that is probably not the reference's, so neither column is computed."""
+    if sdr_solver not in SDR_SOLVERS:
+        raise ValueError("compute_scores: sdr_solver must be one of %s (got %r)" % (SDR_SOLVERS, sdr_solver))
     if est.dim() == 1:
         est, ref = est[None], ref[None]
     if est.dim() != 2 or ref.dim() != 2 or est.shape[0] != ref.shape[0]:
@@ -1254,6 +1340,11 @@ def compute_scores(est, ref, fs, lengths_est=None, lengths_ref=None, flen=512):
     e = torch.where(valid, e, torch.zeros_like(e))
     r = torch.where(valid, r, torch.zeros_like(r))
     S = np.full((n_sig, len(SCORE_LABELS)), np.nan, dtype=np.float64)
+    if sdr_solver == "device":
+        cols = torch.stack([sdr_db(e, r, flen=flen, lengths=ln, solver="device"), snr_db(e, r),
+                            stoi(e, r, fs=fs, lengths=ln)]).cpu().numpy()
+        S[:, 0], S[:, 1], S[:, 5] = cols[0], cols[1], cols[2]
+        return S, list(SCORE_LABELS)
     S[:, 0] = sdr_db(e, r, flen=flen).cpu().numpy()
     S[:, 1] = snr_db(e, r).cpu().numpy()
     S[:, 5] = stoi(e, r, fs=fs, lengths=ln).cpu().numpy()
