@@ -1,6 +1,6 @@
 """ctypes binding of libdrnmf.so (C ABI in include/drnmf.h; the LSTM baseline's in include/drnmf_lstm.h; the
 STOI score's in include/drnmf_score.h; the ragged STFT / iSTFT / int16 stages' in include/drnmf_enhance.h; the
-device-side SDR's in include/drnmf_sdr.h).
+device-side SDR's in include/drnmf_sdr.h; the training-data front end's in include/drnmf_dataset.h).
 
 The library is the product path: there is NO fallback.  If the shared object is missing or a
 call fails, an exception is raised.
@@ -184,6 +184,15 @@ SDR_SIGNATURES = {
     "drnmf_sdr_ragged": (_i32, [_vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/drnmf_dataset.h one to one (a table of its own, like the four above)
+DATASET_SIGNATURES = {
+    "drnmf_stft_pair_chunks": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32,
+                                      _vp, _vp, _vp, _vp, _vp, _vp]),
+    "drnmf_stft_pair_frames": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp,
+                                      _vp, _vp, _vp]),
+}
+TRANSFORMS = {"mag": 0, "logmag": 1}     # DRNMF_TRANSFORM_*
+
 _lib = None
 _handles = {}
 
@@ -207,7 +216,7 @@ def lib():
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(LSTM_SIGNATURES.items()) +
                                   list(SCORE_SIGNATURES.items()) + list(ENHANCE_SIGNATURES.items()) +
-                                  list(SDR_SIGNATURES.items())):
+                                  list(SDR_SIGNATURES.items()) + list(DATASET_SIGNATURES.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

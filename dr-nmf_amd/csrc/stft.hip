@@ -14,6 +14,7 @@
 // not memory bound; the front end is ~600x faster than the recurrent cell consumes frames.
 #include "common.h"
 #include "../../include/drnmf_enhance.h"
+#include "../../include/drnmf_dataset.h"
 
 namespace {
 
@@ -85,16 +86,27 @@ __global__ void __launch_bounds__(256) fft_tables_kernel(int N, int logN) {
     }
 }
 
+// the feature transform of a magnitude (audio_dataset.py:22-28): 0 'mag', 1 'logmag' = log(1 + m) in the
+// reference's own expression (not log1pf).  Every caller passes a constant 0 or a kernel argument.
+__device__ __forceinline__ float mag_transform(float m, int transform) {
+    return transform ? logf(1.0f + m) : m;
+}
+
 // one frame of one signal by the whole workgroup: row0 = element offset of the signal's first sample in pcm,
-// nsampl its length, o = element offset of the frame's output row (shared by the batched and the ragged kernel)
+// nsampl its length, o = element offset of the frame's output row (shared by the batched, the ragged and the
+// paired kernel).  Each of mag / re / im is written only if its pointer is not NULL.  stage_tw = false: tw
+// already holds this size's twiddles (the second member of a pair); the caller has put a barrier behind the
+// previous frame's reads of buf.
 __device__ __forceinline__ void stft_frame(const void* __restrict__ pcm, int is_int16, size_t row0,
                                            int64_t nsampl, int N, int logN, int hop, int frame, size_t o,
                                            float* __restrict__ mag, float* __restrict__ re,
-                                           float* __restrict__ im, float2* buf, float2* tw, int tid) {
+                                           float* __restrict__ im, float2* buf, float2* tw, int tid,
+                                           int transform = 0, bool stage_tw = true) {
     const int64_t base = (int64_t)frame * hop - N;   // first sample of the frame (N leading zeros)
 
     const float* __restrict__ win = g_window[logN - TAB_LOG_MIN];
-    for (int k = tid; k < N / 2; k += 256) tw[k] = g_twiddle[logN - TAB_LOG_MIN][k];
+    if (stage_tw)
+        for (int k = tid; k < N / 2; k += 256) tw[k] = g_twiddle[logN - TAB_LOG_MIN][k];
     for (int i = tid; i < N; i += 256) {
         const int64_t idx = base + i;
         float v = 0.f;
@@ -110,7 +122,7 @@ __device__ __forceinline__ void stft_frame(const void* __restrict__ pcm, int is_
     fft_lds(buf, tw, N, logN, tid);
     for (int k = tid; k <= N / 2; k += 256) {
         const float2 z = buf[k];
-        if (mag) mag[o + k] = sqrtf(z.x * z.x + z.y * z.y);
+        if (mag) mag[o + k] = mag_transform(sqrtf(z.x * z.x + z.y * z.y), transform);
         if (re) re[o + k] = z.x;
         if (im) im[o + k] = -z.y;    // librosa 0.5.1 conjugates the spectrum (util.py:195 via stft)
     }
@@ -216,12 +228,14 @@ __device__ __forceinline__ void stockham_passes(float2 (&v)[R], float2* cur, con
 }
 
 // one frame of one signal by ONE WAVE (lane j): row0 = element offset of the signal's first sample in pcm,
-// nsampl its length, o = element offset of the frame's output row (shared by the batched and the ragged kernel)
+// nsampl its length, o = element offset of the frame's output row (shared by the batched, the ragged and the
+// paired kernel).  Each of mag / re / im is written only if its pointer is not NULL.
 template <int R, int P>
 __device__ __forceinline__ void stft_real_frame(const void* __restrict__ pcm, int is_int16, size_t row0,
                                                 int64_t nsampl, int logN, int hop, int frame, size_t o,
                                                 float* __restrict__ mag, float* __restrict__ re,
-                                                float* __restrict__ im, const float2* tw, float2* cur, int j) {
+                                                float* __restrict__ im, const float2* tw, float2* cur, int j,
+                                                int transform = 0) {
     constexpr int M = RealFft<R, P>::M, N = 2 * M;
     auto pad = [](int i) { return RealFft<R, P>::pad(i); };
     const float* __restrict__ win = g_window[logN - TAB_LOG_MIN];
@@ -280,7 +294,7 @@ __device__ __forceinline__ void stft_real_frame(const void* __restrict__ pcm, in
         const float2 w = k == M ? make_float2(-1.f, 0.f) : tw[k];
         const float2 wb = cmul(b, w);                       // X = a - i w b
         const float xr = a.x + wb.y, xi = a.y - wb.x;
-        if (mag) mag[o + k] = sqrtf(xr * xr + xi * xi);
+        if (mag) mag[o + k] = mag_transform(sqrtf(xr * xr + xi * xi), transform);
         if (re) re[o + k] = xr;
         if (im) im[o + k] = -xi;      // librosa 0.5.1 conjugates the spectrum (util.py:195 via stft)
     };
@@ -651,6 +665,153 @@ overlap_add_ragged_kernel(const float* __restrict__ frames, const int64_t* __res
     y[(size_t)row.sig * stride_y + s] = acc;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Paired training tensors (include/drnmf_dataset.h): the noisy and the clean magnitude of a frame by the SAME
+// workgroup, straight into fit()'s layout (chunks: [n_seq][T][F] padded with the mask value, plus the 0/1
+// weights) or into packed rows (frames: row row0[s] + t).  The frame bodies are the ones above, called with
+// re = im = NULL, so a magnitude is bitwise what drnmf_stft / drnmf_stft_ragged write for that signal and frame.
+// The clean signal decides the frame count (fidx = y_fidx, audio_dataset.py:232-264); the noisy one is framed
+// with its OWN length, as clipping its full STFT does (clip_x_to_y).
+struct PairArgs {
+    const void* pcm_x;            // [n_sig][stride_x] noisy
+    const void* pcm_y;            // [n_sig][stride_y] clean
+    const int64_t* len_x;
+    const int64_t* len_y;
+    int64_t stride_x, stride_y;
+    const int* table;             // chunks: [n_rows][2] (signal, first frame)
+    const int64_t* row0;          // frames: [n_sig] first output row of a signal
+    int64_t total_frames;         // frames: rows of x / y
+    float* x;
+    float* y;
+    float* w;                     // chunks: [n_rows][T]
+    // always NULL: no spectrum is written.  They are ARGUMENTS, as in every other kernel that holds the frame
+    // bodies, and not the constant: with the stores compiled out the bodies' values have other use counts, the
+    // compiler contracts other multiply-adds, and the magnitude differs from drnmf_stft's in the last bit
+    float* re;
+    float* im;
+    int n_sig, T, hop, logN, is_int16, transform;
+    float mask_value;
+    int row_base, tile_base;      // this launch's offset into the rows (grid.y) and the frame tiles (grid.x)
+};
+
+struct PairRow {                  // what a workgroup knows about its row (uniform over the workgroup)
+    int sig;                      // -1: nothing of this row is a frame
+    int64_t f0, nf, len_x, len_y, orow;   // first frame, the clean side's frame count, output row of t = 0
+};
+
+template <bool PACKED>
+__device__ __forceinline__ PairRow pair_row(const PairArgs& a, int k, int N) {
+    PairRow r;
+    r.sig = PACKED ? k : a.table[2 * (size_t)k];
+    r.f0 = PACKED ? 0 : a.table[2 * (size_t)k + 1];
+    r.nf = r.len_x = r.len_y = 0;
+    r.orow = PACKED ? 0 : (int64_t)k * a.T;
+    if (r.sig < 0 || r.sig >= a.n_sig || r.f0 < 0) {
+        r.sig = -1;
+        return r;
+    }
+    int64_t ly = a.len_y[r.sig], lx = a.len_x[r.sig];
+    r.len_y = ly < 0 ? 0 : (ly > a.stride_y ? a.stride_y : ly);
+    r.len_x = lx < 0 ? 0 : (lx > a.stride_x ? a.stride_x : lx);
+    const int64_t nfram = (r.len_y + a.hop - 1) / a.hop;          // as drnmf_stft_frames
+    r.nf = 1 + (nfram * a.hop + (int64_t)N) / a.hop;
+    if (PACKED) {
+        r.orow = a.row0[r.sig];
+        // rows outside [0, total_frames) are not written: a row0 that is not the prefix sum loses frames,
+        // it never writes past the buffers
+        if (r.orow < 0) r.sig = -1;
+        else if (r.nf > a.total_frames - r.orow) r.nf = a.total_frames - r.orow;
+    }
+    return r;
+}
+
+// 0: t holds frame f0 + t of the signal; 1: a padding frame (chunks only); 2: nothing is written
+template <bool PACKED>
+__device__ __forceinline__ int pair_state(const PairRow& r, int64_t t, int T) {
+    if (t >= T) return 2;
+    if (r.sig >= 0 && r.f0 + t < r.nf) return 0;
+    return PACKED ? 2 : 1;
+}
+
+template <int R, int P, bool PACKED>
+__global__ void __launch_bounds__(256) stft_pair_real_kernel(const PairArgs a) {
+    constexpr int N = RealFft<R, P>::N, F = N / 2 + 1;
+    __shared__ float2 tw[N / 2];
+    __shared__ float2 bufs[4][RealFft<R, P>::MP];
+    const int tid = threadIdx.x, wv = tid >> 6, j = tid & 63;
+    const int64_t t0 = ((int64_t)blockIdx.x + a.tile_base) * 4, t = t0 + wv;
+    const int k = (int)blockIdx.y + a.row_base;
+    const PairRow row = pair_row<PACKED>(a, k, N);
+    // the states of a row are 0 up to some t and not 0 behind it: a tile whose first frame is no frame holds
+    // none, and stages nothing (the whole workgroup takes this branch: no barrier is skipped by a part of it)
+    if (pair_state<PACKED>(row, t0, a.T) == 0) {
+        for (int i = tid; i < N / 2; i += 256) tw[i] = g_twiddle[a.logN - TAB_LOG_MIN][i];
+        __syncthreads();
+    }
+    const int st = pair_state<PACKED>(row, t, a.T);
+    if (st == 2) return;                      // (whole waves: no barrier below)
+    const size_t o = (size_t)(row.orow + t) * F;
+    if (st == 1) {                            // padding frame: Masking's value in every bin, weight 0
+        for (int i = j; i < F; i += 64) {
+            a.x[o + i] = a.mask_value;
+            a.y[o + i] = a.mask_value;
+        }
+        if (j == 0) a.w[row.orow + t] = 0.f;
+        return;
+    }
+    const int frame = (int)(row.f0 + t);
+    // ONE copy of the frame body, run for the noisy and then for the clean member (the loop is kept a loop): both
+    // sides execute the same instructions, those of a kernel that holds the body once -- two inlined copies are
+    // free to contract their multiply-adds differently, and then differ from drnmf_stft in the last bit
+#pragma unroll 1
+    for (int side = 0; side < 2; ++side) {
+        const void* pcm = side ? a.pcm_y : a.pcm_x;
+        const int64_t stride = side ? a.stride_y : a.stride_x, len = side ? row.len_y : row.len_x;
+        stft_real_frame<R, P>(pcm, a.is_int16, (size_t)row.sig * stride, len, a.logN, a.hop, frame, o,
+                              side ? a.y : a.x, a.re, a.im, tw, bufs[wv], j, a.transform);
+        // the wave's LDS slice is reused: its reads of this spectrum are issued before the next member's writes,
+        // and LDS serves one wave's requests in order (as between the passes of stockham_passes)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (!PACKED && j == 0) a.w[row.orow + t] = 1.f;
+}
+
+// other sizes: one workgroup per (row, frame), the noisy frame and then the clean one through the same buffer
+template <bool PACKED>
+__global__ void __launch_bounds__(256) stft_pair_kernel(const PairArgs a, int N) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float2* buf = (float2*)smem;
+    float2* tw = buf + N;
+    const int tid = threadIdx.x, F = N / 2 + 1;
+    const int64_t t = (int64_t)blockIdx.x + a.tile_base;
+    const int k = (int)blockIdx.y + a.row_base;
+    const PairRow row = pair_row<PACKED>(a, k, N);
+    const int st = pair_state<PACKED>(row, t, a.T);       // (uniform over the workgroup, as both exits below)
+    if (st == 2) return;
+    const size_t o = (size_t)(row.orow + t) * F;
+    if (st == 1) {
+        for (int i = tid; i < F; i += 256) {
+            a.x[o + i] = a.mask_value;
+            a.y[o + i] = a.mask_value;
+        }
+        if (tid == 0) a.w[row.orow + t] = 0.f;
+        return;
+    }
+    const int frame = (int)(row.f0 + t);
+    for (int k = tid; k < N / 2; k += 256) tw[k] = g_twiddle[a.logN - TAB_LOG_MIN][k];    // once per pair
+    // one copy of the frame body for both members, as in the kernel above
+#pragma unroll 1
+    for (int side = 0; side < 2; ++side) {
+        const void* pcm = side ? a.pcm_y : a.pcm_x;
+        const int64_t stride = side ? a.stride_y : a.stride_x, len = side ? row.len_y : row.len_x;
+        stft_frame(pcm, a.is_int16, (size_t)row.sig * stride, len, N, a.logN, a.hop, frame, o, side ? a.y : a.x,
+                   a.re, a.im, buf, tw, tid, a.transform, false);
+        __syncthreads();                      // this spectrum has been read out of buf
+    }
+    if (!PACKED && tid == 0) a.w[row.orow + t] = 1.f;
+}
+
 }  // namespace
 
 extern "C" int32_t drnmf_stft_frames(int64_t nsampl, int32_t N, int32_t hop) {
@@ -869,6 +1030,108 @@ extern "C" int32_t drnmf_istft_ragged(drnmf_handle_t h, int32_t n_sig, int32_t b
                            dim3(256), 0, stream, frames, lengths, sig_index, n_sig, T, N, hop, crop, y,
                            stride_y);
     }
+    DRNMF_HIP(h, hipGetLastError());
+    return DRNMF_OK;
+}
+
+// ---- paired training tensors (include/drnmf_dataset.h) ----------------------------------------------------
+// Rows (sequences, or signals in the packed mode) go on grid.y in slices of at most 65535 and frame tiles on
+// grid.x in slices of at most 2^23, so neither count is bounded by a grid dimension.
+template <bool PACKED>
+static void launch_stft_pair(PairArgs a, int N, int64_t n_rows, hipStream_t stream) {
+    const bool fast = stft_fast(N);
+    const int64_t tiles = fast ? ((int64_t)a.T + 3) / 4 : (int64_t)a.T;
+    const int64_t max_y = 65535, max_x = (int64_t)1 << 23;
+    const size_t shmem = (size_t)(N + N / 2) * sizeof(float2);
+    for (int64_t r0 = 0; r0 < n_rows; r0 += max_y)
+        for (int64_t x0 = 0; x0 < tiles; x0 += max_x) {
+            a.row_base = (int)r0;
+            a.tile_base = (int)x0;
+            const dim3 grid((unsigned)(tiles - x0 < max_x ? tiles - x0 : max_x),
+                            (unsigned)(n_rows - r0 < max_y ? n_rows - r0 : max_y));
+            if (N == 1024)
+                hipLaunchKernelGGL((stft_pair_real_kernel<8, 3, PACKED>), grid, dim3(256), 0, stream, a);
+            else if (N == 512)
+                hipLaunchKernelGGL((stft_pair_real_kernel<4, 4, PACKED>), grid, dim3(256), 0, stream, a);
+            else
+                hipLaunchKernelGGL((stft_pair_kernel<PACKED>), grid, dim3(256), shmem, stream, a, N);
+        }
+}
+
+// the arguments both entry points share; 0 or a status with the handle's message set
+static int32_t check_stft_pair(drnmf_handle_t h, const char* who, int32_t n_sig, int64_t stride_x,
+                               int64_t stride_y, int32_t N, int32_t hop, int32_t is_int16, int32_t transform) {
+    if (n_sig <= 0 || stride_x <= 0 || stride_y <= 0 || hop <= 0 || (is_int16 != 0 && is_int16 != 1))
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG,
+                   "%s: bad shape n_sig=%d stride_x=%lld stride_y=%lld hop=%d is_int16=%d", who, n_sig,
+                   (long long)stride_x, (long long)stride_y, hop, is_int16);
+    if (N < 64 || N > 4096 || (N & (N - 1)))
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: N=%d must be a power of two in [64,4096]", who, N);
+    if (transform != DRNMF_TRANSFORM_MAG && transform != DRNMF_TRANSFORM_LOGMAG)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: transform=%d is neither DRNMF_TRANSFORM_MAG nor _LOGMAG", who,
+                   transform);
+    if (stride_y / hop + N / hop + 2 > 0x7fffffff)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: stride_y=%lld at hop=%d has more than 2^31-1 frames", who,
+                   (long long)stride_y, hop);
+    return DRNMF_OK;
+}
+
+extern "C" int32_t drnmf_stft_pair_chunks(drnmf_handle_t h, int32_t n_sig, int64_t stride_x, int64_t stride_y,
+                                          const int64_t* len_x, const int64_t* len_y, int32_t n_seq,
+                                          const int32_t* seq_table, int32_t T, int32_t N, int32_t hop,
+                                          int32_t is_int16, int32_t transform, float mask_value,
+                                          const void* pcm_x, const void* pcm_y, float* x, float* y, float* w,
+                                          void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    if (n_seq <= 0 || T <= 0)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stft_pair_chunks: bad shape n_seq=%d T=%d", n_seq, T);
+    const int32_t rc = check_stft_pair(h, "stft_pair_chunks", n_sig, stride_x, stride_y, N, hop, is_int16,
+                                       transform);
+    if (rc) return rc;
+    if (!len_x || !len_y || !seq_table || !pcm_x || !pcm_y || !x || !y || !w)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stft_pair_chunks: NULL pointer argument");
+    int logN = 0;
+    while ((1 << logN) < N) ++logN;
+    hipStream_t stream = (hipStream_t)stream_;
+    {
+        const int32_t trc = ensure_fft_tables(h, N, logN, stream);
+        if (trc) return trc;
+    }
+    PairArgs a = {pcm_x, pcm_y, len_x, len_y, stride_x, stride_y, seq_table, nullptr, 0, x, y, w,
+                  nullptr, nullptr, n_sig, T, hop, logN, is_int16, transform, mask_value, 0, 0};
+    launch_stft_pair<false>(a, N, n_seq, stream);
+    DRNMF_HIP(h, hipGetLastError());
+    return DRNMF_OK;
+}
+
+extern "C" int32_t drnmf_stft_pair_frames(drnmf_handle_t h, int32_t n_sig, int64_t stride_x, int64_t stride_y,
+                                          const int64_t* len_x, const int64_t* len_y, const int64_t* row0,
+                                          int64_t total_frames, int32_t N, int32_t hop, int32_t is_int16,
+                                          int32_t transform, const void* pcm_x, const void* pcm_y,
+                                          float* x_frames, float* y_frames, void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    if (total_frames <= 0)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stft_pair_frames: bad shape total_frames=%lld",
+                   (long long)total_frames);
+    const int32_t rc = check_stft_pair(h, "stft_pair_frames", n_sig, stride_x, stride_y, N, hop, is_int16,
+                                       transform);
+    if (rc) return rc;
+    if (!len_x || !len_y || !row0 || !pcm_x || !pcm_y || !x_frames || !y_frames)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stft_pair_frames: NULL pointer argument");
+    int logN = 0;
+    while ((1 << logN) < N) ++logN;
+    hipStream_t stream = (hipStream_t)stream_;
+    {
+        const int32_t trc = ensure_fft_tables(h, N, logN, stream);
+        if (trc) return trc;
+    }
+    // the grid spans the frames the longest signal can have; a signal's own count is evaluated on the device
+    const int T = drnmf_stft_frames(stride_y, N, hop);
+    PairArgs a = {pcm_x, pcm_y, len_x, len_y, stride_x, stride_y, nullptr, row0, total_frames, x_frames,
+                  y_frames, nullptr, nullptr, nullptr, n_sig, T, hop, logN, is_int16, transform, 0.f, 0, 0};
+    launch_stft_pair<true>(a, N, n_sig, stream);
     DRNMF_HIP(h, hipGetLastError());
     return DRNMF_OK;
 }

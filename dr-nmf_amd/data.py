@@ -3,6 +3,7 @@ numpy, same names and semantics as the reference's helpers so that an enhance.py
 import them from here.
 
     reshape_and_pad_stacks   audio_dataset.py:116-169   concatenated STFT stacks -> (n_seq, maxlen, d)
+    sequence_table_from_lengths  the same chunking from frame counts, as the table the device takes
     sequences_to_stack       enhance.py:1200-1203 + audio_dataset.py:267-278 (the way back)
     masked_seqs_to_frames    util.py:19-27              (n_seq, T, F) + mask -> (F, n_valid_frames)
     pad_axis_toN_with_constant util.py:355-374
@@ -61,6 +62,26 @@ def sequence_table(fidx, maxlen=None):
             rows.append((u, t, min(t + maxlen, int(fidx[u, 1]))))
             t += maxlen
     return np.asarray(rows, dtype=np.int64).reshape(-1, 3), int(maxlen)
+
+
+def sequence_table_from_lengths(n_frames, maxlen=None):
+    """The chunking of `sequence_table` (hence of reshape_and_pad_stacks) from per-utterance frame counts, in
+    the form the device takes (ops.wavs_to_tensors, drnmf_stft_pair_chunks): rows (utterance, first frame
+    WITHIN the utterance) as int32 [n_seq, 2], and T, the frames per sequence.  maxlen None or above the longest
+    utterance: one sequence per utterance and T = the longest; else consecutive pieces of at most maxlen frames
+    (an exact multiple yields no empty trailing piece).  Returns (table, T)."""
+    n_frames = np.asarray(n_frames, dtype=np.int64).reshape(-1)
+    if n_frames.shape[0] < 1 or n_frames.min() < 1:
+        raise ValueError("sequence_table_from_lengths: every utterance has at least one frame")
+    if maxlen is not None and int(maxlen) < 1:
+        raise ValueError("sequence_table_from_lengths: maxlen must be at least 1")
+    ends = np.cumsum(n_frames)
+    fidx = np.stack([ends - n_frames, ends], axis=1)
+    table, T = sequence_table(fidx, None if maxlen is None else int(maxlen))
+    out = np.empty((table.shape[0], 2), dtype=np.int32)
+    out[:, 0] = table[:, 0]
+    out[:, 1] = table[:, 1] - fidx[table[:, 0], 0]
+    return out, T
 
 
 def reshape_and_pad_stacks(x_stack, y_stack, fidx, transform_x=(lambda x: x),

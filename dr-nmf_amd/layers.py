@@ -1681,6 +1681,34 @@ class _SequenceModel(object):
         return hist
 
 
+    def fit_wavs(self, noisy, clean, N=512, hop=128, maxlen=None, transform='mag', validation_wavs=None,
+                 **fit_kwargs):
+        """`fit` on waveform pairs: the reference's load_data (audio_dataset.py:199-264) on the device by
+        ops.wavs_to_tensors, then the existing fit on the device tensors (x, y, sample_weight = the 0/1 mask,
+        enhance.py:1148-1157).  noisy, clean: lists of 1-D int16 / float32 arrays; validation_wavs: a (noisy,
+        clean) pair of such lists, built the same way.  Everything else goes to fit unchanged.  The padding
+        must be the value this model masks: a transform whose mask value (data.get_mask_value) differs from
+        the model's raises ValueError."""
+        from . import data
+        for k in ('sample_weight', 'validation_data'):
+            if k in fit_kwargs:
+                raise ValueError('fit_wavs: %s is built from the waveforms (validation_wavs=)' % k)
+        mv = float(data.get_mask_value(dict(transform_x=transform, transform_y=transform)))
+        if mv != float(self.mask_value):
+            raise ValueError("fit_wavs: transform %r pads with %g, the model masks %g"
+                             % (transform, mv, float(self.mask_value)))
+        if int(N) // 2 + 1 != self._input_width():
+            raise ValueError('fit_wavs: N = %d gives %d bins, the model takes %d'
+                             % (N, int(N) // 2 + 1, self._input_width()))
+        build = lambda a, b: ops.wavs_to_tensors(a, b, N=N, hop=hop, maxlen=maxlen, transform=transform,
+                                                 mask_value=mv, device=self._device())
+        val = None
+        if validation_wavs is not None:
+            noisy_v, clean_v = validation_wavs
+            val = build(noisy_v, clean_v)
+        x, y, w = build(noisy, clean)
+        return self.fit(x, y, sample_weight=w, validation_data=val, **fit_kwargs)
+
     def _validate(self, validation_data, batch_size, take):
         """Validation loss of fit(), evaluated in mini-batches of `batch_size` sequences as Keras'
         test loop does (enhance.py:1152-1157: model.fit(..., validation_data=...)); the reference's

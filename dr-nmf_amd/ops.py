@@ -1154,6 +1154,130 @@ def stft_ragged(pcm, lengths, sig_index=None, T=None, N=512, hop=None, mask_valu
     return x, re, im, nf
 
 
+# ---- training tensors from waveform pairs (include/drnmf_dataset.h) -----------------------------------------
+def stft_pair_chunks_enqueue(pcm_x, pcm_y, len_x_dev, len_y_dev, table_dev, T, N, hop, transform, mask_value,
+                             x, y, w):
+    """drnmf_stft_pair_chunks on tensors the caller owns and has checked: enqueues, reads nothing back."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(pcm_x))
+    rc = L.drnmf_stft_pair_chunks(h, pcm_x.shape[0], pcm_x.shape[1], pcm_y.shape[1], _capi.ptr(len_x_dev),
+                                  _capi.ptr(len_y_dev), table_dev.shape[0], _capi.ptr(table_dev), int(T), int(N),
+                                  int(hop), int(pcm_x.dtype == torch.int16), _capi.TRANSFORMS[transform],
+                                  float(mask_value), _capi.ptr(pcm_x), _capi.ptr(pcm_y), _capi.ptr(x),
+                                  _capi.ptr(y), _capi.ptr(w), _stream())
+    _capi.check(rc, h, "drnmf_stft_pair_chunks")
+
+
+def stft_pair_frames_enqueue(pcm_x, pcm_y, len_x_dev, len_y_dev, row0_dev, N, hop, transform, x_frames,
+                             y_frames):
+    """drnmf_stft_pair_frames on tensors the caller owns and has checked: enqueues, reads nothing back."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(pcm_x))
+    rc = L.drnmf_stft_pair_frames(h, pcm_x.shape[0], pcm_x.shape[1], pcm_y.shape[1], _capi.ptr(len_x_dev),
+                                  _capi.ptr(len_y_dev), _capi.ptr(row0_dev), x_frames.shape[0], int(N), int(hop),
+                                  int(pcm_x.dtype == torch.int16), _capi.TRANSFORMS[transform],
+                                  _capi.ptr(pcm_x), _capi.ptr(pcm_y), _capi.ptr(x_frames), _capi.ptr(y_frames),
+                                  _stream())
+    _capi.check(rc, h, "drnmf_stft_pair_frames")
+
+
+def _check_wav_pairs(noisy, clean, N, hop, transform, what):
+    """Host-side checks of a list of (noisy, clean) waveform pairs, before the device is touched.  Returns
+    (noisy rows, clean rows, numpy dtype, frame counts of the clean side)."""
+    N, hop = int(N), int(hop)
+    if transform not in _capi.TRANSFORMS:
+        raise ValueError("%s: transform must be 'mag' or 'logmag' (got %r)" % (what, transform))
+    if N < 64 or N > 4096 or N & (N - 1) or hop < 1:
+        raise ValueError("%s: N = %d must be a power of two in [64, 4096] and hop = %d positive" % (what, N, hop))
+    rx, ry = [np.asarray(v) for v in noisy], [np.asarray(v) for v in clean]
+    if len(rx) != len(ry):
+        raise ValueError("%s: %d noisy waveforms for %d clean ones" % (what, len(rx), len(ry)))
+    if not rx:
+        raise ValueError("%s: no waveforms" % what)
+    dt = rx[0].dtype
+    if dt not in (np.dtype('int16'), np.dtype('float32')):
+        raise ValueError("%s: waveforms must be int16 or float32 (got %s)" % (what, dt))
+    for v in rx + ry:
+        if v.ndim != 1 or v.dtype != dt or v.shape[0] < 1:
+            raise ValueError("%s: every waveform must be a non-empty 1-D %s array" % (what, dt))
+    frames = lambda n: -(-n // hop) + N // hop + 1                 # drnmf_stft_frames
+    nf = np.array([frames(v.shape[0]) for v in ry], dtype=np.int64)
+    for i, v in enumerate(rx):
+        if frames(v.shape[0]) < nf[i]:
+            # the case the reference means to refuse (audio_dataset.py:239-240) but does not
+            raise ValueError("%s: noisy waveform %d has %d frames, fewer than its clean one's %d"
+                             % (what, i, frames(v.shape[0]), nf[i]))
+    return rx, ry, dt, nf
+
+
+def _upload_wav_side(rows, dt, dev):
+    """One pinned upload of one side: lengths [n] int64 | samples [n][stride].  Returns (pcm, lengths) on the
+    device.  The samples behind a row's own length are left as they are: the kernels never read them."""
+    n = len(rows)
+    lens = np.array([v.shape[0] for v in rows], dtype=np.int64)
+    stride = int(lens.max())
+    off = -(-(8 * n) // 16) * 16
+    host = torch.empty(off + n * stride * dt.itemsize, dtype=torch.uint8, pin_memory=True)
+    hn = host.numpy()
+    hn[:8 * n].view(np.int64)[:] = lens
+    pk = hn[off:].view(dt).reshape(n, stride)
+    for i, v in enumerate(rows):
+        pk[i, :v.shape[0]] = v
+    d = host.to(dev, non_blocking=True)
+    pcm = d[off:].view(torch.int16 if dt == np.dtype('int16') else torch.float32).view(n, stride)
+    return pcm, d[:8 * n].view(torch.int64)
+
+
+def _upload_pinned(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(dev, non_blocking=True)
+
+
+def wavs_to_tensors(noisy, clean, N=512, hop=128, maxlen=None, transform='mag', mask_value=None, device=None):
+    """The reference's load_data (audio_dataset.py:199-264: STFT of every noisy and clean file, the noisy stack
+    clipped to the clean one, the transform, get_padded_data_matrix) on the device: lists of 1-D int16 (scaled
+    by 1/32768) or float32 numpy arrays in, (x, y, w) out as device tensors [n_seq, T, F], [n_seq, T, F] and
+    [n_seq, T] -- what `fit(x, y, sample_weight=w)` takes.  Every utterance is cut into consecutive sequences of
+    at most maxlen frames (data.sequence_table_from_lengths; None: one sequence per utterance), padded with
+    mask_value (default: data.get_mask_value for the transform) and weighted 1 / 0.  The clean side decides an
+    utterance's frame count; a noisy signal with FEWER frames than its clean one raises ValueError, as do lists
+    of different lengths and empty lists.  One pinned upload per side and one of the table, one launch
+    sequence, no download and no synchronisation."""
+    from . import data
+    rx, ry, dt, nf = _check_wav_pairs(noisy, clean, N, hop, transform, "wavs_to_tensors")
+    table, T = data.sequence_table_from_lengths(nf, maxlen)
+    if mask_value is None:
+        mask_value = data.get_mask_value(dict(transform_x=transform, transform_y=transform))
+    dev = torch.device('cuda' if device is None else device)
+    dev = torch.device('cuda', _dev_of(dev))
+    with torch.cuda.device(dev):
+        pcm_x, len_x = _upload_wav_side(rx, dt, dev)
+        pcm_y, len_y = _upload_wav_side(ry, dt, dev)
+        table_d = _upload_pinned(table, dev)
+        n_seq, F = table.shape[0], int(N) // 2 + 1
+        x = torch.empty((n_seq, T, F), dtype=torch.float32, device=dev)
+        y = torch.empty_like(x)
+        w = torch.empty((n_seq, T), dtype=torch.float32, device=dev)
+        stft_pair_chunks_enqueue(pcm_x, pcm_y, len_x, len_y, table_d, T, N, hop, transform, mask_value, x, y, w)
+    return x, y, w
+
+
+def wavs_to_frames(noisy, clean, N, hop, transform='mag'):
+    """The unpadded frames of both sides, as the reference gets them by masked_seqs_to_frames of load_data's
+    tensors (enhance.py:772-813), in the row layout `mu_forward` and the dictionary trainer take: (x_frames,
+    y_frames), each [total_frames, F] on the current device, utterance after utterance.  Arguments and errors
+    as `wavs_to_tensors`."""
+    rx, ry, dt, nf = _check_wav_pairs(noisy, clean, N, hop, transform, "wavs_to_frames")
+    dev = torch.device('cuda', torch.cuda.current_device())
+    total = int(nf.sum())
+    pcm_x, len_x = _upload_wav_side(rx, dt, dev)
+    pcm_y, len_y = _upload_wav_side(ry, dt, dev)
+    row0 = _upload_pinned(np.cumsum(nf) - nf, dev)
+    xf = torch.empty((total, int(N) // 2 + 1), dtype=torch.float32, device=dev)
+    yf = torch.empty_like(xf)
+    stft_pair_frames_enqueue(pcm_x, pcm_y, len_x, len_y, row0, N, hop, transform, xf, yf)
+    return xf, yf
+
+
 def istft_ragged_enqueue(re, im, mask, lengths_dev, sig_index_dev, N, hop, y, crop, workspace=None):
     """drnmf_istft_ragged on tensors the caller owns and has checked: enqueues, reads nothing back."""
     L = _capi.lib()
