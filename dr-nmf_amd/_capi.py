@@ -151,9 +151,13 @@ LSTM_SIGNATURES = {
     "drnmf_lstm_prepare_params": (_i32, [_vp, _LDP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "drnmf_lstm_workspace_bytes": (_sz, [_LDP]),
     "drnmf_lstm_forward": (_i32, [_vp, _LDP, _vp, _f32, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "drnmf_lstm_forward_stateful": (_i32, [_vp, _LDP, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz,
+                                           _vp]),
     "drnmf_lstm_head_forward": (_i32, [_vp, _LDP, _vp, _i32, _vp, _vp, _vp]),
     "drnmf_lstm_train_workspace_bytes": (_sz, [_LDP]),
     "drnmf_lstm_train_forward": (_i32, [_vp, _LDP, _vp, _f32, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "drnmf_lstm_train_forward_stateful": (_i32, [_vp, _LDP, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp,
+                                                 _sz, _vp]),
     "drnmf_lstm_loss_head_backward": (_i32, [_vp, _LDP, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                              _sz, _vp]),
     "drnmf_lstm_backward": (_i32, [_vp, _LDP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

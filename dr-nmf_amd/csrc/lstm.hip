@@ -175,6 +175,68 @@ lstm_init_kernel(float* __restrict__ hring, float* __restrict__ cring, int* ctr,
     if (i < n) { hring[i] = 0.f; cring[i] = 0.f; }
 }
 
+// The *_stateful entry points: caller-owned state arrays [K][B][H]; NULL initial = zeros, NULL final = not wanted
+struct LstmState {
+    const float* initial_h;
+    const float* initial_c;
+    float* final_h;
+    float* final_c;
+};
+
+// lstm_init_kernel with an entering state: frame 0 of layer k reads ring slot (-1) & 1 = 1, so the state
+// [K][B][H] goes there (rows b < B, units n < H); the padded rows B .. Bp-1, the padded units H .. Hc-1 and all of
+// slot 0 are zeros, diagonal counters = 0.  Runs before the replayed frames, outside them.
+__global__ void __launch_bounds__(256)
+lstm_state_scatter_kernel(float* __restrict__ hring, float* __restrict__ cring, int* ctr,
+                          const float* __restrict__ init_h, const float* __restrict__ init_c, size_t n, int B,
+                          int H, int Bp, int Hc) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) { ctr[0] = 0; ctr[16] = 0; }
+    if (i >= n) return;
+    const size_t slab = (size_t)Bp * Hc;
+    const size_t ks = i / slab, e = i % slab;            // ks = 2 k + slot
+    const int b = (int)(e / Hc), u = (int)(e % Hc);
+    float hv = 0.f, cv = 0.f;
+    if ((ks & 1) && b < B && u < H) {
+        const size_t s = ((ks >> 1) * B + b) * H + u;
+        if (init_h) hv = init_h[s];
+        if (init_c) cv = init_c[s];
+    }
+    hring[i] = hv;
+    cring[i] = cv;
+}
+
+// the state leaving the call: ring slot (T - 1) & 1 of every layer -> final_h / final_c [K][B][H] (either may be
+// NULL).  Runs behind the last replayed frame, outside the graphs.
+__global__ void __launch_bounds__(256)
+lstm_state_gather_kernel(const float* __restrict__ hring, const float* __restrict__ cring,
+                         float* __restrict__ fin_h, float* __restrict__ fin_c, size_t n, int B, int H, int Bp,
+                         int Hc, int slot) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const size_t k = i / ((size_t)B * H), e = i % ((size_t)B * H);
+    const size_t b = e / H, u = e % H;
+    const size_t s = ((k * 2 + slot) * Bp + b) * Hc + u;
+    if (fin_h) fin_h[i] = hring[s];
+    if (fin_c) fin_c[i] = cring[s];
+}
+
+// training layout: the entering state into row b (T + 1) of every layer's stash (behind lstm_stash_init_kernel's
+// zero fill), h into hst and c into cst; valid stays 0 there and z zero.  The BPTT reads c_{t-1} at t = 0 from
+// this row, and the recurrent-kernel product its h.
+__global__ void __launch_bounds__(256)
+lstm_stash_state_kernel(float* __restrict__ cst, float* __restrict__ hst, const float* __restrict__ init_h,
+                        const float* __restrict__ init_c, size_t n, int B, int H, int T, size_t RS, int Hc,
+                        int Hq) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const size_t k = i / ((size_t)B * H), e = i % ((size_t)B * H);
+    const size_t b = e / H, u = e % H;
+    const size_t srow = k * RS + b * ((size_t)T + 1);
+    if (init_h) hst[srow * Hq + u] = init_h[i];
+    if (init_c) cst[srow * Hc + u] = init_c[i];
+}
+
 struct EpiLstmXproj {   // xproj = acc + bias_0 (packed columns)
     float* out;
     const float* bias;
@@ -370,21 +432,33 @@ extern "C" int32_t drnmf_lstm_prepare_params(drnmf_handle_t h, const drnmf_lstm_
     return DRNMF_OK;
 }
 
-extern "C" int32_t drnmf_lstm_forward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x,
-                                      float mask_value, const void* params, float* h_out, int32_t ld_h,
-                                      void* workspace,
-                                      size_t workspace_bytes, void* stream_) {
-    DRNMF_LOCK(h);
+// final_h / final_c of a stateful call (nothing to do for st == nullptr or when neither is wanted)
+static int32_t lstm_store_state(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const LstmLayout& L,
+                                const float* hring, const float* cring, const LstmState* st, hipStream_t stream) {
+    if (!st || (!st->final_h && !st->final_c)) return DRNMF_OK;
+    const size_t n = (size_t)d->K * d->B * d->H;
+    hipLaunchKernelGGL(lstm_state_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, hring,
+                       cring, st->final_h, st->final_c, n, d->B, d->H, L.Bp, L.Hc, (d->T - 1) & 1);
+    DRNMF_HIP(h, hipGetLastError());
+    return DRNMF_OK;
+}
+
+// st == nullptr: drnmf_lstm_forward (zero state in, none out); else drnmf_lstm_forward_stateful.  The state
+// kernels run on the stream before and behind the replayed frames, never inside them: the graphs hold no state
+// pointer (the cache key has none), and both entry points replay the same graphs.
+static int32_t lstm_forward_impl(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x, float mask_value,
+                                 const void* params, float* h_out, int32_t ld_h, void* workspace,
+                                 size_t workspace_bytes, void* stream_, const LstmState* st, const char* what) {
     if (!h) return DRNMF_ERR_INVALID_ARG;
     int rc = validate_lstm_desc(h, d, true);
     if (rc) return rc;
     ++h->call_seq;                   // (a top-level call: the graphs it takes are pinned until it returns)
     if (!x || !params || !h_out || !workspace)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_forward: NULL pointer argument");
-    if (ld_h < d->H) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_forward: ld_h %d < H %d", ld_h, d->H);
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: NULL pointer argument", what);
+    if (ld_h < d->H) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: ld_h %d < H %d", what, ld_h, d->H);
     const LstmLayout L = lstm_layout(d);
     if (workspace_bytes < L.ws_total)
-        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "lstm_forward: workspace %zu < required %zu", workspace_bytes,
+        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "%s: workspace %zu < required %zu", what, workspace_bytes,
                    L.ws_total);
     if (((uintptr_t)workspace & 255) || ((uintptr_t)params & 255))
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "workspace/params must be 256-byte aligned");
@@ -402,8 +476,12 @@ extern "C" int32_t drnmf_lstm_forward(drnmf_handle_t h, const drnmf_lstm_desc_t*
     hipLaunchKernelGGL(lstm_pack_x_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, xz, valid,
                        mask_value, rows, d->F, L.Fq);
     const size_t nring = (size_t)d->K * 2 * L.Bp * L.Hc;
-    hipLaunchKernelGGL(lstm_init_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream, hring,
-                       cring, ctr, nring);
+    if (st)
+        hipLaunchKernelGGL(lstm_state_scatter_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream,
+                           hring, cring, ctr, st->initial_h, st->initial_c, nring, d->B, d->H, L.Bp, L.Hc);
+    else
+        hipLaunchKernelGGL(lstm_init_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream, hring,
+                           cring, ctr, nring);
     DRNMF_HIP(h, hipGetLastError());
     {
         gemm::Operands g;
@@ -448,7 +526,29 @@ extern "C" int32_t drnmf_lstm_forward(drnmf_handle_t h, const drnmf_lstm_desc_t*
         (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->H, (uint64_t)d->K,
         (uint64_t)d->recurrent_activation, (uint64_t)(uintptr_t)params, (uint64_t)(uintptr_t)h_out, (uint64_t)ld_h,
         (uint64_t)(uintptr_t)workspace};
-    return replay_frames(h, stream, GraphKind::Lstm, key, {fpg, 1}, 0, frames, frame);
+    rc = replay_frames(h, stream, GraphKind::Lstm, key, {fpg, 1}, 0, frames, frame);
+    if (rc) return rc;
+    return lstm_store_state(h, d, L, hring, cring, st, stream);
+}
+
+extern "C" int32_t drnmf_lstm_forward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x,
+                                      float mask_value, const void* params, float* h_out, int32_t ld_h,
+                                      void* workspace,
+                                      size_t workspace_bytes, void* stream_) {
+    DRNMF_LOCK(h);
+    return lstm_forward_impl(h, d, x, mask_value, params, h_out, ld_h, workspace, workspace_bytes, stream_,
+                             nullptr, "lstm_forward");
+}
+
+extern "C" int32_t drnmf_lstm_forward_stateful(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x,
+                                               float mask_value, const void* params, const float* initial_h,
+                                               const float* initial_c, float* final_h, float* final_c,
+                                               float* h_out, int32_t ld_h, void* workspace,
+                                               size_t workspace_bytes, void* stream_) {
+    DRNMF_LOCK(h);
+    const LstmState st{initial_h, initial_c, final_h, final_c};
+    return lstm_forward_impl(h, d, x, mask_value, params, h_out, ld_h, workspace, workspace_bytes, stream_, &st,
+                             "lstm_forward_stateful");
 }
 
 // With ld_h >= round_up(H, 4) the product contracts the padding columns too (against zero rows of W_out^T): K and
@@ -894,17 +994,19 @@ extern "C" size_t drnmf_lstm_train_workspace_bytes(const drnmf_lstm_desc_t* d) {
     return lstm_train_layout(d).total;
 }
 
-extern "C" int32_t drnmf_lstm_train_forward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x,
-                                            float mask_value, const void* params, float* h_out, int32_t ld_h,
-                                            void* workspace, size_t workspace_bytes, void* stream_) {
-    DRNMF_LOCK(h);
+// st as in lstm_forward_impl; the entering state also goes into row b (T + 1) of the stash, where the BPTT
+// (drnmf_lstm_backward, unchanged) finds it: a constant of the gradient
+static int32_t lstm_train_forward_impl(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x,
+                                       float mask_value, const void* params, float* h_out, int32_t ld_h,
+                                       void* workspace, size_t workspace_bytes, void* stream_,
+                                       const LstmState* st, const char* what) {
     if (!h) return DRNMF_ERR_INVALID_ARG;
     LstmTrainLayout W;
-    int rc = validate_train_call(h, d, workspace, workspace_bytes, "lstm_train_forward", &W);
+    int rc = validate_train_call(h, d, workspace, workspace_bytes, what, &W);
     if (rc) return rc;
     ++h->call_seq;
-    if (!x || !params || !h_out) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_train_forward: NULL pointer argument");
-    if (ld_h < d->H) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_train_forward: ld_h %d < H %d", ld_h, d->H);
+    if (!x || !params || !h_out) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: NULL pointer argument", what);
+    if (ld_h < d->H) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: ld_h %d < H %d", what, ld_h, d->H);
     if ((uintptr_t)params & 255) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "params must be 256-byte aligned");
     const LstmLayout& L = W.L;
     hipStream_t stream = (hipStream_t)stream_;
@@ -923,10 +1025,19 @@ extern "C" int32_t drnmf_lstm_train_forward(drnmf_handle_t h, const drnmf_lstm_d
     hipLaunchKernelGGL(lstm_pack_x_train_kernel, dim3((unsigned)((W.R1 + 3) / 4)), dim3(256), 0, stream, x, xz,
                        valid, mask_value, W.R1, d->T, d->F, L.Fq);
     const size_t nring = (size_t)d->K * 2 * L.Bp * L.Hc;
-    hipLaunchKernelGGL(lstm_init_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream, hring,
-                       cring, ctr, nring);
+    if (st)
+        hipLaunchKernelGGL(lstm_state_scatter_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream,
+                           hring, cring, ctr, st->initial_h, st->initial_c, nring, d->B, d->H, L.Bp, L.Hc);
+    else
+        hipLaunchKernelGGL(lstm_init_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream, hring,
+                           cring, ctr, nring);
     hipLaunchKernelGGL(lstm_stash_init_kernel, dim3((unsigned)(L.Bp + 1), (unsigned)d->K), dim3(256), 0, stream,
                        zst, cst, hst, L.Bp, d->T, W.zk, W.RS, L.NC, L.Hc, L.Hq);
+    if (st && (st->initial_h || st->initial_c)) {
+        const size_t ns = (size_t)d->K * d->B * d->H;
+        hipLaunchKernelGGL(lstm_stash_state_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, stream, cst,
+                           hst, st->initial_h, st->initial_c, ns, d->B, d->H, d->T, W.RS, L.Hc, L.Hq);
+    }
     DRNMF_HIP(h, hipGetLastError());
     {
         gemm::Operands g;
@@ -968,7 +1079,28 @@ extern "C" int32_t drnmf_lstm_train_forward(drnmf_handle_t h, const drnmf_lstm_d
         (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->H, (uint64_t)d->K,
         (uint64_t)d->recurrent_activation, (uint64_t)(uintptr_t)params, (uint64_t)(uintptr_t)h_out, (uint64_t)ld_h,
         (uint64_t)(uintptr_t)workspace};
-    return replay_frames(h, stream, GraphKind::LstmTrain, key, {fpg, 1}, 0, frames, frame);
+    rc = replay_frames(h, stream, GraphKind::LstmTrain, key, {fpg, 1}, 0, frames, frame);
+    if (rc) return rc;
+    return lstm_store_state(h, d, L, hring, cring, st, stream);
+}
+
+extern "C" int32_t drnmf_lstm_train_forward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x,
+                                            float mask_value, const void* params, float* h_out, int32_t ld_h,
+                                            void* workspace, size_t workspace_bytes, void* stream_) {
+    DRNMF_LOCK(h);
+    return lstm_train_forward_impl(h, d, x, mask_value, params, h_out, ld_h, workspace, workspace_bytes, stream_,
+                                   nullptr, "lstm_train_forward");
+}
+
+extern "C" int32_t drnmf_lstm_train_forward_stateful(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x,
+                                                     float mask_value, const void* params,
+                                                     const float* initial_h, const float* initial_c,
+                                                     float* final_h, float* final_c, float* h_out, int32_t ld_h,
+                                                     void* workspace, size_t workspace_bytes, void* stream_) {
+    DRNMF_LOCK(h);
+    const LstmState st{initial_h, initial_c, final_h, final_c};
+    return lstm_train_forward_impl(h, d, x, mask_value, params, h_out, ld_h, workspace, workspace_bytes, stream_,
+                                   &st, "lstm_train_forward_stateful");
 }
 
 extern "C" int32_t drnmf_lstm_loss_head_backward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* y,

@@ -2237,13 +2237,15 @@ class LSTM(_Layer):
     """keras.layers.LSTM as build_lstm uses it (enhance.py:333-335) [K2.0.4-memory]: weights kernel [in, 4H]
     (glorot_uniform), recurrent_kernel [H, 4H] (orthogonal), bias [4H] (zeros, unit_forget_bias=True: the f
     block bias[H:2H] = 1); gate columns i, f, c, o; activation tanh, recurrent_activation hard_sigmoid by
-    default (sigmoid selectable); zero initial states.  The forward runs as part of LSTMModel (csrc/lstm.hip)."""
+    default (sigmoid selectable); zero initial states, or with stateful=True the states the previous batch
+    left (they live in LSTMModel, [K,B,H] for the whole stack).  The forward runs as part of LSTMModel
+    (csrc/lstm.hip)."""
     ordered_weights = True
 
     def __init__(self, units, return_sequences=False, input_shape=None, activation='tanh',
                  recurrent_activation='hard_sigmoid', kernel_initializer='glorot_uniform',
                  recurrent_initializer='orthogonal', bias_initializer='zeros', unit_forget_bias=True,
-                 device=None, **kw):
+                 stateful=False, device=None, **kw):
         super(LSTM, self).__init__(**kw)
         if not return_sequences:
             raise NotImplementedError('LSTM: only return_sequences=True (build_lstm, enhance.py:334)')
@@ -2259,6 +2261,7 @@ class LSTM(_Layer):
         self.input_shape = input_shape
         self.activation, self.recurrent_activation = activation, recurrent_activation
         self.unit_forget_bias = bool(unit_forget_bias)
+        self.stateful = bool(stateful)
         self.device = torch.device(device if device is not None else 'cuda')
         self.kernel = self.recurrent_kernel = self.bias = None
 
@@ -2323,15 +2326,29 @@ class LSTMModel(_SequenceModel):
     """Masking -> LSTM(H, return_sequences=True) x K -> TimeDistributed(Dense(F)) -> sigmoid, the slice of
     keras.Model enhance.py's LSTM branch uses for inference: layers, get/set_weights, save/load_weights,
     predict / predict_on_batch (the shared slab loop, length-aware).  `forward` keeps everything on the device:
-    one drnmf_lstm_forward (input projection + T + K - 1 wavefront launches) and one head launch."""
+    one drnmf_lstm_forward (input projection + T + K - 1 wavefront launches) and one head launch.
+
+    Stateful (every LSTM layer built with stateful=True; a mixed stack is refused): h and c of every layer,
+    [K,B,H] device tensors, are carried from call to call as in Keras -- row i of a batch continues row i of the
+    batch before it -- by forward / predict_on_batch / predict (rows in order, no length-sorted slabs),
+    test_on_batch, train_on_batch and fit (truncated BPTT: the entering state is a constant of the gradient).
+    The states are zeros on first use and after reset_states(), and bound to the batch size they were first
+    used at: a call at another batch size raises ValueError (reset_states(batch_size=...) rebinds them).  fit()
+    shuffles rows unless told shuffle=False, exactly as for the stateful SimpleDeepRNN (and as Keras does):
+    carrying state across batches only means something with shuffle=False.  Validation inside fit() runs on a
+    state of its own that starts at zero, and the training state is put back afterwards: what fit() leaves
+    is the state behind the last training batch."""
 
     def __init__(self, layers, lstms, dense, mask_value, device):
+        if len(set(bool(getattr(l, 'stateful', False)) for l in lstms)) > 1:
+            raise ValueError('LSTMModel: all LSTM layers must be stateful, or none (the stack shares one state)')
         self.layers = layers
         self.lstms, self.dense = lstms, dense
         self.mask_value = mask_value
         self.device = device
         self._prepared = None        # (weight versions, desc key, params block)
         self._ws = None
+        self._states = None          # stateful: (h, c), each [K,B,H]
 
     @property
     def weights(self):
@@ -2356,6 +2373,48 @@ class LSTMModel(_SequenceModel):
 
     def _input_width(self):
         return self.dense.units
+
+    def _stateful(self):
+        return bool(self.lstms[0].stateful)
+
+    def _state(self, B):
+        """The (h, c) pair a call at batch size B carries (None for a model that is not stateful): zeros on
+        first use; ValueError at another batch size than the one the states are bound to."""
+        if not self._stateful():
+            return None
+        if self._states is None:
+            shape = (len(self.lstms), int(B), self.lstms[0].units)
+            self._states = tuple(torch.zeros(shape, dtype=torch.float32, device=self.device) for _ in range(2))
+        elif int(self._states[0].shape[1]) != int(B):
+            raise ValueError('stateful LSTM: the states belong to batch size %d, this call has %d rows '
+                             '(reset_states(batch_size=%d) starts over at the new size)'
+                             % (int(self._states[0].shape[1]), int(B), int(B)))
+        return self._states
+
+    def reset_states(self, batch_size=None):
+        """Keras' model.reset_states(): zero h and c of every layer (in place; before the first call there is
+        nothing to zero).  batch_size: rebind the states to another batch size."""
+        if not self._stateful():
+            raise AttributeError('Layer must be stateful.')
+        if batch_size is not None and self._states is not None and \
+                int(self._states[0].shape[1]) != int(batch_size):
+            self._states = None
+        if self._states is None:
+            if batch_size is not None:
+                self._state(batch_size)
+            return
+        for t in self._states:
+            t.zero_()
+
+    def _validate(self, validation_data, batch_size, take):
+        # a stateful model validates on a state of its own, from zero; the training state comes back untouched
+        if not self._stateful():
+            return super(LSTMModel, self)._validate(validation_data, batch_size, take)
+        saved, self._states = self._states, None
+        try:
+            return super(LSTMModel, self)._validate(validation_data, batch_size, take)
+        finally:
+            self._states = saved
 
     # -- training (enhance.py:1260-1312): loss 'mse_of_masked' = mse(Masking output * sigmoid output, y) with
     #    temporal sample weights, Adam; the trainer itself is _SequenceModel's ------------------------------------
@@ -2439,7 +2498,11 @@ class LSTMModel(_SequenceModel):
         if self._d_hidden is None or tuple(self._d_hidden.shape) != (B, T, desc.H):
             self._d_hidden = torch.empty((B, T, desc.H), dtype=torch.float32, device=self.device)
         ws, gv, ns = self._train_ws, self._gview, self.N_SCALARS
-        h = ops.lstm_train_forward(x, self.mask_value, params, desc, ws)
+        # (stateful: the state enters as a constant of the gradient and the one this batch leaves replaces it in
+        # place -- the kernels read all of the entering state before they write the leaving one, and the BPTT
+        # finds its copy in the workspace)
+        st = self._state(B)
+        h = ops.lstm_train_forward(x, self.mask_value, params, desc, ws, initial_state=st, final_state=st)
         d = self.dense
         ops.lstm_loss_head_backward(y, sample_weight, h, params, d.kernel, desc, ws, self._flat[-ns:-ns + 2],
                                     self._d_hidden, gv[d.weight_names[0]], gv[d.weight_names[1]])
@@ -2487,7 +2550,9 @@ class LSTMModel(_SequenceModel):
         if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-        h = ops.lstm_forward(x, self.mask_value, params, desc, workspace=self._ws)
+        st = self._state(x.shape[0])
+        h = ops.lstm_forward(x, self.mask_value, params, desc, workspace=self._ws, initial_state=st,
+                             final_state=st)
         y = ops.lstm_head_forward(h, params, desc)
         return (y, h) if want_hidden else y
 
@@ -2501,7 +2566,8 @@ class LSTMModel(_SequenceModel):
 def build_lstm(params_lstm, device=None):
     """enhance.py:321-345 with the same parameter dictionary keys (mask_value, maxseq, input_dim, output_dim,
     K_layers, hidden_dim); 'recurrent_activation' (optional, a Keras LSTM argument) selects 'sigmoid' instead
-    of the default 'hard_sigmoid'."""
+    of the default 'hard_sigmoid'; 'stateful' (optional, a Keras LSTM argument, default False) builds every LSTM
+    layer stateful.  The reference's dictionaries have neither key."""
     p = params_lstm
     mask_value, maxseq = p['mask_value'], p['maxseq']
     input_dim, output_dim = int(p['input_dim']), int(p['output_dim'])
@@ -2516,7 +2582,8 @@ def build_lstm(params_lstm, device=None):
     lstms = []
     for k in range(K):
         l = LSTM(H, return_sequences=True, input_shape=(maxseq, input_dim),
-                 recurrent_activation=p.get('recurrent_activation', 'hard_sigmoid'), device=dev)
+                 recurrent_activation=p.get('recurrent_activation', 'hard_sigmoid'),
+                 stateful=bool(p.get('stateful', False)), device=dev)
         l.build((None, maxseq, input_dim if k == 0 else H))
         lstms.append(l)
     dense = Dense(output_dim, device=dev)

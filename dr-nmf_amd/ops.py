@@ -1538,10 +1538,30 @@ def _hidden_ld(t, desc, what):
     return int(ld)
 
 
-def lstm_forward(x, mask_value, params, desc, out=None, workspace=None):
+def _lstm_state_pair(state, desc, what, device):
+    """`state`: None, or (h, c) of contiguous float32 [K,B,H] device tensors, either of which may be None (the C
+    ABI's NULL: zeros on the way in, not wanted on the way out)."""
+    if state is None:
+        return None, None
+    if not isinstance(state, (tuple, list)) or len(state) != 2:
+        raise ValueError("%s must be a pair (h, c)" % what)
+    for t, n in zip(state, ("h", "c")):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or tuple(t.shape) != (desc.K, desc.B, desc.H) or not t.is_contiguous() or \
+                t.device != device:
+            raise ValueError("%s %s must be a contiguous float32 (K,B,H) = (%d,%d,%d) tensor on %s"
+                             % (what, n, desc.K, desc.B, desc.H, device))
+    return state[0], state[1]
+
+
+def lstm_forward(x, mask_value, params, desc, out=None, workspace=None, *, initial_state=None, final_state=None):
     """K stacked Keras LSTM layers (return_sequences=True) behind Masking(mask_value): x [B,T,F] -> the last
     layer's outputs [B,T,H], by default a view of a [B,T,lstm_hidden_ld(H)] buffer whose padding columns the
-    kernel zeroes (`out`: any (B,T,H) tensor with strides (T*ld, ld, 1)).  mask_value None: no frame is masked."""
+    kernel zeroes (`out`: any (B,T,H) tensor with strides (T*ld, ld, 1)).  mask_value None: no frame is masked.
+    initial_state / final_state: (h, c) pairs of [K,B,H] tensors, the state entering frame 0 (None: zeros) and the
+    one leaving frame T-1, written in place (None: not wanted); the same pair may be passed as both
+    (drnmf_lstm_forward_stateful).  Both None: drnmf_lstm_forward."""
     L = _capi.lib()
     h = _capi.handle(_dev_index(x))
     x = _f32c(x, "x")
@@ -1555,6 +1575,14 @@ def lstm_forward(x, mask_value, params, desc, out=None, workspace=None):
     if workspace is None:
         workspace = lstm_workspace(desc, x.device)
     mv = float("nan") if mask_value is None else float(mask_value)
+    if initial_state is not None or final_state is not None:
+        ih, ic = _lstm_state_pair(initial_state, desc, "initial_state", x.device)
+        fh, fc = _lstm_state_pair(final_state, desc, "final_state", x.device)
+        rc = L.drnmf_lstm_forward_stateful(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), _capi.ptr(ih),
+                                           _capi.ptr(ic), _capi.ptr(fh), _capi.ptr(fc), _capi.ptr(out), ld,
+                                           _capi.ptr(workspace), workspace.numel(), _stream())
+        _capi.check(rc, h, "drnmf_lstm_forward_stateful")
+        return out
     rc = L.drnmf_lstm_forward(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), _capi.ptr(out), ld,
                               _capi.ptr(workspace), workspace.numel(), _stream())
     _capi.check(rc, h, "drnmf_lstm_forward")
@@ -1584,9 +1612,11 @@ def lstm_train_workspace(desc, device):
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
-def lstm_train_forward(x, mask_value, params, desc, workspace, out=None):
+def lstm_train_forward(x, mask_value, params, desc, workspace, out=None, *, initial_state=None, final_state=None):
     """lstm_forward (the same hidden states, bit for bit) that also keeps in `workspace` what
-    lstm_loss_head_backward and lstm_backward need."""
+    lstm_loss_head_backward and lstm_backward need.  initial_state / final_state as in lstm_forward
+    (drnmf_lstm_train_forward_stateful): the entering state is kept in the workspace as a constant of the gradient,
+    which lstm_backward then reads there."""
     L = _capi.lib()
     h = _capi.handle(_dev_index(x))
     x = _f32c(x, "x")
@@ -1598,6 +1628,15 @@ def lstm_train_forward(x, mask_value, params, desc, workspace, out=None):
     else:
         ld = _hidden_ld(out, desc, "out")
     mv = float("nan") if mask_value is None else float(mask_value)
+    if initial_state is not None or final_state is not None:
+        ih, ic = _lstm_state_pair(initial_state, desc, "initial_state", x.device)
+        fh, fc = _lstm_state_pair(final_state, desc, "final_state", x.device)
+        rc = L.drnmf_lstm_train_forward_stateful(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params),
+                                                 _capi.ptr(ih), _capi.ptr(ic), _capi.ptr(fh), _capi.ptr(fc),
+                                                 _capi.ptr(out), ld, _capi.ptr(workspace), workspace.numel(),
+                                                 _stream())
+        _capi.check(rc, h, "drnmf_lstm_train_forward_stateful")
+        return out
     rc = L.drnmf_lstm_train_forward(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), _capi.ptr(out), ld,
                                     _capi.ptr(workspace), workspace.numel(), _stream())
     _capi.check(rc, h, "drnmf_lstm_train_forward")

@@ -11,7 +11,7 @@
  *   z = x_t kernel + h_{t-1} recurrent_kernel + bias;
  *   i = s(z_i), f = s(z_f), c_t = f c_{t-1} + i tanh(z_c), o = s(z_o), h_t = o tanh(c_t);
  *   s = hard_sigmoid = clip(0.2 x + 0.5, 0, 1) by default (recurrent_activation), sigmoid selectable;
- *   zero initial h and c.
+ *   zero initial h and c (the *_stateful entry points take and return both).
  * Masking as Theano's masked K.rnn: a frame whose bins ALL equal mask_value is masked; at a masked step the
  * output and both states are the previous step's (zeros before the first valid step), in every layer.
  */
@@ -50,6 +50,27 @@ int32_t drnmf_lstm_forward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const f
                            const void* params, float* h_out, int32_t ld_h, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* drnmf_lstm_forward with h and c carried across calls (Keras' LSTM(stateful=True) [K2.0.4-memory]), named after
+ * the cell's *_stateful entries in drnmf.h.  Every state array is [K][B][H] float32, contiguous and caller-owned
+ * (layer k's state of sequence b at (k B + b) H); nothing is allocated inside the call.
+ *   initial_h / initial_c: the state entering frame 0 of every layer; NULL = zeros (each on its own).
+ *   final_h / final_c: the state leaving frame T-1; NULL = not wanted (nothing is written).
+ * Ordering: EVERY read of initial_* happens before ANY write of final_* -- the entering state is copied into the
+ * workspace by a kernel in front of the recurrence, the leaving state is copied out by one behind it -- so
+ * final_x may alias initial_x (the usual call: one buffer pair carried from call to call).  Both copies run on
+ * the caller's stream outside the replayed frame graphs, which therefore hold no state pointer: calls that
+ * differ only in their state pointers or contents replay the same graphs.
+ * Masking: a masked step copies both states, so a sequence masked for the whole call leaves with exactly the
+ * state it entered with.  At masked frames BEFORE a call's first valid frame h_out is the carried h (the output
+ * the previous call ended on), which makes a run cut into calls equal to the same frames run in one call.
+ * [K2.0.4-memory] difference: Keras' masked K.rnn writes zeros at those frames; they carry weight 0 in every loss
+ * the reference uses.  With all four pointers NULL the call computes what drnmf_lstm_forward computes, bit for
+ * bit. */
+int32_t drnmf_lstm_forward_stateful(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x, float mask_value,
+                                    const void* params, const float* initial_h, const float* initial_c,
+                                    float* final_h, float* final_c, float* h_out, int32_t ld_h, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+
 /* Head: out [B*T][F] = sigmoid(hidden . w_out + b_out), every frame (masked ones included); hidden rows have
  * stride ld_h >= H.  With ld_h >= round_up(H, 4) the columns H .. round_up(H, 4)-1 are read and must be finite
  * (drnmf_lstm_forward writes zeros there). */
@@ -80,6 +101,17 @@ size_t drnmf_lstm_train_workspace_bytes(const drnmf_lstm_desc_t* d);
 int32_t drnmf_lstm_train_forward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x, float mask_value,
                                  const void* params, float* h_out, int32_t ld_h, void* workspace,
                                  size_t workspace_bytes, void* stream);
+/* drnmf_lstm_train_forward with the state arguments of drnmf_lstm_forward_stateful (same layout, NULL rules,
+ * aliasing and masking; the same h_out as drnmf_lstm_forward_stateful bit for bit).  The entering state is also
+ * kept in the training workspace, in the zero frame in front of every sequence, where drnmf_lstm_backward reads
+ * it: c_{t-1} of frame 0 in dz_f, h_{t-1} of frame 0 in the recurrent-kernel gradient.  It is a CONSTANT of the
+ * gradient (as in drnmf_cell_backward_stateful): nothing propagates past frame 0 and no gradient with respect to
+ * the state is returned -- truncated BPTT.  drnmf_lstm_loss_head_backward and drnmf_lstm_backward follow
+ * unchanged; there is no backward entry point of its own. */
+int32_t drnmf_lstm_train_forward_stateful(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x,
+                                          float mask_value, const void* params, const float* initial_h,
+                                          const float* initial_c, float* final_h, float* final_c, float* h_out,
+                                          int32_t ld_h, void* workspace, size_t workspace_bytes, void* stream);
 int32_t drnmf_lstm_loss_head_backward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* y, const float* w,
                                       const float* hidden, int32_t ld_h, const void* params, const float* w_out,
                                       float* sums, float* d_hidden, float* d_w_out, float* d_b_out, void* workspace,
