@@ -1,6 +1,7 @@
 """ctypes binding of libdrnmf.so (C ABI in include/drnmf.h; the LSTM baseline's in include/drnmf_lstm.h; the
 STOI score's in include/drnmf_score.h; the ragged STFT / iSTFT / int16 stages' in include/drnmf_enhance.h; the
-device-side SDR's in include/drnmf_sdr.h; the training-data front end's in include/drnmf_dataset.h).
+device-side SDR's in include/drnmf_sdr.h; the training-data front end's in include/drnmf_dataset.h; the streaming
+STFT / iSTFT's in include/drnmf_stream.h).
 
 The library is the product path: there is NO fallback.  If the shared object is missing or a
 call fails, an exception is raised.
@@ -197,6 +198,17 @@ DATASET_SIGNATURES = {
 }
 TRANSFORMS = {"mag": 0, "logmag": 1}     # DRNMF_TRANSFORM_*
 
+# name -> (restype, argtypes); mirrors include/drnmf_stream.h one to one (a table of its own, like the five above)
+STREAM_SIGNATURES = {
+    "drnmf_stream_counts": (_i32, [_i64, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
+    "drnmf_stream_state_bytes": (_sz, [_i32, _i32, _i32]),
+    "drnmf_stream_reset": (_i32, [_vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "drnmf_stream_forward": (_i32, [_vp, _i32, _i64, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _sz, _vp]),
+    "drnmf_stream_inverse": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp,
+                                    _sz, _vp]),
+}
+
 _lib = None
 _handles = {}
 
@@ -220,7 +232,8 @@ def lib():
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(LSTM_SIGNATURES.items()) +
                                   list(SCORE_SIGNATURES.items()) + list(ENHANCE_SIGNATURES.items()) +
-                                  list(SDR_SIGNATURES.items()) + list(DATASET_SIGNATURES.items())):
+                                  list(SDR_SIGNATURES.items()) + list(DATASET_SIGNATURES.items()) +
+                                  list(STREAM_SIGNATURES.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

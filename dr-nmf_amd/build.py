@@ -40,7 +40,7 @@ def _sources():
 def _deps():
     return _sources() + glob.glob(os.path.join(CSRC, "*.h")) + \
         [os.path.join(os.path.dirname(HERE), "include", n) for n in ("drnmf.h", "drnmf_lstm.h", "drnmf_score.h", "drnmf_enhance.h", "drnmf_sdr.h",
-                                                                     "drnmf_dataset.h")] + \
+                                                                     "drnmf_dataset.h", "drnmf_stream.h")] + \
         [os.path.abspath(__file__)]
 
 

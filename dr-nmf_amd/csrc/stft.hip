@@ -15,6 +15,7 @@
 #include "common.h"
 #include "../../include/drnmf_enhance.h"
 #include "../../include/drnmf_dataset.h"
+#include "../../include/drnmf_stream.h"
 
 namespace {
 
@@ -515,6 +516,42 @@ stft_ragged_kernel(const void* __restrict__ pcm, int is_int16, int64_t stride,
                threadIdx.x);
 }
 
+// one masked frame back to N samples by ONE WAVE (lane j), the mirror of stft_real_frame (the derivation stands
+// in front of istft_real_ragged_kernel): o, om = element offsets of the frame's spectrum and mask rows; on return
+// x[n] * window[n] * scale sits at cur[pad(n >> 1)].x / .y (n even / odd).  Shared by the ragged and the
+// streaming inverse.
+template <int R, int P>
+__device__ __forceinline__ void istft_real_frame(const float* re, const float* im, const float* mask, size_t o,
+                                                 size_t om, const float2* tw, float2* cur, const float* win,
+                                                 float scale, int j) {
+    constexpr int M = RealFft<R, P>::M;
+    auto pad = [](int i) { return RealFft<R, P>::pad(i); };
+    float2 v[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int ka = j + r * (M / R), kc = M - ka;       // 0 <= ka < M, 1 <= kc <= M
+        const float ma = mask ? mask[om + ka] : 1.f, mc = mask ? mask[om + kc] : 1.f;
+        float2 a = make_float2(ma * re[o + ka], ma * im[o + ka]);
+        float2 c = make_float2(mc * re[o + kc], mc * im[o + kc]);
+        if (ka == 0) {
+            a.y = 0.f;
+            c.y = 0.f;
+        }
+        const float2 A = make_float2(a.x + c.x, a.y - c.y);   // W_k + conj W_{M-k}
+        const float2 B = make_float2(a.x - c.x, a.y + c.y);   // W_k - conj W_{M-k}
+        const float2 wB = cmul(B, tw[ka]);
+        v[r] = make_float2(A.x - wB.y, A.y + wB.x);           // A + i w B
+    }
+    stockham_passes<R, P>(v, cur, tw, j);
+#pragma unroll
+    for (int i = 0; i < M / 64; ++i) {
+        const int n = j + 64 * i;
+        const float2 z = cur[pad(n)];
+        const float2 w2 = *(const float2*)(win + 2 * n);
+        cur[pad(n)] = make_float2(z.x * scale * w2.x, z.y * scale * w2.y);
+    }
+}
+
 // Masked inverse for N = 512 / 1024, the mirror of stft_real_kernel.  The frame is real, so its N samples are
 // ONE complex transform of M = N/2 points: with W_k = mask_k S_k (Hermitian, the imaginary parts of W_0 and
 // W_M dropped as the real part of the full transform drops them) and x[n] = sum_{k<N} W_k e^{-2 pi i k n / N},
@@ -575,30 +612,7 @@ istft_real_ragged_kernel(const float* __restrict__ re, const float* __restrict__
         if (f <= f_hi) {
             const size_t o = ((size_t)k * T + (size_t)f) * F;
             const size_t om = ((size_t)k * T + (size_t)f) * (size_t)ld_mask;
-            float2 v[R];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int ka = j + r * (M / R), kc = M - ka;       // 0 <= ka < M, 1 <= kc <= M
-                const float ma = mask ? mask[om + ka] : 1.f, mc = mask ? mask[om + kc] : 1.f;
-                float2 a = make_float2(ma * re[o + ka], ma * im[o + ka]);
-                float2 c = make_float2(mc * re[o + kc], mc * im[o + kc]);
-                if (ka == 0) {
-                    a.y = 0.f;
-                    c.y = 0.f;
-                }
-                const float2 A = make_float2(a.x + c.x, a.y - c.y);   // W_k + conj W_{M-k}
-                const float2 B = make_float2(a.x - c.x, a.y + c.y);   // W_k - conj W_{M-k}
-                const float2 wB = cmul(B, tw[ka]);
-                v[r] = make_float2(A.x - wB.y, A.y + wB.x);           // A + i w B
-            }
-            stockham_passes<R, P>(v, cur, tw, j);
-#pragma unroll
-            for (int i = 0; i < M / 64; ++i) {
-                const int n = j + 64 * i;
-                const float2 z = cur[pad(n)];
-                const float2 w2 = *(const float2*)(win + 2 * n);
-                cur[pad(n)] = make_float2(z.x * scale * w2.x, z.y * scale * w2.y);
-            }
+            istft_real_frame<R, P>(re, im, mask, o, om, tw, cur, win, scale, j);
         }
         __syncthreads();
         // sample i of the run sits at n = s0 + i + N - f hop of frame f (|s0 - f hop| < run + N + hop: int)
@@ -1135,3 +1149,6 @@ extern "C" int32_t drnmf_stft_pair_frames(drnmf_handle_t h, int32_t n_sig, int64
     DRNMF_HIP(h, hipGetLastError());
     return DRNMF_OK;
 }
+
+// ---- streaming (include/drnmf_stream.h) -------------------------------------------------------------------
+#include "stft_stream.h"

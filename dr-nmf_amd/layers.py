@@ -1392,6 +1392,12 @@ class _SequenceModel(object):
             ret.append(masks)
         return ret[0] if len(ret) == 1 else tuple(ret)
 
+    def stream(self, n_streams, N=512, hop=128, dtype='float32', crop=True):
+        """An EnhanceStream over n_streams independent recordings fed in chunks: `enhance` for audio that arrives
+        piece by piece, the carry between pushes on the device.  Needs a stateful model (the recurrent state of
+        stream i is row i of the model's state), which starts from its reset state at batch size n_streams."""
+        return EnhanceStream(self, n_streams, N=N, hop=hop, dtype=dtype, crop=crop)
+
     def free_predict_buffers(self):
         """Drop the pinned staging buffers, device slabs and copy streams `predict` / `predict_on_batch` keep
         between calls (they are re-made on the next call)."""
@@ -1765,6 +1771,72 @@ class _SequenceModel(object):
         return sse * scale + (self._regularization_loss() if hasattr(self, '_train_items') else 0.0)
 
 
+class EnhanceStream(object):
+    """What `model.stream(...)` returns.  push(chunks) takes one chunk per stream (1-D numpy arrays of one type,
+    int16 scaled by 1/32768 or float32; any lengths, 0 included) and returns, per stream, the enhanced samples
+    that have become final: ops.WaveStream.analyse, model.forward on the new frames, ops.WaveStream.synthesise.
+    An open stream's output lags its input by N - hop .. N - 1 samples; close() flushes the rest.  The
+    concatenated float32 output of a stream is what the same stateful model gives on the whole recording
+    (ops.stft_ragged, forward, ops.istft_ragged) up to the model's dependence on the batch shape; dtype='int16'
+    scales by 32767 and truncates as util.wavwrite does but does NOT divide by the recording's peak (unknown
+    before the stream ends): values beyond +-1 saturate at +-32767.
+
+    A row with fewer new frames than the longest of a push is padded with the model's mask_value, through which
+    both recurrences carry their state unchanged; a model without a mask_value takes equal chunk lengths only.
+    The frame count T of a push keys the model's workspace and frame-graph caches: chunk sizes that are a
+    multiple of hop keep it constant."""
+
+    def __init__(self, model, n_streams, N=512, hop=128, dtype='float32', crop=True):
+        if dtype not in ('int16', 'float32'):
+            raise ValueError("stream: dtype must be 'int16' or 'float32'")
+        if not model._stateful():
+            raise ValueError('stream: the model carries no state between calls; build it with stateful=True')
+        N, hop, B = int(N), int(hop), int(n_streams)
+        F = N // 2 + 1
+        if F != model._input_width():
+            raise ValueError('stream: N = %d gives %d bins, the model takes %d' % (N, F, model._input_width()))
+        self.model, self.n_streams, self.dtype = model, B, dtype
+        mv = model.mask_value
+        self._ws = ops.WaveStream(B, N, hop, mask_value=0.0 if mv is None else mv, device=model._device(),
+                                  crop=crop)
+        model.reset_states(batch_size=B)
+
+    @property
+    def closed(self):
+        return self._ws.closed.copy()
+
+    def reset(self):
+        """Every stream fresh and open, the model back at its reset state."""
+        self._ws.reset()
+        self.model.reset_states(batch_size=self.n_streams)
+
+    def push(self, chunks, final=False):
+        ws = self._ws
+        if self.model.mask_value is None:
+            lens = set(int(np.asarray(c).shape[0]) for c in chunks)
+            fins = set(np.atleast_1d(np.asarray(final, dtype=bool)).tolist())
+            if len(lens) > 1 or len(fins) > 1:
+                raise ValueError('stream: a model without a mask_value takes equal chunk lengths only')
+        x, re, im, n_new = ws.analyse(chunks, final=final)
+        if x.shape[1] == 0:
+            return [np.zeros(0, dtype=self.dtype) for _ in range(self.n_streams)]
+        try:
+            mask = self.model.forward(x)
+            if mask.shape[-1] != x.shape[-1]:
+                raise ValueError('stream: the model returns %d bins for %d' % (mask.shape[-1], x.shape[-1]))
+        except Exception:
+            ws._pending = None
+            raise
+        out = ws.synthesise(re, im, mask, dtype=self.dtype)
+        ops.check_status(torch.device(self.model._device()))
+        return out
+
+    def close(self):
+        """End every stream: the samples still held back (zero-padded as offline)."""
+        dt = self._ws.dtype if self._ws.dtype is not None else np.dtype('float32')
+        return self.push([np.zeros(0, dtype=dt) for _ in range(self.n_streams)], final=True)
+
+
 class UnfoldedSNMFModel(_SequenceModel):
     """Masking -> SimpleDeepRNN -> [:r]/[r:] -> DenseNonNegW x2 -> (square) -> A/(A+B).
     Exposes the slice of keras.Model that enhance.py uses: layers, get/set_weights,
@@ -1799,6 +1871,16 @@ class UnfoldedSNMFModel(_SequenceModel):
 
     def _stateful(self):
         return bool(getattr(self.cell, 'stateful', False))
+
+    def reset_states(self, batch_size=None):
+        """Keras' model.reset_states(): zero the cell's carried state.  batch_size: bind the state to that batch
+        size (zeros), whatever it held."""
+        if not self._stateful():
+            raise AttributeError('Layer must be stateful.')
+        if batch_size is None:
+            return self.cell.reset_states()
+        self.cell.states = [torch.zeros((int(batch_size), self.cell.output_dim), dtype=torch.float32,
+                                        device=self.cell.device)]
 
     def forward(self, x, want_hidden=False):
         """Device tensors in, device tensors out, nothing waited for: a fault on the device (a persistent

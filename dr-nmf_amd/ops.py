@@ -1360,6 +1360,185 @@ def to_int16_wav_rows(y, lengths):
     return out
 
 
+# ---- streaming: chunks in, finished samples out (include/drnmf_stream.h) --------------------------------------
+def stream_counts(n_samples, closed, N, hop, crop=False):
+    """(frames, samples) a stream holds after n_samples samples, open or closed (drnmf_stream_counts).  A stream
+    that has never been pushed has (0, 0)."""
+    L = _capi.lib()
+    f, s = _capi.C.c_int64(), _capi.C.c_int64()
+    rc = L.drnmf_stream_counts(int(n_samples), int(bool(closed)), int(N), int(hop), int(bool(crop)),
+                               _capi.C.byref(f), _capi.C.byref(s))
+    if rc != _capi.OK:
+        raise ValueError("stream_counts: n_samples = %d must not be negative and hop = %d must divide N = %d"
+                         % (n_samples, hop, N))
+    return int(f.value), int(s.value)
+
+
+def stream_state(B, N, hop, device):
+    """A reset state buffer for B streams (uint8 on the device)."""
+    nbytes = _capi.lib().drnmf_stream_state_bytes(int(B), int(N), int(hop))
+    if nbytes == 0:
+        raise ValueError("stream_state: B = %d must lie in [1, 65535], N = %d be a power of two in [64, 4096] and "
+                         "hop = %d divide it" % (B, N, hop))
+    state = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    stream_reset_enqueue(state, B, N, hop)
+    return state
+
+
+def stream_reset_enqueue(state, B, N, hop):
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(state))
+    rc = L.drnmf_stream_reset(h, int(B), int(N), int(hop), _capi.ptr(state), state.numel(), _stream())
+    _capi.check(rc, h, "drnmf_stream_reset")
+
+
+def stream_forward_enqueue(chunk, chunk_len_dev, final_dev, N, hop, mask_value, x, re, im, state):
+    """drnmf_stream_forward on tensors the caller owns and has checked: enqueues, reads nothing back."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(chunk))
+    B, stride = chunk.shape
+    rc = L.drnmf_stream_forward(h, B, stride, x.shape[1], int(N), int(hop), int(chunk.dtype == torch.int16),
+                                float(mask_value), _capi.ptr(chunk), _capi.ptr(chunk_len_dev),
+                                _capi.ptr(final_dev), _capi.ptr(x), _capi.ptr(re), _capi.ptr(im), _capi.ptr(state),
+                                state.numel(), _stream())
+    _capi.check(rc, h, "drnmf_stream_forward")
+
+
+def stream_inverse_enqueue(re, im, mask, N, hop, crop, y, state):
+    """drnmf_stream_inverse on tensors the caller owns and has checked (y float32 or int16 [B, stride_y]):
+    enqueues, reads nothing back."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(re))
+    B, T, F = re.shape
+    rc = L.drnmf_stream_inverse(h, B, T, int(N), int(hop), _capi.ptr(re), _capi.ptr(im), _capi.ptr(mask),
+                                0 if mask is None else mask.stride(1), int(bool(crop)),
+                                int(y.dtype == torch.int16), _capi.ptr(y), y.shape[1], _capi.ptr(state),
+                                state.numel(), _stream())
+    _capi.check(rc, h, "drnmf_stream_inverse")
+
+
+class WaveStream(object):
+    """B independent streams through the streaming STFT / iSTFT: owns the state on the device and the host mirror
+    of the counts.  A push is `analyse` (chunks -> the frames that have become complete), whatever turns their
+    magnitude into a mask, then `synthesise` (-> the samples that have become final); every analyse that returns
+    frames must be followed by one synthesise.  Frames and float32 samples are bitwise those of stft_ragged /
+    istft_ragged on the whole signals, whatever the cuts."""
+
+    def __init__(self, B, N, hop, mask_value=-1.0, device=None, crop=True):
+        self.B, self.N, self.hop, self.crop = int(B), int(N), int(hop), bool(crop)
+        self.mask_value = float(mask_value)
+        dev = torch.device('cuda' if device is None else device)
+        self.device = torch.device('cuda', _dev_of(dev))
+        with torch.cuda.device(self.device):
+            self.state = stream_state(self.B, self.N, self.hop, self.device)
+        self._zero_counts()
+
+    def _zero_counts(self):
+        self.n_in = np.zeros(self.B, dtype=np.int64)          # samples pushed
+        self.closed = np.zeros(self.B, dtype=bool)
+        self.frames = np.zeros(self.B, dtype=np.int64)        # frames emitted
+        self.samples = np.zeros(self.B, dtype=np.int64)       # samples emitted (or pending in _new_samples)
+        self.dtype = None                                     # the chunks' type, fixed by the first push
+        self._pending = None                                  # (T, new samples) between analyse and synthesise
+
+    def reset(self):
+        """Every stream fresh and open again."""
+        with torch.cuda.device(self.device):
+            stream_reset_enqueue(self.state, self.B, self.N, self.hop)
+        self._zero_counts()
+
+    def analyse(self, chunks, final=False):
+        """chunks: B 1-D numpy arrays of one type (int16, scaled by 1/32768, or float32), any lengths, 0 included;
+        final: a bool or B bools -- the stream ends with this chunk.  Returns (x, re, im, n_new): device tensors
+        [B, T, N/2+1] with T = max(n_new), x holding mask_value behind a row's own n_new[b] frames, and the int64
+        numpy counts.  The chunks, their lengths and the flags go up in one pinned copy."""
+        B, N, hop = self.B, self.N, self.hop
+        if self._pending is not None:
+            raise ValueError("WaveStream.analyse: the previous push's frames have not been synthesised")
+        rows = [np.asarray(c) for c in chunks]
+        if len(rows) != B:
+            raise ValueError("WaveStream.analyse: %d chunks for %d streams" % (len(rows), B))
+        fin = np.broadcast_to(np.asarray(final, dtype=bool), (B,)) if np.ndim(final) == 0 else \
+            np.asarray(list(final), dtype=bool)
+        if fin.shape != (B,):
+            raise ValueError("WaveStream.analyse: final must be a bool or %d bools" % B)
+        dt = rows[0].dtype if self.dtype is None else self.dtype
+        if dt not in (np.dtype('int16'), np.dtype('float32')):
+            raise ValueError("WaveStream.analyse: chunks must be int16 or float32 (got %s)" % dt)
+        for c in rows:
+            if c.ndim != 1 or c.dtype != dt:
+                raise ValueError("WaveStream.analyse: every chunk must be a 1-D %s array" % dt)
+        lens = np.array([c.shape[0] for c in rows], dtype=np.int64)
+        if np.any(self.closed & (lens > 0)):
+            raise ValueError("WaveStream.analyse: stream %d is closed and takes only empty chunks until reset()"
+                             % int(np.nonzero(self.closed & (lens > 0))[0][0]))
+        n_in, closed = self.n_in + lens, self.closed | fin
+        counts = [stream_counts(n_in[b], closed[b], N, hop, self.crop) for b in range(B)]
+        frames = np.array([c[0] for c in counts], dtype=np.int64)
+        samples = np.array([c[1] for c in counts], dtype=np.int64)
+        n_new = frames - self.frames
+        T = int(n_new.max())
+        stride = max(1, int(lens.max()))
+        # one pinned upload: lengths [B] int64 | flags [B] int32 | samples [B][stride]
+        off = -(-(12 * B) // 16) * 16
+        host = torch.empty(off + B * stride * dt.itemsize, dtype=torch.uint8, pin_memory=True)
+        hn = host.numpy()
+        hn[:8 * B].view(np.int64)[:] = lens
+        hn[8 * B:12 * B].view(np.int32)[:] = fin
+        pk = hn[off:].view(dt).reshape(B, stride)
+        for b, c in enumerate(rows):
+            pk[b, :c.shape[0]] = c
+            pk[b, c.shape[0]:] = 0
+        F = N // 2 + 1
+        with torch.cuda.device(self.device):
+            d = host.to(self.device, non_blocking=True)
+            chunk = d[off:].view(torch.int16 if dt == np.dtype('int16') else torch.float32).view(B, stride)
+            # (T = 0: the call still moves the carry on; its one row of frames is all padding)
+            x = torch.empty((B, max(T, 1), F), dtype=torch.float32, device=self.device)
+            re, im = torch.empty_like(x), torch.empty_like(x)
+            stream_forward_enqueue(chunk, d[:8 * B].view(torch.int64), d[8 * B:12 * B].view(torch.int32), N, hop,
+                                   self.mask_value, x, re, im, self.state)
+        self.dtype = dt
+        new_samples = samples - self.samples
+        self.n_in, self.closed, self.frames, self.samples = n_in, closed, frames, samples
+        if T == 0:
+            return x[:, :0], re[:, :0], im[:, :0], n_new
+        self._pending = (T, new_samples)
+        return x, re, im, n_new
+
+    def synthesise(self, re, im, mask, dtype='float32'):
+        """The masked frames of the latest analyse back to samples: a list of B 1-D numpy arrays (float32, or
+        int16 = truncation of 32767 * sample clamped to +-32767, WITHOUT util.wavwrite's peak normalisation),
+        stream b's holding the samples that have become final.  mask [B, T, N/2+1] (the model's output, a padded
+        row stride is taken in place) or None.  One copy down."""
+        if dtype not in ('int16', 'float32'):
+            raise ValueError("WaveStream.synthesise: dtype must be 'int16' or 'float32'")
+        if self._pending is None:
+            raise ValueError("WaveStream.synthesise: no analysed frames are pending")
+        T, new_samples = self._pending
+        B, F = self.B, self.N // 2 + 1
+        if tuple(re.shape) != (B, T, F) or tuple(im.shape) != (B, T, F):
+            raise ValueError("WaveStream.synthesise: re, im must be the [%d, %d, %d] tensors analyse returned"
+                             % (B, T, F))
+        re, im = _f32c(re, "re"), _f32c(im, "im")
+        if mask is not None:
+            if mask.dtype != torch.float32 or mask.device != re.device or tuple(mask.shape) != (B, T, F):
+                raise ValueError("WaveStream.synthesise: mask must be float32 %s on %s" % ((B, T, F), re.device))
+            if mask.stride(2) != 1 or mask.stride(1) < F or mask.stride(0) != T * mask.stride(1):
+                mask = mask.contiguous()
+        stride_y = max(1, int(new_samples.max()))
+        tdt = torch.int16 if dtype == 'int16' else torch.float32
+        with torch.cuda.device(self.device):
+            y = torch.empty((B, stride_y), dtype=tdt, device=self.device)
+            self._pending = None
+            stream_inverse_enqueue(re, im, mask, self.N, self.hop, self.crop, y, self.state)
+            back = torch.empty(y.shape, dtype=tdt, pin_memory=True)
+            back.copy_(y, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+        bn = back.numpy()
+        return [bn[b, :int(new_samples[b])].copy() for b in range(B)]
+
+
 # ---- STOI and the compute_scores row (score_audio.m:177-238; C ABI in include/drnmf_score.h) ---------------
 STOI_BANDS = 15
 SCORE_LABELS = ['SDR', 'SNR', 'SegSNR local', 'SegSNR global', 'PESQ', 'STOI']
