@@ -140,7 +140,7 @@ SIGNATURES = {
 
 
 class LstmDesc(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("B", "T", "F", "H", "K", "recurrent_activation")]
+    _fields_ = [(n, C.c_int32) for n in ("B", "T", "F", "H", "K", "recurrent_activation", "operand_f16")]
 
 
 _LDP = C.POINTER(LstmDesc)

@@ -9,6 +9,7 @@ import fcntl
 import glob
 import hashlib
 import os
+import re
 import subprocess
 import sys
 
@@ -31,6 +32,29 @@ FLAGS = ARCH + (["-DDRNMF_TIMELINE"] if os.environ.get("DRNMF_TIMELINE") else []
          # loops of gemm_nt_kernel under the powf epilogues of the general beta-divergence (24 "loop not
          # unrolled" warnings); acc[a][b] was then indexed dynamically = 832 bytes of scratch per lane
          "-mllvm", "-pragma-unroll-threshold=262144"]
+
+
+# Kernels that must not spill: source -> kernel name.  These sources are compiled with
+# -Rpass-analysis=kernel-resource-usage and the build fails if a matching kernel reports scratch.
+NO_SCRATCH = {"lstm.hip": "lstm_step_kernel"}
+
+
+def _check_no_scratch(src, remarks):
+    """remarks: the compiler's stderr of `src`.  Raises if a NO_SCRATCH kernel uses scratch (or none was seen)."""
+    want = NO_SCRATCH[os.path.basename(src)]
+    seen, name = 0, None
+    for line in remarks.splitlines():
+        m = re.search(r"remark: Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            continue
+        m = re.search(r"remark:\s+ScratchSize \[bytes/lane\]: (\d+)", line)
+        if m and name and want in name:
+            seen += 1
+            if int(m.group(1)) != 0:
+                raise RuntimeError("%s: kernel %s uses %s bytes of scratch per lane" % (src, name, m.group(1)))
+    if not seen:
+        raise RuntimeError("%s: no resource-usage remark for %s" % (src, want))
 
 
 def _sources():
@@ -98,12 +122,25 @@ def _build_locked(force, verbose):
                 if f.read().strip() == want:
                     continue
         cmd = [HIPCC] + FLAGS + ["-c", src, "-o", obj]
+        log = None
+        if os.path.basename(src) in NO_SCRATCH:
+            cmd.insert(-4, "-Rpass-analysis=kernel-resource-usage")
+            log = open(obj + ".remarks", "w+")
         if verbose:
             print(" ".join(cmd), flush=True)
-        procs.append((src, stamp, want, subprocess.Popen(cmd)))
-    for src, stamp, want, p in procs:
-        if p.wait() != 0:
+        procs.append((src, stamp, want, subprocess.Popen(cmd, stderr=log), log))
+    for src, stamp, want, p, log in procs:
+        rc = p.wait()
+        if log is not None:
+            log.seek(0)
+            remarks = log.read()
+            log.close()
+            if rc != 0 or re.search(r"(warning|error):", remarks):       # as without the flag: show them
+                print(remarks, file=sys.stderr, flush=True)
+        if rc != 0:
             raise RuntimeError("hipcc failed on %s" % src)
+        if log is not None:
+            _check_no_scratch(src, remarks)
         with open(stamp, "w") as f:
             f.write(want + "\n")
     tmp = LIB + ".tmp.%d" % os.getpid()

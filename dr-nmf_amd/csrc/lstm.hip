@@ -18,6 +18,13 @@
 //      (the stacked-matrix idea of dense_step_kernel); layer 0 contracts h_{0,t-1} with recurrent_0 and adds
 //      xproj[t].  Ordering comes from launch boundaries only: no workgroup waits on another.
 // The head (sigmoid(h . W_out + b_out)) is one more gemm::launch with the sigmoid in its epilogue.
+//
+// operand_f16 (drnmf_lstm_desc_t, inference only): step 3 contracts fp16 operands on v_mfma_f32_16x16x32_f16 with
+// fp32 accumulation.  The stacked matrices are STORED as _Float16 (lstm_pack_step_f16_kernel: the plain
+// round-to-nearest cast params.hip uses for the cell's fp16 dictionary -- a weight beyond the fp16 range, |w| >
+// 65504, becomes +-inf and poisons its gate column; nothing saturates or checks), and the h vectors entering the
+// products come from an fp16 shadow of the h ring.  Everything else is as above in fp32: bias, xproj, the gates,
+// c, the carried h, the final state, h_out, and steps 1, 2 and the head (which follow the matrix mode).
 #include "common.h"
 #include "gemm_nt.h"
 #include "gemm_tn.h"
@@ -32,26 +39,36 @@ namespace {
 constexpr int LSTM_UNITS = 8;
 constexpr int LSTM_NW = 4;     // waves per workgroup (the contraction split over them, reduced through LDS)
 constexpr int LSTM_G = 4;      // 16-row chunks in flight per wave
+// 32-row fp16 chunks in flight per wave: 4 waves x 4 = 16 chunks = the whole contraction of H = 244 / 250
+// (Hc = 256, layers k >= 1) in ONE round trip of 12 16-byte loads per lane, the same number the fp32 path keeps in
+// flight.  Smaller H leaves slots over (H = 54: 2 or 4 chunks, H = 70: 3 or 6): they re-read the last valid chunk
+// (the same cache lines) with a zeroed A term.
+constexpr int LSTM_GH = 4;
 
 struct LstmLayout {
     int Bp, Hc, Hq, Fq, numU, NC;
+    bool half;                 // operand_f16: stacked matrices stored as _Float16, Hc a multiple of 32, h16 ring
     size_t off_bias, off_k0t, off_wo, off_bo, params_total;
-    size_t off_xz, off_valid, off_xproj, off_h, off_c, off_ctr, ws_total;
-    // floats before layer k's stacked matrix: layer 0 has Hc rows (recurrent_0), layers k >= 1 have 2 Hc
-    size_t m_floats(int k) const { return k == 0 ? 0 : (size_t)Hc * NC * (2 * k - 1); }
+    size_t off_xz, off_valid, off_xproj, off_h, off_c, off_h16, off_ctr, ws_total;
+    // elements (floats, or halves with operand_f16) before layer k's stacked matrix: layer 0 has Hc rows
+    // (recurrent_0), layers k >= 1 have 2 Hc
+    size_t m_elems(int k) const { return k == 0 ? 0 : (size_t)Hc * NC * (2 * k - 1); }
 };
 
 LstmLayout lstm_layout(const drnmf_lstm_desc_t* d) {
     LstmLayout L;
     L.Bp = pad_b(d->B > 0 ? d->B : 1);
-    L.Hc = round_up(d->H, 16);             // activation width: whole 16-row chunks of the contraction
+    L.half = d->operand_f16 == 1;
+    // activation width: whole chunks of the contraction (16 rows per v_mfma_f32_16x16x4_f32 group, 32 per
+    // v_mfma_f32_16x16x32_f16), so that each half of [h_{k-1,t} | h_{k,t-1}] is whole chunks
+    L.Hc = round_up(d->H, L.half ? 32 : 16);
     L.Hq = round_up(d->H, 4);
     L.Fq = round_up(d->F, 4);              // xz / kernel_0^T rows: 16-byte loads in the gemm
     L.numU = (d->H + LSTM_UNITS - 1) / LSTM_UNITS;
     L.NC = L.numU * 32;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t at = o; o += round_up_sz(bytes, 256); return at; };
-    take(L.m_floats(d->K) * 4);
+    take(L.m_elems(d->K) * (L.half ? 2 : 4));
     L.off_bias = take((size_t)d->K * L.NC * 4);
     L.off_k0t = take((size_t)L.NC * L.Fq * 4);
     L.off_wo = take((size_t)d->F * L.Hq * 4);
@@ -64,6 +81,7 @@ LstmLayout lstm_layout(const drnmf_lstm_desc_t* d) {
     L.off_xproj = take(rows * L.NC * 4);
     L.off_h = take((size_t)d->K * 2 * L.Bp * L.Hc * 4);
     L.off_c = take((size_t)d->K * 2 * L.Bp * L.Hc * 4);
+    L.off_h16 = L.half ? take((size_t)d->K * 2 * L.Bp * L.Hc * 2) : 0;     // fp16 shadow of the h ring
     L.off_ctr = take(256);
     L.ws_total = o;
     return L;
@@ -78,6 +96,8 @@ int validate_lstm_desc(drnmf_handle_t h, const drnmf_lstm_desc_t* d, bool need_b
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG,
                    "recurrent_activation must be DRNMF_ACT_HARD_SIGMOID or DRNMF_ACT_SIGMOID (got %d)",
                    d->recurrent_activation);
+    if (d->operand_f16 != 0 && d->operand_f16 != 1)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "operand_f16 must be 0 or 1 (got %d)", d->operand_f16);
     if (d->H > 8192 || d->F > 65536 || d->K > 1024)
         DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED, "lstm: H <= 8192, F <= 65536, K <= 1024 (got %d, %d, %d)",
                    d->H, d->F, d->K);
@@ -117,6 +137,29 @@ lstm_pack_step_kernel(const float* __restrict__ kern, const float* __restrict__ 
     const int c = i >> 4, kk = i & 15, q = kk >> 2, s = kk & 3;
     const int ab = p >> 5, pc = p & 31;
     M[((size_t)c * numU + ab) * 512 + (pc >> 4) * 256 + (q * 16 + (pc & 15)) * 4 + s] = v;
+}
+
+// The same matrix for the fp16 step kernel (operand_f16), in the operand order of mfma32h: 32-row chunk c, output
+// tile ab -> one block of 1024 halves, two halves of 512 (packed columns 0..15 / 16..31 of the tile); lane (q, j) of
+// a half holds rows 32 c + 8 q + e, e = 0..7, of column j as one 16-byte piece.  Hc is a multiple of 32 here.
+// Plain round-to-nearest cast (as params.hip's fp16 dictionary): |w| > 65504 becomes +-inf.
+__global__ void __launch_bounds__(256)
+lstm_pack_step_f16_kernel(const float* __restrict__ kern, const float* __restrict__ rec, f16* __restrict__ M,
+                          int H, int Hc, int numU, int L) {
+    const int NC = numU * 32;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)L * NC) return;
+    const int i = (int)(idx / NC), p = (int)(idx % NC);
+    const int g = (p & 31) >> 3, unit = (p >> 5) * LSTM_UNITS + (p & 7);
+    float v = 0.f;
+    if (unit < H) {
+        const float* src = kern ? (i < Hc ? kern : rec) : rec;
+        const int r = kern && i >= Hc ? i - Hc : i;
+        if (r < H) v = src[(size_t)r * 4 * H + (size_t)g * H + unit];
+    }
+    const int c = i >> 5, kk = i & 31, q = kk >> 3, e = kk & 7;
+    const int ab = p >> 5, pc = p & 31;
+    M[((size_t)c * numU + ab) * 1024 + (pc >> 4) * 512 + (q * 16 + (pc & 15)) * 8 + e] = (f16)v;
 }
 
 // bias [K][4H] -> [K][NC] in the packed column order
@@ -167,12 +210,17 @@ lstm_pack_x_kernel(const float* __restrict__ x, float* __restrict__ xz, unsigned
     if (l == 0) valid[row] = any ? 1 : 0;
 }
 
-// zero initial h and c of every layer (both ring slots, padding included), diagonal counters = 0
+// zero initial h and c of every layer (both ring slots, padding included; h16: the fp16 shadow of the h ring,
+// NULL without operand_f16), diagonal counters = 0
 __global__ void __launch_bounds__(256)
-lstm_init_kernel(float* __restrict__ hring, float* __restrict__ cring, int* ctr, size_t n) {
+lstm_init_kernel(float* __restrict__ hring, float* __restrict__ cring, f16* __restrict__ h16, int* ctr, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i == 0) { ctr[0] = 0; ctr[16] = 0; }
-    if (i < n) { hring[i] = 0.f; cring[i] = 0.f; }
+    if (i < n) {
+        hring[i] = 0.f;
+        cring[i] = 0.f;
+        if (h16) h16[i] = (f16)0.f;
+    }
 }
 
 // The *_stateful entry points: caller-owned state arrays [K][B][H]; NULL initial = zeros, NULL final = not wanted
@@ -185,9 +233,10 @@ struct LstmState {
 
 // lstm_init_kernel with an entering state: frame 0 of layer k reads ring slot (-1) & 1 = 1, so the state
 // [K][B][H] goes there (rows b < B, units n < H); the padded rows B .. Bp-1, the padded units H .. Hc-1 and all of
-// slot 0 are zeros, diagonal counters = 0.  Runs before the replayed frames, outside them.
+// slot 0 are zeros, diagonal counters = 0.  h16 (NULL without operand_f16): the fp16 shadow of the h ring, the same
+// elements rounded.  Runs before the replayed frames, outside them.
 __global__ void __launch_bounds__(256)
-lstm_state_scatter_kernel(float* __restrict__ hring, float* __restrict__ cring, int* ctr,
+lstm_state_scatter_kernel(float* __restrict__ hring, float* __restrict__ cring, f16* __restrict__ h16, int* ctr,
                           const float* __restrict__ init_h, const float* __restrict__ init_c, size_t n, int B,
                           int H, int Bp, int Hc) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -204,6 +253,7 @@ lstm_state_scatter_kernel(float* __restrict__ hring, float* __restrict__ cring, 
     }
     hring[i] = hv;
     cring[i] = cv;
+    if (h16) h16[i] = (f16)hv;
 }
 
 // the state leaving the call: ring slot (T - 1) & 1 of every layer -> final_h / final_c [K][B][H] (either may be
@@ -275,6 +325,8 @@ struct LstmStepArgs {
     float* hst;                // [K][Bp (T+1)][Hq]
     size_t zk;                 // rows of one layer's block of zst (Bp (T+1) + 1: a zero row behind the last)
     int Hq;
+    // operand_f16 only (lstm_step_kernel<false, true>): M then holds _Float16 (lstm_pack_step_f16_kernel)
+    f16* h16;                  // [K][2][Bp][Hc]: (_Float16)h_{k,t} in slot t & 1, the A operand of the products
 };
 
 // One launch = one diagonal d: workgroup (ab, mb, k) computes frame t = d - k of layer k for rows
@@ -284,10 +336,19 @@ struct LstmStepArgs {
 // 16-byte piece, which is the order the matrix packing puts the rows in.  Ring slots: (k, t) writes slot
 // t & 1 of layer k; in the same launch (k + 1, t - 1) and (k, t) read slot (t - 1) & 1 of layer k, and (k, t)
 // reads slot t & 1 of layer k - 1, which (k - 1, t + 1) does not write (it writes slot (t + 1) & 1).
-// STASH (the training forward): the same arithmetic, plus the stash writes; lstm_step_kernel<false> is the
+// STASH (the training forward): the same arithmetic, plus the stash writes; lstm_step_kernel<false, false> is the
 // inference kernel.
-template <bool STASH>
+// HALF (operand_f16, inference only): the contraction runs on v_mfma_f32_16x16x32_f16, two per 32-row chunk, fp32
+// accumulation; lane (q, row j) takes h16[j][32 c + 8 q .. + 7] from the fp16 shadow ring as one 16-byte piece and
+// two 16-byte pieces of the fp16 packed block.  The cell update is the fp32 one on the fp32 rings (a masked step
+// carries the fp32 h, the final state and h_out are fp32) and ALSO writes (_Float16)h_t into the shadow: the
+// copy at a masked step, zero for a padded unit.  The shadow's slots are the fp32 ring's, written by the same
+// thread in the same launch, so the reasoning above holds for it word for word: (k, t) writes shadow slot t & 1
+// of layer k; in the same launch (k + 1, t - 1) and (k, t) read shadow slot (t - 1) & 1 of layer k, and (k, t)
+// reads shadow slot t & 1 of layer k - 1, which (k - 1, t + 1) does not write.
+template <bool STASH, bool HALF>
 __global__ void __launch_bounds__(64 * LSTM_NW) lstm_step_kernel(const LstmStepArgs a) {
+    static_assert(!(STASH && HALF), "operand_f16 is inference only");
     __shared__ __attribute__((aligned(16))) float red[LSTM_NW * 16 * 32];
     const int ab = blockIdx.x, mb = blockIdx.y, k = blockIdx.z;
     const int d = *a.d_rd;
@@ -297,35 +358,64 @@ __global__ void __launch_bounds__(64 * LSTM_NW) lstm_step_kernel(const LstmStepA
     const int tid = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l = tid & 63, j = l & 15, q = l >> 4;
-    const int Hc = a.Hc, nh = Hc / 16, nch = k == 0 ? nh : 2 * nh;
+    const int Hc = a.Hc;
     const size_t slab = (size_t)a.Bp * Hc;
-    const size_t arow = (size_t)(mb * 16 + j) * Hc + 4 * q;
-    const float* prev = a.hring + ((size_t)k * 2 + ((t + 1) & 1)) * slab + arow;                 // h_{k,t-1}
-    const float* below = k > 0 ? a.hring + ((size_t)(k - 1) * 2 + (t & 1)) * slab + arow : prev;  // h_{k-1,t}
-    const size_t m_off = k == 0 ? 0 : (size_t)Hc * a.NC * (2 * k - 1);
-    const float* brow = a.M + m_off + (size_t)ab * 512 + l * 4;
-    const size_t bstep = (size_t)a.numU * 512;
-
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    for (int c0 = w; c0 < nch; c0 += LSTM_NW * LSTM_G) {
-        f32x4 av[LSTM_G], b0[LSTM_G], b1[LSTM_G];
+    if constexpr (HALF) {
+        const int nh = Hc / 32, nch = k == 0 ? nh : 2 * nh;
+        const size_t arow = (size_t)(mb * 16 + j) * Hc + 8 * q;
+        const f16* prev = a.h16 + ((size_t)k * 2 + ((t + 1) & 1)) * slab + arow;                    // h_{k,t-1}
+        const f16* below = k > 0 ? a.h16 + ((size_t)(k - 1) * 2 + (t & 1)) * slab + arow : prev;     // h_{k-1,t}
+        const size_t m_off = k == 0 ? 0 : (size_t)Hc * a.NC * (2 * k - 1);
+        const f16* brow = (const f16*)a.M + m_off + (size_t)ab * 1024 + l * 8;
+        const size_t bstep = (size_t)a.numU * 1024;
+        const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int c0 = w; c0 < nch; c0 += LSTM_NW * LSTM_GH) {
+            f16x8 av[LSTM_GH], b0[LSTM_GH], b1[LSTM_GH];
 #pragma unroll
-        for (int g = 0; g < LSTM_G; ++g) {
-            const int c = c0 + LSTM_NW * g;
-            const int cc = c < nch ? c : nch - 1;       // (clamped: a valid address, the term zeroed below)
-            const float* ap = k == 0 ? prev + 16 * cc : (cc < nh ? below + 16 * cc : prev + 16 * (cc - nh));
-            av[g] = *(const f32x4*)ap;
-            b0[g] = *(const f32x4*)(brow + (size_t)cc * bstep);
-            b1[g] = *(const f32x4*)(brow + (size_t)cc * bstep + 256);
-            if (c >= nch) av[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int g = 0; g < LSTM_G; ++g)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                acc0 = mfma16(av[g][s], b0[g][s], acc0);
-                acc1 = mfma16(av[g][s], b1[g][s], acc1);
+            for (int g = 0; g < LSTM_GH; ++g) {
+                const int c = c0 + LSTM_NW * g;
+                const int cc = c < nch ? c : nch - 1;       // (clamped: a valid address, the term zeroed below)
+                const f16* ap = k == 0 ? prev + 32 * cc : (cc < nh ? below + 32 * cc : prev + 32 * (cc - nh));
+                av[g] = *(const f16x8*)ap;
+                b0[g] = *(const f16x8*)(brow + (size_t)cc * bstep);
+                b1[g] = *(const f16x8*)(brow + (size_t)cc * bstep + 512);
+                if (c >= nch) av[g] = zero8;
             }
+#pragma unroll
+            for (int g = 0; g < LSTM_GH; ++g) {
+                acc0 = mfma32h(av[g], b0[g], acc0);
+                acc1 = mfma32h(av[g], b1[g], acc1);
+            }
+        }
+    } else {
+        const int nh = Hc / 16, nch = k == 0 ? nh : 2 * nh;
+        const size_t arow = (size_t)(mb * 16 + j) * Hc + 4 * q;
+        const float* prev = a.hring + ((size_t)k * 2 + ((t + 1) & 1)) * slab + arow;                 // h_{k,t-1}
+        const float* below = k > 0 ? a.hring + ((size_t)(k - 1) * 2 + (t & 1)) * slab + arow : prev;  // h_{k-1,t}
+        const size_t m_off = k == 0 ? 0 : (size_t)Hc * a.NC * (2 * k - 1);
+        const float* brow = a.M + m_off + (size_t)ab * 512 + l * 4;
+        const size_t bstep = (size_t)a.numU * 512;
+        for (int c0 = w; c0 < nch; c0 += LSTM_NW * LSTM_G) {
+            f32x4 av[LSTM_G], b0[LSTM_G], b1[LSTM_G];
+#pragma unroll
+            for (int g = 0; g < LSTM_G; ++g) {
+                const int c = c0 + LSTM_NW * g;
+                const int cc = c < nch ? c : nch - 1;       // (clamped: a valid address, the term zeroed below)
+                const float* ap = k == 0 ? prev + 16 * cc : (cc < nh ? below + 16 * cc : prev + 16 * (cc - nh));
+                av[g] = *(const f32x4*)ap;
+                b0[g] = *(const f32x4*)(brow + (size_t)cc * bstep);
+                b1[g] = *(const f32x4*)(brow + (size_t)cc * bstep + 256);
+                if (c >= nch) av[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int g = 0; g < LSTM_G; ++g)
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    acc0 = mfma16(av[g][s], b0[g][s], acc0);
+                    acc1 = mfma16(av[g][s], b1[g][s], acc1);
+                }
+        }
     }
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
@@ -343,6 +433,7 @@ __global__ void __launch_bounds__(64 * LSTM_NW) lstm_step_kernel(const LstmStepA
     const bool real = b < a.B;
     if (n >= a.H) {                                     // padded units stay zero (they meet zero matrix rows)
         if (k == a.K - 1 && real && n < a.ld_h) a.out[frame * a.ld_h + n] = 0.f;
+        if constexpr (HALF) a.h16[((size_t)k * 2 + (t & 1)) * slab + (size_t)b * Hc + n] = (f16)0.f;
         if constexpr (STASH) {
             const size_t srow = (size_t)k * a.Bp * (a.T + 1) + (size_t)b * (a.T + 1) + t + 1;
             float* zp = a.zst + ((size_t)k * a.zk + (size_t)b * (a.T + 1) + t + 1) * a.NC + ab * 32 + u;
@@ -372,6 +463,7 @@ __global__ void __launch_bounds__(64 * LSTM_NW) lstm_step_kernel(const LstmStepA
     }
     a.cring[e_cur] = cn;
     a.hring[e_cur] = hn;
+    if constexpr (HALF) a.h16[e_cur] = (f16)hn;
     if (k == a.K - 1 && real) a.out[frame * a.ld_h + n] = hn;
     if constexpr (STASH) {
         const size_t srow = (size_t)k * a.Bp * (a.T + 1) + (size_t)b * (a.T + 1) + t + 1;
@@ -416,9 +508,15 @@ extern "C" int32_t drnmf_lstm_prepare_params(drnmf_handle_t h, const drnmf_lstm_
     for (int k = 0; k < d->K; ++k) {
         const int rows = k == 0 ? L.Hc : 2 * L.Hc;
         const size_t tot = (size_t)rows * L.NC;
-        hipLaunchKernelGGL(lstm_pack_step_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream,
-                           k == 0 ? nullptr : kernel_rest + (size_t)(k - 1) * HH4, recurrent + (size_t)k * HH4,
-                           (float*)base + L.m_floats(k), d->H, L.Hc, L.numU, rows);
+        const float* kern = k == 0 ? nullptr : kernel_rest + (size_t)(k - 1) * HH4;
+        if (L.half)
+            hipLaunchKernelGGL(lstm_pack_step_f16_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream,
+                               kern, recurrent + (size_t)k * HH4, (f16*)base + L.m_elems(k), d->H, L.Hc, L.numU,
+                               rows);
+        else
+            hipLaunchKernelGGL(lstm_pack_step_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream,
+                               kern, recurrent + (size_t)k * HH4, (float*)base + L.m_elems(k), d->H, L.Hc, L.numU,
+                               rows);
     }
     hipLaunchKernelGGL(lstm_pack_bias_kernel, dim3((unsigned)((d->K * L.NC + 255) / 256)), dim3(256), 0, stream,
                        bias, (float*)(base + L.off_bias), d->H, L.NC, d->K);
@@ -470,6 +568,7 @@ static int32_t lstm_forward_impl(drnmf_handle_t h, const drnmf_lstm_desc_t* d, c
     float* xproj = (float*)(ws + L.off_xproj);
     float* hring = (float*)(ws + L.off_h);
     float* cring = (float*)(ws + L.off_c);
+    f16* h16 = L.half ? (f16*)(ws + L.off_h16) : nullptr;
     int* ctr = (int*)(ws + L.off_ctr);
     const size_t rows = (size_t)d->B * d->T;
 
@@ -478,10 +577,10 @@ static int32_t lstm_forward_impl(drnmf_handle_t h, const drnmf_lstm_desc_t* d, c
     const size_t nring = (size_t)d->K * 2 * L.Bp * L.Hc;
     if (st)
         hipLaunchKernelGGL(lstm_state_scatter_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream,
-                           hring, cring, ctr, st->initial_h, st->initial_c, nring, d->B, d->H, L.Bp, L.Hc);
+                           hring, cring, h16, ctr, st->initial_h, st->initial_c, nring, d->B, d->H, L.Bp, L.Hc);
     else
         hipLaunchKernelGGL(lstm_init_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream, hring,
-                           cring, ctr, nring);
+                           cring, h16, ctr, nring);
     DRNMF_HIP(h, hipGetLastError());
     {
         gemm::Operands g;
@@ -506,6 +605,9 @@ static int32_t lstm_forward_impl(drnmf_handle_t h, const drnmf_lstm_desc_t* d, c
     base.Bp = L.Bp; base.Hc = L.Hc; base.numU = L.numU; base.NC = L.NC;
     base.act = d->recurrent_activation;
     base.ld_h = ld_h;
+    base.h16 = h16;
+    const void* step = L.half ? (const void*)&lstm_step_kernel<false, true>
+                              : (const void*)&lstm_step_kernel<false, false>;
     const dim3 grid((unsigned)L.numU, (unsigned)(L.Bp / 16), (unsigned)d->K);
     // one graph frame = two diagonals: the first reads counter 0 and sets counter 1, the second the other way
     // round (nobody reads a counter in the launch that writes it).  An odd diagonal count ends on one launch
@@ -516,7 +618,7 @@ static int32_t lstm_forward_impl(drnmf_handle_t h, const drnmf_lstm_desc_t* d, c
             a.d_rd = ctr + 16 * p;
             a.d_wr = ctr + 16 * (1 - p);
             void* kp[1] = {&a};
-            DRNMF_HIP(h, chain.add((const void*)&lstm_step_kernel<false>, grid, dim3(64 * LSTM_NW), kp));
+            DRNMF_HIP(h, chain.add(step, grid, dim3(64 * LSTM_NW), kp));
         }
         return DRNMF_OK;
     };
@@ -525,7 +627,7 @@ static int32_t lstm_forward_impl(drnmf_handle_t h, const drnmf_lstm_desc_t* d, c
     const std::vector<uint64_t> key = {
         (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->H, (uint64_t)d->K,
         (uint64_t)d->recurrent_activation, (uint64_t)(uintptr_t)params, (uint64_t)(uintptr_t)h_out, (uint64_t)ld_h,
-        (uint64_t)(uintptr_t)workspace};
+        (uint64_t)(uintptr_t)workspace, (uint64_t)d->operand_f16};
     rc = replay_frames(h, stream, GraphKind::Lstm, key, {fpg, 1}, 0, frames, frame);
     if (rc) return rc;
     return lstm_store_state(h, d, L, hring, cring, st, stream);
@@ -952,6 +1054,9 @@ int validate_train_call(drnmf_handle_t h, const drnmf_lstm_desc_t* d, void* work
                         const char* what, LstmTrainLayout* W) {
     int rc = validate_lstm_desc(h, d, true);
     if (rc) return rc;
+    if (d->operand_f16)
+        DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED,
+                   "%s: operand_f16 = 1 is inference only (train with operand_f16 = 0)", what);
     *W = lstm_train_layout(d);
     if (!workspace) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: NULL workspace", what);
     if (workspace_bytes < W->total)
@@ -991,6 +1096,7 @@ hipError_t lstm_colsum(const LstmTrainLayout& W, char* ws, const float* A, int64
 
 extern "C" size_t drnmf_lstm_train_workspace_bytes(const drnmf_lstm_desc_t* d) {
     if (!d || d->B <= 0 || d->T <= 0 || d->F <= 0 || d->H <= 0 || d->K <= 0) return 0;
+    if (d->operand_f16) return 0;          // inference only: every training entry point refuses the descriptor
     return lstm_train_layout(d).total;
 }
 
@@ -1027,10 +1133,11 @@ static int32_t lstm_train_forward_impl(drnmf_handle_t h, const drnmf_lstm_desc_t
     const size_t nring = (size_t)d->K * 2 * L.Bp * L.Hc;
     if (st)
         hipLaunchKernelGGL(lstm_state_scatter_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream,
-                           hring, cring, ctr, st->initial_h, st->initial_c, nring, d->B, d->H, L.Bp, L.Hc);
+                           hring, cring, (f16*)nullptr, ctr, st->initial_h, st->initial_c, nring, d->B, d->H, L.Bp,
+                           L.Hc);
     else
         hipLaunchKernelGGL(lstm_init_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream, hring,
-                           cring, ctr, nring);
+                           cring, (f16*)nullptr, ctr, nring);
     hipLaunchKernelGGL(lstm_stash_init_kernel, dim3((unsigned)(L.Bp + 1), (unsigned)d->K), dim3(256), 0, stream,
                        zst, cst, hst, L.Bp, d->T, W.zk, W.RS, L.NC, L.Hc, L.Hq);
     if (st && (st->initial_h || st->initial_c)) {
@@ -1062,6 +1169,7 @@ static int32_t lstm_train_forward_impl(drnmf_handle_t h, const drnmf_lstm_desc_t
     base.act = d->recurrent_activation;
     base.ld_h = ld_h;
     base.zst = zst; base.cst = cst; base.hst = hst; base.zk = W.zk; base.Hq = L.Hq;
+    base.h16 = nullptr;
     const dim3 grid((unsigned)L.numU, (unsigned)(L.Bp / 16), (unsigned)d->K);
     auto frame = [&](Launcher& chain, int) -> int32_t {      // two diagonals, as drnmf_lstm_forward
         for (int p = 0; p < 2; ++p) {
@@ -1069,7 +1177,7 @@ static int32_t lstm_train_forward_impl(drnmf_handle_t h, const drnmf_lstm_desc_t
             a.d_rd = ctr + 16 * p;
             a.d_wr = ctr + 16 * (1 - p);
             void* kp[1] = {&a};
-            DRNMF_HIP(h, chain.add((const void*)&lstm_step_kernel<true>, grid, dim3(64 * LSTM_NW), kp));
+            DRNMF_HIP(h, chain.add((const void*)&lstm_step_kernel<true, false>, grid, dim3(64 * LSTM_NW), kp));
         }
         return DRNMF_OK;
     };

@@ -2321,14 +2321,19 @@ class LSTM(_Layer):
     block bias[H:2H] = 1); gate columns i, f, c, o; activation tanh, recurrent_activation hard_sigmoid by
     default (sigmoid selectable); zero initial states, or with stateful=True the states the previous batch
     left (they live in LSTMModel, [K,B,H] for the whole stack).  The forward runs as part of LSTMModel
-    (csrc/lstm.hip)."""
+    (csrc/lstm.hip).  operand_dtype (no Keras counterpart; as SimpleDeepRNN's): 'float16' rounds the operands of
+    the recurrent products to fp16 (fp32 accumulation, gates and states) -- inference only; the weights stay
+    float32 tensors either way."""
     ordered_weights = True
 
     def __init__(self, units, return_sequences=False, input_shape=None, activation='tanh',
                  recurrent_activation='hard_sigmoid', kernel_initializer='glorot_uniform',
                  recurrent_initializer='orthogonal', bias_initializer='zeros', unit_forget_bias=True,
-                 stateful=False, device=None, **kw):
+                 stateful=False, device=None, operand_dtype='float32', **kw):
         super(LSTM, self).__init__(**kw)
+        if operand_dtype not in ('float32', 'float16'):
+            raise ValueError("LSTM: operand_dtype must be 'float32' or 'float16'")
+        self.operand_dtype = operand_dtype
         if not return_sequences:
             raise NotImplementedError('LSTM: only return_sequences=True (build_lstm, enhance.py:334)')
         if activation != 'tanh':
@@ -2424,6 +2429,9 @@ class LSTMModel(_SequenceModel):
     def __init__(self, layers, lstms, dense, mask_value, device):
         if len(set(bool(getattr(l, 'stateful', False)) for l in lstms)) > 1:
             raise ValueError('LSTMModel: all LSTM layers must be stateful, or none (the stack shares one state)')
+        if len(set(getattr(l, 'operand_dtype', 'float32') for l in lstms)) > 1:
+            raise ValueError('LSTMModel: all LSTM layers must have the same operand_dtype (one kernel runs the '
+                             'whole stack)')
         self.layers = layers
         self.lstms, self.dense = lstms, dense
         self.mask_value = mask_value
@@ -2505,7 +2513,11 @@ class LSTMModel(_SequenceModel):
         """model.compile(loss='mse', optimizer=Adam(lr, clipnorm, decay), sample_weight_mode='temporal') on
         output_masked = Masking output * sigmoid output; same arguments and refusals as
         UnfoldedSNMFModel.compile.  The gradients come from csrc/lstm.hip (training forward, loss head, BPTT);
-        there is no host fallback, so a model whose device is not a GPU cannot be trained."""
+        there is no host fallback, so a model whose device is not a GPU cannot be trained.  The kernels train in
+        float32 only."""
+        if self._operand_f16():
+            raise NotImplementedError("LSTMModel: operand_dtype='float16' is inference only -- train a float32 "
+                                      "model, then set_weights / load_weights its weights into a float16 model")
         if self.device.type != 'cuda':
             raise NotImplementedError('LSTMModel: training runs on the GPU kernels only (device %s)' % self.device)
         if loss != 'mse' or optimizer != 'adam' or sample_weight_mode != 'temporal':
@@ -2608,12 +2620,16 @@ class LSTMModel(_SequenceModel):
 
     def _desc(self, B, T):
         l0 = self.lstms[0]
-        return ops.make_lstm_desc(B, T, self.dense.units, l0.units, len(self.lstms), l0.recurrent_activation)
+        return ops.make_lstm_desc(B, T, self.dense.units, l0.units, len(self.lstms), l0.recurrent_activation,
+                                  operand_f16=self._operand_f16())
+
+    def _operand_f16(self):
+        return self.lstms[0].operand_dtype == 'float16'
 
     def _params(self, desc):
         """The prepared block, rebuilt only when a weight tensor changed (torch's in-place version counter)."""
         vers = tuple((w.data_ptr(), w._version) for w in self.weights)
-        key = (desc.F, desc.H, desc.K, desc.recurrent_activation)
+        key = (desc.F, desc.H, desc.K, desc.recurrent_activation, desc.operand_f16)
         if self._prepared is None or self._prepared[0] != vers or self._prepared[1] != key:
             out = self._prepared[2] if self._prepared is not None and self._prepared[1] == key else None
             p = ops.lstm_prepare_params(desc, [l.kernel for l in self.lstms],
@@ -2649,7 +2665,8 @@ def build_lstm(params_lstm, device=None):
     """enhance.py:321-345 with the same parameter dictionary keys (mask_value, maxseq, input_dim, output_dim,
     K_layers, hidden_dim); 'recurrent_activation' (optional, a Keras LSTM argument) selects 'sigmoid' instead
     of the default 'hard_sigmoid'; 'stateful' (optional, a Keras LSTM argument, default False) builds every LSTM
-    layer stateful.  The reference's dictionaries have neither key."""
+    layer stateful; 'operand_dtype' (optional, 'float32' or 'float16', as build_unfolded_snmf's) selects fp16
+    operands for the recurrent products, inference only.  The reference's dictionaries have none of these keys."""
     p = params_lstm
     mask_value, maxseq = p['mask_value'], p['maxseq']
     input_dim, output_dim = int(p['input_dim']), int(p['output_dim'])
@@ -2665,7 +2682,8 @@ def build_lstm(params_lstm, device=None):
     for k in range(K):
         l = LSTM(H, return_sequences=True, input_shape=(maxseq, input_dim),
                  recurrent_activation=p.get('recurrent_activation', 'hard_sigmoid'),
-                 stateful=bool(p.get('stateful', False)), device=dev)
+                 stateful=bool(p.get('stateful', False)), device=dev,
+                 operand_dtype=p.get('operand_dtype', 'float32'))
         l.build((None, maxseq, input_dim if k == 0 else H))
         lstms.append(l)
     dense = Dense(output_dim, device=dev)

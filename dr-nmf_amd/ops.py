@@ -1658,10 +1658,13 @@ def compute_scores(est, ref, fs, lengths_est=None, lengths_ref=None, flen=512, s
 LSTM_ACTIVATIONS = {"hard_sigmoid": _capi.ACTIVATIONS["hard_sigmoid"], "sigmoid": _capi.ACTIVATIONS["sigmoid"]}
 
 
-def make_lstm_desc(B, T, F, H, K, recurrent_activation="hard_sigmoid"):
+def make_lstm_desc(B, T, F, H, K, recurrent_activation="hard_sigmoid", *, operand_f16=False):
+    """operand_f16: fp16 operands in the recurrent products (inference only; drnmf_lstm_desc_t.operand_f16).  The
+    prepared block and the workspace depend on it: prepare, forward and head take descriptors that agree."""
     if recurrent_activation not in LSTM_ACTIVATIONS:
         raise ValueError("recurrent_activation must be one of %s" % sorted(LSTM_ACTIVATIONS))
-    return _capi.LstmDesc(int(B), int(T), int(F), int(H), int(K), LSTM_ACTIVATIONS[recurrent_activation])
+    return _capi.LstmDesc(int(B), int(T), int(F), int(H), int(K), LSTM_ACTIVATIONS[recurrent_activation],
+                          1 if operand_f16 else 0)
 
 
 def lstm_prepare_params(desc, kernels, recurrents, biases, w_out, b_out, out=None):

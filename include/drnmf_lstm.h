@@ -30,6 +30,19 @@ typedef struct drnmf_lstm_desc {
     int32_t H;                     /* hidden_dim (units of every LSTM layer)                         */
     int32_t K;                     /* K_layers                                                       */
     int32_t recurrent_activation;  /* DRNMF_ACT_HARD_SIGMOID (Keras default) or DRNMF_ACT_SIGMOID    */
+    int32_t operand_f16;           /* 0: the recurrent products contract fp32 operands (v_mfma_f32_16x16x4_f32).
+                                    * 1 (extension, as drnmf_cell_desc_t.operand_f16; INFERENCE ONLY): the stacked
+                                    * matrices recurrent_0 and [kernel_k; recurrent_k], k >= 1, are STORED as fp16 and
+                                    * the h vectors are rounded to fp16 where they enter those products
+                                    * (v_mfma_f32_16x16x32_f16, fp32 accumulation).  Everything else stays fp32:
+                                    * x . kernel_0 + bias, the gates, c, the carried h, the states of the
+                                    * *_stateful entry points, h_out and the head.  Conversion is the plain
+                                    * round-to-nearest cast: a weight with |w| > 65504 becomes +-inf (nothing
+                                    * saturates, nothing is checked).  Any other value: DRNMF_ERR_INVALID_ARG.
+                                    * The training entry points return DRNMF_ERR_UNSUPPORTED for 1 (and
+                                    * drnmf_lstm_train_workspace_bytes 0): train with 0 and prepare the same
+                                    * weights with 1.  params and workspace sizes and layouts depend on the field:
+                                    * prepare, forward and head calls must agree on it.              */
 } drnmf_lstm_desc_t;
 
 /* Prepared parameter block (B, T ignored).  Inputs in Keras layouts, float32 row-major:
