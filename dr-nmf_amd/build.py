@@ -36,7 +36,9 @@ FLAGS = ARCH + (["-DDRNMF_TIMELINE"] if os.environ.get("DRNMF_TIMELINE") else []
 
 # Kernels that must not spill: source -> kernel name.  These sources are compiled with
 # -Rpass-analysis=kernel-resource-usage and the build fails if a matching kernel reports scratch.
-NO_SCRATCH = {"lstm.hip": "lstm_step_kernel"}
+NO_SCRATCH = {"lstm.hip": "lstm_step_kernel",
+              # the tile kernel keeps H, num and den of its tiles in registers; the pack / zero kernels ride along
+              "snmf_mask.hip": "snmf_mask_"}
 
 
 def _check_no_scratch(src, remarks):
@@ -64,7 +66,7 @@ def _sources():
 def _deps():
     return _sources() + glob.glob(os.path.join(CSRC, "*.h")) + \
         [os.path.join(os.path.dirname(HERE), "include", n) for n in ("drnmf.h", "drnmf_lstm.h", "drnmf_score.h", "drnmf_enhance.h", "drnmf_sdr.h",
-                                                                     "drnmf_dataset.h", "drnmf_stream.h")] + \
+                                                                     "drnmf_dataset.h", "drnmf_stream.h", "drnmf_snmf.h")] + \
         [os.path.abspath(__file__)]
 
 

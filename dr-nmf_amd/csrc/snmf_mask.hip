@@ -1,0 +1,454 @@
+// The sparse-NMF baseline's inference as one call (include/drnmf_snmf.h; enhance.py:838-852): padded sequences
+// x [B][T][F] in, the ratio mask out.  Two paths:
+//
+//  - the tile kernel (snmf_mask_tile_kernel, beta == 2, N <= 512).  MU inference has no recurrence and no
+//    coupling between frames, so one workgroup takes 16 consecutive frame rows through ALL n_iter iterations:
+//    the loop-invariant numerator V Wn and the denominator live in registers, H in LDS (the operand of the
+//    first product), the dictionary streams from L2 through LDS 32 bins at a time, and Lambda = max(H Wn^T, flr)
+//    exists only as that 16 x 32 chunk.  One launch instead of 3 n_iter, nothing but x and the mask in HBM.
+//  - the GEMM path: a pack kernel, drnmf_mu_forward's launches as they are (snmf.hip), a kernel that zeroes the
+//    masked rows.
+//
+// Tile kernel, per chunk c of FC = 32 bins (Wc = Wn[32 c .. 32 c + 31][:], staged once, serves both products):
+//     Lambda_c = max(H Wc^T, flr)     16 x 32, contraction over the atoms: split over the four waves by
+//                                     16-atom blocks, the four partials added in wave order
+//     den     += Lambda_c Wc          16 x N, contraction over the chunk's bins: every wave owns the 16-column
+//                                     tiles w, w + 4, ... of den, num and H
+// and after the last chunk H <- H * num / max(den + sparsity, flr).  Exact-fp32 MFMA (v_mfma_f32_16x16x4_f32: an
+// fmaf chain in k order), so a row's result depends on nothing but that row, Wn and h_init: bit for bit the same
+// wherever the row sits and whatever its neighbours hold.
+//
+// LDS: Hs [16][LD], Ws [32][LD], LD = Np + 8 (Np = N rounded up to 16).  LD % 16 == 8 makes both operand reads
+// conflict-free: the 16-byte reads of the first product (lane (r, q) reads row r, atoms 16 S + 4 q ..) spread
+// each 16-lane group of ds_read_b128 over all 64 banks, and the 4-byte reads of the second (lane (r, q) reads bin
+// rows two apart for q and q + 1, see bin_base) put the two rows of a 32-lane group 16 banks apart.
+#include "common.h"
+
+#include <atomic>
+#include <type_traits>
+
+#include "../../include/drnmf_snmf.h"
+
+namespace {
+
+constexpr int TR = 16;            // rows per workgroup (one MFMA M-tile)
+constexpr int FC = 32;            // bins per staged dictionary chunk
+constexpr int LLD = 36;           // row stride of the 16 x 32 partial / V chunk buffers
+constexpr int TILE_MAX_N = 512;
+// path = 0 takes the tile kernel up to this many rows: the largest measured row count at which it was the faster
+// path.  Measured (tools/snmf_bench.py, MI355X, F = 257, N = 200, 200 iterations, tile against GEMM path): 3.9 / 8.8
+// ms at 32 rows, 3.9 / 9.4 at 4096, 5.3 / 9.6 at 8192, 10.35 / 10.18 at 16384, 141.4 / 132.9 at 262144 (DESIGN.md
+// section 6h has the table).  Mirrored by _capi.SNMF_TILE_AUTO_MAX_ROWS.
+constexpr int64_t TILE_AUTO_MAX_ROWS = 8192;
+
+inline int tile_np(int N) { return (N + 15) & ~15; }
+inline size_t tile_lds_bytes(int N) {
+    const int LD = tile_np(N) + 8;
+    return ((size_t)(TR + FC) * LD + 4 * TR * LLD + TR) * sizeof(float);
+}
+
+// Contraction slot (q, e) of the second product's k-step S' is bin 16 S' + bin_base(q) + (e & 1) + 4 (e >> 1):
+// lanes q and q + 1 of one 32-lane group read dictionary rows two bins apart.
+__device__ __forceinline__ int bin_base(int q) { return 8 * (q >> 1) + 2 * (q & 1); }
+
+// NTW: 16-column tiles of H / num / den per wave (4: N <= 256, 8: N <= 512).  VEC: N % 4 == 0 and Wn 16-byte
+// aligned -- the dictionary is staged with 16-byte loads.  Waves per SIMD: three workgroups of the shipped N = 200
+// share a CU's LDS (51 KB each); the wide form (one workgroup's LDS at N = 512 is 109 KB) takes the registers it
+// needs.
+template <int NTW, bool VEC>
+__global__ void __launch_bounds__(256, NTW == 4 ? 3 : 1)
+snmf_mask_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn,
+                      const float* __restrict__ h_init, float* __restrict__ mask_out, int64_t rows, int F,
+                      int N, int n_iter, float sparsity, float power, float mask_value, int has_mask) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int Np = (N + 15) & ~15, NT = Np >> 4, LD = Np + 8, NC = (F + FC - 1) / FC;
+    float* Hs = smem;                         // [TR][LD]   current H (first product's A operand)
+    float* Ws = Hs + TR * LD;                 // [FC][LD]   dictionary chunk, zero behind F and N
+    float* Lp = Ws + FC * LD;                 // [4][TR][LLD] per-wave partials of Lambda_c; slot 0 also the V chunk
+    int* valid = (int*)(Lp + 4 * TR * LLD);   // [TR]
+    const int tid = threadIdx.x, l = tid & 63, r = l & 15, q = l >> 4;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t row0 = (int64_t)blockIdx.x * TR;
+    const float flr = 1e-9f;                  // sparse_nmf_gpu.m:172
+
+    // keras.layers.Masking: a frame is masked when every bin equals mask_value (lstm_pack_x_kernel's rule)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int rl = 4 * w + i;
+        const int64_t row = row0 + rl;
+        bool any = false;
+        if (row < rows) {
+            if (has_mask) {
+                for (int f = l; f < F; f += 64) any |= (x[row * F + f] != mask_value);
+            } else {
+                any = true;
+            }
+        }
+        any = __any(any);
+        if (l == 0) valid[rl] = any ? 1 : 0;
+    }
+    __syncthreads();
+    int nvalid = 0;
+#pragma unroll
+    for (int i = 0; i < TR; ++i) nvalid += valid[i];
+    if (nvalid == 0) {                        // nothing to compute: the rows' masks are 0
+        for (int rl = 0; rl < TR; ++rl) {
+            const int64_t row = row0 + rl;
+            if (row >= rows) break;
+            for (int f = tid; f < F; f += 256) mask_out[row * F + f] = 0.f;
+        }
+        return;
+    }
+
+    f32x4 num[NTW], den[NTW];
+#pragma unroll
+    for (int i = 0; i < NTW; ++i) {
+        const int t = w + 4 * i, col = 16 * t + r;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int rl = 4 * q + v;
+            float hv = 0.f;
+            if (t < NT && col < N && valid[rl]) hv = h_init[col];
+            num[i][v] = 0.f;
+            den[i][v] = 0.f;
+            if (t < NT) Hs[rl * LD + col] = hv;
+        }
+    }
+
+    // dictionary chunk: global -> registers (in flight under the previous chunk's products) -> LDS.  Wave w
+    // stages the chunk's rows w, w + 4, ..
+    constexpr int NVP = NTW / 4;
+    f32x4 pf4[FC / 4][NVP];
+    float pf1[FC / 4][NTW];
+    auto gload = [&](int c) {
+#pragma unroll
+        for (int i = 0; i < FC / 4; ++i) {
+            const int bin = c * FC + w + 4 * i;
+            if constexpr (VEC) {
+#pragma unroll
+                for (int p = 0; p < NVP; ++p) {
+                    const int col = 4 * (l + 64 * p);
+                    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                    if (bin < F && col < N) v = *(const f32x4*)(Wn + (size_t)bin * N + col);
+                    pf4[i][p] = v;
+                }
+            } else {
+#pragma unroll
+                for (int p = 0; p < NTW; ++p) {
+                    const int col = l + 64 * p;
+                    float v = 0.f;
+                    if (bin < F && col < N) v = Wn[(size_t)bin * N + col];
+                    pf1[i][p] = v;
+                }
+            }
+        }
+    };
+    auto swrite = [&]() {
+#pragma unroll
+        for (int i = 0; i < FC / 4; ++i) {
+            float* dst = Ws + (w + 4 * i) * LD;
+            if constexpr (VEC) {
+#pragma unroll
+                for (int p = 0; p < NVP; ++p) {
+                    const int col = 4 * (l + 64 * p);
+                    if (col < Np) *(f32x4*)(dst + col) = pf4[i][p];
+                }
+            } else {
+#pragma unroll
+                for (int p = 0; p < NTW; ++p) {
+                    const int col = l + 64 * p;
+                    if (col < Np) dst[col] = pf1[i][p];
+                }
+            }
+        }
+    };
+
+    // This wave's share of H Wc^T (its 16-atom blocks), 16 x 32, into its slot of Lp.  SEL 0: all atoms;
+    // 1: the atoms below rh only; 2: the atoms from rh on (the two halves of the mask).
+    auto lambda_partial = [&](auto sel_tag, int rh) {
+        constexpr int SEL = decltype(sel_tag)::value;
+        f32x4 P[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+        for (int i = 0; i < NTW; ++i) {
+            const int S = w + 4 * i;
+            if (S < NT) {
+                const int k0 = 16 * S + 4 * q;
+                f32x4 a = *(const f32x4*)(Hs + r * LD + k0);
+                if (SEL != 0) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) a[e] = ((k0 + e < rh) == (SEL == 1)) ? a[e] : 0.f;
+                }
+                const f32x4 b0 = *(const f32x4*)(Ws + r * LD + k0);
+                const f32x4 b1 = *(const f32x4*)(Ws + (16 + r) * LD + k0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    P[0] = mfma16(a[e], b0[e], P[0]);
+                    P[1] = mfma16(a[e], b1[e], P[1]);
+                }
+            }
+        }
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) Lp[(w * TR + 4 * q + v) * LLD + 16 * jt + r] = P[jt][v];
+    };
+    // acc [16 x N] += A [16 x 32] Wc, A given as this lane's operand values aF[S'][e] (row r, bin slot (q, e))
+    auto accumulate = [&](const float (&aF)[2][4], f32x4 (&acc)[NTW]) {
+        const float* bq = Ws + bin_base(q) * LD + r;
+#pragma unroll
+        for (int i = 0; i < NTW; ++i) {       // (one wave-uniform branch per tile; another wave's MFMAs fill the
+            const int t = w + 4 * i;          // dependent-accumulator latency of the chain of eight)
+            if (t < NT) {
+#pragma unroll
+                for (int s = 0; s < 2; ++s)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        acc[i] = mfma16(aF[s][e], bq[(16 * s + (e & 1) + 4 * (e >> 1)) * LD + 16 * t], acc[i]);
+            }
+        }
+    };
+
+    gload(0);
+    // num = V Wn, once: V = x^power on valid rows, 0 elsewhere
+    for (int c = 0; c < NC; ++c) {
+        swrite();
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int idx = tid + 256 * k, rl = idx >> 5, b = idx & 31, f = c * FC + b;
+            float v = 0.f;
+            if (valid[rl] && f < F) {
+                const float xv = x[(row0 + rl) * F + f];
+                v = power == 1.f ? xv : (power == 2.f ? xv * xv : powf(xv, power));
+            }
+            Lp[rl * LLD + b] = v;
+        }
+        __syncthreads();
+        gload(c + 1 < NC ? c + 1 : 0);
+        float aF[2][4];
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                aF[s][e] = Lp[r * LLD + 16 * s + bin_base(q) + (e & 1) + 4 * (e >> 1)];
+        accumulate(aF, num);
+        __syncthreads();
+    }
+
+    for (int it = 0; it < n_iter; ++it) {
+#pragma unroll
+        for (int i = 0; i < NTW; ++i) den[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < NC; ++c) {
+            swrite();
+            __syncthreads();                  // Ws (and, for c == 0, the new H) visible
+            gload(c + 1 < NC ? c + 1 : 0);
+            lambda_partial(std::integral_constant<int, 0>{}, 0);
+            __syncthreads();
+            float aF[2][4];
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh) {
+                    const float* p = Lp + r * LLD + 16 * s + bin_base(q) + 4 * hh;
+                    f32x2 sum = *(const f32x2*)p;                 // the four waves' partials, in wave order
+                    sum += *(const f32x2*)(p + TR * LLD);
+                    sum += *(const f32x2*)(p + 2 * TR * LLD);
+                    sum += *(const f32x2*)(p + 3 * TR * LLD);
+                    aF[s][2 * hh] = fmaxf(sum[0], flr);
+                    aF[s][2 * hh + 1] = fmaxf(sum[1], flr);
+                }
+            accumulate(aF, den);
+            __syncthreads();                  // every wave is done with Ws and Lp
+        }
+#pragma unroll
+        for (int i = 0; i < NTW; ++i) {       // sparse_nmf_gpu.m:217-227
+            const int t = w + 4 * i;
+            if (t < NT) {
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    float* hp = Hs + (4 * q + v) * LD + 16 * t + r;      // (this lane's own elements)
+                    *hp = *hp * num[i][v] / fmaxf(den[i][v] + sparsity, flr);
+                }
+            }
+        }
+    }
+
+    // mask = Wc Hc / (1e-9 + Wc Hc + Wn Hn), a chunk at a time (enhance.py:848-852)
+    const int rh = N / 2;
+    for (int c = 0; c < NC; ++c) {
+        swrite();
+        __syncthreads();
+        if (c + 1 < NC) gload(c + 1);
+        float cl[2], ns[2];
+        lambda_partial(std::integral_constant<int, 1>{}, rh);
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int idx = tid + 256 * k;
+            const float* p = Lp + (idx >> 5) * LLD + (idx & 31);
+            cl[k] = ((p[0] + p[TR * LLD]) + p[2 * TR * LLD]) + p[3 * TR * LLD];
+        }
+        __syncthreads();
+        lambda_partial(std::integral_constant<int, 2>{}, rh);
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int idx = tid + 256 * k, rl = idx >> 5, f = c * FC + (idx & 31);
+            const float* p = Lp + rl * LLD + (idx & 31);
+            ns[k] = ((p[0] + p[TR * LLD]) + p[2 * TR * LLD]) + p[3 * TR * LLD];
+            const int64_t row = row0 + rl;
+            if (row < rows && f < F)
+                mask_out[row * F + f] = valid[rl] ? cl[k] / (1e-9f + cl[k] + ns[k]) : 0.f;
+        }
+        __syncthreads();
+    }
+}
+
+// GEMM path, in front of drnmf_mu_forward: V = x^power (masked rows 0), H = h_init in every valid row, the
+// validity flags.  One wave per row.
+__global__ void __launch_bounds__(256)
+snmf_mask_pack_kernel(const float* __restrict__ x, const float* __restrict__ h_init, float* __restrict__ V,
+                      float* __restrict__ H, unsigned char* __restrict__ valid, int64_t rows, int F, int N,
+                      float power, float mask_value, int has_mask) {
+    const int l = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* src = x + row * F;
+    bool any = !has_mask;
+    if (has_mask) {
+        for (int f = l; f < F; f += 64) any |= (src[f] != mask_value);
+        any = __any(any);
+    }
+    for (int f = l; f < F; f += 64) {
+        const float xv = src[f];
+        V[row * F + f] = any ? (power == 1.f ? xv : (power == 2.f ? xv * xv : powf(xv, power))) : 0.f;
+    }
+    for (int c = l; c < N; c += 64) H[row * N + c] = any ? h_init[c] : 0.f;
+    if (l == 0) valid[row] = any ? 1 : 0;
+}
+
+// ... and behind it: the mask of a masked row is 0
+__global__ void __launch_bounds__(256)
+snmf_mask_zero_kernel(float* __restrict__ mask_out, const unsigned char* __restrict__ valid, int64_t rows,
+                      int F) {
+    const int l = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows || valid[row]) return;
+    for (int f = l; f < F; f += 64) mask_out[row * F + f] = 0.f;
+}
+
+struct MaskWs {
+    size_t off_V, off_H, off_W2, off_valid, off_mu, mu_bytes, total;
+};
+MaskWs mask_ws(int64_t rows, int F, int N) {
+    MaskWs w;
+    size_t o = 0;
+    auto take = [&](size_t b) { size_t at = o; o += round_up_sz(b, 256); return at; };
+    w.off_V = take((size_t)rows * F * 4);
+    w.off_H = take((size_t)rows * N * 4);
+    w.off_W2 = take((size_t)F * N * 4);       // drnmf_mu_forward's normalised copy (of the normalised Wn)
+    w.off_valid = take((size_t)rows);
+    w.mu_bytes = drnmf_mu_workspace_bytes(rows, F, N);
+    w.off_mu = take(w.mu_bytes);
+    w.total = o;
+    return w;
+}
+
+template <int NTW, bool VEC>
+hipError_t launch_tile(const float* x, const float* Wn, const float* h_init, float* mask_out, int64_t rows,
+                       int F, int N, int n_iter, float sparsity, float power, float mask_value, int has_mask,
+                       hipStream_t stream, int device) {
+    const size_t lds = tile_lds_bytes(N);
+    auto* kern = snmf_mask_tile_kernel<NTW, VEC>;
+    // once per kernel instance and device: the dynamic-LDS limit of the widest shape the instance takes (a property
+    // of the function, not of a launch; a second thread that gets here first sets the same value again)
+    static std::atomic<bool> raised[64];
+    if (device < 0 || device >= 64 || !raised[device].load(std::memory_order_acquire)) {
+        const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)tile_lds_bytes(NTW == 4 ? 256 : TILE_MAX_N));
+        if (e != hipSuccess) return e;
+        if (device >= 0 && device < 64) raised[device].store(true, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)((rows + TR - 1) / TR)), dim3(256), lds, stream, x, Wn, h_init,
+                       mask_out, rows, F, N, n_iter, sparsity, power, mask_value, has_mask);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int32_t drnmf_snmf_mask_admitted(int32_t F, int32_t N, float beta) {
+    return (F > 0 && N >= 2 && N <= TILE_MAX_N && beta == 2.f) ? 1 : 0;
+}
+
+extern "C" size_t drnmf_snmf_mask_workspace_bytes(int32_t B, int32_t T, int32_t F, int32_t N) {
+    if (B <= 0 || T <= 0 || F <= 0 || N <= 0 || N % 2) return 0;
+    return mask_ws((int64_t)B * T, F, N).total;
+}
+
+extern "C" int32_t drnmf_snmf_mask_forward(drnmf_handle_t h, int32_t B, int32_t T, int32_t F, int32_t N,
+                                           int32_t n_iter, float beta, float sparsity, float power,
+                                           float mask_value, int32_t has_mask, const float* x, const float* Wn,
+                                           const float* h_init, float* mask_out, int32_t path, void* workspace,
+                                           size_t workspace_bytes, void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    if (B <= 0 || T <= 0 || F <= 0 || N <= 0 || n_iter < 0)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_mask_forward: bad shape B=%d T=%d F=%d N=%d iters=%d", B, T, F,
+                   N, n_iter);
+    if (N % 2)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_mask_forward: N = %d must be even (speech and noise halves)", N);
+    if (path < DRNMF_SNMF_PATH_AUTO || path > DRNMF_SNMF_PATH_TILE)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_mask_forward: unknown path %d", path);
+    if (!(sparsity >= 0.f) || (has_mask != 0 && has_mask != 1))
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_mask_forward: sparsity must be >= 0, has_mask 0 or 1");
+    if (!x || !Wn || !h_init || !mask_out)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_mask_forward: NULL pointer argument");
+    const int64_t rows = (int64_t)B * T;
+    if (rows > 0x7fffff00)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_mask_forward: too many rows (%lld)", (long long)rows);
+    const bool admitted = drnmf_snmf_mask_admitted(F, N, beta) != 0;
+    if (path == DRNMF_SNMF_PATH_TILE && !admitted)
+        DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED, "snmf_mask_forward: the tile kernel takes beta == 2 and N <= %d "
+                   "(beta = %g, N = %d)", TILE_MAX_N, (double)beta, N);
+    hipStream_t stream = (hipStream_t)stream_;
+    const bool gemm = !(path == DRNMF_SNMF_PATH_TILE ||
+                        (path == DRNMF_SNMF_PATH_AUTO && admitted && rows <= TILE_AUTO_MAX_ROWS));
+    const MaskWs L = mask_ws(rows, F, N);
+    if (gemm && (!workspace || workspace_bytes < L.total))
+        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "snmf_mask_forward: workspace %zu < required %zu",
+                   workspace ? workspace_bytes : (size_t)0, L.total);
+    if (h->device < 0) DRNMF_FAIL(h, DRNMF_ERR_HIP, "snmf_mask_forward: the handle is bound to no device");
+    if (!gemm) {
+        const bool vec = N % 4 == 0 && ((uintptr_t)Wn & 15) == 0;
+        hipError_t e;
+        if (tile_np(N) <= 256)
+            e = vec ? launch_tile<4, true>(x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity, power, mask_value,
+                                           has_mask, stream, h->device)
+                    : launch_tile<4, false>(x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity, power, mask_value,
+                                            has_mask, stream, h->device);
+        else
+            e = vec ? launch_tile<8, true>(x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity, power, mask_value,
+                                           has_mask, stream, h->device)
+                    : launch_tile<8, false>(x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity, power, mask_value,
+                                            has_mask, stream, h->device);
+        DRNMF_HIP(h, e);
+        return DRNMF_OK;
+    }
+    char* ws = (char*)workspace;
+    float* V = (float*)(ws + L.off_V);
+    float* H = (float*)(ws + L.off_H);
+    float* W2 = (float*)(ws + L.off_W2);
+    unsigned char* valid = (unsigned char*)(ws + L.off_valid);
+    const dim3 rgrid((unsigned)((rows + 3) / 4));
+    hipLaunchKernelGGL(snmf_mask_pack_kernel, rgrid, dim3(256), 0, stream, x, h_init, V, H, valid, rows, F, N,
+                       power, mask_value, has_mask);
+    DRNMF_HIP(h, hipGetLastError());
+    // (Wn's columns have unit norm already: the normalisation in front of the loop rescales by 1 up to rounding)
+    const int32_t rc = drnmf_mu_forward(h, rows, F, N, n_iter, beta, sparsity, V, Wn, W2, H, mask_out,
+                                        ws + L.off_mu, L.mu_bytes, stream_);
+    if (rc != DRNMF_OK) return rc;
+    if (has_mask) {
+        hipLaunchKernelGGL(snmf_mask_zero_kernel, rgrid, dim3(256), 0, stream, mask_out, valid, rows, F);
+        DRNMF_HIP(h, hipGetLastError());
+    }
+    return DRNMF_OK;
+}

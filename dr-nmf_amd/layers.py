@@ -958,6 +958,11 @@ class _SequenceModel(object):
     def _stateful(self):
         return False
 
+    def _carries_state(self):
+        """True when a row's result depends on the calls before it (`enhance` regroups rows, so it refuses).  A
+        stateful model does, unless its frames are independent and there is no state to carry."""
+        return self._stateful()
+
     # -- weight files (enhance.py:1096, 1119-1129, 1135, 1160-1166: ModelCheckpoint(
     #    save_weights_only=True) / save_weights / load_weights on Keras HDF5 files) ------------
     def _weighted_layers(self):
@@ -1300,7 +1305,7 @@ class _SequenceModel(object):
         F = N // 2 + 1
         if F != self._input_width():
             raise ValueError('enhance: N = %d gives %d bins, the model takes %d' % (N, F, self._input_width()))
-        if self._stateful():
+        if self._carries_state():
             raise NotImplementedError('enhance: a stateful model needs its rows in order and at one length; '
                                       'use predict_on_batch')
         dev = torch.device(self._device())
@@ -2690,3 +2695,184 @@ def build_lstm(params_lstm, device=None):
     dense.build((None, maxseq, H))
     layers = [inp, masking] + lstms + [TimeDistributed(dense), TimeDistributed(Activation('sigmoid'))]
     return LSTMModel(layers, lstms, dense, mask_value, dev)
+
+
+# ------------------------------------------------------------------------------------------
+# the classical sparse-NMF baseline (enhance.py:750-928, model == 'snmf')
+# ------------------------------------------------------------------------------------------
+class NMFDictionary(_Layer):
+    """The one weight of the sparse-NMF baseline: W (F, 2r) = [W_clean, W_noise] as train_snmf returns it
+    (enhance.py:813-825), stored under the name 'W'."""
+    ordered_weights = True
+
+    def __init__(self, W, device=None, **kw):
+        super(NMFDictionary, self).__init__(**kw)
+        W = np.asarray(W, np.float32)
+        if W.ndim != 2:
+            raise ValueError('W must be (F, 2r), got shape %s' % (W.shape,))
+        self.device = torch.device(device if device is not None else 'cuda')
+        self.kernel = torch.from_numpy(np.array(W, copy=True, order='C')).to(self.device)    # (owns its memory)
+        self.built = True
+
+    @property
+    def weights(self):
+        return [self.kernel]
+
+    @property
+    def weight_names(self):
+        return ['W']
+
+
+class SparseNMFModel(_SequenceModel):
+    """The reference's sparse-NMF baseline as a model: per valid frame, V = x^spectrogram_power, n_iter
+    multiplicative updates of H with the dictionary W = [W_clean, W_noise] fixed (sparse_nmf_gpu.m:210-229 as
+    enhance.py:838-845 calls it: 200 iterations, conv_eps 0), then the ratio mask
+    Wc Hc / (1e-9 + Wc Hc + Wn Hn) (enhance.py:848-852).  A _SequenceModel like the other two: predict,
+    predict_on_batch, enhance (with ref= scoring), stream and the weight files are inherited; `forward` is one
+    ops.snmf_mask_forward.
+
+    Initial H.  ONE vector h_init (N,) is shared by every frame; by default
+    numpy.random.RandomState(random_seed).rand(N).  The reference draws a fresh n x N matrix inside Matlab
+    (rand('seed', 2016), sparse_nmf_gpu.m), which cannot be reproduced here, and
+    any per-frame draw would make a frame's result depend on where the frame sits in a batch.  With a shared
+    vector the mask of a frame is a function of that frame alone: predict does not depend on the slabs, and a
+    recording streamed in chunks gives the masks of the whole recording.  (For beta = 2, the reference's 'ed'.  For
+    other beta the update raises zeros of V to the smallest positive entry of the CALL's V, sparse_nmf_gpu.m:201-205:
+    a frame that holds a zero bin then depends on the frames it is run with.)  h_init is given for the dictionary as
+    stored; the kernels work in the column-normalised basis (sparse_nmf_gpu.m:163-166) and receive
+    h_init * column norms.
+
+    Streaming.  Frames are independent, so there is no state: _stateful() is True (the streaming contract holds
+    trivially, and predict keeps every row at its own frames: a masked frame's mask is 0, not a repeat of the
+    frame before it) and reset_states() does nothing.
+
+    path: 'auto' (the rule in ops.snmf_mask_forward / DESIGN.md), 'gemm' or 'tile'.  Nothing is compiled or
+    fitted: the dictionary comes from snmf.train_snmf (`from_wavs`)."""
+
+    def __init__(self, W, r, sparsity, n_iter=200, beta=2.0, spectrogram_power=1.0, mask_value=-1.0, h_init=None,
+                 random_seed=2016, path='auto', device=None):
+        W = np.asarray(W, np.float32)
+        r = int(r)
+        if W.ndim != 2 or W.shape[1] % 2 or W.shape[1] != 2 * r or r < 1:
+            raise ValueError('SparseNMFModel: W must be (F, 2r) with r = %d, got shape %s' % (r, W.shape))
+        if path not in _capi.SNMF_PATHS:
+            raise ValueError("SparseNMFModel: path must be 'auto', 'gemm' or 'tile' (got %r)" % (path,))
+        if int(n_iter) < 0 or not float(sparsity) >= 0:
+            raise ValueError('SparseNMFModel: n_iter and sparsity must not be negative')
+        N = 2 * r
+        if h_init is None:
+            h_init = np.random.RandomState(int(random_seed)).rand(N)
+        h_init = np.asarray(h_init, np.float32).reshape(-1)
+        if h_init.shape[0] != N:
+            raise ValueError('SparseNMFModel: h_init must have %d entries, got %d' % (N, h_init.shape[0]))
+        self.device = torch.device(device if device is not None else 'cuda')
+        self.dictionary = NMFDictionary(W, device=self.device, name='snmf_dictionary')
+        self.layers = [InputLayer((None, W.shape[0]), name='masking_1_input'),
+                       Masking(mask_value=mask_value, input_shape=(None, W.shape[0])), self.dictionary]
+        self.r, self.sparsity, self.n_iter, self.beta = r, float(sparsity), int(n_iter), float(beta)
+        self.spectrogram_power, self.mask_value, self.path = float(spectrogram_power), mask_value, path
+        self.h_init = torch.from_numpy(np.array(h_init, copy=True)).to(self.device)
+        self._normalised = None      # (W version, Wn, h_init * column norms)
+        self._ws = None
+
+    @property
+    def weights(self):
+        return self.dictionary.weights
+
+    def get_weights(self):
+        return self.dictionary.get_weights()
+
+    def set_weights(self, weights):
+        """[W]: same shape as the dictionary the model was built with (F rows, 2r atoms)."""
+        self.dictionary.set_weights(weights)
+
+    def _device(self):
+        return self.device
+
+    def _input_width(self):
+        return int(self.dictionary.kernel.shape[0])
+
+    _output_width = _input_width
+
+    def _stateful(self):
+        return True
+
+    def _carries_state(self):
+        return False
+
+    def reset_states(self, batch_size=None):
+        """Nothing to reset: no frame depends on another."""
+
+    def _operands(self):
+        """(Wn, h_init in Wn's basis), remade when W has changed (torch's in-place version counter)."""
+        W = self.dictionary.kernel
+        key = (W.data_ptr(), W._version)
+        if self._normalised is None or self._normalised[0] != key:
+            nrm = torch.sqrt((W * W).sum(dim=0))
+            self._normalised = (key, (W / nrm).contiguous(), (self.h_init * nrm).contiguous())
+        return self._normalised[1], self._normalised[2]
+
+    def forward(self, x):
+        """x [B,T,F] device float32 -> mask [B,T,F]; nothing is waited for."""
+        F = self._input_width()
+        if x.dim() != 3 or x.shape[-1] != F:
+            raise ValueError('forward: x must be (B, T, %d), got %s' % (F, tuple(x.shape)))
+        Wn, hn = self._operands()
+        B, T = int(x.shape[0]), int(x.shape[1])
+        # (kept between calls; ops decides whether the call takes one at all)
+        self._ws = ops.snmf_mask_workspace(self.path, B, T, F, 2 * self.r, self.beta, x.device, have=self._ws)
+        return ops.snmf_mask_forward(x, Wn, hn, self.sparsity, self.n_iter, beta=self.beta,
+                                     power=self.spectrogram_power, mask_value=self.mask_value, path=self.path,
+                                     workspace=self._ws)
+
+    __call__ = forward
+
+    def free_predict_buffers(self):
+        super(SparseNMFModel, self).free_predict_buffers()
+        self._ws = None
+
+    def compile(self, *args, **kwargs):
+        raise NotImplementedError('SparseNMFModel: nothing to compile -- the dictionary is trained by '
+                                  'SparseNMFModel.from_wavs (snmf.train_snmf)')
+
+    def fit(self, *args, **kwargs):
+        raise NotImplementedError('SparseNMFModel: nothing to fit -- the dictionary is trained by '
+                                  'SparseNMFModel.from_wavs (snmf.train_snmf)')
+
+    @classmethod
+    def from_wavs(cls, noisy, clean, params_snmf, N=512, hop=128, device=None):
+        """enhance.py:772-813 from waveform pairs: ops.wavs_to_frames, both sides raised to spectrogram_power,
+        snmf.train_snmf (r speech atoms on the clean frames, then 2r on the noisy ones with the speech half
+        frozen); returns build_snmf(params_snmf, W_noisy)."""
+        from . import snmf
+        dev = torch.device(device if device is not None else 'cuda')
+        dev = torch.device('cuda', ops._dev_of(dev))
+        p = float(params_snmf.get('spectrogram_power', 1.0))
+        with torch.cuda.device(dev):
+            xf, yf = ops.wavs_to_frames(noisy, clean, N, hop)
+            x_frames = (xf ** p).t().cpu().numpy()
+            y_frames = (yf ** p).t().cpu().numpy()
+        W, _, _ = snmf.train_snmf(y_frames, x_frames, params_snmf, save_H=False, device=dev)
+        return build_snmf(params_snmf, W, device=dev)
+
+    def val_loss(self, noisy, clean, N=512, hop=128):
+        """enhance.py:855 on waveform pairs: mean((irm * x - y)^2) over the packed frames of both sides raised
+        to spectrogram_power."""
+        with torch.cuda.device(self.device):
+            xf, yf = ops.wavs_to_frames(noisy, clean, N, hop)
+            irm = self.forward(xf[None])[0]
+            p = self.spectrogram_power
+            return float(((irm * xf ** p - yf ** p) ** 2).mean())
+
+
+def build_snmf(params_snmf, W, device=None):
+    """The sparse-NMF baseline from the reference's params_snmf (enhance.py:590-596, 754-757, 838-845) and a
+    trained dictionary W (F, 2r): keys r, sparsity, cf ('ed' / 'kl' / 'is', or 'beta'), random_seed,
+    spectrogram_power; max_iter / conv_eps are training settings -- inference runs the reference's 200
+    iterations.  Optional keys the reference's dictionaries do not have: 'n_iter', 'mask_value', 'path'."""
+    from . import snmf
+    p = params_snmf
+    return SparseNMFModel(W, int(p['r']), float(p.get('sparsity', 0.0)), n_iter=int(p.get('n_iter', 200)),
+                          beta=snmf._beta(p), spectrogram_power=float(p.get('spectrogram_power', 1.0)),
+                          mask_value=p.get('mask_value', -1.0), random_seed=int(p.get('random_seed', 2016)),
+                          path=p.get('path', 'auto'), device=device)

@@ -801,6 +801,69 @@ def mu_forward(V, W, H, sparsity, n_iter, beta=2.0, want_irm=False):
     return (H, Wn, irm) if want_irm else (H, Wn)
 
 
+def snmf_mask_admitted(F, N, beta=2.0):
+    """True when the tile kernel of `snmf_mask_forward` takes the shape (beta == 2, N <= 512)."""
+    return bool(_capi.lib().drnmf_snmf_mask_admitted(int(F), int(N), float(beta)))
+
+
+def snmf_mask_path(path, rows, F, N, beta=2.0):
+    """'gemm' or 'tile': what `path` means for `rows` frame rows.  'auto' is the tile kernel when the shape is
+    admitted and rows <= _capi.SNMF_TILE_AUTO_MAX_ROWS (the library's own rule for path = 0; measured: DESIGN.md
+    section 6h)."""
+    if path not in _capi.SNMF_PATHS:
+        raise ValueError("path must be 'auto', 'gemm' or 'tile' (got %r)" % (path,))
+    if path != "auto":
+        return path
+    return "tile" if snmf_mask_admitted(F, N, beta) and int(rows) <= _capi.SNMF_TILE_AUTO_MAX_ROWS else "gemm"
+
+
+def snmf_mask_workspace(path, B, T, F, N, beta, device, have=None):
+    """The workspace `snmf_mask_forward` needs for this call: None on the tile path, else a uint8 tensor of
+    drnmf_snmf_mask_workspace_bytes -- `have` itself when it is large enough and on `device`.  The one place the
+    path decision meets the sizing."""
+    if snmf_mask_path(path, int(B) * int(T), F, N, beta) == "tile":
+        return None
+    need = _capi.lib().drnmf_snmf_mask_workspace_bytes(int(B), int(T), int(F), int(N))
+    if have is not None and have.numel() >= need and have.device == torch.device(device):
+        return have
+    return torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+
+
+def snmf_mask_forward(x, Wn, h_init, sparsity, n_iter, beta=2.0, power=1.0, mask_value=None, path="auto",
+                      out=None, workspace=None):
+    """The sparse-NMF baseline's inference on padded sequences (drnmf_snmf_mask_forward, enhance.py:838-852):
+    x [B,T,F], Wn [F,N] with unit-norm columns, h_init [N] (the initial activation of every frame, in the
+    normalised basis) -> mask [B,T,F]; frames whose bins all equal mask_value get a zero mask (None: no frame is
+    masked).  path: 'auto', 'gemm' (drnmf_mu_forward's launches) or 'tile' (one launch, beta == 2 and N <= 512
+    only: ValueError otherwise).  workspace: a uint8 tensor to use on the GEMM path (`snmf_mask_workspace`; allocated
+    here when None or too small)."""
+    if path not in _capi.SNMF_PATHS:
+        raise ValueError("path must be 'auto', 'gemm' or 'tile' (got %r)" % (path,))
+    if x.dim() != 3 or Wn.dim() != 2 or Wn.shape[0] != x.shape[2] or tuple(h_init.shape) != (Wn.shape[1],):
+        raise ValueError("shape mismatch: x %s Wn %s h_init %s" % (tuple(x.shape), tuple(Wn.shape),
+                                                                    tuple(h_init.shape)))
+    if Wn.shape[1] % 2:
+        raise ValueError("Wn must have an even number of atoms (speech and noise halves), got %d" % Wn.shape[1])
+    L = _capi.lib()
+    dev = _dev_index(x)
+    h = _capi.handle(dev)
+    x, Wn, h_init = _f32c(x, "x"), _f32c(Wn, "Wn"), _f32c(h_init, "h_init")
+    B, T, F = x.shape
+    N = Wn.shape[1]
+    if out is None:
+        out = torch.empty((B, T, F), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, T, F) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of shape %s" % ((B, T, F),))
+    workspace = snmf_mask_workspace(path, B, T, F, N, beta, x.device, have=workspace)
+    rc = L.drnmf_snmf_mask_forward(h, B, T, F, N, int(n_iter), float(beta), float(sparsity), float(power),
+                                   0.0 if mask_value is None else float(mask_value), int(mask_value is not None),
+                                   _capi.ptr(x), _capi.ptr(Wn), _capi.ptr(h_init), _capi.ptr(out),
+                                   _capi.SNMF_PATHS[path], _capi.ptr(workspace),
+                                   0 if workspace is None else workspace.numel(), _stream())
+    _capi.check(rc, h, "drnmf_snmf_mask_forward")
+    return out
+
+
 def stft_frames(nsampl, N, hop):
     return int(_capi.lib().drnmf_stft_frames(int(nsampl), int(N), int(hop)))
 
