@@ -1,7 +1,8 @@
 """ctypes binding of libdrnmf.so (C ABI in include/drnmf.h; the LSTM baseline's in include/drnmf_lstm.h; the
 STOI score's in include/drnmf_score.h; the ragged STFT / iSTFT / int16 stages' in include/drnmf_enhance.h; the
 device-side SDR's in include/drnmf_sdr.h; the training-data front end's in include/drnmf_dataset.h; the streaming
-STFT / iSTFT's in include/drnmf_stream.h; the sparse-NMF baseline's inference in include/drnmf_snmf.h).
+STFT / iSTFT's in include/drnmf_stream.h; the sparse-NMF baseline's inference in include/drnmf_snmf.h, on fp16
+operands in include/drnmf_snmf_f16.h).
 
 The library is the product path: there is NO fallback.  If the shared object is missing or a
 call fails, an exception is raised.
@@ -219,6 +220,16 @@ SNMF_SIGNATURES = {
 SNMF_PATHS = {"auto": 0, "gemm": 1, "tile": 2}     # DRNMF_SNMF_PATH_*
 SNMF_TILE_AUTO_MAX_ROWS = 8192                     # csrc/snmf_mask.hip TILE_AUTO_MAX_ROWS: 'auto' takes the tile kernel up to here
 
+# name -> (restype, argtypes); mirrors include/drnmf_snmf_f16.h one to one (a table of its own, like the seven above)
+SNMF_F16_SIGNATURES = {
+    "drnmf_snmf_f16_admitted": (_i32, [_i32, _i32, _f32]),
+    "drnmf_snmf_f16_dict_bytes": (_sz, [_i32, _i32]),
+    "drnmf_snmf_f16_pack_dict": (_i32, [_vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "drnmf_snmf_f16_forward": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp,
+                                      _vp, _vp]),
+}
+SNMF_F16_MAX_N = 512                               # csrc/snmf_f16.hip MAX_N
+
 _lib = None
 _handles = {}
 
@@ -243,7 +254,8 @@ def lib():
         for name, (res, args) in (list(SIGNATURES.items()) + list(LSTM_SIGNATURES.items()) +
                                   list(SCORE_SIGNATURES.items()) + list(ENHANCE_SIGNATURES.items()) +
                                   list(SDR_SIGNATURES.items()) + list(DATASET_SIGNATURES.items()) +
-                                  list(STREAM_SIGNATURES.items()) + list(SNMF_SIGNATURES.items())):
+                                  list(STREAM_SIGNATURES.items()) + list(SNMF_SIGNATURES.items()) +
+                                  list(SNMF_F16_SIGNATURES.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

@@ -38,7 +38,9 @@ FLAGS = ARCH + (["-DDRNMF_TIMELINE"] if os.environ.get("DRNMF_TIMELINE") else []
 # -Rpass-analysis=kernel-resource-usage and the build fails if a matching kernel reports scratch.
 NO_SCRATCH = {"lstm.hip": "lstm_step_kernel",
               # the tile kernel keeps H, num and den of its tiles in registers; the pack / zero kernels ride along
-              "snmf_mask.hip": "snmf_mask_"}
+              "snmf_mask.hip": "snmf_mask_",
+              # its fp16-operand sibling: H (fp32 master), num and den of its tiles in registers as well
+              "snmf_f16.hip": "snmf_f16_"}
 
 
 def _check_no_scratch(src, remarks):
@@ -66,7 +68,7 @@ def _sources():
 def _deps():
     return _sources() + glob.glob(os.path.join(CSRC, "*.h")) + \
         [os.path.join(os.path.dirname(HERE), "include", n) for n in ("drnmf.h", "drnmf_lstm.h", "drnmf_score.h", "drnmf_enhance.h", "drnmf_sdr.h",
-                                                                     "drnmf_dataset.h", "drnmf_stream.h", "drnmf_snmf.h")] + \
+                                                                     "drnmf_dataset.h", "drnmf_stream.h", "drnmf_snmf.h", "drnmf_snmf_f16.h")] + \
         [os.path.abspath(__file__)]
 
 

@@ -2747,10 +2747,17 @@ class SparseNMFModel(_SequenceModel):
     frame before it) and reset_states() does nothing.
 
     path: 'auto' (the rule in ops.snmf_mask_forward / DESIGN.md), 'gemm' or 'tile'.  Nothing is compiled or
-    fitted: the dictionary comes from snmf.train_snmf (`from_wavs`)."""
+    fitted: the dictionary comes from snmf.train_snmf (`from_wavs`).
+
+    operand_dtype (no counterpart in the reference; as SimpleDeepRNN's and LSTM's): 'float16' rounds the operands of
+    the iteration's two products -- the dictionary, H and Lambda -- to fp16 and contracts them on the fp16 matrix
+    cores with fp32 accumulation (csrc/snmf_f16.hip, ops.snmf_f16_forward; every frame scaled by a power of two of
+    its own); the numerator, the update, the master copy of H and the final mask stay float32, and so do the
+    weights.  Such a model ALWAYS runs that kernel (the mode is about operand precision, not speed): beta == 2,
+    2r <= 512 and path 'auto' or 'tile' only."""
 
     def __init__(self, W, r, sparsity, n_iter=200, beta=2.0, spectrogram_power=1.0, mask_value=-1.0, h_init=None,
-                 random_seed=2016, path='auto', device=None):
+                 random_seed=2016, path='auto', device=None, operand_dtype='float32'):
         W = np.asarray(W, np.float32)
         r = int(r)
         if W.ndim != 2 or W.shape[1] % 2 or W.shape[1] != 2 * r or r < 1:
@@ -2759,7 +2766,14 @@ class SparseNMFModel(_SequenceModel):
             raise ValueError("SparseNMFModel: path must be 'auto', 'gemm' or 'tile' (got %r)" % (path,))
         if int(n_iter) < 0 or not float(sparsity) >= 0:
             raise ValueError('SparseNMFModel: n_iter and sparsity must not be negative')
+        if operand_dtype not in ('float32', 'float16'):
+            raise ValueError("SparseNMFModel: operand_dtype must be 'float32' or 'float16'")
         N = 2 * r
+        if operand_dtype == 'float16' and (float(beta) != 2.0 or N > _capi.SNMF_F16_MAX_N or path == 'gemm'):
+            raise ValueError("SparseNMFModel: operand_dtype='float16' runs one kernel, which takes beta == 2, "
+                             "2r <= %d and path 'auto' or 'tile' (beta = %g, 2r = %d, path = %r)" %
+                             (_capi.SNMF_F16_MAX_N, float(beta), N, path))
+        self.operand_dtype = operand_dtype
         if h_init is None:
             h_init = np.random.RandomState(int(random_seed)).rand(N)
         h_init = np.asarray(h_init, np.float32).reshape(-1)
@@ -2772,7 +2786,7 @@ class SparseNMFModel(_SequenceModel):
         self.r, self.sparsity, self.n_iter, self.beta = r, float(sparsity), int(n_iter), float(beta)
         self.spectrogram_power, self.mask_value, self.path = float(spectrogram_power), mask_value, path
         self.h_init = torch.from_numpy(np.array(h_init, copy=True)).to(self.device)
-        self._normalised = None      # (W version, Wn, h_init * column norms)
+        self._normalised = None      # (W version, Wn, h_init * column norms[, Wn packed as fp16])
         self._ws = None
 
     @property
@@ -2804,13 +2818,20 @@ class SparseNMFModel(_SequenceModel):
         """Nothing to reset: no frame depends on another."""
 
     def _operands(self):
-        """(Wn, h_init in Wn's basis), remade when W has changed (torch's in-place version counter)."""
+        """(Wn, h_init in Wn's basis), remade when W has changed (torch's in-place version counter); with
+        operand_dtype='float16' the fp16 packing of Wn is made with them (`_dict16`)."""
         W = self.dictionary.kernel
         key = (W.data_ptr(), W._version)
         if self._normalised is None or self._normalised[0] != key:
             nrm = torch.sqrt((W * W).sum(dim=0))
-            self._normalised = (key, (W / nrm).contiguous(), (self.h_init * nrm).contiguous())
+            Wn = (W / nrm).contiguous()
+            d16 = ops.snmf_f16_pack_dict(Wn) if self.operand_dtype == 'float16' else None
+            self._normalised = (key, Wn, (self.h_init * nrm).contiguous(), d16)
         return self._normalised[1], self._normalised[2]
+
+    def _dict16(self):
+        self._operands()
+        return self._normalised[3]
 
     def forward(self, x):
         """x [B,T,F] device float32 -> mask [B,T,F]; nothing is waited for."""
@@ -2818,6 +2839,9 @@ class SparseNMFModel(_SequenceModel):
         if x.dim() != 3 or x.shape[-1] != F:
             raise ValueError('forward: x must be (B, T, %d), got %s' % (F, tuple(x.shape)))
         Wn, hn = self._operands()
+        if self.operand_dtype == 'float16':
+            return ops.snmf_f16_forward(x, self._dict16(), Wn, hn, self.sparsity, self.n_iter,
+                                        power=self.spectrogram_power, mask_value=self.mask_value)
         B, T = int(x.shape[0]), int(x.shape[1])
         # (kept between calls; ops decides whether the call takes one at all)
         self._ws = ops.snmf_mask_workspace(self.path, B, T, F, 2 * self.r, self.beta, x.device, have=self._ws)
@@ -2869,10 +2893,12 @@ def build_snmf(params_snmf, W, device=None):
     """The sparse-NMF baseline from the reference's params_snmf (enhance.py:590-596, 754-757, 838-845) and a
     trained dictionary W (F, 2r): keys r, sparsity, cf ('ed' / 'kl' / 'is', or 'beta'), random_seed,
     spectrogram_power; max_iter / conv_eps are training settings -- inference runs the reference's 200
-    iterations.  Optional keys the reference's dictionaries do not have: 'n_iter', 'mask_value', 'path'."""
+    iterations.  Optional keys the reference's dictionaries do not have: 'n_iter', 'mask_value', 'path' and
+    'operand_dtype' ('float32' or 'float16', as build_unfolded_snmf's and build_lstm's)."""
     from . import snmf
     p = params_snmf
     return SparseNMFModel(W, int(p['r']), float(p.get('sparsity', 0.0)), n_iter=int(p.get('n_iter', 200)),
                           beta=snmf._beta(p), spectrogram_power=float(p.get('spectrogram_power', 1.0)),
                           mask_value=p.get('mask_value', -1.0), random_seed=int(p.get('random_seed', 2016)),
-                          path=p.get('path', 'auto'), device=device)
+                          path=p.get('path', 'auto'), device=device,
+                          operand_dtype=p.get('operand_dtype', 'float32'))

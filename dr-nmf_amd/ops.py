@@ -864,6 +864,62 @@ def snmf_mask_forward(x, Wn, h_init, sparsity, n_iter, beta=2.0, power=1.0, mask
     return out
 
 
+def snmf_f16_admitted(F, N, beta=2.0):
+    """True when the fp16-operand kernel of `snmf_f16_forward` takes the shape (beta == 2, N even, N <= 512)."""
+    return bool(_capi.lib().drnmf_snmf_f16_admitted(int(F), int(N), float(beta)))
+
+
+def snmf_f16_pack_dict(Wn, out=None):
+    """Wn [F,N] float32 -> the dictionary as `snmf_f16_forward` reads it: float16 [F, N rounded up to 32], zero
+    behind N (drnmf_snmf_f16_pack_dict)."""
+    L = _capi.lib()
+    dev = _dev_index(Wn)
+    h = _capi.handle(dev)
+    Wn = _f32c(Wn, "Wn")
+    if Wn.dim() != 2:
+        raise ValueError("Wn must be [F, N], got %s" % (tuple(Wn.shape),))
+    F, N = Wn.shape
+    shape = (F, (N + 31) // 32 * 32)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float16, device=Wn.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float16 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float16 tensor of shape %s" % (shape,))
+    rc = L.drnmf_snmf_f16_pack_dict(h, F, N, _capi.ptr(Wn), _capi.ptr(out), out.numel() * 2, _stream())
+    _capi.check(rc, h, "drnmf_snmf_f16_pack_dict")
+    return out
+
+
+def snmf_f16_forward(x, dict16, Wn, h_init, sparsity, n_iter, power=1.0, mask_value=None, out=None):
+    """`snmf_mask_forward`'s tile path (beta == 2) with the operands of the iteration's products rounded to fp16
+    (drnmf_snmf_f16_forward): x [B,T,F], dict16 = snmf_f16_pack_dict(Wn), Wn [F,N] float32 with unit-norm columns
+    (the numerator and the final mask read it), h_init [N] -> mask [B,T,F].  N even and at most 512: ValueError
+    otherwise."""
+    if x.dim() != 3 or Wn.dim() != 2 or Wn.shape[0] != x.shape[2] or tuple(h_init.shape) != (Wn.shape[1],):
+        raise ValueError("shape mismatch: x %s Wn %s h_init %s" % (tuple(x.shape), tuple(Wn.shape),
+                                                                    tuple(h_init.shape)))
+    if Wn.shape[1] % 2:
+        raise ValueError("Wn must have an even number of atoms (speech and noise halves), got %d" % Wn.shape[1])
+    B, T, F = x.shape
+    N = Wn.shape[1]
+    if tuple(dict16.shape) != (F, (N + 31) // 32 * 32) or dict16.dtype != torch.float16 or not dict16.is_contiguous():
+        raise ValueError("dict16 must be snmf_f16_pack_dict(Wn): contiguous float16 %s, got %s %s" %
+                         ((F, (N + 31) // 32 * 32), dict16.dtype, tuple(dict16.shape)))
+    L = _capi.lib()
+    dev = _dev_index(x)
+    h = _capi.handle(dev)
+    x, Wn, h_init = _f32c(x, "x"), _f32c(Wn, "Wn"), _f32c(h_init, "h_init")
+    if out is None:
+        out = torch.empty((B, T, F), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, T, F) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of shape %s" % ((B, T, F),))
+    rc = L.drnmf_snmf_f16_forward(h, B, T, F, N, int(n_iter), float(sparsity), float(power),
+                                  0.0 if mask_value is None else float(mask_value), int(mask_value is not None),
+                                  _capi.ptr(x), _capi.ptr(dict16), _capi.ptr(Wn), _capi.ptr(h_init), _capi.ptr(out),
+                                  _stream())
+    _capi.check(rc, h, "drnmf_snmf_f16_forward")
+    return out
+
+
 def stft_frames(nsampl, N, hop):
     return int(_capi.lib().drnmf_stft_frames(int(nsampl), int(N), int(hop)))
 

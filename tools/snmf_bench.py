@@ -1,13 +1,19 @@
 """Wall time of the sparse-NMF baseline's inference, both paths of ops.snmf_mask_forward in one session.
 
     python tools/snmf_bench.py [--iters 200] [--rows 32,4096,262144] [--out profiles/snmf_bench.jsonl]
+                               [--root CHECKOUT] [--label NAME]
 
 At the shipped dictionary size (F = 257, N = 200) and the reference's 200 iterations (enhance.py:842), for
 n = 32, 4096 and 262144 frame rows: median milliseconds of
   gemm     path = 1: pack kernel, drnmf_mu_forward's launches (three device-wide products per iteration), zero kernel
   tile     path = 2: one launch, a workgroup per 16 rows for all iterations
+  f16      ops.snmf_f16_forward: the tile kernel's structure on fp16 matrix-core operands (where the measured
+           package has it), with its largest mask difference from the tile path
   mu       ops.mu_forward with want_irm on the same input -- the entry the package had before, measured before and
-           after the two paths to show drift inside the session.
+           after the paths to show drift inside the session.
+--root measures the package of ANOTHER checkout (built there) with this script -- the parent commit's, in front of
+and behind this one's, is how a session shows that the machine did not drift between two builds; --label names the
+run in the JSON lines.
 Every configuration is warmed once and timed with device events; one JSON line per (rows, path) is appended to
 --out.  Nothing is asserted about speed; the largest difference of the two paths' masks is reported with them."""
 import argparse
@@ -19,8 +25,6 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
 
 F, N, SPARSITY = 257, 200, 1.0
 
@@ -46,7 +50,10 @@ def main():
     ap.add_argument("--rows", default="32,4096,262144")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "snmf_bench.jsonl"))
+    ap.add_argument("--root", default=ROOT, help="the checkout whose package is measured (default: this one)")
+    ap.add_argument("--label", default=None, help="written into every JSON line as 'label'")
     a = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(a.root))
     import __graft_entry__ as G
     G.build()
     if not torch.cuda.is_available():
@@ -67,21 +74,29 @@ def main():
         x = torch.rand((1, n, F), generator=g, device=dev) ** 2 + 1e-3
         ws = torch.empty(max(1, ops._capi.lib().drnmf_snmf_mask_workspace_bytes(1, n, F, N)), dtype=torch.uint8,
                          device=dev)
-        out = {p: torch.empty_like(x) for p in ("gemm", "tile")}
+        out = {p: torch.empty_like(x) for p in ("gemm", "tile", "f16")}
         H = torch.empty((n, N), dtype=torch.float32, device=dev)
         fill = lambda: H.copy_(h0[None].expand(n, N))
         runs = [("mu_before", lambda: ops.mu_forward(x[0], Wd, H, SPARSITY, a.iters, want_irm=True), fill)]
         for p in ("gemm", "tile"):
             runs.append((p, (lambda p=p: ops.snmf_mask_forward(x, Wn, hn, SPARSITY, a.iters, mask_value=-1.0, path=p,
                                                                out=out[p], workspace=ws)), None))
+        if hasattr(ops, "snmf_f16_forward"):
+            d16 = ops.snmf_f16_pack_dict(Wn)
+            runs.append(("f16", lambda: ops.snmf_f16_forward(x, d16, Wn, hn, SPARSITY, a.iters, mask_value=-1.0,
+                                                             out=out["f16"]), None))
         runs.append(("mu_after", runs[0][1], fill))
         for name, fn, prep in runs:
             timed(fn, 1, prep)                       # warm-up: code objects, workspaces
             ms = timed(fn, a.reps, prep)
             line = dict(tool="snmf_bench", path=name, rows=n, F=F, N=N, iters=a.iters, median_ms=float(np.median(ms)),
                         repeats_ms=[float(v) for v in ms])
+            if a.label is not None:
+                line["label"] = a.label
             if name == "tile":
                 line["max_abs_diff_vs_gemm"] = float((out["tile"] - out["gemm"]).abs().max())
+            if name == "f16":
+                line["max_abs_diff_vs_tile"] = float((out["f16"] - out["tile"]).abs().max())
             print(json.dumps(line), flush=True)
             lines.append(line)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
