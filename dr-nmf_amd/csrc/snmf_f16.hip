@@ -32,30 +32,24 @@
 // spreads every 16-lane group of the ds_read_b128 (rows 0-3, 12-15 at q and 4-11 at q + 1) over all sixteen
 // 16-byte slots, and puts the eight bin rows of a 32-lane half of the transposing read (32 bytes each) on
 // disjoint banks.  The fp32 partials have LLH = 40 floats per row for the same reason.  The fp32 phases in front
-// of and behind the iterations use the same memory with snmf_mask.hip's strides.
-#include "common.h"
-
-#include <atomic>
-#include <type_traits>
+// of and behind the iterations are snmf_tile.h's, shared with snmf_mask.hip: they use the same memory with the
+// strides, the slot order and the bank reasoning written there.
+#include "snmf_tile.h"
 
 #include "../../include/drnmf_snmf_f16.h"
 
 namespace {
 
-constexpr int TR = 16;            // rows per workgroup (one MFMA M-tile)
-constexpr int FC = 32;            // bins per staged dictionary chunk = one K-step of the second product
-constexpr int LLD = 36;           // fp32 phases: row stride of the partial / V chunk buffers (as snmf_mask.hip)
+using namespace snmf_tile;        // (FC = 32 bins is also one K-step of the second product here)
+
 constexpr int LLH = 40;           // iterations: row stride of the fp32 partials of Lambda_c
 constexpr int MAX_N = 512;
 
-inline int np16(int N) { return (N + 15) & ~15; }
 inline int np32(int N) { return (N + 31) & ~31; }
 inline size_t f16_lds_bytes(int N) {
     const int LD = np16(N) + 8;   // (the fp16 images fit inside the fp32 ones: 2 (Np32 + 16) <= 4 (Np16 + 8))
     return ((size_t)(TR + FC) * LD + 4 * TR * LLH + 2 * TR) * sizeof(float);
 }
-
-__device__ __forceinline__ int bin_base(int q) { return 8 * (q >> 1) + 2 * (q & 1); }   // snmf_mask.hip
 
 typedef __attribute__((__vector_size__(4 * sizeof(short)))) short s16x4;
 typedef __attribute__((__vector_size__(8 * sizeof(short)))) short s16x8;
@@ -96,7 +90,7 @@ snmf_f16_tile_kernel(const float* __restrict__ x, const f16* __restrict__ dict16
                      const float* __restrict__ h_init, float* __restrict__ mask_out, int64_t rows, int F, int N,
                      int n_iter, float sparsity, float power, float mask_value, int has_mask) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int Np = (N + 15) & ~15, NT = Np >> 4, LD = Np + 8, NC = (F + FC - 1) / FC;
+    const int Np = np16(N), NT = Np >> 4, LD = Np + 8, NC = (F + FC - 1) / FC;
     const int Nh = (N + 31) & ~31, NK = Nh >> 5, LDH = Nh + 16;
     float* Hs = smem;                         // [TR][LD]   fp32 H (final mask only)
     float* Ws = Hs + TR * LD;                 // [FC][LD]   fp32 dictionary chunk (numerator, final mask)
@@ -109,7 +103,6 @@ snmf_f16_tile_kernel(const float* __restrict__ x, const f16* __restrict__ dict16
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int64_t row0 = (int64_t)blockIdx.x * TR;
     const float flr = 1e-9f;                  // sparse_nmf_gpu.m:172
-    auto vpow = [&](float xv) { return power == 1.f ? xv : (power == 2.f ? xv * xv : powf(xv, power)); };
 
     // keras.layers.Masking (snmf_mask.hip's rule) and the row's scale
 #pragma unroll
@@ -122,7 +115,7 @@ snmf_f16_tile_kernel(const float* __restrict__ x, const f16* __restrict__ dict16
             for (int f = l; f < F; f += 64) {
                 const float xv = x[row * F + f];
                 any |= (xv != mask_value);
-                m = fmaxf(m, vpow(xv));       // (fmaxf drops a NaN)
+                m = fmaxf(m, vpow(xv, power));    // (fmaxf drops a NaN)
             }
             if (!has_mask) any = true;
         }
@@ -136,17 +129,7 @@ snmf_f16_tile_kernel(const float* __restrict__ x, const f16* __restrict__ dict16
         }
     }
     __syncthreads();
-    int nvalid = 0;
-#pragma unroll
-    for (int i = 0; i < TR; ++i) nvalid += valid[i];
-    if (nvalid == 0) {                        // nothing to compute: the rows' masks are 0
-        for (int rl = 0; rl < TR; ++rl) {
-            const int64_t row = row0 + rl;
-            if (row >= rows) break;
-            for (int f = tid; f < F; f += 256) mask_out[row * F + f] = 0.f;
-        }
-        return;
-    }
+    if (all_masked(valid, mask_out, row0, rows, F, tid)) return;
 
     // the whole shadow once (the columns behind N and the rows that are not valid stay 0), ...
     for (int i = tid; i < TR * LDH / 2; i += 256) ((unsigned*)Hs16)[i] = 0u;
@@ -212,63 +195,12 @@ snmf_f16_tile_kernel(const float* __restrict__ x, const f16* __restrict__ dict16
             if (scol < Nh) *(f16x8*)(Ws16 + ((4 * i + w) * RPI + srow) * LDH + scol) = pf16[i];
     };
 
-    // fp32 phases (snmf_mask.hip): this wave's share of H Wc^T into its slot of Lp.  SEL 1: the atoms below rh
-    // only; 2: the atoms from rh on (the two halves of the mask).
-    auto lambda_partial = [&](auto sel_tag, int rh) {
-        constexpr int SEL = decltype(sel_tag)::value;
-        f32x4 P[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int i = 0; i < NTW; ++i) {
-            const int S = w + 4 * i;
-            if (S < NT) {
-                const int k0 = 16 * S + 4 * q;
-                f32x4 a = *(const f32x4*)(Hs + r * LD + k0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a[e] = ((k0 + e < rh) == (SEL == 1)) ? a[e] : 0.f;
-                const f32x4 b0 = *(const f32x4*)(Ws + r * LD + k0);
-                const f32x4 b1 = *(const f32x4*)(Ws + (16 + r) * LD + k0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    P[0] = mfma16(a[e], b0[e], P[0]);
-                    P[1] = mfma16(a[e], b1[e], P[1]);
-                }
-            }
-        }
-#pragma unroll
-        for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) Lp[(w * TR + 4 * q + v) * LLD + 16 * jt + r] = P[jt][v];
-    };
-
     // num = (s V) Wn, once, exact fp32: V = x^power on valid rows, 0 elsewhere
     for (int c = 0; c < NC; ++c) {
         stage(c);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int idx = tid + 256 * k, rl = idx >> 5, b = idx & 31, f = c * FC + b;
-            float v = 0.f;
-            if (valid[rl] && f < F) v = vpow(x[(row0 + rl) * F + f]) * rs[rl];
-            Lp[rl * LLD + b] = v;
-        }
+        num_fill(x, Lp, valid, rs, row0, F, c, power, tid);
         __syncthreads();
-        float aF[2][4];
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                aF[s][e] = Lp[r * LLD + 16 * s + bin_base(q) + (e & 1) + 4 * (e >> 1)];
-        const float* bq = Ws + bin_base(q) * LD + r;
-#pragma unroll
-        for (int i = 0; i < NTW; ++i) {
-            const int t = w + 4 * i;
-            if (t < NT) {
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        num[i] = mfma16(aF[s][e], bq[(16 * s + (e & 1) + 4 * (e >> 1)) * LD + 16 * t], num[i]);
-            }
-        }
+        num_accumulate<NTW>(Ws, Lp, LD, NT, w, r, q, num);
         __syncthreads();
     }
 
@@ -351,51 +283,19 @@ snmf_f16_tile_kernel(const float* __restrict__ x, const f16* __restrict__ dict16
             for (int v = 0; v < 4; ++v) Hs[(4 * q + v) * LD + 16 * t + r] = Hm[i][v];
         }
     }
-    const int rh = N / 2;
-    for (int c = 0; c < NC; ++c) {
+    final_mask<NTW>(Hs, Ws, Lp, valid, rs, mask_out, row0, rows, F, N, LD, tid, w, r, q, [&](int c) {
         stage(c);
         __syncthreads();
-        float cl[2], ns[2];
-        lambda_partial(std::integral_constant<int, 1>{}, rh);
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int idx = tid + 256 * k;
-            const float* p = Lp + (idx >> 5) * LLD + (idx & 31);
-            cl[k] = ((p[0] + p[TR * LLD]) + p[2 * TR * LLD]) + p[3 * TR * LLD];
-        }
-        __syncthreads();
-        lambda_partial(std::integral_constant<int, 2>{}, rh);
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int idx = tid + 256 * k, rl = idx >> 5, f = c * FC + (idx & 31);
-            const float* p = Lp + rl * LLD + (idx & 31);
-            ns[k] = ((p[0] + p[TR * LLD]) + p[2 * TR * LLD]) + p[3 * TR * LLD];
-            const int64_t row = row0 + rl;
-            if (row < rows && f < F)
-                mask_out[row * F + f] = valid[rl] ? cl[k] / (1e-9f * rs[rl] + cl[k] + ns[k]) : 0.f;
-        }
-        __syncthreads();
-    }
+    });
 }
 
 template <int NTW>
 hipError_t launch_f16(const float* x, const f16* dict16, const float* Wn, const float* h_init, float* mask_out,
                       int64_t rows, int F, int N, int n_iter, float sparsity, float power, float mask_value,
                       int has_mask, hipStream_t stream, int device) {
-    auto* kern = snmf_f16_tile_kernel<NTW>;
-    // once per kernel instance and device: the dynamic-LDS limit of the widest shape the instance takes
-    static std::atomic<bool> raised[64];
-    if (device < 0 || device >= 64 || !raised[device].load(std::memory_order_acquire)) {
-        const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)f16_lds_bytes(NTW == 4 ? 256 : MAX_N));
-        if (e != hipSuccess) return e;
-        if (device >= 0 && device < 64) raised[device].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((rows + TR - 1) / TR)), dim3(256), f16_lds_bytes(N), stream, x, dict16,
-                       Wn, h_init, mask_out, rows, F, N, n_iter, sparsity, power, mask_value, has_mask);
-    return hipGetLastError();
+    return launch<snmf_f16_tile_kernel<NTW>>(device, f16_lds_bytes(NTW == 4 ? 256 : MAX_N), f16_lds_bytes(N), rows,
+                                             stream, x, dict16, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity,
+                                             power, mask_value, has_mask);
 }
 
 }  // namespace

@@ -18,22 +18,17 @@
 // fmaf chain in k order), so a row's result depends on nothing but that row, Wn and h_init: bit for bit the same
 // wherever the row sits and whatever its neighbours hold.
 //
-// LDS: Hs [16][LD], Ws [32][LD], LD = Np + 8 (Np = N rounded up to 16).  LD % 16 == 8 makes both operand reads
-// conflict-free: the 16-byte reads of the first product (lane (r, q) reads row r, atoms 16 S + 4 q ..) spread
-// each 16-lane group of ds_read_b128 over all 64 banks, and the 4-byte reads of the second (lane (r, q) reads bin
-// rows two apart for q and q + 1, see bin_base) put the two rows of a 32-lane group 16 banks apart.
-#include "common.h"
-
-#include <atomic>
-#include <type_traits>
+// LDS: Hs [16][LD], Ws [32][LD], LD = Np + 8 (Np = N rounded up to 16).  snmf_tile.h holds the phases this kernel
+// shares with its fp16-operand sibling (snmf_f16.hip), the slot order of the second product and why these strides
+// are free of bank conflicts.
+#include "snmf_tile.h"
 
 #include "../../include/drnmf_snmf.h"
 
 namespace {
 
-constexpr int TR = 16;            // rows per workgroup (one MFMA M-tile)
-constexpr int FC = 32;            // bins per staged dictionary chunk
-constexpr int LLD = 36;           // row stride of the 16 x 32 partial / V chunk buffers
+using namespace snmf_tile;
+
 constexpr int TILE_MAX_N = 512;
 // path = 0 takes the tile kernel up to this many rows: the largest measured row count at which it was the faster
 // path.  Measured (tools/snmf_bench.py, MI355X, F = 257, N = 200, 200 iterations, tile against GEMM path): 3.9 / 8.8
@@ -41,15 +36,10 @@ constexpr int TILE_MAX_N = 512;
 // section 6h has the table).  Mirrored by _capi.SNMF_TILE_AUTO_MAX_ROWS.
 constexpr int64_t TILE_AUTO_MAX_ROWS = 8192;
 
-inline int tile_np(int N) { return (N + 15) & ~15; }
 inline size_t tile_lds_bytes(int N) {
-    const int LD = tile_np(N) + 8;
+    const int LD = np16(N) + 8;
     return ((size_t)(TR + FC) * LD + 4 * TR * LLD + TR) * sizeof(float);
 }
-
-// Contraction slot (q, e) of the second product's k-step S' is bin 16 S' + bin_base(q) + (e & 1) + 4 (e >> 1):
-// lanes q and q + 1 of one 32-lane group read dictionary rows two bins apart.
-__device__ __forceinline__ int bin_base(int q) { return 8 * (q >> 1) + 2 * (q & 1); }
 
 // NTW: 16-column tiles of H / num / den per wave (4: N <= 256, 8: N <= 512).  VEC: N % 4 == 0 and Wn 16-byte
 // aligned -- the dictionary is staged with 16-byte loads.  Waves per SIMD: three workgroups of the shipped N = 200
@@ -61,7 +51,7 @@ snmf_mask_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn,
                       const float* __restrict__ h_init, float* __restrict__ mask_out, int64_t rows, int F,
                       int N, int n_iter, float sparsity, float power, float mask_value, int has_mask) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int Np = (N + 15) & ~15, NT = Np >> 4, LD = Np + 8, NC = (F + FC - 1) / FC;
+    const int Np = np16(N), NT = Np >> 4, LD = Np + 8, NC = (F + FC - 1) / FC;
     float* Hs = smem;                         // [TR][LD]   current H (first product's A operand)
     float* Ws = Hs + TR * LD;                 // [FC][LD]   dictionary chunk, zero behind F and N
     float* Lp = Ws + FC * LD;                 // [4][TR][LLD] per-wave partials of Lambda_c; slot 0 also the V chunk
@@ -88,17 +78,7 @@ snmf_mask_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn,
         if (l == 0) valid[rl] = any ? 1 : 0;
     }
     __syncthreads();
-    int nvalid = 0;
-#pragma unroll
-    for (int i = 0; i < TR; ++i) nvalid += valid[i];
-    if (nvalid == 0) {                        // nothing to compute: the rows' masks are 0
-        for (int rl = 0; rl < TR; ++rl) {
-            const int64_t row = row0 + rl;
-            if (row >= rows) break;
-            for (int f = tid; f < F; f += 256) mask_out[row * F + f] = 0.f;
-        }
-        return;
-    }
+    if (all_masked(valid, mask_out, row0, rows, F, tid)) return;
 
     f32x4 num[NTW], den[NTW];
 #pragma unroll
@@ -116,11 +96,12 @@ snmf_mask_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn,
     }
 
     // dictionary chunk: global -> registers (in flight under the previous chunk's products) -> LDS.  Wave w
-    // stages the chunk's rows w, w + 4, ..
+    // stages the chunk's rows w, w + 4, ..  (always_inline: the inliner's budget for a caller of this size is
+    // spent by the time it gets to these two in the <8, false> instance, and a call costs scratch)
     constexpr int NVP = NTW / 4;
     f32x4 pf4[FC / 4][NVP];
     float pf1[FC / 4][NTW];
-    auto gload = [&](int c) {
+    auto gload = [&](int c) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < FC / 4; ++i) {
             const int bin = c * FC + w + 4 * i;
@@ -143,7 +124,7 @@ snmf_mask_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn,
             }
         }
     };
-    auto swrite = [&]() {
+    auto swrite = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < FC / 4; ++i) {
             float* dst = Ws + (w + 4 * i) * LD;
@@ -163,74 +144,14 @@ snmf_mask_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn,
         }
     };
 
-    // This wave's share of H Wc^T (its 16-atom blocks), 16 x 32, into its slot of Lp.  SEL 0: all atoms;
-    // 1: the atoms below rh only; 2: the atoms from rh on (the two halves of the mask).
-    auto lambda_partial = [&](auto sel_tag, int rh) {
-        constexpr int SEL = decltype(sel_tag)::value;
-        f32x4 P[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int i = 0; i < NTW; ++i) {
-            const int S = w + 4 * i;
-            if (S < NT) {
-                const int k0 = 16 * S + 4 * q;
-                f32x4 a = *(const f32x4*)(Hs + r * LD + k0);
-                if (SEL != 0) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) a[e] = ((k0 + e < rh) == (SEL == 1)) ? a[e] : 0.f;
-                }
-                const f32x4 b0 = *(const f32x4*)(Ws + r * LD + k0);
-                const f32x4 b1 = *(const f32x4*)(Ws + (16 + r) * LD + k0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    P[0] = mfma16(a[e], b0[e], P[0]);
-                    P[1] = mfma16(a[e], b1[e], P[1]);
-                }
-            }
-        }
-#pragma unroll
-        for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) Lp[(w * TR + 4 * q + v) * LLD + 16 * jt + r] = P[jt][v];
-    };
-    // acc [16 x N] += A [16 x 32] Wc, A given as this lane's operand values aF[S'][e] (row r, bin slot (q, e))
-    auto accumulate = [&](const float (&aF)[2][4], f32x4 (&acc)[NTW]) {
-        const float* bq = Ws + bin_base(q) * LD + r;
-#pragma unroll
-        for (int i = 0; i < NTW; ++i) {       // (one wave-uniform branch per tile; another wave's MFMAs fill the
-            const int t = w + 4 * i;          // dependent-accumulator latency of the chain of eight)
-            if (t < NT) {
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        acc[i] = mfma16(aF[s][e], bq[(16 * s + (e & 1) + 4 * (e >> 1)) * LD + 16 * t], acc[i]);
-            }
-        }
-    };
-
     gload(0);
     // num = V Wn, once: V = x^power on valid rows, 0 elsewhere
     for (int c = 0; c < NC; ++c) {
         swrite();
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int idx = tid + 256 * k, rl = idx >> 5, b = idx & 31, f = c * FC + b;
-            float v = 0.f;
-            if (valid[rl] && f < F) {
-                const float xv = x[(row0 + rl) * F + f];
-                v = power == 1.f ? xv : (power == 2.f ? xv * xv : powf(xv, power));
-            }
-            Lp[rl * LLD + b] = v;
-        }
+        num_fill(x, Lp, valid, nullptr, row0, F, c, power, tid);
         __syncthreads();
         gload(c + 1 < NC ? c + 1 : 0);
-        float aF[2][4];
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                aF[s][e] = Lp[r * LLD + 16 * s + bin_base(q) + (e & 1) + 4 * (e >> 1)];
-        accumulate(aF, num);
+        num_accumulate<NTW>(Ws, Lp, LD, NT, w, r, q, num);
         __syncthreads();
     }
 
@@ -241,7 +162,7 @@ snmf_mask_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn,
             swrite();
             __syncthreads();                  // Ws (and, for c == 0, the new H) visible
             gload(c + 1 < NC ? c + 1 : 0);
-            lambda_partial(std::integral_constant<int, 0>{}, 0);
+            lambda_partial<NTW, 0>(Hs, Ws, Lp, LD, NT, w, r, q, 0);
             __syncthreads();
             float aF[2][4];
 #pragma unroll
@@ -256,7 +177,7 @@ snmf_mask_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn,
                     aF[s][2 * hh] = fmaxf(sum[0], flr);
                     aF[s][2 * hh + 1] = fmaxf(sum[1], flr);
                 }
-            accumulate(aF, den);
+            accumulate<NTW>(Ws, LD, NT, w, r, q, aF, den);
             __syncthreads();                  // every wave is done with Ws and Lp
         }
 #pragma unroll
@@ -272,35 +193,11 @@ snmf_mask_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn,
         }
     }
 
-    // mask = Wc Hc / (1e-9 + Wc Hc + Wn Hn), a chunk at a time (enhance.py:848-852)
-    const int rh = N / 2;
-    for (int c = 0; c < NC; ++c) {
+    final_mask<NTW>(Hs, Ws, Lp, valid, nullptr, mask_out, row0, rows, F, N, LD, tid, w, r, q, [&](int c) {
         swrite();
         __syncthreads();
         if (c + 1 < NC) gload(c + 1);
-        float cl[2], ns[2];
-        lambda_partial(std::integral_constant<int, 1>{}, rh);
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int idx = tid + 256 * k;
-            const float* p = Lp + (idx >> 5) * LLD + (idx & 31);
-            cl[k] = ((p[0] + p[TR * LLD]) + p[2 * TR * LLD]) + p[3 * TR * LLD];
-        }
-        __syncthreads();
-        lambda_partial(std::integral_constant<int, 2>{}, rh);
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int idx = tid + 256 * k, rl = idx >> 5, f = c * FC + (idx & 31);
-            const float* p = Lp + rl * LLD + (idx & 31);
-            ns[k] = ((p[0] + p[TR * LLD]) + p[2 * TR * LLD]) + p[3 * TR * LLD];
-            const int64_t row = row0 + rl;
-            if (row < rows && f < F)
-                mask_out[row * F + f] = valid[rl] ? cl[k] / (1e-9f + cl[k] + ns[k]) : 0.f;
-        }
-        __syncthreads();
-    }
+    });
 }
 
 // GEMM path, in front of drnmf_mu_forward: V = x^power (masked rows 0), H = h_init in every valid row, the
@@ -320,7 +217,7 @@ snmf_mask_pack_kernel(const float* __restrict__ x, const float* __restrict__ h_i
     }
     for (int f = l; f < F; f += 64) {
         const float xv = src[f];
-        V[row * F + f] = any ? (power == 1.f ? xv : (power == 2.f ? xv * xv : powf(xv, power))) : 0.f;
+        V[row * F + f] = any ? vpow(xv, power) : 0.f;
     }
     for (int c = l; c < N; c += 64) H[row * N + c] = any ? h_init[c] : 0.f;
     if (l == 0) valid[row] = any ? 1 : 0;
@@ -354,23 +251,12 @@ MaskWs mask_ws(int64_t rows, int F, int N) {
 }
 
 template <int NTW, bool VEC>
-hipError_t launch_tile(const float* x, const float* Wn, const float* h_init, float* mask_out, int64_t rows,
-                       int F, int N, int n_iter, float sparsity, float power, float mask_value, int has_mask,
-                       hipStream_t stream, int device) {
-    const size_t lds = tile_lds_bytes(N);
-    auto* kern = snmf_mask_tile_kernel<NTW, VEC>;
-    // once per kernel instance and device: the dynamic-LDS limit of the widest shape the instance takes (a property
-    // of the function, not of a launch; a second thread that gets here first sets the same value again)
-    static std::atomic<bool> raised[64];
-    if (device < 0 || device >= 64 || !raised[device].load(std::memory_order_acquire)) {
-        const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)tile_lds_bytes(NTW == 4 ? 256 : TILE_MAX_N));
-        if (e != hipSuccess) return e;
-        if (device >= 0 && device < 64) raised[device].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((rows + TR - 1) / TR)), dim3(256), lds, stream, x, Wn, h_init,
-                       mask_out, rows, F, N, n_iter, sparsity, power, mask_value, has_mask);
-    return hipGetLastError();
+hipError_t launch_tile(int device, hipStream_t stream, const float* x, const float* Wn, const float* h_init,
+                       float* mask_out, int64_t rows, int F, int N, int n_iter, float sparsity, float power,
+                       float mask_value, int has_mask) {
+    return launch<snmf_mask_tile_kernel<NTW, VEC>>(device, tile_lds_bytes(NTW == 4 ? 256 : TILE_MAX_N),
+                                                   tile_lds_bytes(N), rows, stream, x, Wn, h_init, mask_out, rows, F,
+                                                   N, n_iter, sparsity, power, mask_value, has_mask);
 }
 
 }  // namespace
@@ -420,16 +306,16 @@ extern "C" int32_t drnmf_snmf_mask_forward(drnmf_handle_t h, int32_t B, int32_t 
     if (!gemm) {
         const bool vec = N % 4 == 0 && ((uintptr_t)Wn & 15) == 0;
         hipError_t e;
-        if (tile_np(N) <= 256)
-            e = vec ? launch_tile<4, true>(x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity, power, mask_value,
-                                           has_mask, stream, h->device)
-                    : launch_tile<4, false>(x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity, power, mask_value,
-                                            has_mask, stream, h->device);
+        if (np16(N) <= 256)
+            e = vec ? launch_tile<4, true>(h->device, stream, x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity,
+                                           power, mask_value, has_mask)
+                    : launch_tile<4, false>(h->device, stream, x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity,
+                                            power, mask_value, has_mask);
         else
-            e = vec ? launch_tile<8, true>(x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity, power, mask_value,
-                                           has_mask, stream, h->device)
-                    : launch_tile<8, false>(x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity, power, mask_value,
-                                            has_mask, stream, h->device);
+            e = vec ? launch_tile<8, true>(h->device, stream, x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity,
+                                           power, mask_value, has_mask)
+                    : launch_tile<8, false>(h->device, stream, x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity,
+                                            power, mask_value, has_mask);
         DRNMF_HIP(h, e);
         return DRNMF_OK;
     }

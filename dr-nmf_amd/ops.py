@@ -829,6 +829,30 @@ def snmf_mask_workspace(path, B, T, F, N, beta, device, have=None):
     return torch.empty(max(need, 1), dtype=torch.uint8, device=device)
 
 
+def _snmf_args(x, Wn, h_init, out, dict16=None):
+    """The argument checks `snmf_mask_forward` and `snmf_f16_forward` share -> (lib, handle, x, Wn, h_init, out) with
+    the three inputs contiguous float32 and out [B,T,F] (allocated when None).  dict16: checked against Wn when given."""
+    if x.dim() != 3 or Wn.dim() != 2 or Wn.shape[0] != x.shape[2] or tuple(h_init.shape) != (Wn.shape[1],):
+        raise ValueError("shape mismatch: x %s Wn %s h_init %s" % (tuple(x.shape), tuple(Wn.shape),
+                                                                    tuple(h_init.shape)))
+    if Wn.shape[1] % 2:
+        raise ValueError("Wn must have an even number of atoms (speech and noise halves), got %d" % Wn.shape[1])
+    B, T, F = x.shape
+    N = Wn.shape[1]
+    if dict16 is not None and (tuple(dict16.shape) != (F, (N + 31) // 32 * 32) or dict16.dtype != torch.float16 or
+                               not dict16.is_contiguous()):
+        raise ValueError("dict16 must be snmf_f16_pack_dict(Wn): contiguous float16 %s, got %s %s" %
+                         ((F, (N + 31) // 32 * 32), dict16.dtype, tuple(dict16.shape)))
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(x))
+    x, Wn, h_init = _f32c(x, "x"), _f32c(Wn, "Wn"), _f32c(h_init, "h_init")
+    if out is None:
+        out = torch.empty((B, T, F), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, T, F) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of shape %s" % ((B, T, F),))
+    return L, h, x, Wn, h_init, out
+
+
 def snmf_mask_forward(x, Wn, h_init, sparsity, n_iter, beta=2.0, power=1.0, mask_value=None, path="auto",
                       out=None, workspace=None):
     """The sparse-NMF baseline's inference on padded sequences (drnmf_snmf_mask_forward, enhance.py:838-852):
@@ -839,21 +863,9 @@ def snmf_mask_forward(x, Wn, h_init, sparsity, n_iter, beta=2.0, power=1.0, mask
     here when None or too small)."""
     if path not in _capi.SNMF_PATHS:
         raise ValueError("path must be 'auto', 'gemm' or 'tile' (got %r)" % (path,))
-    if x.dim() != 3 or Wn.dim() != 2 or Wn.shape[0] != x.shape[2] or tuple(h_init.shape) != (Wn.shape[1],):
-        raise ValueError("shape mismatch: x %s Wn %s h_init %s" % (tuple(x.shape), tuple(Wn.shape),
-                                                                    tuple(h_init.shape)))
-    if Wn.shape[1] % 2:
-        raise ValueError("Wn must have an even number of atoms (speech and noise halves), got %d" % Wn.shape[1])
-    L = _capi.lib()
-    dev = _dev_index(x)
-    h = _capi.handle(dev)
-    x, Wn, h_init = _f32c(x, "x"), _f32c(Wn, "Wn"), _f32c(h_init, "h_init")
+    L, h, x, Wn, h_init, out = _snmf_args(x, Wn, h_init, out)
     B, T, F = x.shape
     N = Wn.shape[1]
-    if out is None:
-        out = torch.empty((B, T, F), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, T, F) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous float32 tensor of shape %s" % ((B, T, F),))
     workspace = snmf_mask_workspace(path, B, T, F, N, beta, x.device, have=workspace)
     rc = L.drnmf_snmf_mask_forward(h, B, T, F, N, int(n_iter), float(beta), float(sparsity), float(power),
                                    0.0 if mask_value is None else float(mask_value), int(mask_value is not None),
@@ -894,24 +906,9 @@ def snmf_f16_forward(x, dict16, Wn, h_init, sparsity, n_iter, power=1.0, mask_va
     (drnmf_snmf_f16_forward): x [B,T,F], dict16 = snmf_f16_pack_dict(Wn), Wn [F,N] float32 with unit-norm columns
     (the numerator and the final mask read it), h_init [N] -> mask [B,T,F].  N even and at most 512: ValueError
     otherwise."""
-    if x.dim() != 3 or Wn.dim() != 2 or Wn.shape[0] != x.shape[2] or tuple(h_init.shape) != (Wn.shape[1],):
-        raise ValueError("shape mismatch: x %s Wn %s h_init %s" % (tuple(x.shape), tuple(Wn.shape),
-                                                                    tuple(h_init.shape)))
-    if Wn.shape[1] % 2:
-        raise ValueError("Wn must have an even number of atoms (speech and noise halves), got %d" % Wn.shape[1])
+    L, h, x, Wn, h_init, out = _snmf_args(x, Wn, h_init, out, dict16=dict16)
     B, T, F = x.shape
     N = Wn.shape[1]
-    if tuple(dict16.shape) != (F, (N + 31) // 32 * 32) or dict16.dtype != torch.float16 or not dict16.is_contiguous():
-        raise ValueError("dict16 must be snmf_f16_pack_dict(Wn): contiguous float16 %s, got %s %s" %
-                         ((F, (N + 31) // 32 * 32), dict16.dtype, tuple(dict16.shape)))
-    L = _capi.lib()
-    dev = _dev_index(x)
-    h = _capi.handle(dev)
-    x, Wn, h_init = _f32c(x, "x"), _f32c(Wn, "Wn"), _f32c(h_init, "h_init")
-    if out is None:
-        out = torch.empty((B, T, F), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, T, F) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous float32 tensor of shape %s" % ((B, T, F),))
     rc = L.drnmf_snmf_f16_forward(h, B, T, F, N, int(n_iter), float(sparsity), float(power),
                                   0.0 if mask_value is None else float(mask_value), int(mask_value is not None),
                                   _capi.ptr(x), _capi.ptr(dict16), _capi.ptr(Wn), _capi.ptr(h_init), _capi.ptr(out),

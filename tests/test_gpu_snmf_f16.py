@@ -171,6 +171,21 @@ def test_rows_do_not_depend_on_position_or_neighbours(ops):
     assert float(whole.std()) > 0.05
 
 
+@pytest.mark.parametrize("case", E.CASES + ["range"])
+def test_without_iterations_the_two_tile_kernels_agree_bitwise(ops, case):
+    """n_iter = 0: both tile kernels compute the mask from h_init through nothing but the phases of csrc/snmf_tile.h
+    (validity, the final-mask loop with its staging, partial sums and store).  The fp16 kernel's row scale is a power
+    of two on H and on the epsilon, which commutes with every fp32 rounding of that chain while nothing leaves the
+    normal range -- and these inputs do not (row scales from 2^-14 up to the clamp at 2^40 in the range problem)."""
+    x, W, h_init = E.range_problem() if case == "range" else E.problem(*case)
+    Wn, hn = R.normalised(W, h_init)
+    xd, Wd, hd = (torch.from_numpy(np.array(a)).to(DEV) for a in (x, Wn, hn))
+    f16 = ops.snmf_f16_forward(xd, ops.snmf_f16_pack_dict(Wd), Wd, hd, R.SPARSITY, 0, mask_value=R.MASK_VALUE)
+    f32 = ops.snmf_mask_forward(xd, Wd, hd, R.SPARSITY, 0, mask_value=R.MASK_VALUE, path="tile")
+    assert torch.equal(f16, f32)
+    assert float(f32.max()) > 0
+
+
 # ---- the model ---------------------------------------------------------------------------------------------------
 def _model(n_iter=R.N_ITER):
     from drnmf_amd import layers
