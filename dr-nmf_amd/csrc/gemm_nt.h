@@ -27,7 +27,6 @@ struct Operands {
     int N, K;
     int64_t lda, ldb;
     int ktail = 0;    // extra contraction columns K .. K+ktail-1 (<= 2), see below
-    int thin = 0;     // 1: output column N (row N of Bt) exists BEHIND the N tiled columns, see THIN below
     // split-operand mode only (gemm_nt_x3.h; set by launch()): Bt already split into bf16 planes
     const void* B3 = nullptr;
     int kt3 = 0;
@@ -74,8 +73,9 @@ __device__ __forceinline__ f32x4 load4(const float* base, int64_t row, int64_t n
 // a 2^k+1 STFT (K = 513 = 16 tiles + 1) ride along without a 17th, almost empty k-tile.
 // `static constexpr bool REDUCE = true` in the functor: its operator() RETURNS a float per output element;
 // the kernel sums them per thread (fixed order), per workgroup (LDS tree, fixed order) and stores ONE
-// partial per workgroup at epi.red_out[blockIdx.x] (blockIdx.x < launch_tiles(g)) -- a grid-wide sum (the objective of the dictionary
-// training) rides on a GEMM's epilogue instead of costing its own pass over the outputs; deterministic.
+// partial per workgroup at epi.red_out[tile] (tile < launch_tiles(g); reduce_store below) -- a grid-wide sum
+// (the objective of the dictionary training) rides on a GEMM's epilogue instead of costing its own pass over
+// the outputs; deterministic.
 template <class E, class = void> struct epi_reduce : std::false_type {};
 template <class E> struct epi_reduce<E, std::void_t<decltype(E::REDUCE)>>
     : std::integral_constant<bool, E::REDUCE> {};
@@ -83,6 +83,126 @@ template <class E> struct epi_reduce<E, std::void_t<decltype(E::REDUCE)>>
 template <class E, class = void> struct epi_early : std::true_type {};
 template <class E> struct epi_early<E, std::void_t<decltype(E::EARLY)>>
     : std::integral_constant<bool, E::EARLY> {};
+
+template <int I> using int_c = std::integral_constant<int, I>;
+
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][2]) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.f;
+}
+
+struct TilePos { int64_t m0; int n0, wm, wn, li, kk, nb; };   // tile origin, wave, lane (li, kk), NB of the wave
+
+// Last k-tile and epilogue of a workgroup's 128 x 128 tile at (m0, n0), shared by gemm_nt_kernel and
+// gemm_nt_x3_kernel (gemm_nt_x3.h).  last_tile() contracts the k-tile that sits in LDS into acc: it is the one
+// thing the two kernels do differently here.  Register v of lane l holds row (v&3) + 8*(v>>2) + 4*(l>>5),
+// column l&31.  Row indices are formed in 32 bits (launch() refuses M >= 2^31): the functors'
+// row * ld then is one 32 x 32 -> 64-bit multiply-add instead of a 64 x 32-bit product.
+// Returns this thread's sum of a REDUCE functor's values (0 otherwise).
+// (t's fields are used through references, as the kernels' lambdas captured them: copied into locals, every
+// EARLY functor's kernel went from 235 to 256 VGPRs and 16 .. 128 bytes of scratch.)
+template <bool FULL, class Epi, class LastTile>      // FULL: every row of the tile is inside M
+__device__ __forceinline__ float finish_tile(const Operands& g, const Epi& epi, f32x16 (&acc)[2][2], const TilePos& t,
+                                             const LastTile& last_tile) {
+    const int64_t& m0 = t.m0;
+    const int &n0 = t.n0, &wm = t.wm, &wn = t.wn, &li = t.li, &kk = t.kk, &nb = t.nb;
+    constexpr bool EARLY = epi_early<Epi>::value;
+    constexpr bool RED = epi_reduce<Epi>::value;
+    float red = 0.f;
+    const int M32 = (int)g.M, m032 = (int)m0;
+    auto rowof = [&](int a, int v) { return m032 + wm * 64 + a * 32 + (v & 3) + 8 * (v >> 2) + 4 * kk; };
+    auto colof = [&](int b) { return n0 + wn * 64 + b * 32 + li; };
+    f32x2 pv[EARLY ? 2 : 1][EARLY ? 2 : 1][16];
+    float ta[2] = {0.f, 0.f}, tb[2] = {0.f, 0.f};
+    const bool tk = kk < g.ktail;
+    if (g.ktail) {   // raw loads (clamped addresses); zeroed after the MFMAs
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int64_t r = m0 + wm * 64 + i * 32 + li;
+            const int c = n0 + wn * 64 + i * 32 + li;
+            ta[i] = g.A[(r < g.M ? r : g.M - 1) * g.lda + g.K + (tk ? kk : 0)];
+            tb[i] = g.Bt[(int64_t)(c < g.N ? c : g.N - 1) * g.ldb + g.K + (tk ? kk : 0)];
+        }
+    }
+    if (EARLY) {
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                int col = colof(b);
+                col = col < g.N ? col : g.N - 1;
+#pragma unroll
+                for (int v = 0; v < 16; ++v) {
+                    int row = rowof(a, v);
+                    if (!FULL) row = row < M32 ? row : M32 - 1;
+                    pv[a][b][v] = epi.pre(row, col);
+                }
+            }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    last_tile();
+    if (g.ktail && nb > 0) {      // the odd contraction columns, exact fp32 in either matrix mode
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            if (!(tk && m0 + wm * 64 + i * 32 + li < g.M)) ta[i] = 0.f;
+            if (!(tk && n0 + wn * 64 + i * 32 + li < g.N)) tb[i] = 0.f;
+        }
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[0], tb[0], acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[0], tb[1], acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[1], tb[0], acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[1], tb[1], acc[1][1], 0, 0, 0);
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int col = colof(b);
+            if (col >= g.N) continue;
+            if (!EARLY) {
+#pragma unroll
+                for (int v = 0; v < 16; ++v) {
+                    int row = rowof(a, v);
+                    if (!FULL) row = row < M32 ? row : M32 - 1;
+                    pv[0][0][v] = epi.pre(row, col);
+                }
+            }
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                int row = rowof(a, v);
+                // opaque copy: the store addresses are formed again here instead of 64 64-bit
+                // load addresses staying live across the MFMAs (that cost the second wave per SIMD)
+                if (EARLY) asm volatile("" : "+v"(row));
+                if (FULL || row < M32) {
+                    if constexpr (RED) red += epi(row, col, acc[a][b][v], pv[EARLY ? a : 0][EARLY ? b : 0][v]);
+                    else epi(row, col, acc[a][b][v], pv[EARLY ? a : 0][EARLY ? b : 0][v]);
+                }
+            }
+        }
+    return red;
+}
+template <class Epi, class LastTile>
+__device__ __forceinline__ float finish(const Operands& g, const Epi& epi, f32x16 (&acc)[2][2], const TilePos& t,
+                                        const LastTile& last_tile) {
+    if ((int)t.m0 + BM <= (int)g.M) return finish_tile<true>(g, epi, acc, t, last_tile);
+    return finish_tile<false>(g, epi, acc, t, last_tile);
+}
+
+// REDUCE: the threads' sums added per workgroup (LDS tree, fixed order), ONE partial stored at red_out[slot]
+template <class Epi>
+__device__ __forceinline__ void reduce_store(float* lds, float red, const Epi& epi, int tid, int slot) {
+    __syncthreads();                       // every wave is done with the staged tiles
+    lds[tid] = red;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) lds[tid] += lds[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) epi.red_out[slot] = lds[0];
+}
 
 // THIN (launch() sets it up: VEC, no ktail, N = 128 j + 1 -- the 513 / 257 / 1025 bins of a 2^k + 1 STFT):
 // the one column behind the last full tile is not given a fifth, 1/128-full column of workgroups (a
@@ -109,12 +229,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(const Operands g, const
     const int srow = tid >> 3, sk = (tid & 7) * 4;
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.f;
+    zero_acc(acc);
 
     // The loads of tile kt+1 are issued before tile kt's MFMAs and first consumed after them
     // (swrite).  In the vector path the out-of-range zeroing is therefore applied in swrite, not
@@ -253,104 +368,23 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(const Operands g, const
     gload(0);
     swrite(0, 0);
     __syncthreads();
-    if (nb == 2) {
+    auto body = [&](auto nb_tag) {
         for (int kt = 0; kt + 1 < nkt; ++kt) {
-            ktile(kt & 1, std::true_type{}, (kt + 1) * BK, std::integral_constant<int, 2>{});
+            ktile(kt & 1, std::true_type{}, (kt + 1) * BK, nb_tag);
             __syncthreads();
         }
-    } else if (nb == 1) {
-        for (int kt = 0; kt + 1 < nkt; ++kt) {
-            ktile(kt & 1, std::true_type{}, (kt + 1) * BK, std::integral_constant<int, 1>{});
-            __syncthreads();
-        }
-    } else {
-        for (int kt = 0; kt + 1 < nkt; ++kt) {
-            ktile(kt & 1, std::true_type{}, (kt + 1) * BK, std::integral_constant<int, 0>{});
-            __syncthreads();
-        }
-    }
-
-    // Last k-tile and epilogue.  Register v of lane l holds row (v&3) + 8*(v>>2) + 4*(l>>5),
-    // column l&31.  Row indices are formed in 32 bits (launch() refuses M >= 2^31): the functors'
-    // row * ld then is one 32 x 32 -> 64-bit multiply-add instead of a 64 x 32-bit product.
-    constexpr bool EARLY = epi_early<Epi>::value;
-    constexpr bool RED = epi_reduce<Epi>::value;
-    float red = 0.f;
-    const int M32 = (int)g.M, m032 = (int)m0;
-    auto rowof = [&](int a, int v) { return m032 + wm * 64 + a * 32 + (v & 3) + 8 * (v >> 2) + 4 * kk; };
-    auto colof = [&](int b) { return n0 + wn * 64 + b * 32 + li; };
-    auto finish = [&](auto full_tag) {
-        constexpr bool FULL = decltype(full_tag)::value;   // every row of the tile is inside M
-        f32x2 pv[EARLY ? 2 : 1][EARLY ? 2 : 1][16];
-        float ta[2] = {0.f, 0.f}, tb[2] = {0.f, 0.f};
-        const bool tk = kk < g.ktail;
-        if (g.ktail) {   // raw loads (clamped addresses); zeroed after the MFMAs
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int64_t r = m0 + wm * 64 + i * 32 + li;
-                const int c = n0 + wn * 64 + i * 32 + li;
-                ta[i] = g.A[(r < g.M ? r : g.M - 1) * g.lda + g.K + (tk ? kk : 0)];
-                tb[i] = g.Bt[(int64_t)(c < g.N ? c : g.N - 1) * g.ldb + g.K + (tk ? kk : 0)];
-            }
-        }
-        if (EARLY) {
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    int col = colof(b);
-                    col = col < g.N ? col : g.N - 1;
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) {
-                        int row = rowof(a, v);
-                        if (!FULL) row = row < M32 ? row : M32 - 1;
-                        pv[a][b][v] = epi.pre(row, col);
-                    }
-                }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (nb == 2) ktile((nkt - 1) & 1, std::false_type{}, 0, std::integral_constant<int, 2>{});
-        else if (nb == 1) ktile((nkt - 1) & 1, std::false_type{}, 0, std::integral_constant<int, 1>{});
-        if (g.ktail && nb > 0) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                if (!(tk && m0 + wm * 64 + i * 32 + li < g.M)) ta[i] = 0.f;
-                if (!(tk && n0 + wn * 64 + i * 32 + li < g.N)) tb[i] = 0.f;
-            }
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[0], tb[0], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[0], tb[1], acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[1], tb[0], acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[1], tb[1], acc[1][1], 0, 0, 0);
-        }
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const int col = colof(b);
-                if (col >= g.N) continue;
-                if (!EARLY) {
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) {
-                        int row = rowof(a, v);
-                        if (!FULL) row = row < M32 ? row : M32 - 1;
-                        pv[0][0][v] = epi.pre(row, col);
-                    }
-                }
-#pragma unroll
-                for (int v = 0; v < 16; ++v) {
-                    int row = rowof(a, v);
-                    // opaque copy: the store addresses are formed again here instead of 64 64-bit
-                    // load addresses staying live across the MFMAs (that cost the second wave per SIMD)
-                    if (EARLY) asm volatile("" : "+v"(row));
-                    if (FULL || row < M32) {
-                        if constexpr (RED) red += epi(row, col, acc[a][b][v], pv[EARLY ? a : 0][EARLY ? b : 0][v]);
-                        else epi(row, col, acc[a][b][v], pv[EARLY ? a : 0][EARLY ? b : 0][v]);
-                    }
-                }
-            }
     };
-    if (m032 + BM <= M32) finish(std::true_type{});
-    else finish(std::false_type{});
+    if (nb == 2) body(int_c<2>{});
+    else if (nb == 1) body(int_c<1>{});
+    else body(int_c<0>{});
+
+    constexpr bool RED = epi_reduce<Epi>::value;
+    const int M32 = (int)g.M, m032 = (int)m0;
+    const TilePos pos{m0, n0, wm, wn, li, kk, nb};
+    [[maybe_unused]] float red = finish(g, epi, acc, pos, [&]() __attribute__((always_inline)) {
+        if (nb == 2) ktile((nkt - 1) & 1, std::false_type{}, 0, int_c<2>{});
+        else if (nb == 1) ktile((nkt - 1) & 1, std::false_type{}, 0, int_c<1>{});
+    });
     if (THIN) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -367,16 +401,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(const Operands g, const
             }
         }
     }
-    if constexpr (RED) {
-        __syncthreads();                       // every wave is done with the staged tiles
-        lds[tid] = red;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (tid < o) lds[tid] += lds[tid + o];
-            __syncthreads();
-        }
-        if (tid == 0) epi.red_out[blockIdx.x] = lds[0];
-    }
+    if constexpr (RED) reduce_store(lds, red, epi, tid, (int)blockIdx.x);
 }
 
 inline bool vec_ok(const Operands& g) {
@@ -388,10 +413,10 @@ inline bool thin_applies(const Operands& g) {
     const char* te = measure_env("DRNMF_THIN");                  // measurement aid: 0 = a tile column of its own
     return vec_ok(g) && g.ktail == 0 && g.N > BN && g.N % BN == 1 && !(te && atoi(te) == 0);
 }
-// ... and launch() takes it: in the fp32 kernel only.  gemm_nt_x3_kernel<THIN> lost the rider column of some
-// rows (two rows = lanes 48..63 of a wave at a time) once two workgroups shared a CU -- M >= ~25000 frames,
-// K >= 224 (tests/test_gpu_lstm_edges.py, the 513-bin head at B = 250, T = 500); the split-operand mode gives
-// the odd column a tile column of its own instead.
+// ... and launch() takes it: in the fp32 kernel only.  gemm_nt_x3_kernel has no rider path: the one it had lost
+// the rider column of some rows (two rows = lanes 48..63 of a wave at a time) once two workgroups shared a CU
+// -- M >= ~25000 frames, K >= 224 (tests/test_gpu_lstm_edges.py, the 513-bin head at B = 250, T = 500) -- and
+// was taken out; the split-operand mode gives the odd column a tile column of its own instead.
 inline bool thin_taken(const Operands& g) { return tl_matrix_mode != DRNMF_MATRIX_BF16X3 && thin_applies(g); }
 // workgroups of launch(g, ...) = partials a REDUCE epilogue leaves at red_out[0 .. launch_tiles)
 inline int64_t launch_tiles(const Operands& g) {
@@ -401,20 +426,20 @@ inline int64_t launch_tiles(const Operands& g) {
 
 // gemm_nt_x3.h: the same product with split operands (matrix mode DRNMF_MATRIX_BF16X3)
 template <class Epi>
-inline hipError_t launch_x3(const Operands& g, bool thin, const Epi& epi, hipStream_t stream, bool* taken);
+inline hipError_t launch_x3(const Operands& g, const Epi& epi, hipStream_t stream, bool* taken);
 
 template <class Epi>
 inline hipError_t launch(const Operands& g_in, const Epi& epi, hipStream_t stream) {
     Operands g = g_in;
     const bool vec = vec_ok(g);
     const bool thin = thin_taken(g);
-    if (thin) { g.N -= 1; g.thin = 1; }
+    if (thin) g.N -= 1;      // (row N of Bt and column N of the output exist BEHIND the N tiled ones)
     const int64_t tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
     if (tiles <= 0 || tiles > 0x7fffffff || g.M > 0x7fffff00 || g.ktail < 0 || g.ktail > 2)
         return hipErrorInvalidValue;
     if (vec && tl_matrix_mode == DRNMF_MATRIX_BF16X3) {
         bool taken = false;
-        const hipError_t e = launch_x3(g, thin, epi, stream, &taken);
+        const hipError_t e = launch_x3(g, epi, stream, &taken);
         if (taken || e != hipSuccess) return e;
     }
     if (thin)

@@ -1,6 +1,7 @@
 // C[M x N] = epilogue(A . Bt^T) with SPLIT OPERANDS on the bf16 matrix pipe (matrix mode DRNMF_MATRIX_BF16X3,
-// include/drnmf.h).  Included at the end of gemm_nt.h: same Operands, same epilogue functors, same THIN /
-// ktail / NB / REDUCE conventions; gemm::launch() hands a product over to launch_x3() when the mode is on.
+// include/drnmf.h).  Included at the end of gemm_nt.h: same Operands, same epilogue functors and epilogue
+// (finish, reduce_store), same ktail / NB / REDUCE conventions, no rider column (thin_taken); gemm::launch()
+// hands a product over to launch_x3() when the mode is on.
 //
 // The fp32 matrix pipe of gfx950 runs at 1/16 of the bf16 rate.  An fp32 value is EXACTLY the sum of three
 // bf16 planes (hi = rne(x), mid = rne(x - hi), lo = x - hi - mid: 3 x 8 significand bits + the signs), so
@@ -42,7 +43,7 @@ using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
 constexpr int X3_ROW = 192;                       // bytes per tile row: 3 planes x 32 slots x 2
 constexpr int X3_OPER = BM * X3_ROW;              // bytes per operand tile
 
-// f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{}): indices that MUST be
+// f(int_c<0>{}) ... f(std::integral_constant<int, N - 1>{}): indices that MUST be
 // compile-time constants (register arrays indexed through a lambda parameter end up in scratch)
 template <int... I, class F>
 __device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
@@ -114,7 +115,7 @@ __device__ unsigned long long g_x3_timeline[64][8];
 #define X3_ADD(slot, a, b) do { } while (0)
 #endif
 
-template <class Epi, bool THIN>
+template <class Epi>
 __global__ void __launch_bounds__(256, 2) gemm_nt_x3_kernel(const Operands g, const Epi epi) {
     __shared__ __attribute__((aligned(16))) float lds[2 * X3_OPER / 4];
     const int tid = threadIdx.x;
@@ -147,19 +148,10 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_x3_kernel(const Operands g, co
     const u32x4* B3 = (const u32x4*)g.B3 + (int64_t)tn * g.kt3 * (X3_OPER / 16) + tid;
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.f;
+    zero_acc(acc);
 
-    f32x4 ra[4], rt = {0.f, 0.f, 0.f, 0.f};
+    f32x4 ra[4];
     u32x4 rb[6];
-    float tacc[4] = {0.f, 0.f, 0.f, 0.f};
-    bool mine[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) mine[i] = THIN && (tiles_n >= 4 ? i == tn : i % tiles_n == tn);
     auto raw4 = [&](const float* base, int64_t row, int64_t nrows, int64_t ld, int k) {
         const int64_t rr = row < nrows ? row : nrows - 1;
         const int kc = k < g.K ? k : 0;
@@ -170,7 +162,6 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_x3_kernel(const Operands g, co
     // load, and with one tile of lookahead the split waited for its operand whenever A did not sit in the
     // Infinity Cache (M = 16384: 185, M = 32768: 160 TFLOP/s-eq).  B3 (cache-resident) one tile ahead.
     auto gload_a = [&](int kt) __attribute__((always_inline)) {
-        if (THIN) rt = raw4(g.Bt, g.N, g.N + 1, g.ldb, kt * BK + sk);
 #pragma unroll
         for (int i = 0; i < 4; ++i) ra[i] = raw4(g.A, m0 + srow + 32 * i, g.M, g.lda, kt * BK + sk);
     };
@@ -185,16 +176,11 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_x3_kernel(const Operands g, co
         constexpr int m = decltype(m_tag)::value;
         constexpr bool FULL = decltype(full_tag)::value;
         constexpr int i = m & 3, j = m >> 2;
-        const bool kok = k0 + sk < g.K;
-        const bool ok = FULL || (kok && m0 + srow + 32 * i < g.M);
+        const bool ok = FULL || (k0 + sk < g.K && m0 + srow + 32 * i < g.M);
         const float x0 = ok ? ra[i][2 * j] : 0.f, x1 = ok ? ra[i][2 * j + 1] : 0.f;
         unsigned q0, q1, q2;
         split2(x0, x1, q0, q1, q2);
         pa[i][0][j] = q0; pa[i][1][j] = q1; pa[i][2][j] = q2;
-        if (THIN) {
-            const float t0 = (FULL || kok) ? rt[2 * j] : 0.f, t1 = (FULL || kok) ? rt[2 * j + 1] : 0.f;
-            tacc[i] += x0 * t0 + x1 * t1;
-        }
     };
     const int a_dst = srow * X3_ROW + ((((tid & 7) >> 1) ^ ((srow >> 2) & 3)) << 4) + (tid & 1) * 8;
     auto store_staged = [&]() __attribute__((always_inline)) {
@@ -238,12 +224,12 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_x3_kernel(const Operands g, co
         // (priority over the other workgroup's waves while this one feeds the matrix pipe: they are in their
         // store phase or would only interleave with it -- +2 .. 6 %)
         __builtin_amdgcn_s_setprio(3);
-        fetch(std::integral_constant<int, 0>{});
+        fetch(int_c<0>{});
         __builtin_amdgcn_sched_barrier(0);
         if (STAGE) gload_b(kt_next);
-        fetch(std::integral_constant<int, 1>{});
+        fetch(int_c<1>{});
         // step 0: the 6 loads of the next B3 tile and the 12 fragment reads of step 1 between its MFMAs
-        static_for<24>([&](auto qt) __attribute__((always_inline)) { product(std::integral_constant<int, 0>{}, qt); });
+        static_for<24>([&](auto qt) __attribute__((always_inline)) { product(int_c<0>{}, qt); });
         if (NB == 2) {
 #pragma unroll
             for (int i = 0; i < 12; ++i) {
@@ -257,7 +243,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_x3_kernel(const Operands g, co
         // step 1: one piece of A's split behind each of its first 8 MFMAs, fenced (sched_group_barrier left
         // the VALU operations in one lump behind the MFMAs); then the loads of the A tile after next
         static_for<24>([&](auto qt) __attribute__((always_inline)) {
-            product(std::integral_constant<int, 1>{}, qt);
+            product(int_c<1>{}, qt);
             if constexpr (STAGE && decltype(qt)::value < 8) {
                 split_piece(qt, full_tag, kt_next * BK);
                 if (NB == 2) __builtin_amdgcn_sched_barrier(0);
@@ -312,124 +298,35 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_x3_kernel(const Operands g, co
                 __syncthreads();
             }
         };
-        if (nb == 2) body(std::integral_constant<int, 2>{});
-        else if (nb == 1) body(std::integral_constant<int, 1>{});
-        else body(std::integral_constant<int, 0>{});
+        if (nb == 2) body(int_c<2>{});
+        else if (nb == 1) body(int_c<1>{});
+        else body(int_c<0>{});
     }
 
     X3_T(t_loop_end);
-    // Last k-tile and epilogue (gemm_nt.h).  Register v of lane l holds row (v&3) + 8*(v>>2) + 4*(l>>5),
-    // column l&31.
-    constexpr bool EARLY = epi_early<Epi>::value;
-    constexpr bool RED = epi_reduce<Epi>::value;
-    float red = 0.f;
-    const int M32 = (int)g.M, m032 = (int)m0;
-    auto rowof = [&](int a, int v) { return m032 + wm * 64 + a * 32 + (v & 3) + 8 * (v >> 2) + 4 * kk; };
-    auto colof = [&](int b) { return n0 + wn * 64 + b * 32 + li; };
-    auto finish = [&](auto full_tag) {
-        constexpr bool FULL = decltype(full_tag)::value;   // every row of the tile is inside M
-        f32x2 pv[EARLY ? 2 : 1][EARLY ? 2 : 1][16];
-        float ta[2] = {0.f, 0.f}, tb[2] = {0.f, 0.f};
-        const bool tk = kk < g.ktail;
-        if (g.ktail) {   // raw loads (clamped addresses); zeroed after the MFMAs
+    // Last k-tile and epilogue (gemm_nt.h).  The last tile runs under the epilogue's early loads -- 128 registers
+    // of `pre` values beside the accumulators: fragments are fetched per product, 16 registers at a time,
+    // instead of per step.
+    const TilePos pos{m0, n0, wm, wn, li, kk, nb};
+    [[maybe_unused]] const float red = finish(g, epi, acc, pos, [&]() __attribute__((always_inline)) {
+        if (nb == 0) return;
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int64_t r = m0 + wm * 64 + i * 32 + li;
-                const int c = n0 + wn * 64 + i * 32 + li;
-                ta[i] = g.A[(r < g.M ? r : g.M - 1) * g.lda + g.K + (tk ? kk : 0)];
-                tb[i] = g.Bt[(int64_t)(c < g.N ? c : g.N - 1) * g.ldb + g.K + (tk ? kk : 0)];
-            }
-        }
-        if (EARLY) {
+        for (int st = 0; st < 2; ++st)
 #pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    int col = colof(b);
-                    col = col < g.N ? col : g.N - 1;
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) {
-                        int row = rowof(a, v);
-                        if (!FULL) row = row < M32 ? row : M32 - 1;
-                        pv[a][b][v] = epi.pre(row, col);
-                    }
-                }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // (the last tile under the epilogue's early loads -- 128 registers of `pre` values beside the
-        // accumulators: fragments are fetched per product, 16 registers at a time, instead of per step)
-        if (nb > 0) {
-#pragma unroll
-            for (int st = 0; st < 2; ++st)
-#pragma unroll
-                for (int q = 0; q < 6; ++q) {
-                    const int fo = st ? foff1 : foff0;
-                    const u32x4 a0 = *(const u32x4*)(Ar + 64 * PA[q] + fo);
-                    const u32x4 a1 = *(const u32x4*)(Ar + 32 * X3_ROW + 64 * PA[q] + fo);
-                    const u32x4 b0 = *(const u32x4*)(Br + 64 * PB[q] + fo);
-                    acc[0][0] = mfma_bf16(a0, b0, acc[0][0]);
-                    acc[1][0] = mfma_bf16(a1, b0, acc[1][0]);
-                    if (nb == 2) {
-                        const u32x4 b1 = *(const u32x4*)(Br + 32 * X3_ROW + 64 * PB[q] + fo);
-                        acc[0][1] = mfma_bf16(a0, b1, acc[0][1]);
-                        acc[1][1] = mfma_bf16(a1, b1, acc[1][1]);
-                    }
-                }
-        }
-        if (g.ktail && nb > 0) {      // the odd contraction columns in exact fp32 (gemm_nt.h)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                if (!(tk && m0 + wm * 64 + i * 32 + li < g.M)) ta[i] = 0.f;
-                if (!(tk && n0 + wn * 64 + i * 32 + li < g.N)) tb[i] = 0.f;
-            }
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[0], tb[0], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[0], tb[1], acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[1], tb[0], acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[1], tb[1], acc[1][1], 0, 0, 0);
-        }
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const int col = colof(b);
-                if (col >= g.N) continue;
-                if (!EARLY) {
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) {
-                        int row = rowof(a, v);
-                        if (!FULL) row = row < M32 ? row : M32 - 1;
-                        pv[0][0][v] = epi.pre(row, col);
-                    }
-                }
-#pragma unroll
-                for (int v = 0; v < 16; ++v) {
-                    int row = rowof(a, v);
-                    if (EARLY) asm volatile("" : "+v"(row));
-                    if (FULL || row < M32) {
-                        if constexpr (RED) red += epi(row, col, acc[a][b][v], pv[EARLY ? a : 0][EARLY ? b : 0][v]);
-                        else epi(row, col, acc[a][b][v], pv[EARLY ? a : 0][EARLY ? b : 0][v]);
-                    }
+            for (int q = 0; q < 6; ++q) {
+                const int fo = st ? foff1 : foff0;
+                const u32x4 a0 = *(const u32x4*)(Ar + 64 * PA[q] + fo);
+                const u32x4 a1 = *(const u32x4*)(Ar + 32 * X3_ROW + 64 * PA[q] + fo);
+                const u32x4 b0 = *(const u32x4*)(Br + 64 * PB[q] + fo);
+                acc[0][0] = mfma_bf16(a0, b0, acc[0][0]);
+                acc[1][0] = mfma_bf16(a1, b0, acc[1][0]);
+                if (nb == 2) {
+                    const u32x4 b1 = *(const u32x4*)(Br + 32 * X3_ROW + 64 * PB[q] + fo);
+                    acc[0][1] = mfma_bf16(a0, b1, acc[0][1]);
+                    acc[1][1] = mfma_bf16(a1, b1, acc[1][1]);
                 }
             }
-    };
-    if (m032 + BM <= M32) finish(std::true_type{});
-    else finish(std::false_type{});
-    if (THIN) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (!mine[i]) continue;
-            float t = tacc[i];
-            t += __shfl_xor(t, 1, 64);          // the eight k-lanes (tid & 7) of staging row tid >> 3
-            t += __shfl_xor(t, 2, 64);
-            t += __shfl_xor(t, 4, 64);
-            const int row = m032 + srow + 32 * i;
-            if ((tid & 7) == 0 && row < M32) {
-                const f32x2 pv = epi.pre(row, g.N);
-                if constexpr (RED) red += epi(row, g.N, t, pv);
-                else epi(row, g.N, t, pv);
-            }
-        }
-    }
+    });
 #ifdef X3_TIMELINE
     if (tid == 0 && blockIdx.x < 64) {
         const unsigned long long t_end = __builtin_amdgcn_s_memtime();
@@ -440,21 +337,13 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_x3_kernel(const Operands g, co
         for (int k = 0; k < 8; ++k) g_x3_timeline[blockIdx.x][k] = tl_sum[k];
     }
 #endif
-    if constexpr (RED) {
-        __syncthreads();                       // every wave is done with the staged tiles
-        lds[tid] = red;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (tid < o) lds[tid] += lds[tid + o];
-            __syncthreads();
-        }
-        if (tid == 0) epi.red_out[lin] = lds[0];
-    }
+    // (the partial of TILE lin: the padding workgroups of the XCD-aware order returned above without one)
+    if constexpr (epi_reduce<Epi>::value) reduce_store(lds, red, epi, tid, lin);
 }
 
-// g: as gemm::launch() prepared it (thin column already taken off N).  *taken = false: not run (no scratch)
+// g: as gemm::launch() prepared it (never with a rider column: thin_taken).  *taken = false: not run (no scratch)
 template <class Epi>
-inline hipError_t launch_x3(const Operands& g_in, bool thin, const Epi& epi, hipStream_t stream, bool* taken) {
+inline hipError_t launch_x3(const Operands& g_in, const Epi& epi, hipStream_t stream, bool* taken) {
     Operands g = g_in;
     *taken = false;
     const int KT = (g.K + BK - 1) / BK;
@@ -472,10 +361,7 @@ inline hipError_t launch_x3(const Operands& g_in, bool thin, const Epi& epi, hip
         g.per_xcd = (int)((tiles + 7) / 8);
         tiles = (int64_t)g.per_xcd * 8;
     }
-    if (thin)
-        hipLaunchKernelGGL((gemm_nt_x3_kernel<Epi, true>), dim3((unsigned)tiles), dim3(256), 0, stream, g, epi);
-    else
-        hipLaunchKernelGGL((gemm_nt_x3_kernel<Epi, false>), dim3((unsigned)tiles), dim3(256), 0, stream, g, epi);
+    hipLaunchKernelGGL((gemm_nt_x3_kernel<Epi>), dim3((unsigned)tiles), dim3(256), 0, stream, g, epi);
     *taken = true;
     return hipGetLastError();
 }

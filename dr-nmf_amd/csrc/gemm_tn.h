@@ -15,7 +15,8 @@
 
 namespace gemm_tn {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
+using ::f32x16;
+using gemm::int_c;
 constexpr int BM = 128, BN = 128, BK = 32;
 
 struct Operands {
@@ -50,6 +51,62 @@ __device__ __forceinline__ f32x4 load4(const float* base, int64_t k, int64_t Ken
     return v;
 }
 
+// Workgroup -> (split, tile, k-tile range), XCD-aware: consecutive workgroup ids go round the 8 XCDs, and the
+// tiles of one split read the same rows of A and B, so XCD x takes the contiguous range
+// [x * per, (x+1) * per) of the split-major order: a split's operands then live in ONE L2
+// instead of being fetched into all eight (2.7 GB -> 0.8 GB per C2 weight-gradient GEMM).
+struct Work {
+    int split, m0, n0;
+    int64_t kt0, kt1;    // k-tiles [kt0, kt1) of BK rows; may be empty
+    bool idle;           // a workgroup of the grid's padding to 8 XCDs: nothing to do
+};
+__device__ __forceinline__ Work work_of(const Operands& g) {
+    Work wk = {};
+    const int tiles_n = (g.N + BN - 1) / BN;
+    const int tiles = ((g.M + BM - 1) / BM) * tiles_n;
+    const int splits = g.splits, total = tiles * splits;
+    const int per_xcd = (total + 7) / 8;
+    const int lin = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
+    wk.idle = (int)(blockIdx.x >> 3) >= per_xcd || lin >= total;
+    if (wk.idle) return wk;
+    const int tile = lin % tiles;
+    wk.split = lin / tiles;
+    wk.m0 = (tile / tiles_n) * BM;
+    wk.n0 = (tile % tiles_n) * BN;
+    const int64_t nkt = (g.Kdim + BK - 1) / BK;
+    const int64_t per = (nkt + splits - 1) / splits;
+    wk.kt0 = wk.split * per;
+    wk.kt1 = wk.kt0 + per;
+    if (wk.kt1 > nkt) wk.kt1 = nkt;
+    return wk;
+}
+
+// The split's partial tile handed to the functor.  Register v of lane l holds row (v&3) + 8*(v>>2) + 4*(l>>5),
+// column l&31 (gemm_nt.h); a 32 x 32 block's pre loads are issued together, ahead of its first use.
+template <class Epi>
+__device__ __forceinline__ void store_tile(const Operands& g, const Epi& epi, const f32x16 (&acc)[2][2], int split,
+                                           int m0, int n0, int wm, int wn, int li, int kk) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int n = n0 + wn * 64 + b * 32 + li;
+            if (n >= g.N) continue;
+            float pv[16];
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                int m = m0 + wm * 64 + a * 32 + (v & 3) + 8 * (v >> 2) + 4 * kk;
+                m = m < g.M ? m : g.M - 1;
+                pv[v] = epi.pre(split, m, n);
+            }
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int m = m0 + wm * 64 + a * 32 + (v & 3) + 8 * (v >> 2) + 4 * kk;
+                if (m < g.M) epi(split, m, n, acc[a][b][v], pv[v]);
+            }
+        }
+}
+
 // Epi: float pre(int split, int m, int n) const;  void operator()(int split, int m, int n, float acc, float pre) const
 template <class Epi, bool VEC>
 __global__ void __launch_bounds__(256) gemm_tn_kernel(const Operands g, const Epi epi) {
@@ -58,33 +115,15 @@ __global__ void __launch_bounds__(256) gemm_tn_kernel(const Operands g, const Ep
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 63;
     const int li = l & 31, kk = l >> 5;
     const int wm = w >> 1, wn = w & 1;
-    // Workgroup -> (split, tile), XCD-aware: consecutive workgroup ids go round the 8 XCDs, and the
-    // tiles of one split read the same rows of A and B, so XCD x takes the contiguous range
-    // [x * per, (x+1) * per) of the split-major order: a split's operands then live in ONE L2
-    // instead of being fetched into all eight (2.7 GB -> 0.8 GB per C2 weight-gradient GEMM).
-    const int tiles_n = (g.N + BN - 1) / BN;
-    const int tiles = ((g.M + BM - 1) / BM) * tiles_n;
-    const int splits = g.splits, total = tiles * splits;
-    const int per_xcd = (total + 7) / 8;
-    const int lin = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
-    if ((int)(blockIdx.x >> 3) >= per_xcd || lin >= total) return;
-    const int split = lin / tiles, tile = lin % tiles;
-    const int m0 = (tile / tiles_n) * BM, n0 = (tile % tiles_n) * BN;
-    const int64_t nkt = (g.Kdim + BK - 1) / BK;
-    const int64_t per = (nkt + splits - 1) / splits;
-    const int64_t kt0 = split * per;
-    int64_t kt1 = kt0 + per;
-    if (kt1 > nkt) kt1 = nkt;
+    const Work wk = work_of(g);
+    if (wk.idle) return;
+    const int m0 = wk.m0, n0 = wk.n0;
+    const int64_t kt0 = wk.kt0, kt1 = wk.kt1;
 
     const int kr = tid >> 5, c4 = (tid & 31) * 4;   // staging: row kr + 8*i, 4 columns at c4
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.f;
+    gemm::zero_acc(acc);
 
     // (vector path: the out-of-range zeroing is applied when the staged tile is written to LDS,
     // not right behind the load, so that the loads stay in flight under the MFMAs -- gemm_nt.h)
@@ -183,44 +222,19 @@ __global__ void __launch_bounds__(256) gemm_tn_kernel(const Operands g, const Ep
         gload(kt0);
         swrite(0, kt0);
         __syncthreads();
-        if (na == 2) {
+        auto body = [&](auto na_tag) {
             for (int64_t kt = kt0; kt + 1 < kt1; ++kt) {
-                ktile((int)((kt - kt0) & 1), std::true_type{}, kt + 1, std::integral_constant<int, 2>{});
+                ktile((int)((kt - kt0) & 1), std::true_type{}, kt + 1, na_tag);
                 __syncthreads();
             }
-            ktile((int)((kt1 - 1 - kt0) & 1), std::false_type{}, 0, std::integral_constant<int, 2>{});
-        } else if (na == 1) {
-            for (int64_t kt = kt0; kt + 1 < kt1; ++kt) {
-                ktile((int)((kt - kt0) & 1), std::true_type{}, kt + 1, std::integral_constant<int, 1>{});
-                __syncthreads();
-            }
-            ktile((int)((kt1 - 1 - kt0) & 1), std::false_type{}, 0, std::integral_constant<int, 1>{});
-        } else {
-            for (int64_t kt = kt0; kt + 1 < kt1; ++kt) {
-                ktile((int)((kt - kt0) & 1), std::true_type{}, kt + 1, std::integral_constant<int, 0>{});
-                __syncthreads();
-            }
-        }
+            if constexpr (decltype(na_tag)::value > 0)      // (nothing but padding: no last tile either)
+                ktile((int)((kt1 - 1 - kt0) & 1), std::false_type{}, 0, na_tag);
+        };
+        if (na == 2) body(int_c<2>{});
+        else if (na == 1) body(int_c<1>{});
+        else body(int_c<0>{});
     }
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int n = n0 + wn * 64 + b * 32 + li;
-            if (n >= g.N) continue;
-            float pv[16];
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                int m = m0 + wm * 64 + a * 32 + (v & 3) + 8 * (v >> 2) + 4 * kk;
-                m = m < g.M ? m : g.M - 1;
-                pv[v] = epi.pre(split, m, n);
-            }
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int m = m0 + wm * 64 + a * 32 + (v & 3) + 8 * (v >> 2) + 4 * kk;
-                if (m < g.M) epi(split, m, n, acc[a][b][v], pv[v]);
-            }
-        }
+    store_tile(g, epi, acc, wk.split, m0, n0, wm, wn, li, kk);
 }
 
 // Split-K count for an M x N output contracted over Kdim: tiles x splits workgroups run in rounds of

@@ -1,6 +1,7 @@
 // C[M x N] (+)= A^T B with SPLIT OPERANDS on the bf16 matrix pipe (matrix mode DRNMF_MATRIX_BF16X3): the
 // time-batched weight gradients and the dictionary-training statistics.  Included at the end of gemm_tn.h: same
-// Operands, split / XCD map and epilogue functors; gemm_tn::launch() hands a product over when the mode is on.
+// Operands, split / XCD map (work_of), output loop (store_tile) and epilogue functors; gemm_tn::launch() hands a
+// product over when the mode is on.
 // The arithmetic is gemm_nt_x3.h's (three bf16 planes per fp32 value, six v_mfma_f32_32x32x16_bf16 per product,
 // fp32 accumulate).  What differs is the staging: both operands are activations (no side is constant, nothing
 // to pre-split) and both are contraction-major in memory ([frame][column]), so
@@ -24,6 +25,7 @@ using gemm::u32x2;
 using gemm::split2;
 using gemm::mfma_bf16;
 using gemm::static_for;
+using gemm::int_c;
 constexpr int X3_PLANE = BK * BM * 2;      // bytes: 32 frames x 128 columns x bf16
 constexpr int X3_OPER = 3 * X3_PLANE;
 typedef __attribute__((__vector_size__(4 * sizeof(short)))) short s16x4;
@@ -36,30 +38,15 @@ __global__ void __launch_bounds__(256, 2) gemm_tn_x3_kernel(const Operands g, co
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 63;
     const int li = l & 31, kk = l >> 5;
     const int wm = w >> 1, wn = w & 1;
-    // (split, tile) of this workgroup: gemm_tn.h
-    const int tiles_n = (g.N + BN - 1) / BN;
-    const int tiles = ((g.M + BM - 1) / BM) * tiles_n;
-    const int splits = g.splits, total = tiles * splits;
-    const int per_xcd = (total + 7) / 8;
-    const int lin = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
-    if ((int)(blockIdx.x >> 3) >= per_xcd || lin >= total) return;
-    const int split = lin / tiles, tile = lin % tiles;
-    const int m0 = (tile / tiles_n) * BM, n0 = (tile % tiles_n) * BN;
-    const int64_t nkt = (g.Kdim + BK - 1) / BK;
-    const int64_t per = (nkt + splits - 1) / splits;
-    const int64_t kt0 = split * per;
-    int64_t kt1 = kt0 + per;
-    if (kt1 > nkt) kt1 = nkt;
+    const Work wk = work_of(g);
+    if (wk.idle) return;
+    const int m0 = wk.m0, n0 = wk.n0;
+    const int64_t kt0 = wk.kt0, kt1 = wk.kt1;
 
     const int kr = tid >> 5, c4 = (tid & 31) * 4;   // staging: frame kr + 8 i, 4 columns at c4
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.f;
+    gemm::zero_acc(acc);
 
     f32x4 ra[4], rb[4];
     auto raw4 = [&](const float* base, int64_t k, int64_t ld, int c, int C) {
@@ -141,11 +128,11 @@ __global__ void __launch_bounds__(256, 2) gemm_tn_x3_kernel(const Operands g, co
                 acc[t >> 1][t & 1] = mfma_bf16(fa[st][t >> 1][PA[q]], fb[st][t & 1][PB[q]], acc[t >> 1][t & 1]);
         };
         __builtin_amdgcn_s_setprio(3);        // (gemm_nt_x3.h)
-        fetch(std::integral_constant<int, 0>{});
+        fetch(int_c<0>{});
         __builtin_amdgcn_sched_barrier(0);
         if (STAGE) gload(kt_next);
-        fetch(std::integral_constant<int, 1>{});
-        static_for<24>([&](auto qt) __attribute__((always_inline)) { product(std::integral_constant<int, 0>{}, qt); });
+        fetch(int_c<1>{});
+        static_for<24>([&](auto qt) __attribute__((always_inline)) { product(int_c<0>{}, qt); });
         if (NA == 2) {       // step 0: the 8 global loads of the next tile and the 24 reads of step 1 between its MFMAs
 #pragma unroll
             for (int i = 0; i < 24; ++i) {
@@ -157,7 +144,7 @@ __global__ void __launch_bounds__(256, 2) gemm_tn_x3_kernel(const Operands g, co
         __builtin_amdgcn_sched_barrier(0);
         // step 1: one piece of the split behind each of its first 16 MFMAs, fenced (gemm_nt_x3.h)
         static_for<24>([&](auto qt) __attribute__((always_inline)) {
-            product(std::integral_constant<int, 1>{}, qt);
+            product(int_c<1>{}, qt);
             if constexpr (STAGE && decltype(qt)::value < 16) {
                 split_piece(qt, kt_next);
                 if (NA == 2) __builtin_amdgcn_sched_barrier(0);
@@ -181,29 +168,11 @@ __global__ void __launch_bounds__(256, 2) gemm_tn_x3_kernel(const Operands g, co
             }
             ktile(std::false_type{}, 0, na_tag);
         };
-        if (na == 2) body(std::integral_constant<int, 2>{});
-        else if (na == 1) body(std::integral_constant<int, 1>{});
-        else body(std::integral_constant<int, 0>{});
+        if (na == 2) body(int_c<2>{});
+        else if (na == 1) body(int_c<1>{});
+        else body(int_c<0>{});
     }
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int n = n0 + wn * 64 + b * 32 + li;
-            if (n >= g.N) continue;
-            float pv[16];
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                int m = m0 + wm * 64 + a * 32 + (v & 3) + 8 * (v >> 2) + 4 * kk;
-                m = m < g.M ? m : g.M - 1;
-                pv[v] = epi.pre(split, m, n);
-            }
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int m = m0 + wm * 64 + a * 32 + (v & 3) + 8 * (v >> 2) + 4 * kk;
-                if (m < g.M) epi(split, m, n, acc[a][b][v], pv[v]);
-            }
-        }
+    store_tile(g, epi, acc, wk.split, m0, n0, wm, wn, li, kk);
 }
 
 template <class Epi>

@@ -162,9 +162,10 @@ def test_model_predict_in_x3_mode(dev, x3):
 
 def test_fuzz_frame_parallel_products_in_both_modes(dev):
     """Seeded random shapes on both sides of every tile boundary of gemm_nt_x3.h / gemm_tn_x3.h (128-row / 128-column
-    tiles, 32-slot k-tiles, the 2^k + 1 rider column, 1-2 odd contraction columns, operands that are not 16-byte
-    aligned and fall back to the fp32 kernels): frame-parallel ISTA (two NT products per iteration) and dictionary
-    training (NT + TN products, grid-wide objective sums) in the split-operand mode against the exact-fp32 mode."""
+    tiles, 32-slot k-tiles, the 2^k + 1 wide outputs (a rider column in the fp32 kernel only), 1-2 odd contraction
+    columns, operands that are not 16-byte aligned and fall back to the fp32 kernels): frame-parallel ISTA (two NT
+    products per iteration) and dictionary training (NT + TN products, grid-wide objective sums) in the
+    split-operand mode against the exact-fp32 mode."""
     from drnmf_amd import ops
     rng = np.random.default_rng(606)
     g = torch.Generator(device=dev)
@@ -211,3 +212,66 @@ def test_fuzz_frame_parallel_products_in_both_modes(dev):
                 assert d <= tol, (dict(n=n, F=F, r=r, beta=beta, it=it), d)
     finally:
         ops.set_matrix_mode(prev, dev)
+
+
+def _snmf_step64(V, W0, H0, sparsity, beta, flr=1e-9):
+    """[div, cost] after ONE iteration of sparse_nmf_gpu.m from the inputs, in torch fp64 (the order of
+    oracle.sparse_nmf_train: normalise, H update, W update of every column, renormalise, objective).
+    Row layout: V [n,F], W [F,r], H [n,r]; beta 1 or 2; V > 0."""
+    V, W, H = V.double(), W0.double(), H0.double()
+    wn = (W * W).sum(0).sqrt()
+    W, H = W / wn, H * wn
+    lam = (H @ W.t()).clamp(min=flr)
+    if beta == 1.0:
+        H = H * ((V / lam) @ W) / (W.sum(0) + sparsity).clamp(min=flr)
+    else:
+        H = H * (V @ W) / (lam @ W + sparsity).clamp(min=flr)
+    lam = (H @ W.t()).clamp(min=flr)
+    if beta == 1.0:
+        num = (V / lam).t() @ H
+        den = H.sum(0, keepdim=True).expand_as(num)
+    else:
+        num, den = V.t() @ H, lam.t() @ H
+    dpw = (den + (num * W).sum(0, keepdim=True) * W).clamp(min=flr)
+    W = W * (num + (den * W).sum(0, keepdim=True) * W) / dpw
+    W = W / (W * W).sum(0).sqrt()
+    lam = (H @ W.t()).clamp(min=flr)
+    div = (V * (V / lam).log() - V + lam).sum() if beta == 1.0 else ((V - lam) ** 2).sum()
+    return div.item(), (div + sparsity * H.sum()).item()
+
+
+@pytest.mark.parametrize("beta", [1.0, 2.0])
+def test_objective_sum_under_the_xcd_tile_order(dev, beta):
+    """The grid-wide objective sum (a REDUCE epilogue: one partial per workgroup) where gemm_nt_x3_kernel runs its
+    XCD-aware tile order, which the fuzz above (at most 18 tiles) never reaches: n = 4200 frames x F = 129 bins are
+    33 x 2 = 66 tiles of the lambda product in the split-operand mode (no rider column there), a grid of 72 whose
+    partials are stored at the TILE index and whose 6 padding workgroups store none.  W, H and the objective log of
+    two steps between the modes at the fuzz's 5e-5; the objective of step 0 in either mode against fp64 on the same
+    inputs at the 2e-4 of test_gpu_parity.test_snmf_training_matches_oracle."""
+    from drnmf_amd import ops
+    n, F, r, sparsity = 4200, 129, 20, 0.5
+    g = torch.Generator(device=dev)
+    g.manual_seed(3000)
+    V = torch.rand((n, F), generator=g, device=dev) ** 2 + 1e-3
+    W0 = torch.rand((F, r), generator=g, device=dev)
+    H0 = torch.rand((n, r), generator=g, device=dev)
+    ref = _snmf_step64(V, W0, H0, sparsity, beta)
+    res = {}
+    prev = ops.get_matrix_mode(dev)
+    try:
+        for mode in ("f32", "bf16x3"):
+            ops.set_matrix_mode(mode, dev)
+            tr = ops.SnmfTrainer(V, W0.clone(), H0.clone(), beta=beta)
+            log = torch.zeros((2, 2), dtype=torch.float32, device=dev)
+            for i in range(2):
+                tr.step(sparsity, None, True, obj=log[i])
+            torch.cuda.synchronize()
+            res[mode] = (tr.W.clone(), tr.H.clone(), log.clone())
+    finally:
+        ops.set_matrix_mode(prev, dev)
+    for mode in ("f32", "bf16x3"):
+        got = res[mode][2][0].cpu().numpy()
+        np.testing.assert_allclose(got, np.array(ref), rtol=2e-4, err_msg=mode)
+    for name, a, b in zip("WHo", res["f32"], res["bf16x3"]):
+        d = (a - b).abs().max().item() / max(a.abs().max().item(), 1e-30)
+        assert d <= 5e-5, (name, d)
