@@ -199,6 +199,13 @@ DATASET_SIGNATURES = {
 }
 TRANSFORMS = {"mag": 0, "logmag": 1}     # DRNMF_TRANSFORM_*
 
+# name -> (restype, argtypes); mirrors include/drnmf_target.h one to one (a table of its own, like the others)
+TARGET_SIGNATURES = {
+    "drnmf_stft_pair_chunks_target": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32,
+                                             _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+TARGETS = {"mag": 0, "psa": 1, "tpsa": 2}     # DRNMF_TARGET_*
+
 # name -> (restype, argtypes); mirrors include/drnmf_stream.h one to one (a table of its own, like the five above)
 STREAM_SIGNATURES = {
     "drnmf_stream_counts": (_i32, [_i64, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
@@ -255,7 +262,7 @@ def lib():
                                   list(SCORE_SIGNATURES.items()) + list(ENHANCE_SIGNATURES.items()) +
                                   list(SDR_SIGNATURES.items()) + list(DATASET_SIGNATURES.items()) +
                                   list(STREAM_SIGNATURES.items()) + list(SNMF_SIGNATURES.items()) +
-                                  list(SNMF_F16_SIGNATURES.items())):
+                                  list(SNMF_F16_SIGNATURES.items()) + list(TARGET_SIGNATURES.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

@@ -40,7 +40,9 @@ NO_SCRATCH = {"lstm.hip": "lstm_step_kernel",
               # the tile kernel keeps H, num and den of its tiles in registers; the pack / zero kernels ride along
               "snmf_mask.hip": "snmf_mask_",
               # its fp16-operand sibling: H (fp32 master), num and den of its tiles in registers as well
-              "snmf_f16.hip": "snmf_f16_"}
+              "snmf_f16.hip": "snmf_f16_",
+              # the target kernels keep the noisy member's bins of a frame in registers (up to 27 per lane)
+              "stft.hip": "stft_pair_target_"}
 
 
 def _check_no_scratch(src, remarks):
@@ -68,7 +70,8 @@ def _sources():
 def _deps():
     return _sources() + glob.glob(os.path.join(CSRC, "*.h")) + \
         [os.path.join(os.path.dirname(HERE), "include", n) for n in ("drnmf.h", "drnmf_lstm.h", "drnmf_score.h", "drnmf_enhance.h", "drnmf_sdr.h",
-                                                                     "drnmf_dataset.h", "drnmf_stream.h", "drnmf_snmf.h", "drnmf_snmf_f16.h")] + \
+                                                                     "drnmf_dataset.h", "drnmf_stream.h", "drnmf_snmf.h", "drnmf_snmf_f16.h",
+                                                                     "drnmf_target.h")] + \
         [os.path.abspath(__file__)]
 
 

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "../../include/drnmf_enhance.h"
 #include "../../include/drnmf_dataset.h"
+#include "../../include/drnmf_target.h"
 #include "../../include/drnmf_stream.h"
 
 namespace {
@@ -93,16 +94,54 @@ __device__ __forceinline__ float mag_transform(float m, int transform) {
     return transform ? logf(1.0f + m) : m;
 }
 
+// The training target of include/drnmf_target.h from one bin of the clean (s) and of the noisy (x) member:
+// p = (re_s re_x + im_s im_x) / m_x = |S| cos(theta_S - theta_X), 0 where m_x == 0; 'tpsa' clips it to [0, m_x].
+// Two products, one sum and one true division, each rounded once: no contraction, so the value does not depend
+// on which kernel the expression is inlined into.
+__device__ __forceinline__ float psa_target(float re_s, float im_s, float re_x, float im_x, float m_x, int target) {
+#pragma clang fp contract(off)
+    float p = 0.f;
+    if (m_x > 0.f) {
+        const float a = re_s * re_x, b = im_s * im_x;
+        p = (a + b) / m_x;
+    }
+    return target == DRNMF_TARGET_TPSA ? fminf(fmaxf(p, 0.f), m_x) : p;
+}
+
+// What a target kernel (stft_pair_target_*) carries through the two runs of its frame body.  A lane emits the
+// SAME bins of both members (slot s of a lane is one bin), so the noisy member's re, im and magnitude wait in
+// that lane's registers while the clean member is transformed: nothing is exchanged between lanes, nothing goes
+// through LDS or global memory.  side 0 (noisy): the body's magnitude is stored as it is and the bin is kept;
+// side 1 (clean): the target is stored in its place.  NoTarget: every other kernel, whose bodies are unchanged.
+template <int SLOTS>
+struct PairTarget {
+    static constexpr bool on = true;
+    static constexpr int slots = SLOTS;
+    int side, target;
+    float re[SLOTS], im[SLOTS], m[SLOTS];
+    __device__ __forceinline__ float bin(int s, float re_k, float im_k, float m_k, float out_k) {
+        if (side == 0) {
+            re[s] = re_k, im[s] = im_k, m[s] = m_k;
+            return out_k;
+        }
+        return psa_target(re_k, im_k, re[s], im[s], m[s], target);
+    }
+};
+struct NoTarget {
+    static constexpr bool on = false;
+};
+
 // one frame of one signal by the whole workgroup: row0 = element offset of the signal's first sample in pcm,
 // nsampl its length, o = element offset of the frame's output row (shared by the batched, the ragged and the
 // paired kernel).  Each of mag / re / im is written only if its pointer is not NULL.  stage_tw = false: tw
 // already holds this size's twiddles (the second member of a pair); the caller has put a barrier behind the
-// previous frame's reads of buf.
+// previous frame's reads of buf.  tg: see PairTarget (thread tid emits bin tid + 256 s in slot s).
+template <class TG = NoTarget>
 __device__ __forceinline__ void stft_frame(const void* __restrict__ pcm, int is_int16, size_t row0,
                                            int64_t nsampl, int N, int logN, int hop, int frame, size_t o,
                                            float* __restrict__ mag, float* __restrict__ re,
                                            float* __restrict__ im, float2* buf, float2* tw, int tid,
-                                           int transform = 0, bool stage_tw = true) {
+                                           int transform = 0, bool stage_tw = true, TG* tg = nullptr) {
     const int64_t base = (int64_t)frame * hop - N;   // first sample of the frame (N leading zeros)
 
     const float* __restrict__ win = g_window[logN - TAB_LOG_MIN];
@@ -121,6 +160,21 @@ __device__ __forceinline__ void stft_frame(const void* __restrict__ pcm, int is_
     }
     __syncthreads();
     fft_lds(buf, tw, N, logN, tid);
+    if constexpr (TG::on) {
+        // the loop below with its trips counted at compile time, so that the slots are registers
+#pragma unroll
+        for (int s = 0; s < TG::slots; ++s) {
+            const int k = tid + 256 * s;
+            if (k <= N / 2) {
+                const float2 z = buf[k];
+                const float m = sqrtf(z.x * z.x + z.y * z.y);
+                if (mag) mag[o + k] = tg->bin(s, z.x, -z.y, m, mag_transform(m, transform));
+                if (re) re[o + k] = z.x;
+                if (im) im[o + k] = -z.y;
+            }
+        }
+        return;
+    }
     for (int k = tid; k <= N / 2; k += 256) {
         const float2 z = buf[k];
         if (mag) mag[o + k] = mag_transform(sqrtf(z.x * z.x + z.y * z.y), transform);
@@ -230,13 +284,14 @@ __device__ __forceinline__ void stockham_passes(float2 (&v)[R], float2* cur, con
 
 // one frame of one signal by ONE WAVE (lane j): row0 = element offset of the signal's first sample in pcm,
 // nsampl its length, o = element offset of the frame's output row (shared by the batched, the ragged and the
-// paired kernel).  Each of mag / re / im is written only if its pointer is not NULL.
-template <int R, int P>
+// paired kernel).  Each of mag / re / im is written only if its pointer is not NULL.  tg: see PairTarget (lane j
+// emits bin j + 64 s in slot s < M/64, and lane 0 bin M in slot M/64).
+template <int R, int P, class TG = NoTarget>
 __device__ __forceinline__ void stft_real_frame(const void* __restrict__ pcm, int is_int16, size_t row0,
                                                 int64_t nsampl, int logN, int hop, int frame, size_t o,
                                                 float* __restrict__ mag, float* __restrict__ re,
                                                 float* __restrict__ im, const float2* tw, float2* cur, int j,
-                                                int transform = 0) {
+                                                int transform = 0, TG* tg = nullptr) {
     constexpr int M = RealFft<R, P>::M, N = 2 * M;
     auto pad = [](int i) { return RealFft<R, P>::pad(i); };
     const float* __restrict__ win = g_window[logN - TAB_LOG_MIN];
@@ -287,7 +342,7 @@ __device__ __forceinline__ void stft_real_frame(const void* __restrict__ pcm, in
     }
     stockham_passes<R, P>(v, cur, tw, j);
     // split + output: k = j + 64 i, i < M/64, and k = M
-    auto emit = [&](int k) {
+    auto emit = [&](int k, int slot) {
         const float2 zk = cur[pad(k & (M - 1))];
         const float2 zc = cur[pad((M - k) & (M - 1))];     // Z[M-k] (Z[M] = Z[0])
         const float2 a = make_float2(0.5f * (zk.x + zc.x), 0.5f * (zk.y - zc.y));   // (Z_k + conj Z_{M-k}) / 2
@@ -295,13 +350,18 @@ __device__ __forceinline__ void stft_real_frame(const void* __restrict__ pcm, in
         const float2 w = k == M ? make_float2(-1.f, 0.f) : tw[k];
         const float2 wb = cmul(b, w);                       // X = a - i w b
         const float xr = a.x + wb.y, xi = a.y - wb.x;
-        if (mag) mag[o + k] = mag_transform(sqrtf(xr * xr + xi * xi), transform);
+        if constexpr (TG::on) {
+            const float m = sqrtf(xr * xr + xi * xi);
+            if (mag) mag[o + k] = tg->bin(slot, xr, -xi, m, mag_transform(m, transform));
+        } else {
+            if (mag) mag[o + k] = mag_transform(sqrtf(xr * xr + xi * xi), transform);
+        }
         if (re) re[o + k] = xr;
         if (im) im[o + k] = -xi;      // librosa 0.5.1 conjugates the spectrum (util.py:195 via stft)
     };
 #pragma unroll
-    for (int i = 0; i < M / 64; ++i) emit(j + 64 * i);
-    if (j == 0) emit(M);
+    for (int i = 0; i < M / 64; ++i) emit(j + 64 * i, i);
+    if (j == 0) emit(M, M / 64);
 }
 
 
@@ -747,11 +807,12 @@ __device__ __forceinline__ int pair_state(const PairRow& r, int64_t t, int T) {
     return PACKED ? 2 : 1;
 }
 
-template <int R, int P, bool PACKED>
-__global__ void __launch_bounds__(256) stft_pair_real_kernel(const PairArgs a) {
+// The frames of a workgroup of the fast path: tw [N/2] and bufs [4][MP] are the kernel's LDS, tg its PairTarget
+// (stft_pair_target_real_kernel) or a NoTarget (stft_pair_real_kernel).
+template <int R, int P, bool PACKED, class TG>
+__device__ __forceinline__ void pair_real_frames(const PairArgs& a, float2* tw, float2 (*bufs)[RealFft<R, P>::MP],
+                                                 TG* tg) {
     constexpr int N = RealFft<R, P>::N, F = N / 2 + 1;
-    __shared__ float2 tw[N / 2];
-    __shared__ float2 bufs[4][RealFft<R, P>::MP];
     const int tid = threadIdx.x, wv = tid >> 6, j = tid & 63;
     const int64_t t0 = ((int64_t)blockIdx.x + a.tile_base) * 4, t = t0 + wv;
     const int k = (int)blockIdx.y + a.row_base;
@@ -781,8 +842,9 @@ __global__ void __launch_bounds__(256) stft_pair_real_kernel(const PairArgs a) {
     for (int side = 0; side < 2; ++side) {
         const void* pcm = side ? a.pcm_y : a.pcm_x;
         const int64_t stride = side ? a.stride_y : a.stride_x, len = side ? row.len_y : row.len_x;
+        if constexpr (TG::on) tg->side = side;
         stft_real_frame<R, P>(pcm, a.is_int16, (size_t)row.sig * stride, len, a.logN, a.hop, frame, o,
-                              side ? a.y : a.x, a.re, a.im, tw, bufs[wv], j, a.transform);
+                              side ? a.y : a.x, a.re, a.im, tw, bufs[wv], j, a.transform, tg);
         // the wave's LDS slice is reused: its reads of this spectrum are issued before the next member's writes,
         // and LDS serves one wave's requests in order (as between the passes of stockham_passes)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -791,10 +853,28 @@ __global__ void __launch_bounds__(256) stft_pair_real_kernel(const PairArgs a) {
     if (!PACKED && j == 0) a.w[row.orow + t] = 1.f;
 }
 
+template <int R, int P, bool PACKED>
+__global__ void __launch_bounds__(256) stft_pair_real_kernel(const PairArgs a) {
+    __shared__ float2 tw[RealFft<R, P>::N / 2];
+    __shared__ float2 bufs[4][RealFft<R, P>::MP];
+    NoTarget none;
+    pair_real_frames<R, P, PACKED>(a, tw, bufs, &none);
+}
+
+// the same with y = the 'psa' / 'tpsa' target (drnmf_stft_pair_chunks_target; x and w as above, bit for bit)
+template <int R, int P>
+__global__ void __launch_bounds__(256) stft_pair_target_real_kernel(const PairArgs a, int target) {
+    __shared__ float2 tw[RealFft<R, P>::N / 2];
+    __shared__ float2 bufs[4][RealFft<R, P>::MP];
+    PairTarget<RealFft<R, P>::M / 64 + 1> tg;
+    tg.target = target;
+    pair_real_frames<R, P, false>(a, tw, bufs, &tg);
+}
+
 // other sizes: one workgroup per (row, frame), the noisy frame and then the clean one through the same buffer
-template <bool PACKED>
-__global__ void __launch_bounds__(256) stft_pair_kernel(const PairArgs a, int N) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
+// (smem: the kernel's dynamic LDS, N points and N/2 twiddles)
+template <bool PACKED, class TG>
+__device__ __forceinline__ void pair_frame(const PairArgs& a, int N, float* smem, TG* tg) {
     float2* buf = (float2*)smem;
     float2* tw = buf + N;
     const int tid = threadIdx.x, F = N / 2 + 1;
@@ -819,11 +899,27 @@ __global__ void __launch_bounds__(256) stft_pair_kernel(const PairArgs a, int N)
     for (int side = 0; side < 2; ++side) {
         const void* pcm = side ? a.pcm_y : a.pcm_x;
         const int64_t stride = side ? a.stride_y : a.stride_x, len = side ? row.len_y : row.len_x;
+        if constexpr (TG::on) tg->side = side;
         stft_frame(pcm, a.is_int16, (size_t)row.sig * stride, len, N, a.logN, a.hop, frame, o, side ? a.y : a.x,
-                   a.re, a.im, buf, tw, tid, a.transform, false);
+                   a.re, a.im, buf, tw, tid, a.transform, false, tg);
         __syncthreads();                      // this spectrum has been read out of buf
     }
     if (!PACKED && tid == 0) a.w[row.orow + t] = 1.f;
+}
+
+template <bool PACKED>
+__global__ void __launch_bounds__(256) stft_pair_kernel(const PairArgs a, int N) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    NoTarget none;
+    pair_frame<PACKED>(a, N, smem, &none);
+}
+
+// the target sibling: thread tid holds bins tid + 256 s, s < 9 (F <= 2049)
+__global__ void __launch_bounds__(256) stft_pair_target_kernel(const PairArgs a, int N, int target) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    PairTarget<TAB_N_MAX / 2 / 256 + 1> tg;
+    tg.target = target;
+    pair_frame<false>(a, N, smem, &tg);
 }
 
 }  // namespace
@@ -1052,7 +1148,8 @@ extern "C" int32_t drnmf_istft_ragged(drnmf_handle_t h, int32_t n_sig, int32_t b
 // Rows (sequences, or signals in the packed mode) go on grid.y in slices of at most 65535 and frame tiles on
 // grid.x in slices of at most 2^23, so neither count is bounded by a grid dimension.
 template <bool PACKED>
-static void launch_stft_pair(PairArgs a, int N, int64_t n_rows, hipStream_t stream) {
+static void launch_stft_pair(PairArgs a, int N, int64_t n_rows, hipStream_t stream,
+                             int target = DRNMF_TARGET_MAG) {
     const bool fast = stft_fast(N);
     const int64_t tiles = fast ? ((int64_t)a.T + 3) / 4 : (int64_t)a.T;
     const int64_t max_y = 65535, max_x = (int64_t)1 << 23;
@@ -1063,7 +1160,14 @@ static void launch_stft_pair(PairArgs a, int N, int64_t n_rows, hipStream_t stre
             a.tile_base = (int)x0;
             const dim3 grid((unsigned)(tiles - x0 < max_x ? tiles - x0 : max_x),
                             (unsigned)(n_rows - r0 < max_y ? n_rows - r0 : max_y));
-            if (N == 1024)
+            if (!PACKED && target != DRNMF_TARGET_MAG) {
+                if (N == 1024)
+                    hipLaunchKernelGGL((stft_pair_target_real_kernel<8, 3>), grid, dim3(256), 0, stream, a, target);
+                else if (N == 512)
+                    hipLaunchKernelGGL((stft_pair_target_real_kernel<4, 4>), grid, dim3(256), 0, stream, a, target);
+                else
+                    hipLaunchKernelGGL(stft_pair_target_kernel, grid, dim3(256), shmem, stream, a, N, target);
+            } else if (N == 1024)
                 hipLaunchKernelGGL((stft_pair_real_kernel<8, 3, PACKED>), grid, dim3(256), 0, stream, a);
             else if (N == 512)
                 hipLaunchKernelGGL((stft_pair_real_kernel<4, 4, PACKED>), grid, dim3(256), 0, stream, a);
@@ -1090,6 +1194,39 @@ static int32_t check_stft_pair(drnmf_handle_t h, const char* who, int32_t n_sig,
     return DRNMF_OK;
 }
 
+// the argument checks of drnmf_stft_pair_chunks and drnmf_stft_pair_chunks_target (who), then their enqueue
+static int32_t check_stft_pair_chunks(drnmf_handle_t h, const char* who, int32_t n_sig, int64_t stride_x,
+                                      int64_t stride_y, const int64_t* len_x, const int64_t* len_y, int32_t n_seq,
+                                      const int32_t* seq_table, int32_t T, int32_t N, int32_t hop,
+                                      int32_t is_int16, int32_t transform, const void* pcm_x, const void* pcm_y,
+                                      const float* x, const float* y, const float* w) {
+    if (n_seq <= 0 || T <= 0) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: bad shape n_seq=%d T=%d", who, n_seq, T);
+    const int32_t rc = check_stft_pair(h, who, n_sig, stride_x, stride_y, N, hop, is_int16, transform);
+    if (rc) return rc;
+    if (!len_x || !len_y || !seq_table || !pcm_x || !pcm_y || !x || !y || !w)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: NULL pointer argument", who);
+    return DRNMF_OK;
+}
+
+static int32_t enqueue_stft_pair_chunks(drnmf_handle_t h, int32_t n_sig, int64_t stride_x, int64_t stride_y,
+                                        const int64_t* len_x, const int64_t* len_y, int32_t n_seq,
+                                        const int32_t* seq_table, int32_t T, int32_t N, int32_t hop,
+                                        int32_t is_int16, int32_t transform, int32_t target, float mask_value,
+                                        const void* pcm_x, const void* pcm_y, float* x, float* y, float* w,
+                                        hipStream_t stream) {
+    int logN = 0;
+    while ((1 << logN) < N) ++logN;
+    {
+        const int32_t trc = ensure_fft_tables(h, N, logN, stream);
+        if (trc) return trc;
+    }
+    PairArgs a = {pcm_x, pcm_y, len_x, len_y, stride_x, stride_y, seq_table, nullptr, 0, x, y, w,
+                  nullptr, nullptr, n_sig, T, hop, logN, is_int16, transform, mask_value, 0, 0};
+    launch_stft_pair<false>(a, N, n_seq, stream, target);
+    DRNMF_HIP(h, hipGetLastError());
+    return DRNMF_OK;
+}
+
 extern "C" int32_t drnmf_stft_pair_chunks(drnmf_handle_t h, int32_t n_sig, int64_t stride_x, int64_t stride_y,
                                           const int64_t* len_x, const int64_t* len_y, int32_t n_seq,
                                           const int32_t* seq_table, int32_t T, int32_t N, int32_t hop,
@@ -1098,25 +1235,36 @@ extern "C" int32_t drnmf_stft_pair_chunks(drnmf_handle_t h, int32_t n_sig, int64
                                           void* stream_) {
     DRNMF_LOCK(h);
     if (!h) return DRNMF_ERR_INVALID_ARG;
-    if (n_seq <= 0 || T <= 0)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stft_pair_chunks: bad shape n_seq=%d T=%d", n_seq, T);
-    const int32_t rc = check_stft_pair(h, "stft_pair_chunks", n_sig, stride_x, stride_y, N, hop, is_int16,
-                                       transform);
+    const int32_t rc = check_stft_pair_chunks(h, "stft_pair_chunks", n_sig, stride_x, stride_y, len_x, len_y, n_seq,
+                                              seq_table, T, N, hop, is_int16, transform, pcm_x, pcm_y, x, y, w);
     if (rc) return rc;
-    if (!len_x || !len_y || !seq_table || !pcm_x || !pcm_y || !x || !y || !w)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stft_pair_chunks: NULL pointer argument");
-    int logN = 0;
-    while ((1 << logN) < N) ++logN;
-    hipStream_t stream = (hipStream_t)stream_;
-    {
-        const int32_t trc = ensure_fft_tables(h, N, logN, stream);
-        if (trc) return trc;
-    }
-    PairArgs a = {pcm_x, pcm_y, len_x, len_y, stride_x, stride_y, seq_table, nullptr, 0, x, y, w,
-                  nullptr, nullptr, n_sig, T, hop, logN, is_int16, transform, mask_value, 0, 0};
-    launch_stft_pair<false>(a, N, n_seq, stream);
-    DRNMF_HIP(h, hipGetLastError());
-    return DRNMF_OK;
+    return enqueue_stft_pair_chunks(h, n_sig, stride_x, stride_y, len_x, len_y, n_seq, seq_table, T, N, hop,
+                                    is_int16, transform, DRNMF_TARGET_MAG, mask_value, pcm_x, pcm_y, x, y, w,
+                                    (hipStream_t)stream_);
+}
+
+// include/drnmf_target.h
+extern "C" int32_t drnmf_stft_pair_chunks_target(drnmf_handle_t h, int32_t n_sig, int64_t stride_x,
+                                                 int64_t stride_y, const int64_t* len_x, const int64_t* len_y,
+                                                 int32_t n_seq, const int32_t* seq_table, int32_t T, int32_t N,
+                                                 int32_t hop, int32_t is_int16, int32_t transform, int32_t target,
+                                                 float mask_value, const void* pcm_x, const void* pcm_y, float* x,
+                                                 float* y, float* w, void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    const char* who = "stft_pair_chunks_target";
+    if (target != DRNMF_TARGET_MAG && target != DRNMF_TARGET_PSA && target != DRNMF_TARGET_TPSA)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: target=%d is none of DRNMF_TARGET_MAG, _PSA, _TPSA", who, target);
+    const int32_t rc = check_stft_pair_chunks(h, who, n_sig, stride_x, stride_y, len_x, len_y, n_seq, seq_table, T,
+                                              N, hop, is_int16, transform, pcm_x, pcm_y, x, y, w);
+    if (rc) return rc;
+    if (target != DRNMF_TARGET_MAG && transform != DRNMF_TRANSFORM_MAG)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: target=%d is defined for DRNMF_TRANSFORM_MAG only (transform=%d)",
+                   who, target, transform);
+    if (h->device < 0) DRNMF_FAIL(h, DRNMF_ERR_HIP, "%s: the handle is bound to no device", who);
+    return enqueue_stft_pair_chunks(h, n_sig, stride_x, stride_y, len_x, len_y, n_seq, seq_table, T, N, hop,
+                                    is_int16, transform, target, mask_value, pcm_x, pcm_y, x, y, w,
+                                    (hipStream_t)stream_);
 }
 
 extern "C" int32_t drnmf_stft_pair_frames(drnmf_handle_t h, int32_t n_sig, int64_t stride_x, int64_t stride_y,

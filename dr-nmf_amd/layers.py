@@ -1693,14 +1693,16 @@ class _SequenceModel(object):
 
 
     def fit_wavs(self, noisy, clean, N=512, hop=128, maxlen=None, transform='mag', validation_wavs=None,
-                 **fit_kwargs):
+                 target='mag', **fit_kwargs):
         """`fit` on waveform pairs: the reference's load_data (audio_dataset.py:199-264) on the device by
         ops.wavs_to_tensors, then the existing fit on the device tensors (x, y, sample_weight = the 0/1 mask,
         enhance.py:1148-1157).  noisy, clean: lists of 1-D int16 / float32 arrays; validation_wavs: a (noisy,
         clean) pair of such lists, built the same way.  Everything else goes to fit unchanged.  The padding
         must be the value this model masks: a transform whose mask value (data.get_mask_value) differs from
-        the model's raises ValueError."""
+        the model's raises ValueError.  target: 'mag', 'psa' or 'tpsa' (ops.wavs_to_tensors), the y of the
+        training AND of the validation tensors, so val_loss and whatever monitors it are against that target."""
         from . import data
+        ops._check_target(target, transform, 'fit_wavs')
         for k in ('sample_weight', 'validation_data'):
             if k in fit_kwargs:
                 raise ValueError('fit_wavs: %s is built from the waveforms (validation_wavs=)' % k)
@@ -1712,7 +1714,7 @@ class _SequenceModel(object):
             raise ValueError('fit_wavs: N = %d gives %d bins, the model takes %d'
                              % (N, int(N) // 2 + 1, self._input_width()))
         build = lambda a, b: ops.wavs_to_tensors(a, b, N=N, hop=hop, maxlen=maxlen, transform=transform,
-                                                 mask_value=mv, device=self._device())
+                                                 mask_value=mv, device=self._device(), target=target)
         val = None
         if validation_wavs is not None:
             noisy_v, clean_v = validation_wavs

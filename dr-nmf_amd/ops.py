@@ -1284,6 +1284,21 @@ def stft_pair_chunks_enqueue(pcm_x, pcm_y, len_x_dev, len_y_dev, table_dev, T, N
     _capi.check(rc, h, "drnmf_stft_pair_chunks")
 
 
+def stft_pair_target_enqueue(pcm_x, pcm_y, len_x_dev, len_y_dev, table_dev, T, N, hop, transform, target,
+                              mask_value, x, y, w):
+    """drnmf_stft_pair_chunks_target (include/drnmf_target.h) on tensors the caller owns and has checked:
+    stft_pair_chunks_enqueue with y = the 'mag' / 'psa' / 'tpsa' target.  Enqueues, reads nothing back."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(pcm_x))
+    rc = L.drnmf_stft_pair_chunks_target(h, pcm_x.shape[0], pcm_x.shape[1], pcm_y.shape[1], _capi.ptr(len_x_dev),
+                                         _capi.ptr(len_y_dev), table_dev.shape[0], _capi.ptr(table_dev), int(T),
+                                         int(N), int(hop), int(pcm_x.dtype == torch.int16),
+                                         _capi.TRANSFORMS[transform], _capi.TARGETS[target], float(mask_value),
+                                         _capi.ptr(pcm_x), _capi.ptr(pcm_y), _capi.ptr(x), _capi.ptr(y),
+                                         _capi.ptr(w), _stream())
+    _capi.check(rc, h, "drnmf_stft_pair_chunks_target")
+
+
 def stft_pair_frames_enqueue(pcm_x, pcm_y, len_x_dev, len_y_dev, row0_dev, N, hop, transform, x_frames,
                              y_frames):
     """drnmf_stft_pair_frames on tensors the caller owns and has checked: enqueues, reads nothing back."""
@@ -1348,7 +1363,16 @@ def _upload_pinned(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(dev, non_blocking=True)
 
 
-def wavs_to_tensors(noisy, clean, N=512, hop=128, maxlen=None, transform='mag', mask_value=None, device=None):
+def _check_target(target, transform, what):
+    """The training target of include/drnmf_target.h against the transform, before the device is touched."""
+    if target not in _capi.TARGETS:
+        raise ValueError("%s: target must be 'mag', 'psa' or 'tpsa' (got %r)" % (what, target))
+    if target != 'mag' and transform != 'mag':
+        raise ValueError("%s: target %r is defined for transform 'mag' only (got %r)" % (what, target, transform))
+
+
+def wavs_to_tensors(noisy, clean, N=512, hop=128, maxlen=None, transform='mag', mask_value=None, device=None,
+                    target='mag'):
     """The reference's load_data (audio_dataset.py:199-264: STFT of every noisy and clean file, the noisy stack
     clipped to the clean one, the transform, get_padded_data_matrix) on the device: lists of 1-D int16 (scaled
     by 1/32768) or float32 numpy arrays in, (x, y, w) out as device tensors [n_seq, T, F], [n_seq, T, F] and
@@ -1357,8 +1381,15 @@ def wavs_to_tensors(noisy, clean, N=512, hop=128, maxlen=None, transform='mag', 
     mask_value (default: data.get_mask_value for the transform) and weighted 1 / 0.  The clean side decides an
     utterance's frame count; a noisy signal with FEWER frames than its clean one raises ValueError, as do lists
     of different lengths and empty lists.  One pinned upload per side and one of the table, one launch
-    sequence, no download and no synchronisation."""
+    sequence, no download and no synchronisation.
+
+    target: what y holds in a valid frame.  'mag': the clean magnitude, as the reference trains.  'psa': the
+    phase-sensitive target p = |S| cos(theta_S - theta_X) (Erdogan et al., ICASSP 2015), the clean magnitude
+    projected on the noisy phase the enhanced signal is put back on; it may be negative and may exceed x.
+    'tpsa': p clipped to [0, x], what a mask in [0, 1] can reach.  p is 0 where the noisy bin is 0.  x and w do not
+    depend on the target.  'psa' and 'tpsa' need transform='mag' (ValueError otherwise)."""
     from . import data
+    _check_target(target, transform, "wavs_to_tensors")
     rx, ry, dt, nf = _check_wav_pairs(noisy, clean, N, hop, transform, "wavs_to_tensors")
     table, T = data.sequence_table_from_lengths(nf, maxlen)
     if mask_value is None:
@@ -1373,7 +1404,11 @@ def wavs_to_tensors(noisy, clean, N=512, hop=128, maxlen=None, transform='mag', 
         x = torch.empty((n_seq, T, F), dtype=torch.float32, device=dev)
         y = torch.empty_like(x)
         w = torch.empty((n_seq, T), dtype=torch.float32, device=dev)
-        stft_pair_chunks_enqueue(pcm_x, pcm_y, len_x, len_y, table_d, T, N, hop, transform, mask_value, x, y, w)
+        if target == 'mag':
+            stft_pair_chunks_enqueue(pcm_x, pcm_y, len_x, len_y, table_d, T, N, hop, transform, mask_value, x, y, w)
+        else:
+            stft_pair_target_enqueue(pcm_x, pcm_y, len_x, len_y, table_d, T, N, hop, transform, target, mask_value,
+                                     x, y, w)
     return x, y, w
 
 

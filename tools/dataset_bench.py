@@ -1,7 +1,7 @@
 """ops.wavs_to_tensors against the path composed of the per-file entry points, and the paired kernel against two
 ragged launches: one JSON line, appended to profiles/dataset_bench.jsonl.
 
-    python tools/dataset_bench.py [--utts 1980] [--reps 5] [--skip-e2e] [--skip-kernel]
+    python tools/dataset_bench.py [--utts 1980] [--reps 5] [--skip-e2e] [--skip-kernel] [--target mag|psa|tpsa]
 
 The utterances are those of tools/enhance_bench.py: lengths drawn (seed 0) uniformly from 2 to 12 s at 16 kHz, int16
 noise-like samples, the clean side a second draw of the same lengths; N = 512, hop = 128; maxlen None and 500.
@@ -14,9 +14,13 @@ Fields per maxlen:
                           bytes of length per signal and side, 8 per sequence); composed = int16 up, float32
                           magnitudes of both sides down, padded x, y and mask up
   max_abs_diff            of x, y and w between the two paths (0: bitwise equal)
+--target psa / tpsa (include/drnmf_target.h): the composed path has no such target and is not run; device_s is timed
+alternating with target='mag' in the same process (mag_s, ratio = device_s / mag_s), x_w_equal_mag: x and w bitwise
+those of 'mag'.
 Paired kernel alone (device events, median of --reps after a warm-up), 250 pairs of 2000 frames, int16:
   pair_chunks_us, and ragged_x2_us = two drnmf_stft_ragged launches writing the same rows (which also write re and
-  im: ragged_x2_bytes counts them), each with its bytes in + out over time as a share of the 8 TB/s HBM rate.
+  im: ragged_x2_bytes counts them), each with its bytes in + out over time as a share of the 8 TB/s HBM rate;
+  pair_psa_us / pair_tpsa_us = drnmf_stft_pair_chunks_target on the same buffers (the same bytes), in the same run.
 JSON goes to stdout, nothing else does.
 """
 import argparse
@@ -96,6 +100,12 @@ def kernel_case(ops, n_sig, frames, reps):
                                                                  -1.0, x, y, w))
     rag, rag_all = events(two_ragged)
     same = bool(torch.equal(x, x2) and torch.equal(y, y2))
+    targets = {}
+    for target in ("psa", "tpsa"):
+        t, t_all = events(lambda: ops.stft_pair_target_enqueue(px, py, ld, ld, table, frames, N_FFT, HOP, "mag", target,
+                                                               -1.0, x, y, w))
+        targets.update({"pair_%s_us" % target: round(t, 1), "pair_%s_us_all" % target: t_all,
+                        "pair_%s_over_mag" % target: round(t / pair, 3)})
     pcm = 2 * n_sig * nsampl * 2
     pair_bytes = pcm + 2 * n_sig * frames * F * 4 + n_sig * frames * 4
     rag_bytes = pcm + 6 * n_sig * frames * F * 4
@@ -103,7 +113,8 @@ def kernel_case(ops, n_sig, frames, reps):
                 pair_chunks_us_all=pair_all, ragged_x2_us=round(rag, 1), ragged_x2_us_all=rag_all,
                 pair_bytes=pair_bytes, ragged_x2_bytes=rag_bytes,
                 pair_hbm_share=round(pair_bytes / (pair * 1e-6) / HBM_BYTES_PER_S, 4),
-                ragged_x2_hbm_share=round(rag_bytes / (rag * 1e-6) / HBM_BYTES_PER_S, 4), bitwise_equal=same)
+                ragged_x2_hbm_share=round(rag_bytes / (rag * 1e-6) / HBM_BYTES_PER_S, 4), bitwise_equal=same,
+                **targets)
 
 
 def main():
@@ -112,6 +123,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--skip-e2e", action="store_true")
     ap.add_argument("--skip-kernel", action="store_true")
+    ap.add_argument("--target", choices=("mag", "psa", "tpsa"), default="mag")
     a = ap.parse_args()
     import __graft_entry__ as G
     G.build()
@@ -124,7 +136,7 @@ def main():
     noisy = [rng.integers(-3000, 3000, size=int(l)).astype(np.int16) for l in lengths]
     clean = [rng.integers(-3000, 3000, size=int(l)).astype(np.int16) for l in lengths]
     res = dict(tool="dataset_bench", utts=n, fs=fs, lengths="uniform 2-12 s (seed 0)", N=N_FFT, hop=HOP,
-               reps=a.reps, total_s=float(lengths.sum()) / fs, device=torch.cuda.get_device_name(0))
+               reps=a.reps, total_s=float(lengths.sum()) / fs, device=torch.cuda.get_device_name(0), target=a.target)
     if not a.skip_e2e:
         nf = np.array([ops.stft_frames(int(l), N_FFT, HOP) for l in lengths], dtype=np.int64)
         for maxlen in (None, 500):
@@ -133,7 +145,24 @@ def main():
             padded = n_seq * T * (2 * F + 1) * 4
             pcie = dict(device=int(4 * lengths.sum() + 16 * n + 8 * n_seq),
                         composed=int(4 * lengths.sum() + 2 * int(nf.sum()) * F * 4 + padded))
-            dev_fn = lambda: ops.wavs_to_tensors(noisy, clean, N=N_FFT, hop=HOP, maxlen=maxlen, device=DEV)
+            dev_fn = lambda: ops.wavs_to_tensors(noisy, clean, N=N_FFT, hop=HOP, maxlen=maxlen, device=DEV,
+                                                 target=a.target)
+            if a.target != "mag":
+                mag_fn = lambda: ops.wavs_to_tensors(noisy, clean, N=N_FFT, hop=HOP, maxlen=maxlen, device=DEV)
+                got, want = dev_fn(), mag_fn()                           # warm-up of both
+                same = bool(torch.equal(got[0], want[0]) and torch.equal(got[2], want[2]))
+                del got, want
+                td, tm = [], []
+                for _ in range(a.reps):
+                    td.append(timed(dev_fn))
+                    tm.append(timed(mag_fn))
+                md, mm = float(np.median(td)), float(np.median(tm))
+                res["maxlen_%s" % maxlen] = dict(
+                    n_seq=int(n_seq), T=int(T), tensor_bytes=int(padded), device_s=round(md, 4), mag_s=round(mm, 4),
+                    device_s_all=[round(t, 4) for t in td], mag_s_all=[round(t, 4) for t in tm],
+                    ratio=round(md / mm, 3), pcie_bytes=pcie["device"], x_w_equal_mag=same)
+                torch.cuda.empty_cache()
+                continue
             cmp_fn = lambda: composed(ops, data, noisy, clean, maxlen)
             got, want = dev_fn(), cmp_fn()                               # warm-up of both paths
             diff = max(float((g - w).abs().max()) for g, w in zip(got, want))
