@@ -659,11 +659,14 @@ dlogd_kernel(const float* __restrict__ P, const float* __restrict__ Dn, float* _
     }
 }
 
+__device__ __forceinline__ float softplus(float z) { return (z > 20.f) ? z : log1pf(expf(z)); }
+
 // per-atom sums over all frames of layer k: Sb = sum dz, Sgi = sum dz * (h_k - base) (= ia * sum dz G)
 // and, for F = 16 j + 1 (the 2^k + 1 STFT sizes), the ODD BIN's row of the two weight-gradient
 // products -- S1 = sum_t r_k[t][Fm] dz_k[t][n], S2 = sum_t d r_k[t][Fm] h_{k-1}[t][n] -- which would
 // otherwise cost the TN GEMMs a fifth, 1/128-full row of output tiles (M = 528: 5 x 128).  dz and
-// h_{k-1} are streamed here anyway.
+// h_{k-1} are streamed here anyway.  One kernel template, colreduce_kernel<V, LANES, U> (launch_colreduce
+// picks the instantiation), and one fold, colreduce_fold_kernel<LANES>.
 constexpr int CR_SLOTS = 4;
 struct ColRedArgs {
     const float* hall;
@@ -680,316 +683,214 @@ struct ColRedArgs {
     float u0d, u0o, uko;
     int k, B, T, N, K, Bp, Np, ldr;
 };
-__global__ void __launch_bounds__(256) colreduce_kernel(const ColRedArgs a) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    const int sp = blockIdx.y;
-    if (n >= a.N) return;
-    const int64_t BT = (int64_t)a.B * a.T;
+template <int V> using crvec = float __attribute__((ext_vector_type(V)));
+template <int V> struct CrSums { crvec<V> s[CR_SLOTS]; };     // Sb, Sgi, S1, S2 of V atoms
+
+// rows [r0, r1) of the B*T frames that split sp sums
+__device__ __forceinline__ void cr_split_rows(int sp, int64_t BT, int64_t& r0, int64_t& r1) {
     const int64_t per = (BT + CR_SPLITS - 1) / CR_SPLITS;
-    const int64_t r0 = sp * per;
-    int64_t r1 = r0 + per;
+    r0 = sp * per;
+    r1 = r0 + per;
     if (r1 > BT) r1 = BT;
-    const int KN = a.K * a.N;
-    const float bk = a.bias[n];
-    float h0v = 0.f;
-    if (a.k == 0) {
-        const float z = a.log_h0[n];
-        h0v = (z > 20.f) ? z : log1pf(expf(z));
-    }
-    const bool tail = a.rt != nullptr, tail2 = tail && a.k >= 1;
-    float sb = 0.f, sg = 0.f, s1 = 0.f, s2 = 0.f;
-    int b = (int)(r0 / a.T), t = (int)(r0 % a.T) - 1;
-    // dz is sparse (it inherits the zeros of h): its loads decide everything else, so eight of
-    // them are in flight at a time (one dependent load per row made this kernel latency-bound:
-    // 1.7 ms per layer at the C2 shape)
-    constexpr int U = 8;
-    const float* dzp = a.dz_all + (size_t)a.k * a.N + n;
-    const float* hpp = a.hall + (size_t)(a.k >= 1 ? a.k - 1 : 0) * a.N + n;
-    for (int64_t bt0 = r0; bt0 < r1; bt0 += U) {
-        float dzv[U], hpv[U], rtv[U], drv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t bt = bt0 + u < r1 ? bt0 + u : r1 - 1;
-            dzv[u] = dzp[bt * KN];
-            if (tail) rtv[u] = a.rt[bt * a.ldr];
-            if (tail2) {
-                hpv[u] = hpp[bt * KN];
-                drv[u] = a.drt[bt * a.ldr];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t bt = bt0 + u;
-            if (bt >= r1) break;
-            if (++t == a.T) { t = 0; ++b; }
-            if (tail2) s2 = fmaf(drv[u], hpv[u], s2);
-            const float dz = dzv[u];
-            if (dz == 0.f) continue;
-            if (tail) s1 = fmaf(rtv[u], dz, s1);
-            const float ps = a.psum_all[(size_t)t * a.Bp + b];
-            const float hk = a.hall[bt * KN + (size_t)a.k * a.N + n];
-            float base;
-            if (a.k == 0) {
-                const float p = a.seen[(size_t)t * a.Bp + b]
-                                    ? a.hall[(bt - 1) * KN + (size_t)(a.K - 1) * a.N + n]
-                                    : (a.init ? a.init[(size_t)b * a.N + n] : h0v);
-                base = a.u0d * p + a.u0o * (ps - p) + bk;
-            } else {
-                base = (tail2 ? hpv[u] : a.hall[bt * KN + (size_t)(a.k - 1) * a.N + n]) + bk +
-                       a.uko * ps;
-            }
-            sb += dz;
-            sg = fmaf(dz, hk - base, sg);
-        }
-    }
-    float* o = a.part + (size_t)sp * CR_SLOTS * a.Np + n;
-    o[0] = sb;
-    o[(size_t)a.Np] = sg;
-    o[(size_t)2 * a.Np] = s1;
-    o[(size_t)3 * a.Np] = s2;
 }
 
-// Same sums, four atoms per thread (N % 4 == 0): the dz / h_{k-1} streams come in 16-byte loads,
-// 4 KB contiguous per row and workgroup (the scalar kernel above moved 2 GB per layer at 1.4 TB/s).
-// The rarely taken branch -- dz != 0 -- still gathers h_k / p with scalar loads.
-__global__ void __launch_bounds__(256) colreduce4_kernel(const ColRedArgs a) {
-    const int n = (blockIdx.x * 256 + threadIdx.x) * 4;
-    const int sp = blockIdx.y;
-    if (n >= a.N) return;
-    const int64_t BT = (int64_t)a.B * a.T;
-    const int64_t per = (BT + CR_SPLITS - 1) / CR_SPLITS;
-    const int64_t r0 = sp * per;
-    int64_t r1 = r0 + per;
-    if (r1 > BT) r1 = BT;
+// The partial sums of 4 lanes that share column `col` meet in LDS and are added in a fixed order
+// (deterministic); lane 0 leaves with the totals.
+template <typename T>
+__device__ __forceinline__ void cr_combine_lanes(T (&acc)[CR_SLOTS][4][64], T (&s)[CR_SLOTS], int lane, int col) {
+#pragma unroll
+    for (int sl = 0; sl < CR_SLOTS; ++sl) acc[sl][lane][col] = s[sl];
+    __syncthreads();
+    if (lane != 0) return;
+#pragma unroll
+    for (int sl = 0; sl < CR_SLOTS; ++sl)
+        s[sl] = (acc[sl][0][col] + acc[sl][1][col]) + (acc[sl][2][col] + acc[sl][3][col]);
+}
+
+// The rows r0 + rl, r0 + rl + LANES, ... of split [r0, r1) for the V atoms n .. n + V - 1, U rows in flight:
+// dz is sparse (it inherits the zeros of h) and its loads decide everything else (one dependent load
+// per row made the kernel latency-bound: 1.7 ms per layer at the C2 shape).  An atom with dz == 0 adds
+// nothing to Sb, Sgi and S1; S2 takes every row.  The rarely taken branch -- dz != 0 -- gathers h_k / p.
+// (The sums are locals returned by value: accumulated through a reference parameter they cost every
+// instantiation an occupancy step -- 45 -> 75 and 94 -> 112 VGPRs.)
+template <int V, int LANES, int U>
+__device__ __forceinline__ CrSums<V> colreduce_rows(const ColRedArgs& a, int n, int rl, int64_t r0, int64_t r1) {
+    using vec = crvec<V>;
+    vec sb = {}, sg = {}, s1 = {}, s2 = {};
     const int KN = a.K * a.N;
-    const f32x4 bk = *(const f32x4*)(a.bias + n);
-    f32x4 h0v = {0.f, 0.f, 0.f, 0.f};
+    const vec bk = *(const vec*)(a.bias + n);
+    vec h0v = {};
     if (a.k == 0) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float z = a.log_h0[n + e];
-            h0v[e] = (z > 20.f) ? z : log1pf(expf(z));
-        }
+        for (int e = 0; e < V; ++e) h0v[e] = softplus(a.log_h0[n + e]);
     }
     const bool tail = a.rt != nullptr, tail2 = tail && a.k >= 1;
-    f32x4 sb = {0.f, 0.f, 0.f, 0.f}, sg = sb, s1 = sb, s2 = sb;
-    int b = (int)(r0 / a.T), t = (int)(r0 % a.T) - 1;
-    constexpr int U = 4;
+    // one row lane walks consecutive rows and follows (b, t) along; several derive it where it is needed
+    int b = 0, t = 0;
+    if constexpr (LANES == 1) {
+        b = (int)(r0 / a.T);
+        t = (int)(r0 % a.T) - 1;
+    }
     const float* dzp = a.dz_all + (size_t)a.k * a.N + n;
     const float* hpp = a.hall + (size_t)(a.k >= 1 ? a.k - 1 : 0) * a.N + n;
-    for (int64_t bt0 = r0; bt0 < r1; bt0 += U) {
-        f32x4 dzv[U], hpv[U];
+    for (int64_t bt0 = r0 + rl; bt0 < r1; bt0 += LANES * U) {
+        vec dzv[U], hpv[U];
         float rtv[U], drv[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int64_t bt = bt0 + u < r1 ? bt0 + u : r1 - 1;
-            dzv[u] = *(const f32x4*)(dzp + bt * KN);
+            int64_t bt = bt0 + LANES * u;
+            bt = bt < r1 ? bt : r1 - 1;
+            dzv[u] = *(const vec*)(dzp + bt * KN);
             if (tail) rtv[u] = a.rt[bt * a.ldr];
             if (tail2) {
-                hpv[u] = *(const f32x4*)(hpp + bt * KN);
+                hpv[u] = *(const vec*)(hpp + bt * KN);
                 drv[u] = a.drt[bt * a.ldr];
             }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int64_t bt = bt0 + u;
+            const int64_t bt = bt0 + LANES * u;
             if (bt >= r1) break;
-            if (++t == a.T) { t = 0; ++b; }
+            if constexpr (LANES == 1) {
+                if (++t == a.T) { t = 0; ++b; }
+            }
             if (tail2) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) s2[e] = fmaf(drv[u], hpv[u][e], s2[e]);
+                for (int e = 0; e < V; ++e) s2[e] = fmaf(drv[u], hpv[u][e], s2[e]);
             }
-            const f32x4 dz = dzv[u];
-            if (dz[0] == 0.f && dz[1] == 0.f && dz[2] == 0.f && dz[3] == 0.f) continue;
+            const vec dz = dzv[u];
+            bool zero = true;
+#pragma unroll
+            for (int e = 0; e < V; ++e) zero = zero && dz[e] == 0.f;
+            if (zero) continue;
+            if constexpr (LANES > 1) {
+                b = (int)(bt / a.T);
+                t = (int)(bt - (int64_t)b * a.T);
+            }
             const float ps = a.psum_all[(size_t)t * a.Bp + b];
-            const f32x4 hk = *(const f32x4*)(a.hall + bt * KN + (size_t)a.k * a.N + n);
-            f32x4 base;
+            const vec hk = *(const vec*)(a.hall + bt * KN + (size_t)a.k * a.N + n);
+            vec base;
             if (a.k == 0) {
-                f32x4 p = h0v;
+                vec p = h0v;
                 if (a.seen[(size_t)t * a.Bp + b])
-                    p = *(const f32x4*)(a.hall + (bt - 1) * KN + (size_t)(a.K - 1) * a.N + n);
+                    p = *(const vec*)(a.hall + (bt - 1) * KN + (size_t)(a.K - 1) * a.N + n);
                 else if (a.init)
-                    p = *(const f32x4*)(a.init + (size_t)b * a.N + n);
+                    p = *(const vec*)(a.init + (size_t)b * a.N + n);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) base[e] = a.u0d * p[e] + a.u0o * (ps - p[e]) + bk[e];
+                for (int e = 0; e < V; ++e) base[e] = a.u0d * p[e] + a.u0o * (ps - p[e]) + bk[e];
             } else {
-                const f32x4 hp = tail2 ? hpv[u]
-                                       : *(const f32x4*)(a.hall + bt * KN + (size_t)(a.k - 1) * a.N + n);
+                const vec hp = tail2 ? hpv[u] : *(const vec*)(a.hall + bt * KN + (size_t)(a.k - 1) * a.N + n);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) base[e] = hp[e] + bk[e] + a.uko * ps;
+                for (int e = 0; e < V; ++e) base[e] = hp[e] + bk[e] + a.uko * ps;
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (dz[e] == 0.f) continue;          // (exactly the scalar kernel's terms and order)
+            for (int e = 0; e < V; ++e) {
+                if (dz[e] == 0.f) continue;
                 if (tail) s1[e] = fmaf(rtv[u], dz[e], s1[e]);
                 sb[e] += dz[e];
                 sg[e] = fmaf(dz[e], hk[e] - base[e], sg[e]);
             }
         }
     }
-    float* o = a.part + (size_t)sp * CR_SLOTS * a.Np + n;
-    *(f32x4*)o = sb;
-    *(f32x4*)(o + (size_t)a.Np) = sg;
-    *(f32x4*)(o + (size_t)2 * a.Np) = s1;
-    *(f32x4*)(o + (size_t)3 * a.Np) = s2;
+    return {{sb, sg, s1, s2}};
 }
 
-// The same sums for NARROW dictionaries (N / 4 <= 64 atom quads): the 256 threads of a workgroup are
-// 64 quads x 4 row lanes -- lane rl takes the rows r0 + rl, r0 + rl + 4, ... of the split -- and the four
-// partial sums meet in LDS in a fixed order.  (With one thread per quad an N = 200 layer ran 50 threads
-// per workgroup through 62 dependent rows each: 72 us.)
-__global__ void __launch_bounds__(256) colreduce4_rows_kernel(const ColRedArgs a) {
-    __shared__ f32x4 acc[4][4][64];
-    const int qn = threadIdx.x & 63, rl = threadIdx.x >> 6;
-    const int n = qn * 4;
+// Workgroup = 256 / LANES column groups of V atoms x LANES row lanes; grid.y = the split.
+//   <1, 1, 8>  any N: one atom per thread.
+//   <4, 1, 4>  N % 4 == 0 (then Np, K*N and the buffers' bases are multiples of 4 floats): the dz / h_{k-1}
+//              streams come in 16-byte loads, 4 KB contiguous per row and workgroup (one atom per thread
+//              moved 2 GB per layer at 1.4 TB/s).
+//   <4, 4, 4>  NARROW dictionaries, N / 4 <= 64 atom quads: with one thread per quad an N = 200 layer ran
+//              50 threads per workgroup through 62 dependent rows each (72 us).
+template <int V, int LANES, int U>
+__global__ void __launch_bounds__(256) colreduce_kernel(const ColRedArgs a) {
+    constexpr int COLS = 256 / LANES;
+    // (one lane: rl is the constant 0, so that the row index stays in scalar registers)
+    const int col = LANES == 1 ? threadIdx.x : threadIdx.x % COLS, rl = LANES == 1 ? 0 : threadIdx.x / COLS;
+    const int n = (blockIdx.x * COLS + col) * V;
     const int sp = blockIdx.y;
     const bool live = n < a.N;
-    const int64_t BT = (int64_t)a.B * a.T;
-    const int64_t per = (BT + CR_SPLITS - 1) / CR_SPLITS;
-    const int64_t r0 = sp * per;
-    int64_t r1 = r0 + per;
-    if (r1 > BT) r1 = BT;
-    const int KN = a.K * a.N;
-    f32x4 sb = {0.f, 0.f, 0.f, 0.f}, sg = sb, s1 = sb, s2 = sb;
+    if (LANES == 1 && !live) return;
+    CrSums<V> sums = {};
     if (live) {
-        const f32x4 bk = *(const f32x4*)(a.bias + n);
-        f32x4 h0v = {0.f, 0.f, 0.f, 0.f};
-        if (a.k == 0) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float z = a.log_h0[n + e];
-                h0v[e] = (z > 20.f) ? z : log1pf(expf(z));
-            }
-        }
-        const bool tail = a.rt != nullptr, tail2 = tail && a.k >= 1;
-        const float* dzp = a.dz_all + (size_t)a.k * a.N + n;
-        const float* hpp = a.hall + (size_t)(a.k >= 1 ? a.k - 1 : 0) * a.N + n;
-        constexpr int U = 4;
-        for (int64_t bt0 = r0 + rl; bt0 < r1; bt0 += 4 * U) {
-            f32x4 dzv[U], hpv[U];
-            float rtv[U], drv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                int64_t bt = bt0 + 4 * u;
-                bt = bt < r1 ? bt : r1 - 1;
-                dzv[u] = *(const f32x4*)(dzp + bt * KN);
-                if (tail) rtv[u] = a.rt[bt * a.ldr];
-                if (tail2) {
-                    hpv[u] = *(const f32x4*)(hpp + bt * KN);
-                    drv[u] = a.drt[bt * a.ldr];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t bt = bt0 + 4 * u;
-                if (bt >= r1) break;
-                if (tail2) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) s2[e] = fmaf(drv[u], hpv[u][e], s2[e]);
-                }
-                const f32x4 dz = dzv[u];
-                if (dz[0] == 0.f && dz[1] == 0.f && dz[2] == 0.f && dz[3] == 0.f) continue;
-                const int b = (int)(bt / a.T), t = (int)(bt - (int64_t)b * a.T);
-                const float ps = a.psum_all[(size_t)t * a.Bp + b];
-                const f32x4 hk = *(const f32x4*)(a.hall + bt * KN + (size_t)a.k * a.N + n);
-                f32x4 base;
-                if (a.k == 0) {
-                    f32x4 p = h0v;
-                    if (a.seen[(size_t)t * a.Bp + b])
-                        p = *(const f32x4*)(a.hall + (bt - 1) * KN + (size_t)(a.K - 1) * a.N + n);
-                    else if (a.init)
-                        p = *(const f32x4*)(a.init + (size_t)b * a.N + n);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) base[e] = a.u0d * p[e] + a.u0o * (ps - p[e]) + bk[e];
-                } else {
-                    const f32x4 hp = tail2 ? hpv[u]
-                                           : *(const f32x4*)(a.hall + bt * KN + (size_t)(a.k - 1) * a.N + n);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) base[e] = hp[e] + bk[e] + a.uko * ps;
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (dz[e] == 0.f) continue;
-                    if (tail) s1[e] = fmaf(rtv[u], dz[e], s1[e]);
-                    sb[e] += dz[e];
-                    sg[e] = fmaf(dz[e], hk[e] - base[e], sg[e]);
-                }
-            }
-        }
+        int64_t r0, r1;
+        cr_split_rows(sp, (int64_t)a.B * a.T, r0, r1);
+        sums = colreduce_rows<V, LANES, U>(a, n, rl, r0, r1);
     }
-    acc[0][rl][qn] = sb; acc[1][rl][qn] = sg; acc[2][rl][qn] = s1; acc[3][rl][qn] = s2;
-    __syncthreads();
-    if (rl == 0 && live) {
-        float* o = a.part + (size_t)sp * CR_SLOTS * a.Np + n;
-#pragma unroll
-        for (int sl = 0; sl < 4; ++sl)
-            *(f32x4*)(o + (size_t)sl * a.Np) = (acc[sl][0][qn] + acc[sl][1][qn]) + (acc[sl][2][qn] + acc[sl][3][qn]);
+    if constexpr (LANES > 1) {
+        static_assert(LANES == 4 && V == 4, "cr_combine_lanes: 4 lanes x 64 columns");
+        __shared__ crvec<V> acc[CR_SLOTS][4][64];
+        cr_combine_lanes(acc, sums.s, rl, col);
+        if (rl != 0 || !live) return;
     }
+    float* o = a.part + (size_t)sp * CR_SLOTS * a.Np + n;
+#pragma unroll
+    for (int sl = 0; sl < CR_SLOTS; ++sl) *(crvec<V>*)(o + (size_t)sl * a.Np) = sums.s[sl];
+}
+void launch_colreduce(const ColRedArgs& ca, hipStream_t stream) {
+    const int N = ca.N;
+    if (N % 4 == 0 && N / 4 <= 64)
+        hipLaunchKernelGGL((colreduce_kernel<4, 4, 4>), dim3(1, CR_SPLITS), dim3(256), 0, stream, ca);
+    else if (N % 4 == 0)
+        hipLaunchKernelGGL((colreduce_kernel<4, 1, 4>), dim3((N / 4 + 255) / 256, CR_SPLITS), dim3(256), 0,
+                           stream, ca);
+    else
+        hipLaunchKernelGGL((colreduce_kernel<1, 1, 8>), dim3((N + 255) / 256, CR_SPLITS), dim3(256), 0,
+                           stream, ca);
 }
 
 // stage 1 of the scalar gradients: the CR_SPLITS partial sums of every atom, added in split order
-// (one thread per atom; slot 0 of `part` receives the totals).  With an odd-bin row (Ptail != null)
-// its gradient ia[n] S1[n] - S2[n] goes where the GEMM partials of that row would have been: split 0
-// of P, zeros in the other splits (dlogd_kernel adds the splits up).
+// (slot 0 of `part` receives the totals).  With an odd-bin row (Ptail != null) its gradient
+// ia[n] S1[n] - S2[n] goes where the GEMM partials of that row would have been: split 0 of P, zeros in
+// the other splits (dlogd_kernel adds the splits up).
+//   <1>  one thread per atom.
+//   <4>  narrow dictionaries: 64 atoms x 4 split lanes per workgroup, lane sl takes the splits sl, sl + 4, ...
+//        (one thread per atom walked 256 splits x 4 slots of dependent loads: 30 us for N = 200).
+template <int LANES>
 __global__ void __launch_bounds__(256)
 colreduce_fold_kernel(float* __restrict__ part, int N, int Np, float* __restrict__ Ptail,
                       const float* __restrict__ ia, int splits, size_t pstride) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= N) return;
-    float sb = 0.f, sg = 0.f, s1 = 0.f, s2 = 0.f;
+    constexpr int COLS = 256 / LANES;
+    const int col = LANES == 1 ? threadIdx.x : threadIdx.x % COLS, sl = LANES == 1 ? 0 : threadIdx.x / COLS;
+    const int n = blockIdx.x * COLS + col;
+    if (LANES == 1 && n >= N) return;
+    float s[CR_SLOTS] = {};
     static_assert(CR_SPLITS % 32 == 0, "colreduce folds walk the splits eight at a time");
-    for (int s0 = 0; s0 < CR_SPLITS; s0 += 8) {          // (32 loads in flight, added in split order)
-        float v[8][4];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const float* p = part + (size_t)(s0 + u) * CR_SLOTS * Np + n;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[u][k] = p[(size_t)k * Np];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { sb += v[u][0]; sg += v[u][1]; s1 += v[u][2]; s2 += v[u][3]; }
-    }
-    part[n] = sb;
-    part[(size_t)Np + n] = sg;
-    if (Ptail) {
-        Ptail[n] = ia[n] * s1 - s2;
-        for (int s = 1; s < splits; ++s) Ptail[s * pstride + n] = 0.f;
-    }
-}
-
-// The same for narrow dictionaries: 64 atoms x 4 split lanes per workgroup (one thread per atom walked
-// 256 splits x 4 slots of dependent loads: 30 us for N = 200); fixed combination order.
-__global__ void __launch_bounds__(256)
-colreduce_fold_lanes_kernel(float* __restrict__ part, int N, int Np, float* __restrict__ Ptail,
-                            const float* __restrict__ ia, int splits, size_t pstride) {
-    __shared__ float acc[4][4][64];
-    const int c = threadIdx.x & 63, sl = threadIdx.x >> 6;
-    const int n = blockIdx.x * 64 + c;
-    float sb = 0.f, sg = 0.f, s1 = 0.f, s2 = 0.f;
-    if (n < N)
-        for (int s0 = sl; s0 < CR_SPLITS; s0 += 32) {   // (eight of the lane's splits = 32 loads in flight)
-            float v[8][4];
+    if (LANES == 1 || n < N)     // (one lane: the others have left)
+        for (int s0 = sl; s0 < CR_SPLITS; s0 += 8 * LANES) {   // (eight of the lane's splits = 32 loads in flight)
+            float v[8][CR_SLOTS];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                const float* p = part + (size_t)(s0 + 4 * u) * CR_SLOTS * Np + n;
+                const float* p = part + (size_t)(s0 + LANES * u) * CR_SLOTS * Np + n;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) v[u][k] = p[(size_t)k * Np];
+                for (int k = 0; k < CR_SLOTS; ++k) v[u][k] = p[(size_t)k * Np];
             }
 #pragma unroll
-            for (int u = 0; u < 8; ++u) { sb += v[u][0]; sg += v[u][1]; s1 += v[u][2]; s2 += v[u][3]; }
-        }
-    acc[0][sl][c] = sb; acc[1][sl][c] = sg; acc[2][sl][c] = s1; acc[3][sl][c] = s2;
-    __syncthreads();
-    if (sl != 0 || n >= N) return;
-    float t[4];
+            for (int u = 0; u < 8; ++u)
 #pragma unroll
-    for (int k = 0; k < 4; ++k) t[k] = (acc[k][0][c] + acc[k][1][c]) + (acc[k][2][c] + acc[k][3][c]);
-    part[n] = t[0];
-    part[(size_t)Np + n] = t[1];
-    if (Ptail) {
-        Ptail[n] = ia[n] * t[2] - t[3];
-        for (int s = 1; s < splits; ++s) Ptail[s * pstride + n] = 0.f;
+                for (int k = 0; k < CR_SLOTS; ++k) s[k] += v[u][k];
+        }
+    if constexpr (LANES > 1) {
+        static_assert(LANES == 4, "cr_combine_lanes: 4 lanes x 64 columns");
+        __shared__ float acc[CR_SLOTS][4][64];
+        cr_combine_lanes(acc, s, sl, col);
+        if (sl != 0 || n >= N) return;
     }
+    part[n] = s[0];
+    part[(size_t)Np + n] = s[1];
+    if (Ptail) {
+        Ptail[n] = ia[n] * s[2] - s[3];
+        for (int sp = 1; sp < splits; ++sp) Ptail[sp * pstride + n] = 0.f;
+    }
+}
+void launch_colreduce_fold(float* part, int N, int Np, float* Ptail, const float* ia, int splits,
+                           size_t pstride, hipStream_t stream) {
+    if (N <= 512)
+        hipLaunchKernelGGL(colreduce_fold_kernel<4>, dim3((N + 63) / 64), dim3(256), 0, stream, part, N, Np,
+                           Ptail, ia, splits, pstride);
+    else
+        hipLaunchKernelGGL(colreduce_fold_kernel<1>, dim3((N + 255) / 256), dim3(256), 0, stream, part, N,
+                           Np, Ptail, ia, splits, pstride);
 }
 
 // d log_alph / d log_lam1 of layer k from the per-atom sums: ia = exp(-log_alph), b = -lam * ia
@@ -1100,10 +1001,7 @@ state_matrix_kernel(const float* __restrict__ hall, const unsigned char* __restr
     float v;
     if (seen[(size_t)t * Bp + b]) v = hall[(bt - 1) * K * N + (size_t)(K - 1) * N + n];
     else if (init) v = init[(size_t)b * N + n];
-    else {
-        const float z = log_h0[n];
-        v = (z > 20.f) ? z : log1pf(expf(z));
-    }
+    else v = softplus(log_h0[n]);
     P[i] = v;
 }
 
@@ -1447,7 +1345,7 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
             Aop = Rk;
         }
         // M = Fp: the padded bins of R / X / dR are zero, and whole 4-column groups keep the loads
-        // vectorised.  F = 16 j + 1: M = F - 1, the odd bin's row comes from colreduce_kernel.
+        // vectorised.  F = 16 j + 1: M = F - 1, the odd bin's row comes from the column reduction (colreduce_rows).
         const bool odd = (F % 16 == 1) && F > 16 && !nonlin;   // (KL / beta: no odd-bin side path at all)
         const int Mg = odd ? F - 1 : W.Fp;
         gemm_tn::Operands t1{Aop, dz_all + (size_t)k * N, BT, Mg, N, W.Fp, KN};
@@ -1486,23 +1384,10 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
         ca.seen = seen; ca.log_h0 = log_h0; ca.init = initial_state; ca.part = crp;
         ca.u0d = u0_diag; ca.u0o = u0_off; ca.uko = uk_off;
         ca.k = k; ca.B = B; ca.T = T; ca.N = N; ca.K = K; ca.Bp = W.Bp; ca.Np = W.Np;
-        if (N % 4 == 0 && N / 4 <= 64)
-            hipLaunchKernelGGL(colreduce4_rows_kernel, dim3(1, CR_SPLITS), dim3(256), 0, stream, ca);
-        else if (N % 4 == 0)   // (Np, K*N, the buffers' bases: multiples of 4 floats then)
-            hipLaunchKernelGGL(colreduce4_kernel, dim3((N / 4 + 255) / 256, CR_SPLITS), dim3(256), 0,
-                               stream, ca);
-        else
-            hipLaunchKernelGGL(colreduce_kernel, dim3((N + 255) / 256, CR_SPLITS), dim3(256), 0,
-                               stream, ca);
+        launch_colreduce(ca, stream);
         const int ka = d->n_alph == 1 ? 0 : k, kl = d->n_lam == 1 ? 0 : k;
-        if (N <= 512)
-            hipLaunchKernelGGL(colreduce_fold_lanes_kernel, dim3((N + 63) / 64), dim3(256), 0, stream,
-                               crp, N, W.Np, odd ? P + (size_t)(F - 1) * W.Np : (float*)nullptr,
-                               ia_of(k), nsplit, pstr);
-        else
-            hipLaunchKernelGGL(colreduce_fold_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, crp,
-                               N, W.Np, odd ? P + (size_t)(F - 1) * W.Np : (float*)nullptr, ia_of(k),
-                               nsplit, pstr);
+        launch_colreduce_fold(crp, N, W.Np, odd ? P + (size_t)(F - 1) * W.Np : (float*)nullptr, ia_of(k),
+                              nsplit, pstr, stream);
         const int kd = d->n_D == 1 ? 0 : k;
         if (N % 4 == 0) {
             // (cpart: the split >= 2 slots of the column-reduction partials, dead after the fold)

@@ -22,6 +22,8 @@ work = [   # (substring, label, flops per launch, bytes per launch)
     ('gemm_tn_kernel<(anonymous namespace)::EpiP1', 'gemm_tn EpiP1 (dD += r^T g, all frames)', 2.0 * BT * F * N, None),
     ('gemm_tn_kernel<(anonymous namespace)::EpiP2', 'gemm_tn EpiP2 (dD -= dr^T h, all frames)', 2.0 * BT * F * N, None),
     ('colreduce4_kernel', 'colreduce4 (column sums of three B T x N streams)', None, 3.0 * BT * N * 4),
+    # (its name since the three column-reduction kernels are instantiations of one template)
+    ('colreduce_kernel<4, 1, 4>', 'colreduce<4, 1, 4> (column sums of three B T x N streams)', None, 3.0 * BT * N * 4),
     ('gemm_nt_kernel<(anonymous namespace)::EpiHead', 'head GEMMs (A, Bn, mask)', 2.0 * BT * (N // 2) * F, None),
     ('adam_flat_kernel', 'Adam over the flat buffer', None, None),
 ]

@@ -183,6 +183,53 @@ def test_stateful_training_gradients_match_autograd(dev, divergence):
     assert not model.cell.states[0].any()
 
 
+@pytest.mark.parametrize("cfg", [
+    # the per-atom column reduction of the BPTT (cell_backward.hip: launch_colreduce / launch_colreduce_fold)
+    # picks its kernel by N = 2 r: N % 4 != 0 one atom per thread, N % 4 == 0 four (N <= 256: with row lanes),
+    # N <= 512 the fold with split lanes.  F = 33 has an odd-bin row (F % 16 == 1), F = 21 has none.
+    dict(r=7, F=33, K=3),
+    dict(r=130, F=33, K=2),
+    dict(r=130, F=21, K=2),
+    dict(r=258, F=33, K=2),
+    dict(r=7, F=33, K=3, stateful=True),         # layer 0 reads the ENTERING state instead of softplus(log_h0)
+])
+def test_column_reduction_branches_match_autograd(dev, cfg):
+    """Every gradient tensor (log_lam1 included: it and log_alph come from the column sums, log_D's odd-bin row
+    too) against fp64 autograd at the smallest dictionary widths that reach each column-reduction kernel."""
+    cfg = dict(cfg)
+    stateful = cfg.pop("stateful", False)
+    B, T, K = 3, 6, cfg["K"]
+    model, P, wmask = _setup(B, T, cfg["F"], cfg["r"], K, untied=("log_D", "log_alph"),
+                             trainable=("log_D", "log_alph", "log_lam1"))
+    state = None
+    if stateful:
+        model.cell.stateful = True
+    model.compile(lr=1e-3)
+    if stateful:
+        state = 0.2 * np.random.default_rng(3).random((B, 2 * cfg["r"]))
+        model.cell.states = [torch.from_numpy(state.astype(np.float32)).to(dev)]
+        state = model.cell.states[0].cpu().numpy().astype(np.float64)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+    flat = model.loss_and_grads(t(P["X"]), t(P["Y"]), t(wmask)).clone()
+    torch.cuda.synchronize()
+    ref_loss, ref, cnt = _autograd(model, P, wmask, K, False, initial_state=state)
+    assert abs(float(flat[-4]) - ref_loss) <= 1e-5 * abs(ref_loss) + 1e-9
+    assert float(flat[-3]) == cnt
+    name_map = {"kernel_clean": "kc", "kernel_noise": "kn"}
+    checked = set()
+    for n, _ in model._train_items:
+        g = model._gview[n].cpu().numpy()
+        if stateful and n == "log_h0":
+            assert not g.any()                      # the entering state was supplied: log_h0 unused
+            continue
+        r_ = ref[name_map.get(n, n)]
+        assert r_ is not None, n
+        scale = max(np.max(np.abs(r_)), 1e-12)
+        err = np.max(np.abs(g - r_)) / scale
+        assert err <= G_TOL, "%s: rel err %.3e (max ref %.3e)" % (n, err, scale)
+        checked.update(p for p in ("log_D", "log_alph", "log_lam1") if n.startswith(p))
+    assert checked == {"log_D", "log_alph", "log_lam1"}, checked
+
 
 @pytest.mark.parametrize("cfg", [
     # T >= 200: the BPTT replays hipGraphs of up to 64 frames (cell_backward.hip: fpg_max) plus
