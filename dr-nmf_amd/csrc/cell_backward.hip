@@ -14,6 +14,7 @@
 // log_h0.  Masked steps follow K.rnn: no gradient enters a masked frame; the gradient of its
 // (repeated) output is handed to the last valid frame and the state gradient passes through.
 #include "cell_shared.h"
+#include "cell_host.h"
 #include "cell_gram.h"
 #include "cell_gram_persist.h"
 #include "gemm_nt.h"
@@ -1058,9 +1059,17 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
                                   size_t fwd_workspace_bytes, void* bwd_workspace,
                                   size_t bwd_workspace_bytes, float* d_log_D,
                                   float* d_log_alph, float* d_log_lam1, float* d_log_h0,
-                                  void* stream_, float* prof_ms, float beta = 0.f,
-                                  const float* initial_state = nullptr) {
+                                  void* stream_, float* prof_ms, const char* what, bool ista,
+                                  float beta = 0.f, const float* initial_state = nullptr) {
     if (!h) return DRNMF_ERR_INVALID_ARG;
+    // the cell the entry serves (`what` names it; ista: KL / beta, else the reference's Euclidean one)
+    if (ista && (!d || (d->divergence != DRNMF_DIV_KL && d->divergence != DRNMF_DIV_BETA)))
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: d->divergence must be DRNMF_DIV_KL or DRNMF_DIV_BETA", what);
+    if (!ista && d && d->divergence != DRNMF_DIV_ED)
+        DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED,
+                   "%s is the reference's (Euclidean) cell; KL / beta: drnmf_cell_backward_ista", what);
+    if (initial_state && ((uintptr_t)initial_state & 15))
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: initial_state must be 16-byte aligned", what);
     // (No implicit look at the handle's fault word here: a host-side read-and-clear at the entry of the
     // NEXT call races with the stream-ordered drnmf_status_take_device of a training step -- the host
     // could consume the word before the device-side guard of the fused Adam launch has seen it.  Faults
@@ -1094,24 +1103,13 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
     if (((uintptr_t)bwd_workspace & 255) || ((uintptr_t)fwd_workspace & 255))
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "workspaces must be 256-byte aligned");
     hipStream_t stream = (hipStream_t)stream_;
-    const ParamsLayout PL = params_layout(d);
-    const char* pb = (const char*)params;
-    const char* fw = (const char*)fwd_workspace;
+    // (the forward's workspace, read only here, and the prepared block: the views its drivers use, cell_host.h)
+    const CellCtx C{*d, W, params_layout(d), (char*)const_cast<void*>(fwd_workspace), (const char*)params};
     char* bw = (char*)bwd_workspace;
     const int K = d->K, N = d->N, F = d->F, T = d->T, B = d->B;
     const int64_t BT = (int64_t)B * T;
     // MFMA bin tiles: the odd bins of a 2^k+1 STFT are handled by rank-1 terms, as in the forward
     const int numM = W.Bp / ROWS, nft = W.nft_main;
-    const bool half = d->operand_f16 != 0;
-    const float* Dp_base = (const float*)(pb + (half ? PL.off_dn32 : PL.off_dn));
-    const size_t dstride = (size_t)PL.Fp * PL.Np;
-    const float* DpA_base = half ? Dp_base + (size_t)d->n_D * dstride : (const float*)(pb + PL.off_dnA);
-    auto Dp_of = [&](int k) { return Dp_base + (d->n_D == 1 ? 0 : (size_t)k * dstride); };
-    auto ia_of = [&](int k) { return (const float*)(pb + PL.off_inv_alpha) + (size_t)k * PL.Np; };
-    auto b_of = [&](int k) { return (const float*)(pb + PL.off_bias) + (size_t)k * PL.Np; };
-    const unsigned char* valid = (const unsigned char*)(fw + W.off_valid);
-    const unsigned char* seen = (const unsigned char*)(fw + W.off_seen);
-    const float* psum_all = (const float*)(fw + W.off_psum_all);
 
     float* dstate = (float*)(bw + L.off_dstate);
     float* gq = (float*)(bw + L.off_gq);
@@ -1143,22 +1141,19 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
     const dim3 grid_b(8u * (unsigned)(numM / W.RB), (unsigned)(round_up(nft * W.KS, 8) / 8));
 
     EdgeArgs ea;
-    ea.hall = hall; ea.d_out = d_out; ea.dz_all = dz_all; ea.ia_last = ia_of(K - 1);
+    ea.hall = hall; ea.d_out = d_out; ea.dz_all = dz_all; ea.ia_last = C.ia_of(K - 1);
     ea.dstate = dstate; ea.gq = gq; ea.dzp_top = dzp[(K - 1) & 1]; ea.dGp_top = W.gram ? dGp[(K - 1) & 1] : nullptr;
     ea.dzp0 = nonlin ? dzp[1] : dzp[0];      // (KL / beta: layer 0's launch leaves d p in dzp[(0 - 1) & 1])
     ea.dz0s_part = z0s; ea.dps_part = dps; ea.dh0_part = dh0_part;
-    ea.valid = valid;
+    ea.valid = C.valid;
     const bool edge_only = K == 1 && !nonlin;            // a frame of the ED cell with K = 1: the edge alone
     ea.c_rd = edge_only ? cA : cB;
     ea.c_wr = edge_only ? nullptr : cA;
     ea.u0d = u0_diag; ea.u0o = u0_off;
     ea.B = B; ea.T = T; ea.N = N; ea.K = K; ea.Bp = W.Bp; ea.Np = W.Np; ea.numA = W.numA;
-    auto tail_of = [&](int k) {
-        return (const float*)(pb + PL.off_tail) + (d->n_D == 1 ? 0 : (size_t)k * MAX_TAIL * PL.Np);
-    };
     float* dq = (float*)(bw + L.off_dq);
     const size_t dqstride = (size_t)MAX_TAIL * W.Bp * W.numA;
-    ea.Dtail_top = tail_of(K - 1);
+    ea.Dtail_top = C.tail_of(K - 1);
     ea.dq_out = dq + (size_t)((K - 1) & 1) * dqstride;   // partials of layer k live in buffer k & 1
     ea.ntail = W.gram ? 0 : W.ntail;
     ea.nparts = W.gram ? W.numO : W.numA;
@@ -1166,10 +1161,10 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
     auto make_g = [&](int k) {       // Gram form: one launch per layer-step (cell_gram.h)
         GramBwdArgs g;
         memset(&g, 0, sizeof(g));
-        g.G = (const float*)(pb + PL.off_gram) + (d->n_D == 1 ? 0 : (size_t)k * PL.Np * PL.Np);
+        g.G = C.G_of(k);
         g.dGp_in = dGp[k & 1];
         g.dzp_in = dzp[k & 1];
-        g.ia_prev = ia_of(k - 1);
+        g.ia_prev = C.ia_of(k - 1);
         g.dzp_out = dzp[(k - 1) & 1];
         g.dGp_out = dGp[(k - 1) & 1];
         g.hall = hall; g.dz_all = dz_all;
@@ -1183,14 +1178,14 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
     const dim3 grid_g(8u * (unsigned)numM, (unsigned)(round_up(W.numO, 8) / 8));
 
     // (the fp16-operand forward counts 32-atom chunks; the fp32 kernels of this pass 16-atom ones)
-    const int nch_ks_b = half ? W.Np / 16 : W.nch_ks;
+    const int nch_ks_b = C.half ? W.Np / 16 : W.nch_ks;
     const bool qred = qred_wanted(W.numA, W.ntail, nft, W.KS, W.RB);
     float* DpIa = (float*)(bw + L.off_dpia);
     if (!W.gram) {
         const size_t tot = (size_t)W.Fp * W.Np;
         for (int k = kmin; k < K; ++k)
             hipLaunchKernelGGL(scale_pack_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
-                               stream, Dp_of(k), ia_of(k), DpIa + (size_t)k * tot, tot, W.Np);
+                               stream, C.Dp_of(k), C.ia_of(k), DpIa + (size_t)k * tot, tot, W.Np);
     }
     auto make_b = [&](int k) {
         CellBArgs b;
@@ -1209,8 +1204,8 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
     };
     auto make_a = [&](int k) {
         BwdAArgs a;
-        a.Dn = DpA_base + (d->n_D == 1 ? 0 : (size_t)k * dstride);
-        a.ia_prev = ia_of(k >= 1 ? k - 1 : 0);
+        a.Dn = C.DpA_of(k);
+        a.ia_prev = C.ia_of(k >= 1 ? k - 1 : 0);
         a.drpart = drpart;
         a.dzp_in = dzp[k & 1];
         a.dzp_out = dzp[(k - 1) & 1];
@@ -1223,8 +1218,8 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
         a.uko = uk_off;
         a.k = k; a.B = B; a.T = T; a.N = N; a.K = K; a.Bp = W.Bp; a.Fp = W.Fp; a.Np = W.Np;
         a.numA = W.numA; a.nchunks = nft;
-        a.Dtail = tail_of(k);
-        a.Dtail_prev = tail_of(k >= 1 ? k - 1 : 0);
+        a.Dtail = C.tail_of(k);
+        a.Dtail_prev = C.tail_of(k >= 1 ? k - 1 : 0);
         a.dq_in = qred ? (const float*)(bw + L.off_dqsum) : dq + (size_t)(k & 1) * dqstride;
         a.dq_out = dq + (size_t)((k - 1) & 1) * dqstride;
         a.ntail = W.ntail;
@@ -1237,13 +1232,13 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
     if (persist) {
         GramPersistBwdArgs pa;
         memset(&pa, 0, sizeof(pa));
-        pa.G = (const float*)(pb + PL.off_gram);
-        pa.g_stride = d->n_D == 1 ? 0 : (size_t)PL.Np * PL.Np;
-        pa.ia = (const float*)(pb + PL.off_inv_alpha);
+        pa.G = C.G_of(0);
+        pa.g_stride = C.g_stride();
+        pa.ia = C.ia_of(0);
         pa.hall = hall; pa.d_out = d_out; pa.dz_all = dz_all;
         pa.dGp[0] = dGp[0]; pa.dGp[1] = dGp[1];
         pa.z0s_part = z0s; pa.dps_part = dps; pa.dh0_part = dh0_part; pa.dstate = dstate;
-        pa.valid = valid;
+        pa.valid = C.valid;
         pa.bar = (unsigned*)(bw + L.off_cnt + 256);            // (zeroed by the memset above)
         pa.host_flag = h->persist_flag;
         pa.u0d = u0_diag; pa.u0o = u0_off; pa.uko = uk_off;
@@ -1268,11 +1263,11 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
             CellBArgs b = make_b(k);
             DRNMF_HIP(h, chain.add(pick_b_func(nch_ks_b, W.RB, false, qred), grid_b, 64 * NW_B, CellBParams(b).p));
             if (nonlin) {                          // d x^ = d r * dg/dx^ (x_t, x^_{t,k}), in place
-                const float* xpp = (const float*)(fw + W.off_xp);
-                const float* xh = (const float*)(fw + W.off_xhat);
+                const float* xpp = C.xp;
+                const float* xh = C.xhat;
                 float* drp = drpart;
                 const int* crd = cA;
-                const unsigned char* vp = valid;
+                const unsigned char* vp = C.valid;
                 int Tv = T, kv = k, Kv = K, dv = d->divergence, Fv = F, Fpv = W.Fp, Bpv = W.Bp;
                 float bt = beta;
                 void* ks[13] = {&xpp, &xh, &drp, &crd, &vp, &Tv, &kv, &Kv, &dv, &bt, &Fv, &Fpv, &Bpv};
@@ -1290,18 +1285,13 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
         return DRNMF_OK;
     };
     if (!persist) {
-        uint32_t bb[4];
-        memcpy(&bb[0], &beta, 4);
-        memcpy(&bb[1], &u0_diag, 4); memcpy(&bb[2], &u0_off, 4); memcpy(&bb[3], &uk_off, 4);
         const std::vector<uint64_t> key = {
-            (uint64_t)W.gram, (uint64_t)d->divergence, bb[0], (uint64_t)B, (uint64_t)T, (uint64_t)F, (uint64_t)N,
+            (uint64_t)W.gram, (uint64_t)d->divergence, f32_bits(beta), (uint64_t)B, (uint64_t)T, (uint64_t)F, (uint64_t)N,
             (uint64_t)K, (uint64_t)d->n_D, (uint64_t)(uintptr_t)params, (uint64_t)(uintptr_t)hall,
             (uint64_t)(uintptr_t)d_out, (uint64_t)(uintptr_t)fwd_workspace, (uint64_t)(uintptr_t)bwd_workspace,
-            bb[1], bb[2], bb[3]};
+            f32_bits(u0_diag), f32_bits(u0_off), f32_bits(uk_off)};
         // several frames per graph, as in the forward (cell_forward.hip)
-        int fpg = 800 / (2 * K - 1);         // ~800 kernel nodes per graph
-        fpg = fpg < 1 ? 1 : (fpg > 64 ? 64 : fpg);
-        if (fpg > T) fpg = T;
+        const int fpg = frames_per_graph(800, 2 * K - 1, T);         // ~800 kernel nodes per graph
         const int32_t grc = replay_frames(h, stream, GraphKind::Backward, key, {fpg, 1}, 0, T, frame);
         if (grc) return grc;
     }
@@ -1324,7 +1314,7 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
     for (int k = 0; k < K; ++k) {
         const size_t tot = (size_t)W.Fp * W.Np;
         hipLaunchKernelGGL(unpack_dn_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
-                           stream, Dp_of(k), Dn_rm, W.Fp, W.Np);
+                           stream, C.Dp_of(k), Dn_rm, W.Fp, W.Np);
         const float* Aop = xpad;
         const int perm_all = 16 * nft;       // the chain kernels' saved copies: every MFMA bin tile
         int perm1 = 0;
@@ -1332,12 +1322,12 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
             // R_k = g(X, X^_k) of EVERY layer, layer 0 included, from the x^ the forward kept
             const size_t tot2 = (size_t)BT * W.Fp;
             hipLaunchKernelGGL(unpack_g_kernel, dim3((unsigned)((tot2 + 255) / 256)), dim3(256), 0, stream,
-                               x, (const float*)(fw + W.off_xhat), Rk, valid, B, T, F, W.Fp, W.Bp, k, K,
+                               x, (const float*)C.xhat, Rk, (const unsigned char*)C.valid, B, T, F, W.Fp, W.Bp, k, K,
                                d->divergence, beta);
             Aop = Rk;
-        } else if (k >= 1 && W.off_rsave != 0) {
+        } else if (k >= 1 && C.rsave) {
             // the forward left r_k of every frame in its workspace (cell_a_kernel, Rsave)
-            Aop = (const float*)(fw + W.off_rsave) + (size_t)(k - 1) * BT * W.Fp;
+            Aop = C.rsave + (size_t)(k - 1) * BT * W.Fp;
             perm1 = perm_all;
         } else if (k >= 1) {
             gemm::Operands g1{hall + (size_t)(k - 1) * N, Dn_rm, BT, F, N, KN, W.Np};
@@ -1351,7 +1341,7 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
         gemm_tn::Operands t1{Aop, dz_all + (size_t)k * N, BT, Mg, N, W.Fp, KN};
         const int nsplit = tn_splits(Mg, N, BT);
         const float* dRk_tail = nullptr;
-        DRNMF_HIP(h, gemm_tn::launch(t1, EpiP1{P, ia_of(k), W.Np, pstr, perm1}, nsplit, stream));
+        DRNMF_HIP(h, gemm_tn::launch(t1, EpiP1{P, C.ia_of(k), W.Np, pstr, perm1}, nsplit, stream));
         if (k >= 1) {
             const float* dRk = dR_all + (size_t)k * BT * W.Fp;
             if (W.gram) {
@@ -1359,7 +1349,7 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
                 // product, against the dictionary scaled by 1/alpha_k
                 float* DnIa = (float*)(bw + L.off_dnia);
                 hipLaunchKernelGGL(unpack_scaled_kernel, dim3((unsigned)((tot + 255) / 256)),
-                                   dim3(256), 0, stream, Dp_of(k), ia_of(k), DnIa, W.Fp, W.Np);
+                                   dim3(256), 0, stream, C.Dp_of(k), C.ia_of(k), DnIa, W.Fp, W.Np);
                 gemm::Operands g2{dz_all + (size_t)k * N, DnIa, BT, W.Fp, N, KN, W.Np};
                 DRNMF_HIP(h, gemm::launch(g2, EpiStore{dR_all, W.Fp}, stream));
                 dRk = dR_all;
@@ -1372,7 +1362,7 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
             float* Pst = (float*)(bw + L.off_pst);
             const size_t totp = (size_t)BT * N;
             hipLaunchKernelGGL(state_matrix_kernel, dim3((unsigned)((totp + 255) / 256)), dim3(256), 0,
-                               stream, hall, seen, log_h0, Pst, B, T, N, K, W.Bp, initial_state);
+                               stream, hall, (const unsigned char*)C.seen, log_h0, Pst, B, T, N, K, W.Bp, initial_state);
             gemm_tn::Operands t2{dR_all, Pst, BT, Mg, N, W.Fp, N};
             DRNMF_HIP(h, gemm_tn::launch(t2, EpiP2{P, W.Np, pstr, perm_all}, nsplit, stream));
         }
@@ -1380,13 +1370,13 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
         ca.rt = odd ? Aop + (F - 1) : nullptr;
         ca.drt = dRk_tail;
         ca.ldr = W.Fp;
-        ca.hall = hall; ca.dz_all = dz_all; ca.bias = b_of(k); ca.psum_all = psum_all;
-        ca.seen = seen; ca.log_h0 = log_h0; ca.init = initial_state; ca.part = crp;
+        ca.hall = hall; ca.dz_all = dz_all; ca.bias = C.b_of(k); ca.psum_all = C.psum_all;
+        ca.seen = C.seen; ca.log_h0 = log_h0; ca.init = initial_state; ca.part = crp;
         ca.u0d = u0_diag; ca.u0o = u0_off; ca.uko = uk_off;
         ca.k = k; ca.B = B; ca.T = T; ca.N = N; ca.K = K; ca.Bp = W.Bp; ca.Np = W.Np;
         launch_colreduce(ca, stream);
         const int ka = d->n_alph == 1 ? 0 : k, kl = d->n_lam == 1 ? 0 : k;
-        launch_colreduce_fold(crp, N, W.Np, odd ? P + (size_t)(F - 1) * W.Np : (float*)nullptr, ia_of(k),
+        launch_colreduce_fold(crp, N, W.Np, odd ? P + (size_t)(F - 1) * W.Np : (float*)nullptr, C.ia_of(k),
                               nsplit, pstr, stream);
         const int kd = d->n_D == 1 ? 0 : k;
         if (N % 4 == 0) {
@@ -1406,7 +1396,7 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
                                d_log_D + (size_t)kd * F * N, F, N, W.Np, nsplit, pstr,
                                (d->n_D == 1 && k > 0) ? 1 : 0);
         }
-        hipLaunchKernelGGL(scalar_grads_kernel, dim3(1), dim3(256), 0, stream, crp, b_of(k),
+        hipLaunchKernelGGL(scalar_grads_kernel, dim3(1), dim3(256), 0, stream, crp, C.b_of(k),
                            d_log_alph + (size_t)ka * d->alph_len, d_log_lam1 + kl, N, W.Np,
                            d->alph_len, (d->n_alph == 1 && k > 0) ? 1 : 0,
                            (d->n_lam == 1 && k > 0) ? 1 : 0);
@@ -1432,12 +1422,9 @@ extern "C" int32_t drnmf_cell_backward(drnmf_handle_t h, const drnmf_cell_desc_t
                                        float* d_log_alph, float* d_log_lam1, float* d_log_h0,
                                        void* stream_) {
     DRNMF_LOCK(h);
-    if (h && d && d->divergence != DRNMF_DIV_ED)
-        DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED,
-                   "cell_backward is the reference's (Euclidean) cell; KL / beta: drnmf_cell_backward_ista");
     return cell_backward_impl(h, d, x, params, log_h0, u0_diag, u0_off, uk_off, hall, d_out,
                               fwd_workspace, fwd_workspace_bytes, bwd_workspace, bwd_workspace_bytes,
-                              d_log_D, d_log_alph, d_log_lam1, d_log_h0, stream_, nullptr);
+                              d_log_D, d_log_alph, d_log_lam1, d_log_h0, stream_, nullptr, "cell_backward", false);
 }
 
 // Stateful training (custom_layers.py:296-318; Keras Recurrent stateful=True under fit / train_on_batch):
@@ -1454,13 +1441,10 @@ extern "C" int32_t drnmf_cell_backward_stateful(drnmf_handle_t h, const drnmf_ce
                                                 float* d_log_D, float* d_log_alph, float* d_log_lam1,
                                                 float* d_log_h0, void* stream_) {
     DRNMF_LOCK(h);
-    if (h && d && d->divergence != DRNMF_DIV_ED)
-        DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED, "cell_backward_stateful is the reference's (Euclidean) cell");
-    if (h && initial_state && ((uintptr_t)initial_state & 15))
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "cell_backward_stateful: initial_state must be 16-byte aligned");
     return cell_backward_impl(h, d, x, params, log_h0, u0_diag, u0_off, uk_off, hall, d_out,
                               fwd_workspace, fwd_workspace_bytes, bwd_workspace, bwd_workspace_bytes,
-                              d_log_D, d_log_alph, d_log_lam1, d_log_h0, stream_, nullptr, 0.f, initial_state);
+                              d_log_D, d_log_alph, d_log_lam1, d_log_h0, stream_, nullptr, "cell_backward_stateful", false,
+                              0.f, initial_state);
 }
 
 extern "C" int32_t drnmf_cell_backward_ista(drnmf_handle_t h, const drnmf_cell_desc_t* d,
@@ -1471,13 +1455,9 @@ extern "C" int32_t drnmf_cell_backward_ista(drnmf_handle_t h, const drnmf_cell_d
                                             float* d_log_D, float* d_log_alph, float* d_log_lam1,
                                             float* d_log_h0, void* stream_) {
     DRNMF_LOCK(h);
-    if (!h) return DRNMF_ERR_INVALID_ARG;
-    if (!d || (d->divergence != DRNMF_DIV_KL && d->divergence != DRNMF_DIV_BETA))
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG,
-                   "cell_backward_ista: d->divergence must be DRNMF_DIV_KL or DRNMF_DIV_BETA");
     return cell_backward_impl(h, d, x, params, log_h0, 1.f, 0.f, 0.f, hall, d_out, fwd_workspace,
                               fwd_workspace_bytes, bwd_workspace, bwd_workspace_bytes, d_log_D,
-                              d_log_alph, d_log_lam1, d_log_h0, stream_, nullptr, beta);
+                              d_log_alph, d_log_lam1, d_log_h0, stream_, nullptr, "cell_backward_ista", true, beta);
 }
 
 // ... and of a stateful KL / beta cell (drnmf_cell_forward_ista with an initial state, return_all_hidden = 1)
@@ -1490,15 +1470,10 @@ extern "C" int32_t drnmf_cell_backward_ista_stateful(drnmf_handle_t h, const drn
                                                      float* d_log_alph, float* d_log_lam1, float* d_log_h0,
                                                      void* stream_) {
     DRNMF_LOCK(h);
-    if (!h) return DRNMF_ERR_INVALID_ARG;
-    if (!d || (d->divergence != DRNMF_DIV_KL && d->divergence != DRNMF_DIV_BETA))
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG,
-                   "cell_backward_ista_stateful: d->divergence must be DRNMF_DIV_KL or DRNMF_DIV_BETA");
-    if (initial_state && ((uintptr_t)initial_state & 15))
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "cell_backward_ista_stateful: initial_state must be 16-byte aligned");
     return cell_backward_impl(h, d, x, params, log_h0, 1.f, 0.f, 0.f, hall, d_out, fwd_workspace,
                               fwd_workspace_bytes, bwd_workspace, bwd_workspace_bytes, d_log_D,
-                              d_log_alph, d_log_lam1, d_log_h0, stream_, nullptr, beta, initial_state);
+                              d_log_alph, d_log_lam1, d_log_h0, stream_, nullptr, "cell_backward_ista_stateful", true, beta,
+                              initial_state);
 }
 
 extern "C" int32_t drnmf_cell_backward_profile(
@@ -1508,11 +1483,8 @@ extern "C" int32_t drnmf_cell_backward_profile(
     size_t bwd_workspace_bytes, float* d_log_D, float* d_log_alph, float* d_log_lam1,
     float* d_log_h0, void* stream_, float* out_ms_host) {
     DRNMF_LOCK(h);
-    if (!h) return DRNMF_ERR_INVALID_ARG;
-    if (!out_ms_host) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "cell_backward_profile: NULL out_ms_host");
-    if (d && d->divergence != DRNMF_DIV_ED)
-        DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED, "cell_backward_profile brackets the Euclidean cell's BPTT");
+    if (h && !out_ms_host) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "cell_backward_profile: NULL out_ms_host");
     return cell_backward_impl(h, d, x, params, log_h0, u0_diag, u0_off, uk_off, hall, d_out,
                               fwd_workspace, fwd_workspace_bytes, bwd_workspace, bwd_workspace_bytes,
-                              d_log_D, d_log_alph, d_log_lam1, d_log_h0, stream_, out_ms_host);
+                              d_log_D, d_log_alph, d_log_lam1, d_log_h0, stream_, out_ms_host, "cell_backward_profile", false);
 }

@@ -35,6 +35,7 @@
 // they are not shared between the waves of a workgroup, so an LDS round trip would only add
 // latency; all of a wave's operand loads are issued before its first MFMA.
 #include "cell_shared.h"
+#include "cell_host.h"
 #include "cell_gram.h"
 #include "cell_gram_persist.h"
 #include "gemm_nt.h"
@@ -779,7 +780,7 @@ init_state_kernel(const float* __restrict__ log_h0, float* __restrict__ state,
 // KL / beta cell: r = g(x_t, x^) on the packed [Bp][Fp] residual buffer, in place (x^ was left
 // there by cell_b in its no-input mode).  g = x/x^ - 1 (KL) or x x^(beta-2) - x^(beta-1)
 // (enhance.py:431, 450); padded bins are forced to 0 (0/0 otherwise).  Also the frame-counter
-// hand-over of the frame's first kernel (see cell_forward_impl).
+// hand-over of the frame's first kernel (see drnmf_cell_forward_ista).
 // xsave (training forward): x^ of this (frame, layer) is kept, packed as it is, at
 // xsave + t * xsave_tstride (the pointer already carries the layer's offset) for the BPTT.
 __global__ void __launch_bounds__(256)
@@ -885,53 +886,91 @@ extern "C" size_t drnmf_cell_workspace_bytes(const drnmf_cell_desc_t* d) {
     return workspace_layout(d).total;
 }
 
+// ---- what the three forward drivers share (the call context itself: cell_host.h) ------------------
+static void launch_seen(const CellCtx& C, hipStream_t stream) {
+    hipLaunchKernelGGL(seen_kernel, dim3((C.W.Bp + 3) / 4), dim3(256), 0, stream, C.valid, C.seen, C.d.T,
+                       C.W.Bp);
+}
+
+// Per-call prologue: the input packed and masked (x16: once more as fp16), the validity prefix (`seen`;
+// a driver that orders it elsewhere calls launch_seen itself), the initial state with its row sums in
+// rs_parts partials, frame counters = 0.
+static int32_t cell_prologue(drnmf_handle_t h, const CellCtx& C, const float* x, float mask_value,
+                             const float* log_h0, const float* initial_state, f16* x16, int rs_parts,
+                             int by_row, bool seen, hipStream_t stream) {
+    const drnmf_cell_desc_t* d = &C.d;
+    const Workspace& W = C.W;
+    const size_t rows = (size_t)d->T * W.Bp;
+    hipLaunchKernelGGL(pack_input_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, C.xp,
+                       C.valid, mask_value, d->B, d->T, d->F, W.Bp, W.Fp, x16);
+    if (seen) launch_seen(C, stream);
+    if (initial_state)
+        hipLaunchKernelGGL(load_state_kernel, dim3((W.Bp + 3) / 4), dim3(256), 0, stream, initial_state,
+                           C.state, C.rs_part, C.tA, d->B, d->N, W.Np, W.Bp, rs_parts, by_row);
+    else
+        hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(256), 0, stream, log_h0, C.state, C.rs_part,
+                           C.tA, d->N, W.Np, W.Bp, rs_parts, by_row);
+    DRNMF_HIP(h, hipGetLastError());
+    return DRNMF_OK;
+}
+
+// The state a call leaves behind, unpacked to final_state [B][N] (NULL: not wanted).  Reports the HIP
+// status of the launch; the caller decides what a failure means.
+static hipError_t store_final_state(const CellCtx& C, float* final_state, hipStream_t stream) {
+    if (!final_state) return hipSuccess;
+    const size_t tot = (size_t)C.d.B * C.d.N;
+    hipLaunchKernelGGL(store_state_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream,
+                       (const float*)C.state, final_state, C.d.B, C.d.N, C.W.Np);
+    return hipGetLastError();
+}
+
+// What cell_a is told alike as layer k of the reference cell and as an ISTA step of the KL / beta cell; the two
+// builders (factored_start, drnmf_cell_forward_ista) set what differs: residual source, counters, U scalars,
+// chunks, odd bins.  Everything else is zero.
+static CellAArgs cell_a_common(const CellCtx& C, int k, float* h_out) {
+    const drnmf_cell_desc_t& d = C.d;
+    const Workspace& W = C.W;
+    CellAArgs a;
+    memset(&a, 0, sizeof(a));
+    a.Dn = C.DnA_of(k);
+    a.inv_alpha = C.ia_of(k);
+    a.bias = C.b_of(k);
+    a.h_in = (k == 0) ? C.state : C.hb[(k - 1) & 1];
+    a.h_out = (k == d.K - 1) ? C.state : C.hb[k & 1];
+    a.state = C.state;
+    a.rs_part = C.rs_part;
+    a.psum = C.psum;
+    a.psum_all = C.psum_all;
+    a.valid = C.valid;
+    a.out = h_out;
+    a.B = d.B; a.T = d.T; a.N = d.N; a.Bp = W.Bp; a.Fp = W.Fp; a.Np = W.Np;
+    a.numA = W.numA; a.KS = W.KS; a.tail_tile = W.nft_main;
+    a.Dtail = C.tail_of(k);
+    a.xtail = C.xtail;
+    a.xcur = C.xcur;
+    a.out_width = d.return_all_hidden ? d.N * d.K : d.N;
+    a.out_off = d.return_all_hidden ? k * d.N : 0;
+    a.write_out = (d.return_all_hidden || k == d.K - 1) ? 1 : 0;
+    return a;
+}
+
 // ---- Gram form (cell_gram.h): K-1 launches per frame --------------------------------------------
-static int32_t cell_forward_gram(drnmf_handle_t h, const drnmf_cell_desc_t* d, const float* x,
-                                 float mask_value, const void* params, const float* log_h0,
-                                 float u0_diag, float u0_off, float uk_off, float* h_out,
-                                 void* workspace, hipStream_t stream, const float* initial_state) {
-    const Workspace W = workspace_layout(d);
-    const ParamsLayout L = params_layout(d);
-    char* ws = (char*)workspace;
-    const char* pb = (const char*)params;
+// Enqueues the whole sequence on `stream`.
+static int32_t cell_forward_gram(drnmf_handle_t h, const CellCtx& C, const float* x, float mask_value,
+                                 const float* log_h0, float u0_diag, float u0_off, float uk_off,
+                                 float* h_out, hipStream_t stream, const float* initial_state) {
+    const drnmf_cell_desc_t* d = &C.d;
+    const Workspace& W = C.W;
     const int K = d->K, NAC = W.Np / 16, numO = W.numO, numM = W.Bp / ROWS;
-    unsigned char* valid = (unsigned char*)(ws + W.off_valid);
-    float* hb[2] = {(float*)(ws + W.off_h0), (float*)(ws + W.off_h1)};
-    float* state = (float*)(ws + W.off_state);
-    float* rs_part = (float*)(ws + W.off_rs);
-    float* qb[2] = {(float*)(ws + W.off_q0), (float*)(ws + W.off_q1)};
-    float* Cp = (float*)(ws + W.off_cp);
-    float* xpad = (float*)(ws + W.off_xpad);
-    int* tA = (int*)(ws + W.off_t);
-    int* tB = tA + 16;
     const size_t cstride = (size_t)W.Bp * W.Np;
-    auto ia_of = [&](int k) { return (const float*)(pb + L.off_inv_alpha) + (size_t)k * L.Np; };
-    auto b_of = [&](int k) { return (const float*)(pb + L.off_bias) + (size_t)k * L.Np; };
-    auto G_of = [&](int k) {
-        return (const float*)(pb + L.off_gram) + (d->n_D == 1 ? 0 : (size_t)k * L.Np * L.Np);
-    };
-    auto DnT_of = [&](int k) {
-        return (const float*)(pb + L.off_dnT) + (d->n_D == 1 ? 0 : (size_t)k * L.Np * L.Fp);
-    };
     // ---- prologue: validity flags, initial state, c_k for every frame and layer -------------------
     {
-        const size_t rows = (size_t)d->T * W.Bp;
-        hipLaunchKernelGGL(pack_input_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
-                           stream, x, (float*)(ws + W.off_xp), valid, mask_value, d->B, d->T, d->F,
-                           W.Bp, W.Fp);
-        hipLaunchKernelGGL(seen_kernel, dim3((W.Bp + 3) / 4), dim3(256), 0, stream, valid,
-                           (unsigned char*)(ws + W.off_seen), d->T, W.Bp);
-        if (initial_state)
-            hipLaunchKernelGGL(load_state_kernel, dim3((W.Bp + 3) / 4), dim3(256), 0, stream,
-                               initial_state, state, rs_part, tA, d->B, d->N, W.Np, W.Bp,
-                               (numO + 1) / 2);
-        else
-            hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(256), 0, stream, log_h0, state,
-                               rs_part, tA, d->N, W.Np, W.Bp, (numO + 1) / 2);
-        DRNMF_HIP(h, hipGetLastError());
+        int32_t rc = cell_prologue(h, C, x, mask_value, log_h0, initial_state, nullptr, (numO + 1) / 2, 0,
+                                   true, stream);
+        if (rc) return rc;
         // padded batch rows of c are never produced by the GEMM: keep them finite
         if (W.Bp != d->B)
-            DRNMF_HIP(h, hipMemsetAsync(Cp, 0, (size_t)W.cp_frames * K * cstride * 4, stream));
+            DRNMF_HIP(h, hipMemsetAsync(C.Cp, 0, (size_t)W.cp_frames * K * cstride * 4, stream));
     }
     // c_k of one block of GRAM_TB frames into its ring slot (stream-ordered behind the chain of the
     // block that used the slot before)
@@ -944,25 +983,22 @@ static int32_t cell_forward_gram(drnmf_handle_t h, const drnmf_cell_desc_t* d, c
         const int tbc = cp_full ? d->T : (d->T - t0 < GRAM_TB ? d->T - t0 : GRAM_TB);
         const size_t tot = (size_t)d->B * tbc * W.Fp;
         hipLaunchKernelGGL(gather_block_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
-                           stream, x, xpad, d->B, d->T, d->F, W.Fp, t0, tbc);
+                           stream, x, C.xpad, d->B, d->T, d->F, W.Fp, t0, tbc);
         DRNMF_HIP(h, hipGetLastError());
-        float* slot = Cp + (size_t)(t0 & cp_mask) * K * cstride;
-        if (d->n_D == K && K > 1) {      // untied: all layers in one product (EpiCPackAll)
-            gemm::Operands g{xpad, DnT_of(0), (int64_t)d->B * tbc, K * W.Np, W.Fp, W.Fp, W.Fp};
-            EpiCPackAll epi{slot, ia_of(0), b_of(0), tbc, K, NAC, W.Np, cstride};
+        float* slot = C.Cp + (size_t)(t0 & cp_mask) * K * cstride;
+        auto product = [&](int k, int cols, auto epi) -> int32_t {      // x Dn_k^T, `cols` atoms wide
+            gemm::Operands g{C.xpad, C.DnT_of(k), (int64_t)d->B * tbc, cols, W.Fp, W.Fp, W.Fp};
             DRNMF_HIP(h, gemm::launch(g, epi, stream));
             return DRNMF_OK;
-        }
-        if (d->n_D == 1 && K > 1) {      // tied: one product, K epilogue writes (EpiCPackTied)
-            gemm::Operands g{xpad, DnT_of(0), (int64_t)d->B * tbc, W.Np, W.Fp, W.Fp, W.Fp};
-            EpiCPackTied epi{slot, ia_of(0), b_of(0), tbc, K, NAC, W.Np, cstride};
-            DRNMF_HIP(h, gemm::launch(g, epi, stream));
-            return DRNMF_OK;
-        }
+        };
+        if (d->n_D == K && K > 1)        // untied: all layers in one product (EpiCPackAll)
+            return product(0, K * W.Np, EpiCPackAll{slot, C.ia_of(0), C.b_of(0), tbc, K, NAC, W.Np, cstride});
+        if (d->n_D == 1 && K > 1)        // tied: one product, K epilogue writes (EpiCPackTied)
+            return product(0, W.Np, EpiCPackTied{slot, C.ia_of(0), C.b_of(0), tbc, K, NAC, W.Np, cstride});
         for (int k = 0; k < K; ++k) {
-            gemm::Operands g{xpad, DnT_of(k), (int64_t)d->B * tbc, W.Np, W.Fp, W.Fp, W.Fp};
-            EpiCPack epi{slot + (size_t)k * cstride, ia_of(k), b_of(k), tbc, K, NAC, cstride};
-            DRNMF_HIP(h, gemm::launch(g, epi, stream));
+            int32_t rc = product(k, W.Np, EpiCPack{slot + (size_t)k * cstride, C.ia_of(k), C.b_of(k), tbc, K, NAC,
+                                                   cstride});
+            if (rc) return rc;
         }
         return DRNMF_OK;
     };
@@ -973,45 +1009,47 @@ static int32_t cell_forward_gram(drnmf_handle_t h, const drnmf_cell_desc_t* d, c
         if (rc) return rc;
         const size_t tot = cstride;
         hipLaunchKernelGGL(gram_init_q_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
-                           stream, state, Cp, qb[0], u0_diag, u0_off, tot);
+                           stream, C.state, C.Cp, C.qb[0], u0_diag, u0_off, tot);
         DRNMF_HIP(h, hipGetLastError());
     }
     const dim3 grid(8u * (unsigned)numM, (unsigned)(round_up(numO, 8) / 8));
-    auto make = [&](int k, int par) {
-        GramFwdArgs a;
+    // what a layer-step launch (GramFwdArgs) and a persistent launch (GramPersistArgs) are told alike
+    auto common = [&](auto& a) {
         memset(&a, 0, sizeof(a));
-        a.G = G_of(k);
-        a.a_in = (k == 1) ? qb[par] : hb[(k - 1) & 1];
-        a.ia = ia_of(k);
-        a.Cp = Cp;
-        a.h_out = hb[k & 1];
-        a.state = state;
-        a.qnext = qb[par ^ 1];
-        a.rs_part = rs_part;
-        a.psum = (float*)(ws + W.off_psum);
-        a.psum_all = (float*)(ws + W.off_psum_all);
-        a.valid = valid;
+        a.Cp = C.Cp;
+        a.state = C.state;
+        a.rs_part = C.rs_part;
+        a.psum = C.psum;
+        a.psum_all = C.psum_all;
+        a.valid = C.valid;
         a.out = h_out;
-        if (K == 2) {                    // one launch per frame: the two counters alternate
-            a.t_rd = par ? tB : tA; a.t_wr = par ? tA : tB; a.t_wr_add = 1;
-        } else if (k == 1) { a.t_rd = tB; a.t_wr = tA; a.t_wr_add = 0; }
-        else if (k == K - 1) { a.t_rd = tA; a.t_wr = tB; a.t_wr_add = 1; }
-        else { a.t_rd = tA; a.t_wr = nullptr; a.t_wr_add = 0; }
         a.u0d = u0_diag; a.u0o = u0_off; a.uko = uk_off;
-        a.B = d->B; a.T = d->T; a.N = d->N; a.K = K; a.k = k; a.Bp = W.Bp; a.Np = W.Np;
-        a.numO = numO;
+        a.B = d->B; a.T = d->T; a.N = d->N; a.K = K; a.Bp = W.Bp; a.Np = W.Np; a.numO = numO;
         a.out_width = d->return_all_hidden ? d->N * K : d->N;
         a.all_hidden = d->return_all_hidden ? 1 : 0;
-        a.par = par;
         a.cp_mask = cp_mask;
+    };
+    auto make = [&](int k, int par) {
+        GramFwdArgs a;
+        common(a);
+        a.G = C.G_of(k);
+        a.a_in = (k == 1) ? C.qb[par] : C.hb[(k - 1) & 1];
+        a.ia = C.ia_of(k);
+        a.h_out = C.hb[k & 1];
+        a.qnext = C.qb[par ^ 1];
+        if (K == 2) {                    // one launch per frame: the two counters alternate
+            a.t_rd = par ? C.tB : C.tA; a.t_wr = par ? C.tA : C.tB; a.t_wr_add = 1;
+        } else if (k == 1) { a.t_rd = C.tB; a.t_wr = C.tA; a.t_wr_add = 0; }
+        else if (k == K - 1) { a.t_rd = C.tA; a.t_wr = C.tB; a.t_wr_add = 1; }
+        else { a.t_rd = C.tA; a.t_wr = nullptr; a.t_wr_add = 0; }
+        a.k = k;
+        a.par = par;
         return a;
     };
-    uint32_t ub[3];
-    memcpy(&ub[0], &u0_diag, 4); memcpy(&ub[1], &u0_off, 4); memcpy(&ub[2], &uk_off, 4);
     const std::vector<uint64_t> key = {
         (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->N, (uint64_t)K, (uint64_t)d->n_D,
-        (uint64_t)d->return_all_hidden, (uint64_t)(uintptr_t)params, (uint64_t)(uintptr_t)h_out,
-        (uint64_t)(uintptr_t)workspace, ub[0], ub[1], ub[2]};
+        (uint64_t)d->return_all_hidden, (uint64_t)(uintptr_t)C.pb, (uint64_t)(uintptr_t)h_out,
+        (uint64_t)(uintptr_t)C.ws, f32_bits(u0_diag), f32_bits(u0_off), f32_bits(uk_off)};
     // one frame: K-1 launches; the frame's parity inside its block selects the q buffers
     auto frame = [&](Launcher& chain, int i) -> int32_t {
         for (int k = 1; k < K; ++k) {
@@ -1026,36 +1064,23 @@ static int32_t cell_forward_gram(drnmf_handle_t h, const drnmf_cell_desc_t* d, c
     // limits, or persistent launches of another stream still in flight on this handle keep the
     // launch-per-layer-step graphs.
     if (persist_shape_ok(h, numM, numO, K) && persist_admit(h, stream)) {
-        unsigned* bar = (unsigned*)(ws + W.off_t + 256);
         const int tb = cp_full ? d->T : GRAM_TB;          // frames per launch
         for (int j = 0; j * tb < d->T; ++j) {
             const int t0 = j * tb;
             const int t1 = (j + 1) * tb < d->T ? (j + 1) * tb : d->T;
             GramPersistArgs a;
-            memset(&a, 0, sizeof(a));
-            a.G = (const float*)(pb + L.off_gram);
-            a.g_stride = d->n_D == 1 ? 0 : (size_t)L.Np * L.Np;
-            a.ia = (const float*)(pb + L.off_inv_alpha);
-            a.Cp = Cp;
-            a.hb[0] = hb[0]; a.hb[1] = hb[1];
-            a.qb[0] = qb[0]; a.qb[1] = qb[1];
-            a.state = state;
-            a.rs_part = rs_part;
-            a.psum = (float*)(ws + W.off_psum);
-            a.psum_all = (float*)(ws + W.off_psum_all);
-            a.valid = valid;
-            a.out = h_out;
-            a.bar = bar;
+            common(a);
+            a.G = C.G_of(0);
+            a.g_stride = C.g_stride();
+            a.ia = C.ia_of(0);
+            a.hb[0] = C.hb[0]; a.hb[1] = C.hb[1];
+            a.qb[0] = C.qb[0]; a.qb[1] = C.qb[1];
+            a.bar = C.bar;
             a.host_flag = h->persist_flag;
-            a.u0d = u0_diag; a.u0o = u0_off; a.uko = uk_off;
-            a.B = d->B; a.T = d->T; a.N = d->N; a.K = K; a.Bp = W.Bp; a.Np = W.Np; a.numO = numO;
             a.numM = numM;
-            a.out_width = d->return_all_hidden ? d->N * K : d->N;
-            a.all_hidden = d->return_all_hidden ? 1 : 0;
             a.t0 = t0; a.nfr = t1 - t0;
-            a.cp_mask = cp_mask;
             a.nwait = persist_nwait(numO);
-            DRNMF_HIP(h, hipMemsetAsync(bar, 0, PERSIST_SYNC_BYTES, stream));   // arrivals, abort, XCC masks
+            DRNMF_HIP(h, hipMemsetAsync(C.bar, 0, PERSIST_SYNC_BYTES, stream));   // arrivals, abort, XCC masks
             void* kp[1] = {&a};
             DRNMF_HIP(h, hipLaunchKernel(pick_persist_fwd(NAC), dim3(8u * (unsigned)(numO * persist_rounds(numM))),
                                          dim3(64 * (NW_G + 1)), kp,
@@ -1081,270 +1106,94 @@ static int32_t cell_forward_gram(drnmf_handle_t h, const drnmf_cell_desc_t* d, c
     return DRNMF_OK;
 }
 
-// What one sub-batch of a split call still has to replay once its prologue is enqueued: the caller
-// interleaves the graph launches of all sub-batches (see the split branch of cell_forward_impl).
-struct FwdPlan {
-    hipGraphExec_t exec_n = nullptr, exec_1 = nullptr;
-    int fpg = 1, n_full = 0, n_rem = 0;
+// ---- factored form: one frame = 2K-1 launches, as a cached hipGraph ------------------------------
+// Everything that describes the chain of one call (or of one sub-batch of a split call), for its three
+// consumers: plain replay (replay_frames), the sub-batch plan (plan_frames) and the profile run
+// (drnmf_cell_profile).  The grids and make_a / make_b live inside `frame`.
+struct FwdChain {
+    std::vector<uint64_t> key;      // GraphKind::Forward
+    int fpg = 1;                    // frames per graph; the remainder T mod fpg runs on a one-frame graph
+    FrameFn frame;
 };
+// profile run: called ahead of every launch of a frame with its kind (0 = cell_a middle layer, 1 = cell_b, 2 = other)
+using MarkFn = std::function<hipError_t(int)>;
 
-static int32_t cell_forward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, const float* x,
-                                 float mask_value, const void* params, const float* log_h0,
-                                 float u0_diag, float u0_off, float uk_off, float* h_out,
-                                 void* workspace, size_t workspace_bytes, void* stream_,
-                                 int profile_frames, float* out_us,
-                                 const float* initial_state = nullptr, float* final_state = nullptr,
-                                 bool allow_split = true, FwdPlan* plan = nullptr) {
-    if (!h) return DRNMF_ERR_INVALID_ARG;
-    // (No implicit look at the handle's fault word here: a host-side read-and-clear at the entry of the
-    // NEXT call races with the stream-ordered drnmf_status_take_device of a training step -- the host
-    // could consume the word before the device-side guard of the fused Adam launch has seen it.  Faults
-    // are reported by drnmf_check_status / drnmf_status_take_device only.)
-    int rc = validate_cell_desc(h, d);
-    if (rc) return rc;
-    if (!plan) ++h->call_seq;        // (a top-level call: the graphs it takes are pinned until it returns)
-    if (d->divergence != DRNMF_DIV_ED)
-        DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED,
-                   "cell_forward is the reference's (Euclidean) cell; KL / beta: drnmf_cell_forward_ista");
-    if (!x || !params || !log_h0 || !h_out || !workspace)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "cell_forward: NULL pointer argument");
-    const Workspace W = workspace_layout(d, allow_split);
-    if (workspace_bytes < W.total)
-        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "cell_forward: workspace %zu < required %zu",
-                   workspace_bytes, W.total);
-    if (((uintptr_t)workspace & 255) || ((uintptr_t)params & 255))
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "workspace/params must be 256-byte aligned");
-    hipStream_t stream = (hipStream_t)stream_;
-    auto store_final = [&](const Workspace& Wl) -> int32_t {
-        if (!final_state) return DRNMF_OK;
-        const size_t tot = (size_t)d->B * d->N;
-        hipLaunchKernelGGL(store_state_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream,
-                           (const float*)((char*)workspace + Wl.off_state), final_state, d->B, d->N, Wl.Np);
-        DRNMF_HIP(h, hipGetLastError());
-        return DRNMF_OK;
-    };
-    if (W.gram) {
-        if (profile_frames > 0)
-            DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED,
-                       "cell_profile brackets the factored launches; this call takes the Gram form");
-        rc = cell_forward_gram(h, d, x, mask_value, params, log_h0, u0_diag, u0_off, uk_off,
-                               h_out, workspace, stream, initial_state);
-        return rc ? rc : store_final(W);
-    }
-    if (W.split > 1 && profile_frames <= 0) {
-        // ---- independent sub-batches on the caller's stream + side streams (Workspace::split) ----
-        for (int i = 0; i + 1 < W.split; ++i) {
-            if (!h->side_stream[i]) DRNMF_HIP(h, hipStreamCreateWithFlags(&h->side_stream[i], hipStreamNonBlocking));
-            if (!h->join_ev[i]) DRNMF_HIP(h, hipEventCreateWithFlags(&h->join_ev[i], hipEventDisableTiming));
-        }
-        if (!h->fork_ev) DRNMF_HIP(h, hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming));
-        DRNMF_HIP(h, hipEventRecord(h->fork_ev, stream));
-        const size_t width = (size_t)d->N * (d->return_all_hidden ? d->K : 1);
-        // (every sub-batch may take two graphs from the cache; entries taken by THIS call are pinned -- an
-        // insertion for a later sub-batch never retires an executable an earlier one's plan holds -- and
-        // cache hits cost nothing: room is made only when an entry is actually inserted)
-        int32_t first_err = DRNMF_OK;
-        // (from here on a failing HIP call is RECORDED and the code falls through to the join loop: side
-        // streams may already be writing h_out / the workspace, and the caller's stream must not run ahead
-        // of them -- ADVICE r4)
-        auto note = [&](hipError_t e, const char* what) {
-            if (e == hipSuccess || first_err) return;
-            first_err = DRNMF_ERR_HIP;
-            snprintf(h->err, sizeof(h->err), "cell_forward (split): %s failed: %s", what, hipGetErrorString(e));
-        };
-        FwdPlan plans[MAX_SPLIT];
-        hipStream_t sts[MAX_SPLIT];
-        int nsub = 0;
-        for (int sidx = 0; sidx < W.split && !first_err; ++sidx) {
-            const int b0 = sidx * W.split_rows;
-            if (b0 >= d->B) break;
-            drnmf_cell_desc_t ds = *d;
-            ds.B = (d->B - b0 < W.split_rows) ? d->B - b0 : W.split_rows;
-            hipStream_t st = sidx == 0 ? stream : h->side_stream[sidx - 1];
-            sts[sidx] = st;
-            nsub = sidx + 1;
-            if (sidx > 0) {
-                note(hipStreamWaitEvent(st, h->fork_ev, 0), "hipStreamWaitEvent");
-                if (first_err) break;
-            }
-            // prologue (input packing, initial state) enqueued; the frame graphs come back as a plan
-            const int32_t src = cell_forward_impl(
-                h, &ds, x + (size_t)b0 * d->T * d->F, mask_value, params, log_h0, u0_diag, u0_off, uk_off,
-                h_out + (size_t)b0 * d->T * width, (char*)workspace + (size_t)sidx * W.split_bytes,
-                W.split_bytes, (void*)st, 0, nullptr,
-                initial_state ? initial_state + (size_t)b0 * d->N : nullptr, nullptr, false, &plans[sidx]);
-            if (src && !first_err) first_err = src;
-            if (src) plans[sidx] = FwdPlan{};
-        }
-        // Round-robin over the sub-batches, one graph launch (a block of frames) each: a host that
-        // enqueued one sub-batch's whole sequence first would fill the hardware queue with it (T = 2000:
-        // ~100 k packets) and the side streams would only start when the first was nearly done --
-        // measured: the 250 x 2000 slab at 445 k frames/s, against 656 k with 200-frame sequences.
-        {
-            int most = 0;
-            for (int i = 0; i < nsub; ++i) most = plans[i].n_full > most ? plans[i].n_full : most;
-            for (int c = 0; c < most && !first_err; ++c)
-                for (int i = 0; i < nsub && !first_err; ++i)
-                    if (c < plans[i].n_full) note(hipGraphLaunch(plans[i].exec_n, sts[i]), "hipGraphLaunch");
-            most = 0;
-            for (int i = 0; i < nsub; ++i) most = plans[i].n_rem > most ? plans[i].n_rem : most;
-            for (int c = 0; c < most && !first_err; ++c)
-                for (int i = 0; i < nsub && !first_err; ++i)
-                    if (c < plans[i].n_rem) note(hipGraphLaunch(plans[i].exec_1, sts[i]), "hipGraphLaunch");
-        }
-        for (int sidx = 0; sidx < nsub; ++sidx) {
-            const int b0 = sidx * W.split_rows;
-            hipStream_t st = sts[sidx];
-            if (final_state && !first_err) {
-                drnmf_cell_desc_t ds = *d;
-                ds.B = (d->B - b0 < W.split_rows) ? d->B - b0 : W.split_rows;
-                const Workspace Ws = workspace_layout(&ds, false);
-                const size_t tot = (size_t)ds.B * d->N;
-                hipLaunchKernelGGL(store_state_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st,
-                                   (const float*)((char*)workspace + (size_t)sidx * W.split_bytes + Ws.off_state),
-                                   final_state + (size_t)b0 * d->N, ds.B, d->N, Ws.Np);
-                note(hipGetLastError(), "store_state_kernel launch");
-            }
-            // (join also after a failed sub-call: the caller's stream must not run ahead of side work)
-            if (sidx > 0) {
-                const hipError_t e1 = hipEventRecord(h->join_ev[sidx - 1], st);
-                note(e1, "hipEventRecord");
-                if (e1 == hipSuccess) note(hipStreamWaitEvent(stream, h->join_ev[sidx - 1], 0), "hipStreamWaitEvent");
-            }
-        }
-        return first_err;
-    }
-    const ParamsLayout L = params_layout(d);
-    char* ws = (char*)workspace;
-    const char* pb = (const char*)params;
-    float* xp = (float*)(ws + W.off_xp);
-    unsigned char* valid = (unsigned char*)(ws + W.off_valid);
-    float* rpart = (float*)(ws + W.off_rpart);
-    float* hb[2] = {(float*)(ws + W.off_h0), (float*)(ws + W.off_h1)};
-    f16* hb16[2] = {(f16*)(ws + W.off_h16_0), (f16*)(ws + W.off_h16_1)};
-    f16* r16 = (f16*)(ws + W.off_r16);
-    float* state = (float*)(ws + W.off_state);
-    float* rs_part = (float*)(ws + W.off_rs);
-    float* psum = (float*)(ws + W.off_psum);
-    int* tA = (int*)(ws + W.off_t);      // frame index read by every kernel of a frame
-    int* tB = tA + 16;                   // next frame index, published by the last kernel
-    const int K = d->K;
-    const bool half = d->operand_f16 != 0;
-
-    // ---- per-call prologue ------------------------------------------------------------------
+// Enqueues the factored form's prologue on `stream` and describes its chain.
+static int32_t factored_start(drnmf_handle_t h, const CellCtx& C, const float* x, float mask_value,
+                              const float* log_h0, float u0_diag, float u0_off, float uk_off,
+                              float* h_out, hipStream_t stream, const float* initial_state,
+                              FwdChain* out, MarkFn mark = [](int) { return hipSuccess; }) {
+    // (the frame callable outlives this function: it refers to the caller's context, which must outlive the
+    // chain, and holds copies of everything else)
+    const drnmf_cell_desc_t& d = C.d;
+    const Workspace& W = C.W;
+    const int K = d.K;
+    const bool half = C.half;
     {
-        const size_t rows = (size_t)d->T * W.Bp;
-        hipLaunchKernelGGL(pack_input_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
-                           stream, x, xp, valid, mask_value, d->B, d->T, d->F, W.Bp, W.Fp,
-                           half ? (f16*)(ws + W.off_xp16) : (f16*)nullptr);
-        hipLaunchKernelGGL(seen_kernel, dim3((W.Bp + 3) / 4), dim3(256), 0, stream, valid,
-                           (unsigned char*)(ws + W.off_seen), d->T, W.Bp);
-        if (initial_state)
-            hipLaunchKernelGGL(load_state_kernel, dim3((W.Bp + 3) / 4), dim3(256), 0, stream,
-                               initial_state, state, rs_part, tA, d->B, d->N, W.Np, W.Bp, round_up(W.numA, 4), 1);
-        else
-            hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(256), 0, stream, log_h0, state,
-                               rs_part, tA, d->N, W.Np, W.Bp, round_up(W.numA, 4), 1);
-        DRNMF_HIP(h, hipGetLastError());
+        int32_t rc = cell_prologue(h, C, x, mask_value, log_h0, initial_state, C.xp16, round_up(W.numA, 4), 1,
+                                   true, stream);
+        if (rc) return rc;
         // fp16 mode: cell_b writes the MFMA bin tiles of Rp16 only; the padding of the last 32-bin
         // chunk (and the odd-bin tile) must be finite: it meets zero dictionary slots
-        if (half) DRNMF_HIP(h, hipMemsetAsync(r16, 0, (size_t)W.Bp * W.Fp * 2, stream));
+        if (half) DRNMF_HIP(h, hipMemsetAsync(C.r16, 0, (size_t)W.Bp * W.Fp * 2, stream));
         // training: the saved residuals' padding bins (past the odd bins) are never written
-        if (W.off_rsave != 0 && W.ntail > 0)
-            DRNMF_HIP(h, hipMemsetAsync(ws + W.off_rsave, 0,
-                                        (size_t)(K - 1) * d->B * d->T * W.Fp * 4, stream));
+        if (C.rsave && W.ntail > 0)
+            DRNMF_HIP(h, hipMemsetAsync(C.rsave, 0, (size_t)(K - 1) * d.B * d.T * W.Fp * 4, stream));
     }
 
-    // ---- one frame = 2K-1 launches, as a cached hipGraph -------------------------------------
     // measurement aid: DRNMF_ABLATE=1 launches the same grids but every workgroup exits at once
     // (launch/boundary floor of the frame graph; results are garbage)
     const bool ablate = measure_env("DRNMF_ABLATE") != nullptr;
-    uint32_t ub[3];
-    memcpy(&ub[0], &u0_diag, 4); memcpy(&ub[1], &u0_off, 4); memcpy(&ub[2], &uk_off, 4);
-    const std::vector<uint64_t> key = {
-        (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->N, (uint64_t)d->K,
-        (uint64_t)d->n_D, (uint64_t)d->return_all_hidden + 2 * (uint64_t)(d->operand_f16 != 0),
-        (uint64_t)(uintptr_t)params,
-        (uint64_t)(uintptr_t)h_out, (uint64_t)(uintptr_t)workspace, (uint64_t)ablate,
+    out->key = {
+        (uint64_t)d.B, (uint64_t)d.T, (uint64_t)d.F, (uint64_t)d.N, (uint64_t)d.K,
+        (uint64_t)d.n_D, (uint64_t)d.return_all_hidden + 2 * (uint64_t)(d.operand_f16 != 0),
+        (uint64_t)(uintptr_t)C.pb,
+        (uint64_t)(uintptr_t)h_out, (uint64_t)(uintptr_t)C.ws, (uint64_t)ablate,
         // the layout choices baked into the nodes: a sub-batch of a split call and a direct call of the same
         // B take different row blockings (workspace_layout's `need`), and the tuning variables move them too
         (uint64_t)W.RB | ((uint64_t)W.RBa << 8) | ((uint64_t)W.KS << 16) | ((uint64_t)W.nch_ks << 24),
-        ub[0], ub[1], ub[2]};
+        f32_bits(u0_diag), f32_bits(u0_off), f32_bits(uk_off)};
     // frames per graph: the kernels advance the device-side frame counters themselves, so a
     // graph may hold several frames' worth of nodes (fewer graph launches from the host)
     // (measured at the C2 shape: 1 / 2 / 4 / 8 / 20 frames per graph -> 251.1k / 253.9k / 255.6k /
     // 256.1k / 256.3k frames/s).  The remainder T mod FPG runs on a one-frame graph.
-    int fpg_max = 800 / (2 * d->K - 1);      // ~800 kernel nodes per graph
-    fpg_max = fpg_max < 1 ? 1 : (fpg_max > 64 ? 64 : fpg_max);
+    out->fpg = frames_per_graph(800, 2 * d.K - 1, 64);      // ~800 kernel nodes per graph
     if (const char* e = tune_env("DRNMF_FPG")) {
         const int v = atoi(e);
-        if (v >= 1 && v <= 64) fpg_max = v;
+        if (v >= 1 && v <= 64) out->fpg = v;
     }
-    if (fpg_max > d->T) fpg_max = d->T;
+    if (out->fpg > d.T) out->fpg = d.T;
 
     const int numM = W.Bp / (ROWS * W.RB), nft = W.nft_main;   // MFMA bin tiles (tail bins handled apart)
     const dim3 grid_a(8u * (unsigned)(W.Bp / (ROWS * W.RBa)), (unsigned)(round_up(W.numA, 8) / 8));
     const dim3 grid_b(8u * (unsigned)numM, (unsigned)(round_up(nft * W.KS, 8) / 8));
     const bool qred = qred_wanted(W.numA, W.ntail, nft, W.KS, W.RB);
-    // per stored layer: the fp32 packing of cell_b (Fp*Np*4 bytes; cell_a's lies at off_dnA), or the ONE
-    // fp16 packing both kernels read (Fp*Np*2 bytes)
-    const char* Dn_base = pb + L.off_dn;
-    const size_t dstride = (size_t)L.Fp * L.Np * (half ? 2 : 4);
-    auto Dn_of = [&](int k) { return Dn_base + (d->n_D == 1 ? 0 : (size_t)k * dstride); };
-    auto DnB_of = [&](int k) { return Dn_of(k); };
-    auto DnA_of = [&](int k) {      // cell_a's operand: the fp16 packing again, or the fp32 cell_a packing
-        return half ? Dn_of(k) : pb + L.off_dnA + (d->n_D == 1 ? 0 : (size_t)k * dstride);
-    };
-    auto tail_of = [&](int k) {
-        return (const float*)(pb + L.off_tail) + (d->n_D == 1 ? 0 : (size_t)k * MAX_TAIL * L.Np);
-    };
 
     // fp16 mode, untied layers: the cell_a launch ahead of a cell_b prefetches that cell_b's dictionary
     // (cell_a_kernel's fifth wave; DRNMF_PF=0 switches it off: measurement aid)
-    const bool pf_on = half && d->n_D == K && K > 1 && !(measure_env("DRNMF_PF") && atoi(measure_env("DRNMF_PF")) == 0);
-    auto make_a = [&](int k) {
-        CellAArgs a;
-        a.Dn = DnA_of(k);
-        a.inv_alpha = (const float*)(pb + L.off_inv_alpha) + (size_t)k * L.Np;
-        a.bias = (const float*)(pb + L.off_bias) + (size_t)k * L.Np;
-        a.rsrc = (k == 0) ? xp : (half ? (const float*)r16 : rpart);
-        a.h_in = (k == 0) ? state : hb[(k - 1) & 1];
-        a.h_out = (k == K - 1) ? state : hb[k & 1];
-        a.h16_out = hb16[k & 1];
-        a.state = state;
-        a.rs_part = rs_part;
-        a.psum = psum;
-        a.psum_all = (float*)(ws + W.off_psum_all);
-        a.valid = valid;
-        a.out = h_out;
+    const bool pf_on = half && d.n_D == K && K > 1 && !(measure_env("DRNMF_PF") && atoi(measure_env("DRNMF_PF")) == 0);
+    auto make_a = [=, &C, &W, &d](int k) {
+        CellAArgs a = cell_a_common(C, k, h_out);
+        a.rsrc = (k == 0) ? C.xp : (half ? (const float*)C.r16 : C.rpart);
+        a.h16_out = C.hb16[k & 1];
         // frame counters: the first kernel of a frame reads tB and republishes it as tA; the last
         // publishes tB = t+1; nobody reads a counter in the kernel that writes it.  K == 1 has a
         // single kernel per frame and uses the separate advance kernel instead.
-        if (K == 1) { a.t_rd = tA; a.t_wr = nullptr; a.t_wr_add = 0; }
-        else if (k == 0) { a.t_rd = tB; a.t_wr = tA; a.t_wr_add = 0; }
-        else if (k == K - 1) { a.t_rd = tA; a.t_wr = tB; a.t_wr_add = 1; }
-        else { a.t_rd = tA; a.t_wr = nullptr; a.t_wr_add = 0; }
+        if (K == 1) { a.t_rd = C.tA; a.t_wr = nullptr; a.t_wr_add = 0; }
+        else if (k == 0) { a.t_rd = C.tB; a.t_wr = C.tA; a.t_wr_add = 0; }
+        else if (k == K - 1) { a.t_rd = C.tA; a.t_wr = C.tB; a.t_wr_add = 1; }
+        else { a.t_rd = C.tA; a.t_wr = nullptr; a.t_wr_add = 0; }
         a.u0d = u0_diag; a.u0o = u0_off; a.uko = uk_off;
-        a.B = d->B; a.T = d->T; a.N = d->N; a.Bp = W.Bp; a.Fp = W.Fp; a.Np = W.Np;
-        a.numA = W.numA; a.nchunks = half ? (nft + 1) / 2 : nft; a.KS = W.KS; a.ntail = W.ntail;
-        a.tail_tile = nft;
-        a.Dtail = tail_of(k);
-        a.Dtail_next = tail_of(k + 1 < K ? k + 1 : k);
-        float* qp = (float*)(ws + W.off_qpart);
+        a.nchunks = half ? (nft + 1) / 2 : nft; a.ntail = W.ntail;
+        a.Dtail_next = C.tail_of(k + 1 < K ? k + 1 : k);
         const size_t qstride = (size_t)W.numA * MAX_TAIL * W.Bp;
-        a.q_in = qred ? (const float*)(ws + W.off_qsum)   // layer k-1's partials, summed by cell_b
-                      : qp + (size_t)((k + 1) & 1) * qstride;
-        a.q_out = qp + (size_t)(k & 1) * qstride;
-        a.xtail = (float*)(ws + W.off_xtail);
-        a.xcur = (float*)(ws + W.off_xcur);
-        a.out_width = d->return_all_hidden ? d->N * K : d->N;
-        a.out_off = d->return_all_hidden ? k * d->N : 0;
-        a.write_out = (d->return_all_hidden || k == K - 1) ? 1 : 0;
+        a.q_in = qred ? (const float*)C.qsum   // layer k-1's partials, summed by cell_b
+                      : C.qpart + (size_t)((k + 1) & 1) * qstride;
+        a.q_out = C.qpart + (size_t)(k & 1) * qstride;
 #ifdef DRNMF_MEASURE
         a.ablate = tune_env("DRNMF_ABLATE_A") ? atoi(tune_env("DRNMF_ABLATE_A")) : 0;
 #endif
-        a.Rsave = (W.off_rsave != 0 && k >= 1)
-                      ? (float*)(ws + W.off_rsave) + (size_t)(k - 1) * d->B * d->T * W.Fp : nullptr;
+        a.Rsave = (C.rsave && k >= 1) ? C.rsave + (size_t)(k - 1) * d.B * d.T * W.Fp : nullptr;
         // fp16 mode, a cell_b launch behind this one: its dictionary goes into the L2s meanwhile
         a.Dn_pf = nullptr;
         a.pf_tiles = nft;
@@ -1352,17 +1201,17 @@ static int32_t cell_forward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, c
         // latency-critical part.  Delay in units of 512 cycles, us per launch at the config-5 shape:
         // 0 8.58-8.62, 2 8.58, 4 8.55, 8 8.47, 12 8.42, 16 8.54, 24 9.28, 32 10.2; no prefetch 8.82)
         a.pf_sleep = measure_env("DRNMF_PF_SLEEP") ? atoi(measure_env("DRNMF_PF_SLEEP")) : 10;
-        a.x16 = half ? (const f16*)(ws + W.off_xp16) : nullptr;
-        if (pf_on && k + 1 < K) a.Dn_pf = DnB_of(k + 1);
+        a.x16 = C.xp16;
+        if (pf_on && k + 1 < K) a.Dn_pf = C.Dn_of(k + 1);
         return a;
     };
-    auto make_b = [&](int k) {   // between layer k and k+1
+    auto make_b = [=, &C, &W](int k) {   // between layer k and k+1
         CellBArgs b;
-        b.Dn_next = DnB_of(k + 1);
-        b.h = half ? (const float*)hb16[k & 1] : hb[k & 1];
-        b.xp = (const float*)(ws + W.off_xcur);
-        b.rpart = half ? (float*)r16 : rpart;
-        b.t_rd = tA;
+        b.Dn_next = C.Dn_of(k + 1);
+        b.h = half ? (const float*)C.hb16[k & 1] : C.hb[k & 1];
+        b.xp = C.xcur;
+        b.rpart = half ? (float*)C.r16 : C.rpart;
+        b.t_rd = C.tA;
         b.Bp = W.Bp; b.Fp = W.Fp; b.Np = W.Np; b.nft = nft; b.KS = W.KS;
         b.logKS = 0;
         while ((1 << b.logKS) < W.KS) ++b.logKS;
@@ -1370,34 +1219,20 @@ static int32_t cell_forward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, c
 #ifdef DRNMF_MEASURE
         b.ablate = tune_env("DRNMF_ABLATE_B") ? atoi(tune_env("DRNMF_ABLATE_B")) : 0;
 #endif
-        b.q_in = (const float*)(ws + W.off_qpart) + (size_t)(k & 1) * W.numA * MAX_TAIL * W.Bp;
-        b.qsum = (float*)(ws + W.off_qsum);
+        b.q_in = C.qpart + (size_t)(k & 1) * W.numA * MAX_TAIL * W.Bp;
+        b.qsum = C.qsum;
         b.numA = W.numA; b.ntail = W.ntail;
         return b;
     };
-
-
-    // profile mode (drnmf_cell_profile): plain launches, each bracketed by a HIP event on the stream
-    std::vector<hipEvent_t> ev;
-    std::vector<int> kind;   // 0 = cell_a middle layer, 1 = cell_b, 2 = other
-    auto mark = [&](int k_) -> hipError_t {
-        if (profile_frames <= 0) return hipSuccess;
-        hipEvent_t e;
-        hipError_t er = hipEventCreate(&e);
-        if (er != hipSuccess) return er;
-        ev.push_back(e);
-        kind.push_back(k_);
-        return hipEventRecord(e, stream);
-    };
     // one frame = 2K-1 launches (K = 1: cell_a and the frame-counter advance)
-    auto frame = [&](Launcher& chain, int) -> int32_t {
+    out->frame = [=, &C, &W, &d](Launcher& chain, int) -> int32_t {
         for (int k = 0; k < K; ++k) {
             CellAArgs a = make_a(k);
             CellAParams ka(a);
             DRNMF_HIP(h, mark((k > 0 && k < K - 1) ? 0 : 2));
             DRNMF_HIP(h, chain.add(ablate ? (void*)&noop_kernel
                                           : pick_a_func(a.nchunks, W.KS, W.RBa, k == 0, k == K - 1,
-                                                        d->return_all_hidden != 0, half, qred),
+                                                        d.return_all_hidden != 0, half, qred),
                                    grid_a, 64 * (NW_A + (half ? 1 : 0)), ka.p));
             if (k < K - 1) {
                 CellBArgs b = make_b(k);
@@ -1408,65 +1243,156 @@ static int32_t cell_forward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, c
             }
         }
         if (K == 1) {
-            int* tp = tA;
+            int* tp = C.tA;
             void* kt[1] = {&tp};
             DRNMF_HIP(h, mark(2));
             DRNMF_HIP(h, chain.add((void*)&advance_frame_kernel, dim3(1), 1, kt));
         }
         return DRNMF_OK;
     };
-
-    if (profile_frames > 0) {
-        const int T_run = profile_frames < d->T ? profile_frames : d->T;
-        Launcher direct{nullptr, stream};
-        for (int t = 0; t < T_run; ++t) {
-            rc = frame(direct, t);
-            if (rc) return rc;
-        }
-        DRNMF_HIP(h, mark(3));
-        DRNMF_HIP(h, hipGetLastError());
-        DRNMF_HIP(h, hipStreamSynchronize(stream));
-        double sum[3] = {0, 0, 0};
-        long cnt[3] = {0, 0, 0};
-        const size_t per_frame = (ev.size() - 1) / (size_t)T_run;
-        const size_t skip = T_run > 1 ? per_frame : 0;          // first frame = warm-up
-        for (size_t i = skip; i + 1 < ev.size(); ++i) {
-            float ms = 0.f;
-            DRNMF_HIP(h, hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-            if (kind[i] < 2) { sum[kind[i]] += ms; cnt[kind[i]]++; }
-            sum[2] += ms;
-        }
-        const int frames_timed = T_run > 1 ? T_run - 1 : 1;
-        if (out_us) {
-            out_us[0] = cnt[0] ? (float)(sum[0] / cnt[0] * 1e3) : 0.f;
-            out_us[1] = cnt[1] ? (float)(sum[1] / cnt[1] * 1e3) : 0.f;
-            out_us[2] = (float)(sum[2] / frames_timed * 1e3);
-        }
-        for (auto e : ev) (void)hipEventDestroy(e);
-        return store_final(W);
-    }
-    if (plan && !tune_env("DRNMF_NO_GRAPH")) {
-        // (both executables stay pinned by this call until the caller has enqueued their launches)
-        rc = graph_cache_get(h, stream, GraphKind::Forward, key, fpg_max, frame, &plan->exec_n);
-        if (rc) return rc;
-        plan->fpg = fpg_max;
-        plan->n_full = d->T / fpg_max;
-        plan->n_rem = d->T % fpg_max;
-        return plan->n_rem ? graph_cache_get(h, stream, GraphKind::Forward, key, 1, frame, &plan->exec_1) : DRNMF_OK;
-    }
-    rc = replay_frames(h, stream, GraphKind::Forward, key, {fpg_max, 1}, 0, d->T, frame);
-    return rc ? rc : store_final(W);
+    return DRNMF_OK;
 }
 
-extern "C" int32_t drnmf_cell_forward(drnmf_handle_t h, const drnmf_cell_desc_t* d, const float* x,
-                                      float mask_value, const void* params, const float* log_h0,
-                                      float u0_diag, float u0_off, float uk_off, float* h_out,
-                                      void* workspace, size_t workspace_bytes, void* stream_) {
-    DRNMF_LOCK(h);
-    return cell_forward_impl(h, d, x, mask_value, params, log_h0, u0_diag, u0_off, uk_off, h_out,
-                             workspace, workspace_bytes, stream_, 0, nullptr);
+// What one sub-batch of a split call still has to replay once its prologue is enqueued: the caller
+// interleaves the graph launches of all sub-batches (cell_forward_split).  Empty: nothing left.
+struct FwdPlan {      // [0]: graphs of FwdChain::fpg frames, [1]: one-frame graphs for the remainder
+    hipGraphExec_t exec[2] = {nullptr, nullptr};
+    int n[2] = {0, 0};
+};
+static int32_t plan_frames(drnmf_handle_t h, hipStream_t stream, const FwdChain& ch, int T, FwdPlan* plan) {
+    if (tune_env("DRNMF_NO_GRAPH"))
+        return replay_frames(h, stream, GraphKind::Forward, ch.key, {ch.fpg, 1}, 0, T, ch.frame);
+    // (both executables stay pinned by this call until the caller has enqueued their launches)
+    int32_t rc = graph_cache_get(h, stream, GraphKind::Forward, ch.key, ch.fpg, ch.frame, &plan->exec[0]);
+    if (rc) return rc;
+    plan->n[0] = T / ch.fpg;
+    plan->n[1] = T % ch.fpg;
+    return plan->n[1] ? graph_cache_get(h, stream, GraphKind::Forward, ch.key, 1, ch.frame, &plan->exec[1]) : DRNMF_OK;
 }
 
+// ---- independent sub-batches on the caller's stream + side streams (Workspace::split) ----
+// Every sub-batch chooses its own form: a Gram sub-batch enqueues its whole sequence on its stream at
+// once and leaves an empty plan.
+static int32_t cell_forward_split(drnmf_handle_t h, const drnmf_cell_desc_t* d, const Workspace& W,
+                                  const float* x, float mask_value, const void* params, const float* log_h0,
+                                  float u0_diag, float u0_off, float uk_off, float* h_out, void* workspace,
+                                  hipStream_t stream, const float* initial_state, float* final_state) {
+    for (int i = 0; i + 1 < W.split; ++i) {
+        if (!h->side_stream[i]) DRNMF_HIP(h, hipStreamCreateWithFlags(&h->side_stream[i], hipStreamNonBlocking));
+        if (!h->join_ev[i]) DRNMF_HIP(h, hipEventCreateWithFlags(&h->join_ev[i], hipEventDisableTiming));
+    }
+    if (!h->fork_ev) DRNMF_HIP(h, hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming));
+    DRNMF_HIP(h, hipEventRecord(h->fork_ev, stream));
+    const size_t width = (size_t)d->N * (d->return_all_hidden ? d->K : 1);
+    const ParamsLayout L = params_layout(d);
+    // (every sub-batch may take two graphs from the cache; entries taken by THIS call are pinned -- an
+    // insertion for a later sub-batch never retires an executable an earlier one's plan holds -- and
+    // cache hits cost nothing: room is made only when an entry is actually inserted)
+    int32_t first_err = DRNMF_OK;
+    // (from here on a failing HIP call is RECORDED and the code falls through to the join loop: side
+    // streams may already be writing h_out / the workspace, and the caller's stream must not run ahead
+    // of them -- ADVICE r4)
+    auto note = [&](hipError_t e, const char* what) {
+        if (e == hipSuccess || first_err) return;
+        first_err = DRNMF_ERR_HIP;
+        snprintf(h->err, sizeof(h->err), "cell_forward (split): %s failed: %s", what, hipGetErrorString(e));
+    };
+    std::vector<CellCtx> subs;       // (built once per sub-batch; its chain and its final store refer to it)
+    subs.reserve(MAX_SPLIT);
+    FwdPlan plans[MAX_SPLIT];
+    hipStream_t sts[MAX_SPLIT];
+    int nsub = 0;
+    for (int sidx = 0; sidx < W.split && !first_err; ++sidx) {
+        const int b0 = sidx * W.split_rows;
+        if (b0 >= d->B) break;
+        hipStream_t st = sidx == 0 ? stream : h->side_stream[sidx - 1];
+        sts[sidx] = st;
+        nsub = sidx + 1;
+        if (sidx > 0) {
+            note(hipStreamWaitEvent(st, h->fork_ev, 0), "hipStreamWaitEvent");
+            if (first_err) break;
+        }
+        // prologue (input packing, initial state) enqueued; the frame graphs come back as a plan
+        drnmf_cell_desc_t ds = *d;
+        ds.B = (d->B - b0 < W.split_rows) ? d->B - b0 : W.split_rows;
+        subs.push_back(CellCtx{ds, workspace_layout(&ds, false), L, (char*)workspace + (size_t)sidx * W.split_bytes,
+                               (const char*)params});
+        const CellCtx& Cs = subs.back();
+        const float* xs = x + (size_t)b0 * d->T * d->F;
+        float* hs = h_out + (size_t)b0 * d->T * width;
+        const float* is = initial_state ? initial_state + (size_t)b0 * d->N : nullptr;
+        int32_t src;
+        if (Cs.W.total > W.split_bytes) {
+            // (the slices are sized for split_rows rows; a smaller last sub-batch may take the Gram form, whose
+            // ring of hoisted c_k can outgrow its slice: refused before anything of it is enqueued)
+            snprintf(h->err, sizeof(h->err), "cell_forward: workspace %zu < required %zu", W.split_bytes, Cs.W.total);
+            src = DRNMF_ERR_WORKSPACE;
+        } else if (Cs.W.gram) {
+            src = cell_forward_gram(h, Cs, xs, mask_value, log_h0, u0_diag, u0_off, uk_off, hs, st, is);
+        } else {
+            FwdChain ch;
+            src = factored_start(h, Cs, xs, mask_value, log_h0, u0_diag, u0_off, uk_off, hs, st, is, &ch);
+            if (!src) src = plan_frames(h, st, ch, d->T, &plans[sidx]);
+        }
+        if (src && !first_err) first_err = src;
+        if (src) plans[sidx] = FwdPlan{};
+    }
+    // Round-robin over the sub-batches, one graph launch (a block of frames) each: a host that
+    // enqueued one sub-batch's whole sequence first would fill the hardware queue with it (T = 2000:
+    // ~100 k packets) and the side streams would only start when the first was nearly done --
+    // measured: the 250 x 2000 slab at 445 k frames/s, against 656 k with 200-frame sequences.
+    for (int g = 0; g < 2; ++g) {
+        int most = 0;
+        for (int i = 0; i < nsub; ++i) most = plans[i].n[g] > most ? plans[i].n[g] : most;
+        for (int c = 0; c < most && !first_err; ++c)
+            for (int i = 0; i < nsub && !first_err; ++i)
+                if (c < plans[i].n[g]) note(hipGraphLaunch(plans[i].exec[g], sts[i]), "hipGraphLaunch");
+    }
+    for (int sidx = 0; sidx < nsub; ++sidx) {
+        hipStream_t st = sts[sidx];
+        if (final_state && !first_err)
+            note(store_final_state(subs[sidx], final_state + (size_t)sidx * W.split_rows * d->N, st),
+                 "store_state_kernel launch");
+        // (join also after a failed sub-call: the caller's stream must not run ahead of side work)
+        if (sidx > 0) {
+            const hipError_t e1 = hipEventRecord(h->join_ev[sidx - 1], st);
+            note(e1, "hipEventRecord");
+            if (e1 == hipSuccess) note(hipStreamWaitEvent(stream, h->join_ev[sidx - 1], 0), "hipStreamWaitEvent");
+        }
+    }
+    return first_err;
+}
+
+// What the forward entries check before they enqueue anything; *W: the call's layout.  ista: the KL / beta
+// cell's entry, else the reference's (Euclidean) cell.  `what` names the entry.
+static int32_t cell_forward_validate(drnmf_handle_t h, const drnmf_cell_desc_t* d, bool ista, const float* x,
+                                     const void* params, const float* log_h0, float* h_out, void* workspace,
+                                     size_t workspace_bytes, Workspace* W, const char* what) {
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    // (No implicit look at the handle's fault word here: a host-side read-and-clear at the entry of the
+    // NEXT call races with the stream-ordered drnmf_status_take_device of a training step -- the host
+    // could consume the word before the device-side guard of the fused Adam launch has seen it.  Faults
+    // are reported by drnmf_check_status / drnmf_status_take_device only.)
+    int rc = validate_cell_desc(h, d);
+    if (rc) return rc;
+    if (ista && d->divergence != DRNMF_DIV_KL && d->divergence != DRNMF_DIV_BETA)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: d->divergence must be DRNMF_DIV_KL or DRNMF_DIV_BETA", what);
+    if (!ista && d->divergence != DRNMF_DIV_ED)
+        DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED,
+                   "%s is the reference's (Euclidean) cell; KL / beta: drnmf_cell_forward_ista", what);
+    if (!x || !params || !log_h0 || !h_out || !workspace)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: NULL pointer argument", what);
+    *W = workspace_layout(d);
+    if (workspace_bytes < W->total)
+        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "%s: workspace %zu < required %zu", what, workspace_bytes, W->total);
+    if (((uintptr_t)workspace & 255) || ((uintptr_t)params & 255))
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "workspace/params must be 256-byte aligned");
+    ++h->call_seq;                   // (a top-level call: the graphs it takes are pinned until it returns)
+    return DRNMF_OK;
+}
+
+// Entry of the reference cell's forward: validation, then the form the layout chose.  initial_state NULL:
+// softplus(log_h0); final_state NULL: not wanted.
 extern "C" int32_t drnmf_cell_forward_stateful(drnmf_handle_t h, const drnmf_cell_desc_t* d,
                                                const float* x, float mask_value, const void* params,
                                                const float* log_h0, float u0_diag, float u0_off,
@@ -1474,22 +1400,96 @@ extern "C" int32_t drnmf_cell_forward_stateful(drnmf_handle_t h, const drnmf_cel
                                                float* final_state, float* h_out, void* workspace,
                                                size_t workspace_bytes, void* stream_) {
     DRNMF_LOCK(h);
-    return cell_forward_impl(h, d, x, mask_value, params, log_h0, u0_diag, u0_off, uk_off, h_out,
-                             workspace, workspace_bytes, stream_, 0, nullptr, initial_state, final_state);
+    Workspace W;
+    int32_t rc = cell_forward_validate(h, d, false, x, params, log_h0, h_out, workspace, workspace_bytes, &W,
+                                       "cell_forward");
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (W.split > 1)            // (never the Gram form: workspace_layout)
+        return cell_forward_split(h, d, W, x, mask_value, params, log_h0, u0_diag, u0_off, uk_off, h_out,
+                                  workspace, stream, initial_state, final_state);
+    const CellCtx C{*d, W, params_layout(d), (char*)workspace, (const char*)params};
+    if (W.gram) {
+        rc = cell_forward_gram(h, C, x, mask_value, log_h0, u0_diag, u0_off, uk_off, h_out, stream,
+                               initial_state);
+    } else {
+        FwdChain ch;
+        rc = factored_start(h, C, x, mask_value, log_h0, u0_diag, u0_off, uk_off, h_out, stream,
+                            initial_state, &ch);
+        if (!rc) rc = replay_frames(h, stream, GraphKind::Forward, ch.key, {ch.fpg, 1}, 0, d->T, ch.frame);
+    }
+    if (rc) return rc;
+    DRNMF_HIP(h, store_final_state(C, final_state, stream));
+    return DRNMF_OK;
 }
 
+extern "C" int32_t drnmf_cell_forward(drnmf_handle_t h, const drnmf_cell_desc_t* d, const float* x,
+                                      float mask_value, const void* params, const float* log_h0,
+                                      float u0_diag, float u0_off, float uk_off, float* h_out,
+                                      void* workspace, size_t workspace_bytes, void* stream_) {
+    return drnmf_cell_forward_stateful(h, d, x, mask_value, params, log_h0, u0_diag, u0_off, uk_off, nullptr,
+                                       nullptr, h_out, workspace, workspace_bytes, stream_);
+}
+
+// Profile run: the factored chain as plain launches, each bracketed by a HIP event on the stream.  A batch
+// large enough to split is profiled unsplit, on the layout of the whole call.
 extern "C" int32_t drnmf_cell_profile(drnmf_handle_t h, const drnmf_cell_desc_t* d, const float* x,
                                       float mask_value, const void* params, const float* log_h0,
                                       float u0_diag, float u0_off, float uk_off, float* h_out,
                                       void* workspace, size_t workspace_bytes, void* stream_,
-                                      int32_t frames, float* out_us_host) {
+                                      int32_t frames, float* out_us) {
     DRNMF_LOCK(h);
-    if (frames <= 0 || !out_us_host) {
+    if (frames <= 0 || !out_us) {
         if (h) snprintf(h->err, sizeof(h->err), "cell_profile: frames must be > 0, out non-NULL");
         return DRNMF_ERR_INVALID_ARG;
     }
-    return cell_forward_impl(h, d, x, mask_value, params, log_h0, u0_diag, u0_off, uk_off, h_out,
-                             workspace, workspace_bytes, stream_, frames, out_us_host);
+    Workspace W;
+    int32_t rc = cell_forward_validate(h, d, false, x, params, log_h0, h_out, workspace, workspace_bytes, &W,
+                                       "cell_forward");
+    if (rc) return rc;
+    if (W.gram)
+        DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED,
+                   "cell_profile brackets the factored launches; this call takes the Gram form");
+    hipStream_t stream = (hipStream_t)stream_;
+    std::vector<hipEvent_t> ev;
+    std::vector<int> kind;   // 0 = cell_a middle layer, 1 = cell_b, 2 = other
+    const MarkFn mark = [&](int k_) -> hipError_t {
+        hipEvent_t e;
+        hipError_t er = hipEventCreate(&e);
+        if (er != hipSuccess) return er;
+        ev.push_back(e);
+        kind.push_back(k_);
+        return hipEventRecord(e, stream);
+    };
+    const CellCtx C{*d, W, params_layout(d), (char*)workspace, (const char*)params};
+    FwdChain ch;
+    rc = factored_start(h, C, x, mask_value, log_h0, u0_diag, u0_off, uk_off, h_out, stream, nullptr, &ch, mark);
+    if (rc) return rc;
+    const int T_run = frames < d->T ? frames : d->T;
+    Launcher direct{nullptr, stream};
+    for (int t = 0; t < T_run; ++t) {
+        rc = ch.frame(direct, t);
+        if (rc) return rc;
+    }
+    DRNMF_HIP(h, mark(3));
+    DRNMF_HIP(h, hipGetLastError());
+    DRNMF_HIP(h, hipStreamSynchronize(stream));
+    double sum[3] = {0, 0, 0};
+    long cnt[3] = {0, 0, 0};
+    const size_t per_frame = (ev.size() - 1) / (size_t)T_run;
+    const size_t skip = T_run > 1 ? per_frame : 0;          // first frame = warm-up
+    for (size_t i = skip; i + 1 < ev.size(); ++i) {
+        float ms = 0.f;
+        DRNMF_HIP(h, hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+        if (kind[i] < 2) { sum[kind[i]] += ms; cnt[kind[i]]++; }
+        sum[2] += ms;
+    }
+    const int frames_timed = T_run > 1 ? T_run - 1 : 1;
+    out_us[0] = cnt[0] ? (float)(sum[0] / cnt[0] * 1e3) : 0.f;
+    out_us[1] = cnt[1] ? (float)(sum[1] / cnt[1] * 1e3) : 0.f;
+    out_us[2] = (float)(sum[2] / frames_timed * 1e3);
+    for (auto e : ev) (void)hipEventDestroy(e);
+    return DRNMF_OK;
 }
 
 extern "C" int32_t drnmf_cell_forward_ista(drnmf_handle_t h, const drnmf_cell_desc_t* d,
@@ -1499,51 +1499,22 @@ extern "C" int32_t drnmf_cell_forward_ista(drnmf_handle_t h, const drnmf_cell_de
                                            float* h_out, void* workspace, size_t workspace_bytes,
                                            void* stream_) {
     DRNMF_LOCK(h);
-    if (!h) return DRNMF_ERR_INVALID_ARG;
-    int rc = validate_cell_desc(h, d);
+    Workspace W;
+    int32_t rc = cell_forward_validate(h, d, true, x, params, log_h0, h_out, workspace, workspace_bytes, &W,
+                                       "cell_forward_ista");
     if (rc) return rc;
-    if (d->divergence != DRNMF_DIV_KL && d->divergence != DRNMF_DIV_BETA)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG,
-                   "cell_forward_ista: d->divergence must be DRNMF_DIV_KL or DRNMF_DIV_BETA");
-    if (!x || !params || !log_h0 || !h_out || !workspace)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "cell_forward_ista: NULL pointer argument");
-    const Workspace W = workspace_layout(d);
-    if (workspace_bytes < W.total)
-        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "cell_forward_ista: workspace %zu < required %zu",
-                   workspace_bytes, W.total);
-    if (((uintptr_t)workspace & 255) || ((uintptr_t)params & 255))
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "workspace/params must be 256-byte aligned");
-    ++h->call_seq;                   // (a top-level call: the graphs it takes are pinned until it returns)
     hipStream_t stream = (hipStream_t)stream_;
-    const ParamsLayout L = params_layout(d);
-    char* ws = (char*)workspace;
-    const char* pb = (const char*)params;
-    float* xp = (float*)(ws + W.off_xp);
-    unsigned char* valid = (unsigned char*)(ws + W.off_valid);
-    float* rpart = (float*)(ws + W.off_rpart);
-    float* hb[2] = {(float*)(ws + W.off_h0), (float*)(ws + W.off_h1)};
-    float* state = (float*)(ws + W.off_state);
-    float* rs_part = (float*)(ws + W.off_rs);
-    float* psum = (float*)(ws + W.off_psum);
-    int* tA = (int*)(ws + W.off_t);
-    int* tB = tA + 16;
+    const CellCtx C{*d, W, params_layout(d), (char*)workspace, (const char*)params};
     const int K = d->K;
 
     {   // prologue as the reference cell's (pack + mask, initial state, counters = 0)
-        const size_t rows = (size_t)d->T * W.Bp;
-        hipLaunchKernelGGL(pack_input_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
-                           stream, x, xp, valid, mask_value, d->B, d->T, d->F, W.Bp, W.Fp);
-        if (initial_state)
-            hipLaunchKernelGGL(load_state_kernel, dim3((W.Bp + 3) / 4), dim3(256), 0, stream,
-                               initial_state, state, rs_part, tA, d->B, d->N, W.Np, W.Bp, round_up(W.numA, 4), 1);
-        else
-            hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(256), 0, stream, log_h0, state,
-                               rs_part, tA, d->N, W.Np, W.Bp, round_up(W.numA, 4), 1);
-        DRNMF_HIP(h, hipMemsetAsync(psum, 0, (size_t)W.Bp * 4, stream));   // read (times 0) by cell_a
+        rc = cell_prologue(h, C, x, mask_value, log_h0, initial_state, nullptr, round_up(W.numA, 4), 1, false,
+                           stream);
+        if (rc) return rc;
+        DRNMF_HIP(h, hipMemsetAsync(C.psum, 0, (size_t)W.Bp * 4, stream));   // read (times 0) by cell_a
         if (d->return_all_hidden) {      // the BPTT reads these (times 0) as the reference cell's does
-            DRNMF_HIP(h, hipMemsetAsync(ws + W.off_psum_all, 0, (size_t)d->T * W.Bp * 4, stream));
-            hipLaunchKernelGGL(seen_kernel, dim3((W.Bp + 3) / 4), dim3(256), 0, stream, valid,
-                               (unsigned char*)(ws + W.off_seen), d->T, W.Bp);
+            DRNMF_HIP(h, hipMemsetAsync(C.psum_all, 0, (size_t)d->T * W.Bp * 4, stream));
+            launch_seen(C, stream);
         }
         DRNMF_HIP(h, hipGetLastError());
     }
@@ -1552,59 +1523,32 @@ extern "C" int32_t drnmf_cell_forward_ista(drnmf_handle_t h, const drnmf_cell_de
     const dim3 grid_a(8u * (unsigned)numM, (unsigned)(round_up(W.numA, 8) / 8));
     const dim3 grid_b(8u * (unsigned)numM, (unsigned)(round_up(nft * W.KS, 8) / 8));
     const dim3 grid_r((unsigned)((size_t)W.Bp * W.Fp / 256));
-    const size_t dstride = (size_t)L.Fp * L.Np * 4;
-    auto Dn_of = [&](int k) { return pb + L.off_dn + (d->n_D == 1 ? 0 : (size_t)k * dstride); };
-    auto DnA_of = [&](int k) { return pb + L.off_dnA + (d->n_D == 1 ? 0 : (size_t)k * dstride); };
-    auto tail_of = [&](int k) {
-        return (const float*)(pb + L.off_tail) + (d->n_D == 1 ? 0 : (size_t)k * MAX_TAIL * L.Np);
-    };
     // layer k of a frame: cell_b (x^ = h_in Dn_k^T) -> resid_div (r = g(x_t, x^)) -> cell_a as a
     // MIDDLE layer of the reference cell (h' = relu(h_in + (r Dn_k) / alpha_k + b_k), uko = 0);
     // h_in = the state for k = 0.  Frame counters: the first resid kernel of a frame reads tB and
     // republishes it as tA, the last cell_a reads tA and publishes tB = t + 1.
-    auto h_in_of = [&](int k) { return k == 0 ? state : hb[(k - 1) & 1]; };
     auto make_b = [&](int k) {
         CellBArgs b;
-        b.Dn_next = Dn_of(k);
-        b.h = h_in_of(k);
+        b.Dn_next = C.Dn_of(k);
+        b.h = k == 0 ? C.state : C.hb[(k - 1) & 1];
         b.xp = nullptr;                 // rpart = + x^
-        b.rpart = rpart;
-        b.t_rd = tA;
+        b.rpart = C.rpart;
+        b.t_rd = C.tA;
         b.Bp = W.Bp; b.Fp = W.Fp; b.Np = W.Np; b.nft = nft; b.KS = W.KS;
         b.logKS = 0;
         b.nch_ks = W.nch_ks;
         return b;
     };
     auto make_a = [&](int k) {
-        CellAArgs a;
-        memset(&a, 0, sizeof(a));
-        a.Dn = DnA_of(k);
-        a.inv_alpha = (const float*)(pb + L.off_inv_alpha) + (size_t)k * L.Np;
-        a.bias = (const float*)(pb + L.off_bias) + (size_t)k * L.Np;
-        a.rsrc = rpart;
-        a.h_in = h_in_of(k);
-        a.h_out = (k == K - 1) ? state : hb[k & 1];
-        a.state = state;
-        a.rs_part = rs_part;
-        a.psum = psum;
-        a.psum_all = (float*)(ws + W.off_psum_all);
-        a.valid = valid;
-        a.out = h_out;
-        a.t_rd = tA;
-        a.t_wr = (k == K - 1) ? tB : nullptr;
+        CellAArgs a = cell_a_common(C, k, h_out);
+        a.rsrc = C.rpart;
+        a.t_rd = C.tA;
+        a.t_wr = (k == K - 1) ? C.tB : nullptr;
         a.t_wr_add = 1;
         a.u0d = 0.f; a.u0o = 0.f; a.uko = 0.f;
-        a.B = d->B; a.T = d->T; a.N = d->N; a.Bp = W.Bp; a.Fp = W.Fp; a.Np = W.Np;
-        a.numA = W.numA; a.nchunks = nft; a.KS = W.KS; a.ntail = 0; a.tail_tile = nft;
-        a.Dtail = tail_of(k);
-        a.Dtail_next = tail_of(k);
-        float* qp = (float*)(ws + W.off_qpart);
-        a.q_in = qp; a.q_out = qp;
-        a.xtail = (float*)(ws + W.off_xtail);
-        a.xcur = (float*)(ws + W.off_xcur);
-        a.out_width = d->return_all_hidden ? d->N * K : d->N;
-        a.out_off = d->return_all_hidden ? k * d->N : 0;
-        a.write_out = (d->return_all_hidden || k == K - 1) ? 1 : 0;
+        a.nchunks = nft; a.ntail = 0;
+        a.Dtail_next = C.tail_of(k);
+        a.q_in = C.qpart; a.q_out = C.qpart;
         return a;
     };
     const int div = d->divergence;
@@ -1615,13 +1559,13 @@ extern "C" int32_t drnmf_cell_forward_ista(drnmf_handle_t h, const drnmf_cell_de
         for (int k = 0; k < K; ++k) {
             CellBArgs b = make_b(k);
             DRNMF_HIP(h, chain.add(pick_b_func(W.nch_ks, W.RB, false), grid_b, 64 * NW_B, CellBParams(b).p));
-            const float* xpp = xp;
-            float* rp = rpart;
-            const int* trd = (k == 0) ? tB : tA;
-            int* twr = (k == 0) ? tA : nullptr;
+            const float* xpp = C.xp;
+            float* rp = C.rpart;
+            const int* trd = (k == 0) ? C.tB : C.tA;
+            int* twr = (k == 0) ? C.tA : nullptr;
             int dv = div;
             float bt = beta;
-            float* xsv = W.off_xhat ? (float*)(ws + W.off_xhat) + (size_t)k * Bp * Fp : nullptr;
+            float* xsv = C.xhat ? C.xhat + (size_t)k * Bp * Fp : nullptr;
             size_t xst = (size_t)K * Bp * Fp;
             void* kr[11] = {&xpp, &rp, &trd, &twr, &dv, &bt, &F, &Fp, &Bp, &xsv, &xst};
             DRNMF_HIP(h, chain.add((void*)&resid_div_kernel, grid_r, 256, kr));
@@ -1634,22 +1578,13 @@ extern "C" int32_t drnmf_cell_forward_ista(drnmf_handle_t h, const drnmf_cell_de
         }
         return DRNMF_OK;
     };
-    int fpg = 600 / (3 * K);
-    fpg = fpg < 1 ? 1 : (fpg > 64 ? 64 : fpg);
-    if (fpg > d->T) fpg = d->T;
-    uint32_t bbits;
-    memcpy(&bbits, &beta, 4);
+    const int fpg = frames_per_graph(600, 3 * K, d->T);
     const std::vector<uint64_t> key = {
         (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->N, (uint64_t)d->K, (uint64_t)d->n_D,
-        (uint64_t)d->return_all_hidden, (uint64_t)d->divergence, (uint64_t)bbits, (uint64_t)(uintptr_t)params,
+        (uint64_t)d->return_all_hidden, (uint64_t)d->divergence, f32_bits(beta), (uint64_t)(uintptr_t)params,
         (uint64_t)(uintptr_t)h_out, (uint64_t)(uintptr_t)workspace};
     rc = replay_frames(h, stream, GraphKind::IstaForward, key, {fpg, 1}, 0, d->T, frame);
     if (rc) return rc;
-    if (final_state) {
-        const size_t tot = (size_t)d->B * d->N;
-        hipLaunchKernelGGL(store_state_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
-                           stream, state, final_state, d->B, d->N, W.Np);
-        DRNMF_HIP(h, hipGetLastError());
-    }
+    DRNMF_HIP(h, store_final_state(C, final_state, stream));
     return DRNMF_OK;
 }

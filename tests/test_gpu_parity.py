@@ -1159,3 +1159,70 @@ def test_large_batch_sub_batches_on_side_streams(dev, monkeypatch, B, split, r, 
                                       mask_value=-1.0, initial_state=init.astype(np.float64), return_state=True)
     _check_h(outs[0], ref)
     np.testing.assert_allclose(fin.cpu().numpy(), st, atol=H_TOL * max(np.max(np.abs(st)), 1e-30))
+
+
+@pytest.mark.parametrize("K", [3, 1])
+def test_cell_profile_leaves_the_forward_s_output(dev, monkeypatch, K):
+    """drnmf_cell_profile (bench.py, tools/profile_shape.py) launches the factored chain directly, a HIP event
+    ahead of every launch: the same kernels on the same arguments as the graphs of drnmf_cell_forward.  All T
+    frames must leave the forward's output bit for bit, two frames its first two; the three times come back
+    finite, the frame's positive.  K = 1: one cell_a launch and the frame-counter advance per frame.  The
+    entry brackets the factored launches only: a call that takes the Gram form is refused (-2)."""
+    from drnmf_amd import ops
+    monkeypatch.setenv("DRNMF_GRAM", "0")
+    B, T, F, r = 20, 6, 33, 20
+    P, alt, labels, N = _problem(B, T, F, r, K, ragged=True)
+    stack = lambda name: np.stack([alt[k] for k in dict.fromkeys(labels[name])], 0)
+    logD, logA, logL = stack("log_D"), stack("log_alph"), stack("log_lam1")
+    desc = ops.make_desc(B, T, F, N, K, n_D=logD.shape[0], n_alph=logA.shape[0],
+                         alph_len=int(np.asarray(logA[0]).size), n_lam=logL.shape[0])
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+    params = ops.prepare_params(desc, t(logD), t(logA.reshape(logA.shape[0], -1)), t(logL.reshape(-1)))
+    x, h0 = t(P["X"]), t(P["log_h0"])
+    u = O.u_scalars(alt, np.float32)
+    nbytes = ops.cell_workspace(desc, dev).numel()
+    ws = lambda: torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    ref = ops.cell_forward(x, -1.0, params, desc, h0, u, workspace=ws())
+    torch.cuda.synchronize()
+    ref = ref.cpu().numpy()
+    for frames in (T, 2):
+        out = torch.full((B, T, N), -7.0, dtype=torch.float32, device=dev)
+        us = ops.cell_profile(x, -1.0, params, desc, h0, u, out, ws(), frames=frames)
+        torch.cuda.synchronize()
+        assert np.array_equal(out.cpu().numpy()[:, :frames], ref[:, :frames]), frames
+        assert all(np.isfinite(us[k]) for k in ("cell_a_us", "cell_b_us", "frame_us")), us
+        assert us["frame_us"] > 0, us
+    if K >= 2:                                       # (K = 1 never takes the Gram form)
+        monkeypatch.setenv("DRNMF_GRAM", "1")
+        out = torch.empty((B, T, N), dtype=torch.float32, device=dev)
+        unsupported = -2                             # DRNMF_ERR_UNSUPPORTED (include/drnmf.h)
+        with pytest.raises(ValueError, match=r"drnmf_cell_profile failed \(%d\)" % unsupported):
+            ops.cell_profile(x, -1.0, params, desc, h0, u, out, ops.cell_workspace(desc, dev), frames=T)
+    ops.check_status(dev)
+
+
+def test_split_call_refuses_a_sub_batch_that_outgrows_its_slice(dev, monkeypatch):
+    """The slices of a split call's workspace are sized for a sub-batch of split_rows rows.  A smaller LAST
+    sub-batch may take the Gram form (its size rule grows with the batch), and the Gram form's ring of hoisted
+    c_k is far larger than a factored slice: B = 160, N = 1000 runs as 64 + 64 factored rows and 32 Gram rows
+    whose layout ends tens of MB past the workspace drnmf_cell_workspace_bytes asks for.  Such a call must come
+    back with DRNMF_ERR_WORKSPACE, before anything of that sub-batch is enqueued, and leave the handle usable."""
+    from drnmf_amd import ops
+    monkeypatch.delenv("DRNMF_GRAM", raising=False)
+    monkeypatch.delenv("DRNMF_SPLIT", raising=False)
+    B, T, F, N, K = 160, 8, 257, 1000, 5
+    desc = ops.make_desc(B, T, F, N, K, n_D=K, n_alph=K)
+    rng = np.random.default_rng(0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+    params = ops.prepare_params(desc, t(np.log(rng.random((K, F, N)) + 0.1)), t(np.full((K, 1), np.log(N / 4.0))),
+                                t(np.full((1,), np.log(0.3))))
+    x, h0 = t(rng.random((B, T, F))), t(np.zeros(N))
+    workspace_err = -4                               # DRNMF_ERR_WORKSPACE (include/drnmf.h)
+    with pytest.raises(ValueError, match=r"drnmf_cell_forward failed \(%d\): cell_forward: workspace" % workspace_err):
+        ops.cell_forward(x, -1.0, params, desc, h0, (1.0, 0.0, 0.0))
+    torch.cuda.synchronize()
+    ops.check_status(dev)
+    small = ops.make_desc(32, T, F, N, K, n_D=K, n_alph=K)          # the same rows as a call of their own: fine
+    h = ops.cell_forward(x[:32].contiguous(), -1.0, params, small, h0, (1.0, 0.0, 0.0))
+    torch.cuda.synchronize()
+    assert np.all(np.isfinite(h.cpu().numpy()))
