@@ -2,7 +2,7 @@
 STOI score's in include/drnmf_score.h; the ragged STFT / iSTFT / int16 stages' in include/drnmf_enhance.h; the
 device-side SDR's in include/drnmf_sdr.h; the training-data front end's in include/drnmf_dataset.h; the streaming
 STFT / iSTFT's in include/drnmf_stream.h; the sparse-NMF baseline's inference in include/drnmf_snmf.h, on fp16
-operands in include/drnmf_snmf_f16.h).
+operands in include/drnmf_snmf_f16.h; ESTOI beside STOI in include/drnmf_estoi.h).
 
 The library is the product path: there is NO fallback.  If the shared object is missing or a
 call fails, an exception is raised.
@@ -206,6 +206,13 @@ TARGET_SIGNATURES = {
 }
 TARGETS = {"mag": 0, "psa": 1, "tpsa": 2}     # DRNMF_TARGET_*
 
+# name -> (restype, argtypes); mirrors include/drnmf_estoi.h one to one (a table of its own, like the others)
+ESTOI_SIGNATURES = {
+    "drnmf_stoi_ext_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "drnmf_stoi_ext": (_i32, [_vp, _i32, _i64, C.POINTER(_i64), _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                              _vp]),
+}
+
 # name -> (restype, argtypes); mirrors include/drnmf_stream.h one to one (a table of its own, like the five above)
 STREAM_SIGNATURES = {
     "drnmf_stream_counts": (_i32, [_i64, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
@@ -262,7 +269,8 @@ def lib():
                                   list(SCORE_SIGNATURES.items()) + list(ENHANCE_SIGNATURES.items()) +
                                   list(SDR_SIGNATURES.items()) + list(DATASET_SIGNATURES.items()) +
                                   list(STREAM_SIGNATURES.items()) + list(SNMF_SIGNATURES.items()) +
-                                  list(SNMF_F16_SIGNATURES.items()) + list(TARGET_SIGNATURES.items())):
+                                  list(SNMF_F16_SIGNATURES.items()) + list(TARGET_SIGNATURES.items()) +
+                                  list(ESTOI_SIGNATURES.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

@@ -42,7 +42,9 @@ NO_SCRATCH = {"lstm.hip": "lstm_step_kernel",
               # its fp16-operand sibling: H (fp32 master), num and den of its tiles in registers as well
               "snmf_f16.hip": "snmf_f16_",
               # the target kernels keep the noisy member's bins of a frame in registers (up to 27 per lane)
-              "stft.hip": "stft_pair_target_"}
+              "stft.hip": "stft_pair_target_",
+              # the ESTOI segment kernel holds a 30-frame row, then two 15-band columns, of fp64 per lane
+              "stoi.hip": "estoi_"}
 
 
 def _check_no_scratch(src, remarks):
@@ -71,7 +73,7 @@ def _deps():
     return _sources() + glob.glob(os.path.join(CSRC, "*.h")) + \
         [os.path.join(os.path.dirname(HERE), "include", n) for n in ("drnmf.h", "drnmf_lstm.h", "drnmf_score.h", "drnmf_enhance.h", "drnmf_sdr.h",
                                                                      "drnmf_dataset.h", "drnmf_stream.h", "drnmf_snmf.h", "drnmf_snmf_f16.h",
-                                                                     "drnmf_target.h")] + \
+                                                                     "drnmf_target.h", "drnmf_estoi.h")] + \
         [os.path.abspath(__file__)]
 
 

@@ -23,11 +23,18 @@
 //                  epilogue sums |X_k|^2 over the 15 one-third-octave bands and stores sqrt as float32.
 //   stoi_segment   one lane per (30-frame segment, band), fp64: alpha, the clipped Y', the centred correlation.
 //   stoi_mean      one workgroup per signal: the fp64 mean of its segment scores in a fixed order.
+// ESTOI (Jensen & Taal, IEEE/ACM TASLP 24(11), 2016; include/drnmf_estoi.h, tests/estoi_ref.py [ESTOI-memory]) is
+// the same three first stages and another last step, through drnmf_stoi_ext:
+//   estoi_segment  one wave per 30-frame segment: both 15 x 30 tiles in LDS as fp64, rows then columns centred and
+//                  normalised, the 30 column products added in frame order.
+//   estoi_mean     as stoi_mean, one value per segment.
+// Plain arithmetic there too: a zero norm (a constant band, a silent stretch of the estimate) is 0 / 0 = NaN.
 // Matlab edge semantics (not pystoi's): fewer than 30 band frames -> NaN; fmin ignores NaN, so a segment with
 // sum Y^2 = 0 (alpha = inf, inf * 0 = NaN) takes Y' = X (1 + c) and scores 1; a zero-variance vector divides
 // 0 by 0 and the NaN reaches the mean.
 #include "common.h"
 #include "../../include/drnmf_score.h"
+#include "../../include/drnmf_estoi.h"
 
 namespace {
 
@@ -348,17 +355,10 @@ stoi_segment_kernel(const float* __restrict__ env_x, const float* __restrict__ e
     d[(size_t)sig * S * ST_J + g] = rho;
 }
 
-__global__ void __launch_bounds__(256)
-stoi_mean_kernel(const double* __restrict__ d, const int* __restrict__ nkept, int S, float* __restrict__ out) {
-    __shared__ double red[256];
-    const int sig = blockIdx.x, tid = threadIdx.x;
-    const int nseg = nkept[sig] - 1 - (ST_SEG - 1);
-    if (nseg <= 0) {                           // Matlab's mean of an empty set
-        if (tid == 0) out[sig] = __int_as_float(0x7fc00000);
-        return;
-    }
-    const int cnt = nseg * ST_J;
-    const double* __restrict__ ds = d + (size_t)sig * S * ST_J;
+// the fp64 mean of ds[0 .. cnt) by one workgroup, in a fixed order (cnt > 0)
+__device__ __forceinline__ void mean_fixed_order(const double* __restrict__ ds, int cnt, double (&red)[256],
+                                                 float* __restrict__ out) {
+    const int tid = threadIdx.x;
     double s = 0.0;
     for (int g = tid; g < cnt; g += 256) s += ds[g];
     red[tid] = s;
@@ -367,7 +367,118 @@ stoi_mean_kernel(const double* __restrict__ d, const int* __restrict__ nkept, in
         if (tid < o) red[tid] += red[tid + o];
         __syncthreads();
     }
-    if (tid == 0) out[sig] = (float)(red[0] / (double)cnt);
+    if (tid == 0) *out = (float)(red[0] / (double)cnt);
+}
+
+__global__ void __launch_bounds__(256)
+stoi_mean_kernel(const double* __restrict__ d, const int* __restrict__ nkept, int S, float* __restrict__ out) {
+    __shared__ double red[256];
+    const int sig = blockIdx.x;
+    const int nseg = nkept[sig] - 1 - (ST_SEG - 1);
+    if (nseg <= 0) {                           // Matlab's mean of an empty set
+        if (threadIdx.x == 0) out[sig] = __int_as_float(0x7fc00000);
+        return;
+    }
+    mean_fixed_order(d + (size_t)sig * S * ST_J, nseg * ST_J, red, out + sig);
+}
+
+// ESTOI's last step (include/drnmf_estoi.h, step 4'): grid (ceil(S / 4), n_sig), one wave per 30-frame segment, 4 per
+// workgroup; d [n_sig][S].  The wave stages its two 15 x 30 tiles (band by frame) as fp64 in a wave-private LDS
+// slice, normalises the rows with one lane per (tile, band), then the columns with one lane per frame, and lane 0
+// adds the 30 column terms in frame order.  No workgroup barrier: whole waves leave at the top.
+__global__ void __launch_bounds__(256)
+estoi_segment_kernel(const float* __restrict__ env_x, const float* __restrict__ env_y,
+                     const int* __restrict__ nkept, int F, int S, double* __restrict__ d) {
+    constexpr int TILE = ST_J * ST_SEG;
+    __shared__ double tiles[4][2][TILE];       // [wave][x, y][band * 30 + frame]
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int sig = blockIdx.y, seg = blockIdx.x * 4 + wv;
+    if (seg >= nkept[sig] - 1 - (ST_SEG - 1)) return;
+    double* tx = tiles[wv][0];
+    double* ty = tiles[wv][1];
+    // frames seg .. seg + 29 are 450 consecutive floats of each envelope
+    const float* __restrict__ ex = env_x + ((size_t)sig * F + seg) * ST_J;
+    const float* __restrict__ ey = env_y + ((size_t)sig * F + seg) * ST_J;
+    for (int i = lane; i < TILE; i += 64) {
+        const int f = i / ST_J, b = i - f * ST_J;
+        tx[b * ST_SEG + f] = (double)ex[i];
+        ty[b * ST_SEG + f] = (double)ey[i];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    // rows: lanes 0-14 the bands of x, lanes 32-46 the bands of y
+    if ((lane & 31) < ST_J) {
+        double* row = tiles[wv][lane >> 5] + (lane & 31) * ST_SEG;
+        double a[ST_SEG];
+        double m = 0.0;
+#pragma unroll
+        for (int f = 0; f < ST_SEG; ++f) {
+            a[f] = row[f];
+            m += a[f];
+        }
+        m /= ST_SEG;
+        double n = 0.0;
+#pragma unroll
+        for (int f = 0; f < ST_SEG; ++f) {
+            a[f] -= m;
+            n = fma(a[f], a[f], n);
+        }
+        n = sqrt(n);
+#pragma unroll
+        for (int f = 0; f < ST_SEG; ++f) row[f] = a[f] / n;      // a constant band: 0 / 0 = NaN
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    // columns: lane f normalises frame f of both tiles and multiplies them
+    double term = 0.0;
+    if (lane < ST_SEG) {
+        double x[ST_J], y[ST_J];
+        double mx = 0.0, my = 0.0;
+#pragma unroll
+        for (int b = 0; b < ST_J; ++b) {
+            x[b] = tx[b * ST_SEG + lane];
+            y[b] = ty[b * ST_SEG + lane];
+            mx += x[b];
+            my += y[b];
+        }
+        mx /= ST_J;
+        my /= ST_J;
+        double nx = 0.0, ny = 0.0;
+#pragma unroll
+        for (int b = 0; b < ST_J; ++b) {
+            x[b] -= mx;
+            y[b] -= my;
+            nx = fma(x[b], x[b], nx);
+            ny = fma(y[b], y[b], ny);
+        }
+        nx = sqrt(nx);
+        ny = sqrt(ny);
+#pragma unroll
+        for (int b = 0; b < ST_J; ++b) term = fma(x[b] / nx, y[b] / ny, term);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();           // every lane has read its column: tx is free
+    if (lane < ST_SEG) tx[lane] = term;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) {
+        double acc = 0.0;
+#pragma unroll
+        for (int f = 0; f < ST_SEG; ++f) acc += tx[f];
+        d[(size_t)sig * S + seg] = acc / ST_SEG;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+estoi_mean_kernel(const double* __restrict__ d, const int* __restrict__ nkept, int S, float* __restrict__ out) {
+    __shared__ double red[256];
+    const int sig = blockIdx.x;
+    const int nseg = nkept[sig] - 1 - (ST_SEG - 1);
+    if (nseg <= 0) {                           // as STOI: the mean of an empty set
+        if (threadIdx.x == 0) out[sig] = __int_as_float(0x7fc00000);
+        return;
+    }
+    mean_fixed_order(d + (size_t)sig * S, nseg, red, out + sig);
 }
 
 int gcd_i(int a, int b) {
@@ -445,31 +556,39 @@ extern "C" size_t drnmf_stoi_workspace_bytes(int32_t n_sig, int64_t max_len, int
     return stoi_layout(n_sig, max_len, fs, Lo) ? Lo.total : 0;
 }
 
-extern "C" int32_t drnmf_stoi(drnmf_handle_t h, int32_t n_sig, int64_t stride, const int64_t* lengths_host,
-                              int32_t fs, const float* est, const float* ref, float* stoi_out, uint8_t* keep_out,
-                              float* env_ref_out, float* env_est_out, void* workspace, size_t workspace_bytes,
-                              void* stream_) {
-    DRNMF_LOCK(h);
-    if (!h) return DRNMF_ERR_INVALID_ARG;
-    if (n_sig <= 0 || n_sig > 65535 || stride <= 0 || !lengths_host || !est || !ref || !stoi_out || !workspace)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stoi: bad argument (n_sig in [1, 65535], stride > 0, non-NULL)");
-    int64_t max_len = 0;
+namespace {
+
+// what steps 1 to 3 leave on the device for the last step of either score
+struct StoiFront {
+    const int* nk;           // [n_sig] kept frames
+    const float* envx;       // [n_sig][F][15] band envelopes of the reference ...
+    const float* envy;       // ... and of the estimate
+};
+
+// The checks of drnmf_stoi and drnmf_stoi_ext (`who` names the caller in the message); fills Lo and max_len.
+int32_t stoi_check(drnmf_handle_t h, const char* who, int32_t n_sig, int64_t stride, const int64_t* lengths_host,
+                   int32_t fs, const float* est, const float* ref, bool have_out, const void* workspace,
+                   StoiLayout& Lo, int64_t& max_len) {
+    if (n_sig <= 0 || n_sig > 65535 || stride <= 0 || !lengths_host || !est || !ref || !have_out || !workspace)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: bad argument (n_sig in [1, 65535], stride > 0, non-NULL)", who);
+    max_len = 0;
     for (int i = 0; i < n_sig; ++i) {
         const int64_t l = lengths_host[i];
         if (l < 0 || l > stride || l > ST_MAX_LEN)
-            DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stoi: lengths[%d] = %lld outside [0, min(stride, 2^30)]", i,
+            DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: lengths[%d] = %lld outside [0, min(stride, 2^30)]", who, i,
                        (long long)l);
         if (l > max_len) max_len = l;
     }
-    StoiLayout Lo;
     if (!stoi_layout(n_sig, max_len, fs, Lo))
         DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED,
-                   "stoi: fs = %d unsupported (10000/fs reduced to p/q must have max(p, q) <= 160)", fs);
-    if (workspace_bytes < Lo.total)
-        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "stoi: workspace too small (%zu < %zu bytes)", workspace_bytes,
-                   Lo.total);
-    hipStream_t stream = (hipStream_t)stream_;
-    char* ws = (char*)workspace;
+                   "%s: fs = %d unsupported (10000/fs reduced to p/q must have max(p, q) <= 160)", who, fs);
+    return DRNMF_OK;
+}
+
+// Steps 1 to 3: lengths, resampling, the silence decision and the band envelopes of the whole batch.
+StoiFront stoi_front(const StoiLayout& Lo, int32_t n_sig, int64_t stride, const int64_t* lengths_host,
+                     int64_t max_len, const float* est, const float* ref, uint8_t* keep_out, float* env_ref_out,
+                     float* env_est_out, char* ws, hipStream_t stream) {
     int64_t* lens = (int64_t*)(ws + Lo.off_len);
     for (int base = 0; base < n_sig; base += ST_LEN_CHUNK) {
         LenChunk c;
@@ -482,7 +601,6 @@ extern "C" int32_t drnmf_stoi(drnmf_handle_t h, int32_t n_sig, int64_t stride, c
     int* nk = (int*)(ws + Lo.off_nk);
     float* envx = env_ref_out ? env_ref_out : (float*)(ws + Lo.off_envx);
     float* envy = env_est_out ? env_est_out : (float*)(ws + Lo.off_envy);
-    double* d = (double*)(ws + Lo.off_d);
     const int V = Lo.V > 0 ? Lo.V : 1;
     uint8_t* keep = Lo.V > 0 ? keep_out : nullptr;
     const dim3 band_grid((unsigned)((Lo.F + 3) / 4), (unsigned)n_sig);
@@ -505,11 +623,82 @@ extern "C" int32_t drnmf_stoi(drnmf_handle_t h, int32_t n_sig, int64_t stride, c
         hipLaunchKernelGGL(stoi_band_kernel<float>, band_grid, dim3(256), 0, stream, ref, est, stride,
                            (const int*)kidx, (const int*)nk, V, Lo.F, envx, envy);
     }
+    return StoiFront{nk, envx, envy};
+}
+
+// STOI's step 4 and its mean
+void stoi_back(const StoiLayout& Lo, int32_t n_sig, const StoiFront& fr, float* stoi_out, char* ws,
+               hipStream_t stream) {
+    double* d = (double*)(ws + Lo.off_d);
     hipLaunchKernelGGL(stoi_segment_kernel, dim3((unsigned)((Lo.S * ST_J + 255) / 256), (unsigned)n_sig),
-                       dim3(256), 0, stream, (const float*)envx, (const float*)envy, (const int*)nk, Lo.F, Lo.S,
-                       d);
-    hipLaunchKernelGGL(stoi_mean_kernel, dim3((unsigned)n_sig), dim3(256), 0, stream, (const double*)d,
-                       (const int*)nk, Lo.S, stoi_out);
+                       dim3(256), 0, stream, fr.envx, fr.envy, fr.nk, Lo.F, Lo.S, d);
+    hipLaunchKernelGGL(stoi_mean_kernel, dim3((unsigned)n_sig), dim3(256), 0, stream, (const double*)d, fr.nk,
+                       Lo.S, stoi_out);
+}
+
+// drnmf_stoi_ext's workspace: drnmf_stoi's, then the per-segment ESTOI scores d [n_sig][S] fp64
+size_t estoi_d_bytes(const StoiLayout& Lo, int32_t n_sig) {
+    return round_up_sz((size_t)n_sig * Lo.S * sizeof(double), 256);
+}
+
+}  // namespace
+
+extern "C" int32_t drnmf_stoi(drnmf_handle_t h, int32_t n_sig, int64_t stride, const int64_t* lengths_host,
+                              int32_t fs, const float* est, const float* ref, float* stoi_out, uint8_t* keep_out,
+                              float* env_ref_out, float* env_est_out, void* workspace, size_t workspace_bytes,
+                              void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    StoiLayout Lo;
+    int64_t max_len;
+    const int32_t rc = stoi_check(h, "stoi", n_sig, stride, lengths_host, fs, est, ref, stoi_out != nullptr,
+                                  workspace, Lo, max_len);
+    if (rc != DRNMF_OK) return rc;
+    if (workspace_bytes < Lo.total)
+        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "stoi: workspace too small (%zu < %zu bytes)", workspace_bytes,
+                   Lo.total);
+    hipStream_t stream = (hipStream_t)stream_;
+    const StoiFront fr = stoi_front(Lo, n_sig, stride, lengths_host, max_len, est, ref, keep_out, env_ref_out,
+                                    env_est_out, (char*)workspace, stream);
+    stoi_back(Lo, n_sig, fr, stoi_out, (char*)workspace, stream);
+    DRNMF_HIP(h, hipGetLastError());
+    return DRNMF_OK;
+}
+
+extern "C" size_t drnmf_stoi_ext_workspace_bytes(int32_t n_sig, int64_t max_len, int32_t fs) {
+    StoiLayout Lo;
+    return stoi_layout(n_sig, max_len, fs, Lo) ? Lo.total + estoi_d_bytes(Lo, n_sig) : 0;
+}
+
+extern "C" int32_t drnmf_stoi_ext(drnmf_handle_t h, int32_t n_sig, int64_t stride, const int64_t* lengths_host,
+                                  int32_t fs, const float* est, const float* ref, float* stoi_out, float* estoi_out,
+                                  uint8_t* keep_out, float* env_ref_out, float* env_est_out, double* d_ext_out,
+                                  void* workspace, size_t workspace_bytes, void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    StoiLayout Lo;
+    int64_t max_len;
+    const int32_t rc = stoi_check(h, "stoi_ext", n_sig, stride, lengths_host, fs, est, ref,
+                                  stoi_out != nullptr || estoi_out != nullptr, workspace, Lo, max_len);
+    if (rc != DRNMF_OK) return rc;
+    const size_t need = Lo.total + estoi_d_bytes(Lo, n_sig);
+    if (workspace_bytes < need)
+        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "stoi_ext: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+    if (((uintptr_t)workspace & 255) != 0)
+        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "stoi_ext: workspace is not 256-byte aligned");
+    if (h->device < 0) DRNMF_FAIL(h, DRNMF_ERR_HIP, "stoi_ext: the handle is bound to no device");
+    hipStream_t stream = (hipStream_t)stream_;
+    const StoiFront fr = stoi_front(Lo, n_sig, stride, lengths_host, max_len, est, ref, keep_out, env_ref_out,
+                                    env_est_out, (char*)workspace, stream);
+    if (stoi_out) stoi_back(Lo, n_sig, fr, stoi_out, (char*)workspace, stream);
+    if (estoi_out || d_ext_out) {
+        double* d = d_ext_out ? d_ext_out : (double*)((char*)workspace + Lo.total);
+        hipLaunchKernelGGL(estoi_segment_kernel, dim3((unsigned)((Lo.S + 3) / 4), (unsigned)n_sig), dim3(256), 0,
+                           stream, fr.envx, fr.envy, fr.nk, Lo.F, Lo.S, d);
+        if (estoi_out)
+            hipLaunchKernelGGL(estoi_mean_kernel, dim3((unsigned)n_sig), dim3(256), 0, stream, (const double*)d,
+                               fr.nk, Lo.S, estoi_out);
+    }
     DRNMF_HIP(h, hipGetLastError());
     return DRNMF_OK;
 }

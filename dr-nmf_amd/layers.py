@@ -1277,7 +1277,7 @@ class _SequenceModel(object):
         return rows, np.array([w.shape[0] for w in rows], dtype=np.int64), dt
 
     def enhance(self, wavs, N=512, hop=128, batch_size=250, crop=False, dtype='int16', ref=None, fs=16000,
-                return_masks=False, lengths=None, ref_lengths=None, sdr_solver='host'):
+                return_masks=False, lengths=None, ref_lengths=None, sdr_solver='host', extended_scores=False):
         """The reference's enhancement loop (enhance.py:1181-1203; audio_dataset.py:267-339: STFT, padding, the
         model, reconstruct_x, wavwrite) as ONE call, on the device from the samples to the samples.  wavs: a list
         of 1-D int16 (scaled by 1/32768, util.py:29-35) or float32 numpy arrays, or a 2-D array / device tensor
@@ -1295,7 +1295,8 @@ class _SequenceModel(object):
         ref= (the clean waveforms, same container types; ref_lengths= with a 2-D array): returns (wavs_out, S,
         labels) with S = ops.compute_scores(int16 output / 32768, ref, fs, ...): the rows the reference gets for
         the files it wrote and read back (audio_dataset.py:399-435, score_audio.m:184-203); SegSNR / PESQ stay
-        NaN; sdr_solver= is passed on to it ('device': SDR without a host step, ops.sdr_db).  return_masks=True
+        NaN; sdr_solver= is passed on to it ('device': SDR without a host step, ops.sdr_db), and so is
+        extended_scores= as extended= (True: a seventh column, ESTOI, ops.estoi).  return_masks=True
         appends the list of (n_frames_i, F) masks.  No file IO, no resampling."""
         if dtype not in ('int16', 'float32'):
             raise ValueError("enhance: dtype must be 'int16' or 'float32'")
@@ -1391,7 +1392,7 @@ class _SequenceModel(object):
                 rd = torch.from_numpy(rp).to(dev)
             rd = rd.to(torch.float32) / 32768.0 if rd.dtype == torch.int16 else rd
             S, labels = ops.compute_scores(q.to(torch.float32) / 32768.0, rd, fs, n_out, rlens,
-                                           sdr_solver=sdr_solver)
+                                           sdr_solver=sdr_solver, extended=extended_scores)
             ret += [S, labels]
         if return_masks:
             ret.append(masks)

@@ -1714,16 +1714,7 @@ def _host_lengths(lengths, n_sig, n):
     return lh
 
 
-def stoi(est, ref, fs=16000, lengths=None, return_parts=False):
-    """STOI per signal, as `stoi(xref, xest, fs)` of compute_scores (score_audio.m:231) [STOI-memory]:
-    short-time objective intelligibility (Taal et al., 2011), restated in include/drnmf_score.h and
-    tests/stoi_ref.py.  est, ref: device float32 [n_sig, n] (or 1-D); lengths: per-row valid samples (host
-    ints or a tensor; default n).  Returns a float32 [n_sig] device tensor -- NaN for a row with fewer than 30
-    band frames, as Matlab's mean of an empty set.  return_parts=True returns (stoi, parts), parts = dict(
-    keep=[n_sig, V] bool silence decision on ref, env_ref / env_est=[n_sig, max(V-1, 1), 15] band envelopes
-    (rows past a signal's own n_kept - 1 band frames are unspecified), n_kept=[n_sig] int64)."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(est))
+def _stoi_pair_args(est, ref, lengths):
     est, ref = _f32c(est, "est"), _f32c(ref, "ref")
     if est.dim() == 1:
         est, ref = est[None], ref[None]
@@ -1732,8 +1723,24 @@ def stoi(est, ref, fs=16000, lengths=None, return_parts=False):
                          (tuple(est.shape), tuple(ref.shape)))
     if ref.device != est.device:
         raise ValueError("est and ref must be on one device")
+    return est, ref, _host_lengths(lengths, est.shape[0], est.shape[1])
+
+
+def stoi(est, ref, fs=16000, lengths=None, return_parts=False, extended=False):
+    """STOI per signal, as `stoi(xref, xest, fs)` of compute_scores (score_audio.m:231) [STOI-memory]:
+    short-time objective intelligibility (Taal et al., 2011), restated in include/drnmf_score.h and
+    tests/stoi_ref.py.  est, ref: device float32 [n_sig, n] (or 1-D); lengths: per-row valid samples (host
+    ints or a tensor; default n).  Returns a float32 [n_sig] device tensor -- NaN for a row with fewer than 30
+    band frames, as Matlab's mean of an empty set.  return_parts=True returns (stoi, parts), parts = dict(
+    keep=[n_sig, V] bool silence decision on ref, env_ref / env_est=[n_sig, max(V-1, 1), 15] band envelopes
+    (rows past a signal's own n_kept - 1 band frames are unspecified), n_kept=[n_sig] int64).
+    extended=True is `estoi` with the same arguments: ESTOI, not STOI, comes back."""
+    if extended:
+        return estoi(est, ref, fs, lengths=lengths, return_parts=return_parts)
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(est))
+    est, ref, lh = _stoi_pair_args(est, ref, lengths)
     n_sig, n = est.shape
-    lh = _host_lengths(lengths, n_sig, n)
     max_len = int(lh.max()) if n_sig else 0
     V = stoi_vad_frames(max_len, fs)
     dev = est.device
@@ -1755,7 +1762,55 @@ def stoi(est, ref, fs=16000, lengths=None, return_parts=False):
     return out, dict(keep=kb, env_ref=env_r, env_est=env_e, n_kept=kb.sum(dim=1))
 
 
-def compute_scores(est, ref, fs, lengths_est=None, lengths_ref=None, flen=512, sdr_solver="host"):
+def stoi_ext(est, ref, fs=16000, lengths=None, return_parts=False, want_stoi=True, want_estoi=True):
+    """STOI and ESTOI of the same pairs from ONE drnmf_stoi_ext call (include/drnmf_estoi.h): resampling, the
+    silence decision and the band envelopes run once, then each score's own last step.  Arguments as `stoi`.
+    Returns (stoi, estoi), float32 [n_sig] device tensors, None for a score not wanted; stoi has the bits `stoi`
+    returns.  return_parts=True appends `stoi`'s parts plus d_ext=[n_sig, max(V - 30, 1)] float64, the ESTOI of
+    each 30-frame segment (entries past a signal's own n_kept - 30 segments are unspecified)."""
+    if not (want_stoi or want_estoi):
+        raise ValueError("stoi_ext: nothing to compute (want_stoi and want_estoi are both False)")
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(est))
+    est, ref, lh = _stoi_pair_args(est, ref, lengths)
+    n_sig, n = est.shape
+    max_len = int(lh.max()) if n_sig else 0
+    V = stoi_vad_frames(max_len, fs)
+    dev = est.device
+    nbytes = L.drnmf_stoi_ext_workspace_bytes(n_sig, max_len, int(fs))
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    out_s = torch.empty(n_sig, dtype=torch.float32, device=dev) if want_stoi else None
+    out_e = torch.empty(n_sig, dtype=torch.float32, device=dev) if want_estoi else None
+    keep = env_r = env_e = d_ext = None
+    if return_parts:
+        keep = torch.zeros((n_sig, V), dtype=torch.uint8, device=dev)
+        env_r = torch.zeros((n_sig, max(V - 1, 1), STOI_BANDS), dtype=torch.float32, device=dev)
+        env_e = torch.zeros_like(env_r)
+        d_ext = torch.zeros((n_sig, max(V - 30, 1)), dtype=torch.float64, device=dev)
+    rc = L.drnmf_stoi_ext(h, n_sig, n, lh.ctypes.data_as(C.POINTER(C.c_int64)), int(fs), _capi.ptr(est),
+                          _capi.ptr(ref), _capi.ptr(out_s), _capi.ptr(out_e), _capi.ptr(keep if V > 0 else None),
+                          _capi.ptr(env_r), _capi.ptr(env_e), _capi.ptr(d_ext), _capi.ptr(ws), ws.numel(), _stream())
+    _capi.check(rc, h, "drnmf_stoi_ext")
+    if not return_parts:
+        return out_s, out_e
+    kb = keep.bool()
+    return out_s, out_e, dict(keep=kb, env_ref=env_r, env_est=env_e, n_kept=kb.sum(dim=1), d_ext=d_ext)
+
+
+def estoi(est, ref, fs=16000, lengths=None, return_parts=False):
+    """ESTOI per signal [ESTOI-memory]: the extended STOI of Jensen & Taal (IEEE/ACM TASLP 24(11), 2016), which
+    unlike STOI sees temporally modulated maskers; restated in include/drnmf_estoi.h and tests/estoi_ref.py.  STOI's
+    band envelopes, then every 15 x 30 segment of each is normalised (mean and norm) along time, then along the
+    bands; a segment scores the sum of the products / 30, a signal the mean over its segments.  Arguments and
+    return as `stoi`: float32 [n_sig] on the device, NaN below 30 band frames; the parts are `stoi`'s plus
+    d_ext=[n_sig, max(V - 30, 1)] float64 (see `stoi_ext`).  Plain arithmetic, no epsilon: a zero norm is
+    0 / 0, so a band constant over 30 frames or a digitally silent stretch of the estimate gives NaN for the
+    signal (an all-zero estimate: STOI 1, ESTOI NaN); a signal against itself gives 1."""
+    res = stoi_ext(est, ref, fs, lengths=lengths, return_parts=return_parts, want_stoi=False)
+    return (res[1], res[2]) if return_parts else res[1]
+
+
+def compute_scores(est, ref, fs, lengths_est=None, lengths_ref=None, flen=512, sdr_solver="host", extended=False):
     """One row per file as compute_scores (score_audio.m:177-238) returns it:
         S = [SDR, SNR, SegSNR local, SegSNR global, PESQ, STOI]        (score_audio.m:233-236)
     est [n_sig, n_est], ref [n_sig, n_ref]: device float32 (or 1-D), each row valid up to its length
@@ -1765,6 +1820,9 @@ def compute_scores(est, ref, fs, lengths_est=None, lengths_ref=None, flen=512, s
     sdr_solver="device": SDR runs over each pair's own length with the normal equations solved on the device
     (`sdr_db(..., lengths=, solver="device")`), nothing waits for the host between the three scores, and all
     columns come down in one copy.
+    extended=True appends a seventh column, ESTOI (`estoi`; not a column of the reference's row): S is
+    [n_sig, 7], labels SCORE_LABELS + ['ESTOI'], and STOI and ESTOI come from one `stoi_ext` call on the truncated
+    pairs.  The first six columns are those of extended=False.
 
     SegSNR and PESQ are NaN.  SegSNR is voicebox `snrseg` (score_audio.m:212), whose default mode runs a P.56
     speech-activity detector and a sub-sample delay search whose exact definitions are not available to this
@@ -1793,16 +1851,21 @@ def compute_scores(est, ref, fs, lengths_est=None, lengths_ref=None, flen=512, s
     r[:, :wr] = _f32c(ref, "ref")[:, :wr]
     e = torch.where(valid, e, torch.zeros_like(e))
     r = torch.where(valid, r, torch.zeros_like(r))
-    S = np.full((n_sig, len(SCORE_LABELS)), np.nan, dtype=np.float64)
+    labels = list(SCORE_LABELS) + (['ESTOI'] if extended else [])
+    S = np.full((n_sig, len(labels)), np.nan, dtype=np.float64)
+
+    def intelligibility():          # [STOI] or [STOI, ESTOI], device tensors
+        return list(stoi_ext(e, r, fs=fs, lengths=ln)) if extended else [stoi(e, r, fs=fs, lengths=ln)]
+
     if sdr_solver == "device":
-        cols = torch.stack([sdr_db(e, r, flen=flen, lengths=ln, solver="device"), snr_db(e, r),
-                            stoi(e, r, fs=fs, lengths=ln)]).cpu().numpy()
-        S[:, 0], S[:, 1], S[:, 5] = cols[0], cols[1], cols[2]
-        return S, list(SCORE_LABELS)
+        cols = torch.stack([sdr_db(e, r, flen=flen, lengths=ln, solver="device"), snr_db(e, r)] +
+                           intelligibility()).cpu().numpy()
+        S[:, 0], S[:, 1], S[:, 5:] = cols[0], cols[1], cols[2:].T
+        return S, labels
     S[:, 0] = sdr_db(e, r, flen=flen).cpu().numpy()
     S[:, 1] = snr_db(e, r).cpu().numpy()
-    S[:, 5] = stoi(e, r, fs=fs, lengths=ln).cpu().numpy()
-    return S, list(SCORE_LABELS)
+    S[:, 5:] = torch.stack(intelligibility()).cpu().numpy().T
+    return S, labels
 
 
 # ---- LSTM baseline (build_lstm, enhance.py:321-345; C ABI in include/drnmf_lstm.h) -----------------------

@@ -1,6 +1,6 @@
 """STOI over a batch sized like the CHiME2 test set: one JSON line.
 
-    python tools/stoi_bench.py [--pairs 1980] [--fs 16000] [--reps 5] [--oracle-pairs 3]
+    python tools/stoi_bench.py [--pairs 1980] [--fs 16000] [--reps 5] [--oracle-pairs 3] [--extended]
 
 The real utterance lengths are not part of this project, so they are drawn (seed 0) uniformly from 2 to 12 s
 (mean 7 s).  Rows are slices of a bank of 8 speech-like 12 s references (tests/stoi_ref.py: speech_like);
@@ -10,6 +10,12 @@ estimates add white noise at an SNR drawn from {-6, -3, 0, 3, 6, 9} dB.  Fields:
   utt_per_s       pairs / gpu_ms
   oracle_s_per_pair  the fp64 numpy restatement (tests/stoi_ref.py) on the CPU, mean over --oracle-pairs rows
   max_abs_err     max |GPU - oracle| over those rows
+--extended times three calls in one session, each as gpu_ms is timed, and adds:
+  estoi_ms        ops.estoi alone (the envelopes, then ESTOI's segment and mean kernels)
+  pair_ms         ops.stoi_ext: STOI and ESTOI from one set of envelopes (drnmf_stoi_ext)
+  pair_over_stoi  pair_ms / gpu_ms
+  estoi_max_abs_err  max |GPU - tests/estoi_ref.py| over the oracle rows; pair_bits_equal: the pair call returns
+                  the bits of the two single calls
 JSON goes to stdout, nothing else does.
 """
 import argparse
@@ -32,6 +38,7 @@ def main():
     ap.add_argument("--fs", type=int, default=16000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--oracle-pairs", type=int, default=3)
+    ap.add_argument("--extended", action="store_true")
     a = ap.parse_args()
     import __graft_entry__ as G
     G.build()
@@ -58,18 +65,29 @@ def main():
     p_ref = (ref.double() ** 2).sum(1) / (noise.double() ** 2).sum(1)
     scale = torch.sqrt(p_ref / torch.from_numpy(10.0 ** (snr / 10.0)).to(dev)).float()
     est = (ref + noise * scale[:, None]).contiguous()
-    out = ops.stoi(est, ref, fs=fs, lengths=lengths)          # warm-up
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(a.reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        out = ops.stoi(est, ref, fs=fs, lengths=lengths)
-        t1.record()
+
+    def timed(fn):
+        out = fn()                                            # warm-up
         torch.cuda.synchronize()
-        times.append(t0.elapsed_time(t1))
+        times = []
+        for _ in range(a.reps):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            out = fn()
+            t1.record()
+            torch.cuda.synchronize()
+            times.append(t0.elapsed_time(t1))
+        return out, times
+
+    out, times = timed(lambda: ops.stoi(est, ref, fs=fs, lengths=lengths))
     gpu_ms = float(np.median(times))
     got = out.cpu().numpy()
+    ext = {}
+    if a.extended:
+        import estoi_ref as ER
+        out_e, t_e = timed(lambda: ops.estoi(est, ref, fs=fs, lengths=lengths))
+        (pair_s, pair_e), t_p = timed(lambda: ops.stoi_ext(est, ref, fs=fs, lengths=lengths))
+        got_e = out_e.cpu().numpy()
     rows = np.argsort(lengths)[:: max(1, n // max(a.oracle_pairs, 1))][:a.oracle_pairs]
     E, X = est.cpu().numpy(), ref.cpu().numpy()
     errs, t_or = [], 0.0
@@ -78,12 +96,22 @@ def main():
         want = R.stoi(X[i, :lengths[i]].astype(np.float64), E[i, :lengths[i]].astype(np.float64), fs)
         t_or += time.perf_counter() - t
         errs.append(abs(float(got[i]) - want))
+    if a.extended:
+        errs_e = [abs(float(got_e[i]) - ER.estoi(X[i, :lengths[i]].astype(np.float64),
+                                                 E[i, :lengths[i]].astype(np.float64), fs)) for i in rows]
+        ext = dict(estoi_ms=round(float(np.median(t_e)), 3), estoi_ms_all=[round(t, 3) for t in t_e],
+                   pair_ms=round(float(np.median(t_p)), 3), pair_ms_all=[round(t, 3) for t in t_p],
+                   pair_over_stoi=round(float(np.median(t_p)) / gpu_ms, 3),
+                   estoi_max_abs_err=float(max(errs_e)) if errs_e else None, mean_estoi=float(np.nanmean(got_e)),
+                   estoi_nan_rows=int(np.isnan(got_e).sum()),
+                   pair_bits_equal=bool(pair_s.cpu().numpy().tobytes() == got.tobytes() and
+                                        pair_e.cpu().numpy().tobytes() == got_e.tobytes()))
     print(json.dumps(dict(
         tool="stoi_bench", pairs=n, fs=fs, lengths="uniform 2-12 s (seed 0)", total_s=float(lengths.sum()) / fs,
         gpu_ms=round(gpu_ms, 3), gpu_ms_all=[round(t, 3) for t in times], utt_per_s=round(n / gpu_ms * 1e3, 1),
         oracle_s_per_pair=round(t_or / max(len(rows), 1), 3), oracle_pairs=int(len(rows)),
         max_abs_err=float(max(errs)) if errs else None, mean_stoi=float(np.nanmean(got)),
-        device=torch.cuda.get_device_name(0))))
+        device=torch.cuda.get_device_name(0), **ext)))
 
 
 if __name__ == "__main__":
