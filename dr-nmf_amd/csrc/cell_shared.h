@@ -491,7 +491,10 @@ Workspace workspace_layout(const drnmf_cell_desc_t* d, bool allow_split = true) 
     while (KS < (blocked ? 2 : 4) && tiles * KS < 192 && nchN / (KS * 2) >= 4) KS *= 2;
     if (const char* e = tune_env("DRNMF_KS")) {   // tuning aid: force the number of atom ranges
         const int v = atoi(e);
-        if ((v == 1 || v == 2 || v == 4 || v == 8) && (!blocked || v <= 2) && nchN / v >= 1) KS = v;
+        // (only a count that leaves no range empty: cell_b has no path for a range without chunks -- it would
+        // run one chunk from behind the range's end, e.g. 18 chunks in 8 ranges of 3: ranges 6 and 7)
+        const bool no_empty = v >= 1 && (v - 1) * ((nchN + v - 1) / v) < nchN;
+        if ((v == 1 || v == 2 || v == 4 || v == 8) && (!blocked || v <= 2) && no_empty) KS = v;
     }
     if (nonlin) KS = 1;
     if (W.half) KS = 1;        // the fp16 residual is stored once, already rounded (cell_b_kernel)

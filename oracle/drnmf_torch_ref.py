@@ -12,16 +12,15 @@ def unit_cols(logD):
     return D / torch.sqrt((D * D).sum(0, keepdim=True))
 
 
-def model_loss(x, y, w, alt, labels_per_k, K, log_h0, kc, kn, mask_value=-1.0, square=False,
-               normalise=True, snmf_cost_l1_weight=None, divergence='ed', beta=1.5, initial_state=None):
-    """x, y: (B,T,F) float64 tensors; w: (B,T) sample weights (= validity mask in the reference).
-    alt: dict name -> tensor (requires_grad where wanted).  Returns (loss, mask, h).
+def cell_outputs(x, alt, labels_per_k, K, log_h0, mask_value=-1.0, divergence='ed', beta=1.5,
+                 initial_state=None, pre_acts=None):
+    """The recurrent cell alone: x (B,T,F) -> the last layer's outputs (B,T,N), a masked frame repeating
+    the last valid one (zeros before the first).  alt: dict name -> tensor (requires_grad where wanted).
     divergence 'kl' | 'beta': the KL / beta variant of the cell (oracle.cell_forward_ista_warm: every
     layer, layer 0 included, a full ista_kl / ista_beta step from its input -- enhance.py:421-456 --
-    and no U term)."""
+    and no U term).  pre_acts: a list that receives (t, k, pre-activation (B,N)) of every layer-step."""
     B, T, F = x.shape
     N = log_h0.shape[0]
-    r = N // 2
     valid = (x != mask_value).any(-1)
     xm = x * valid[..., None].to(x.dtype)
     U1 = torch.exp(alt['log_U1'])
@@ -33,6 +32,11 @@ def model_loss(x, y, w, alt, labels_per_k, K, log_h0, kc, kn, mask_value=-1.0, s
     state = h0[None, :].expand(B, N) if initial_state is None else initial_state.detach()
     out_prev = torch.zeros(B, N, dtype=x.dtype)
     outs = []
+
+    def act(t, k, pre):
+        if pre_acts is not None:
+            pre_acts.append((t, k, pre))
+        return torch.relu(pre)
     # the maps from the log-domain parameters are evaluated once per graph execution, outside the
     # scan over time (custom_layers.py:234-287 builds Wk/Sk/bk in build(), not in step())
     Dns = [unit_cols(alt[labels_per_k['log_D'][k]]) for k in range(K)]
@@ -43,11 +47,11 @@ def model_loss(x, y, w, alt, labels_per_k, K, log_h0, kc, kn, mask_value=-1.0, s
         ps = p.sum(1, keepdim=True)
         xt = xm[:, t]
         if divergence == 'ed':
-            h = torch.relu(u0d * p + u0o * (ps - p) + (xt @ Dns[0]) * ias[0] - lams[0] * ias[0])
+            h = act(t, 0, u0d * p + u0o * (ps - p) + (xt @ Dns[0]) * ias[0] - lams[0] * ias[0])
             for k in range(1, K):
                 Dn, ia, lam = Dns[k], ias[k], lams[k]
                 rr = xt - h @ Dn.t()
-                h = torch.relu(h + (rr @ Dn) * ia - lam * ia + uko * ps)
+                h = act(t, k, h + (rr @ Dn) * ia - lam * ia + uko * ps)
         else:
             h = p
             vrow = valid[:, t][:, None]
@@ -61,12 +65,18 @@ def model_loss(x, y, w, alt, labels_per_k, K, log_h0, kc, kn, mask_value=-1.0, s
                     rr = xt / xe - 1.0                                   # enhance.py:431
                 else:
                     rr = xt * xe ** (beta - 2.0) - xe ** (beta - 1.0)    # enhance.py:450
-                h = torch.relu(h + (rr @ Dn) * ia - lam * ia)
+                h = act(t, k, h + (rr @ Dn) * ia - lam * ia)
         v = valid[:, t][:, None]
         out_prev = torch.where(v, h, out_prev)
         state = torch.where(v, h, state)
         outs.append(out_prev)
-    hs = torch.stack(outs, 1)
+    return torch.stack(outs, 1)
+
+
+def head_terms(x, y, w, hs, kc, kn, square=False, snmf_cost_l1_weight=None):
+    """The loss head alone on ANY hidden tensor hs (..., 2r): x, y (..., F), w (...).  Returns (sum over
+    frames of w * the per-frame loss, number of frames with w != 0, mask)."""
+    r = hs.shape[-1] // 2
     A = hs[..., :r] @ torch.exp(kc)
     Bn = hs[..., r:] @ torch.exp(kn)
     if square:
@@ -79,6 +89,16 @@ def model_loss(x, y, w, alt, labels_per_k, K, log_h0, kc, kn, mask_value=-1.0, s
         mse = ((x * mask - y) ** 2).mean(-1)            # y_pred = x_raw * mask (enhance.py:1042)
     sse = (mse * w).sum()
     cnt = (w != 0).to(x.dtype).sum()
+    return sse, cnt, mask
+
+
+def model_loss(x, y, w, alt, labels_per_k, K, log_h0, kc, kn, mask_value=-1.0, square=False,
+               normalise=True, snmf_cost_l1_weight=None, divergence='ed', beta=1.5, initial_state=None):
+    """x, y: (B,T,F) float64 tensors; w: (B,T) sample weights (= validity mask in the reference).
+    alt: dict name -> tensor (requires_grad where wanted).  Returns (loss, mask, h): cell_outputs
+    followed by head_terms."""
+    hs = cell_outputs(x, alt, labels_per_k, K, log_h0, mask_value, divergence, beta, initial_state)
+    sse, cnt, mask = head_terms(x, y, w, hs, kc, kn, square, snmf_cost_l1_weight)
     loss = sse / cnt if normalise else sse
     return loss, mask, hs
 
