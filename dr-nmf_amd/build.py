@@ -41,6 +41,9 @@ NO_SCRATCH = {"lstm.hip": "lstm_step_kernel",
               "snmf_mask.hip": "snmf_mask_",
               # its fp16-operand sibling: H (fp32 master), num and den of its tiles in registers as well
               "snmf_f16.hip": "snmf_f16_",
+              # the adaptive baseline's H pass keeps num and den in registers, its statistics pass four accumulators per
+              # 16-atom tile; the small kernels of the file ride along
+              "snmf_adapt.hip": "snmf_adapt_",
               # the target kernels keep the noisy member's bins of a frame in registers (up to 27 per lane)
               "stft.hip": "stft_pair_target_",
               # the ESTOI segment kernel holds a 30-frame row, then two 15-band columns, of fp64 per lane
@@ -73,7 +76,7 @@ def _deps():
     return _sources() + glob.glob(os.path.join(CSRC, "*.h")) + \
         [os.path.join(os.path.dirname(HERE), "include", n) for n in ("drnmf.h", "drnmf_lstm.h", "drnmf_score.h", "drnmf_enhance.h", "drnmf_sdr.h",
                                                                      "drnmf_dataset.h", "drnmf_stream.h", "drnmf_snmf.h", "drnmf_snmf_f16.h",
-                                                                     "drnmf_target.h", "drnmf_estoi.h")] + \
+                                                                     "drnmf_target.h", "drnmf_estoi.h", "drnmf_snmf_adapt.h")] + \
         [os.path.abspath(__file__)]
 
 

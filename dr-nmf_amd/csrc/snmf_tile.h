@@ -5,6 +5,7 @@
 // stride of Hs and Ws), the row scale (rs: nullptr = none, and then no multiply either; else s[rl] multiplies V
 // and the mask's epsilon) and how a chunk of the dictionary gets into Ws (a callable).  The per-wave partials in
 // Lp are TR * LLD floats apart in both kernels (the fp16 kernel's wider stride is its iterations' own).
+// snmf_adapt.hip runs the same phases on a dictionary per batch row.
 // Everything is passed as plain pointer and int arguments: no tile state is held across the kernel.
 //
 // Layout.  Hs [16][LD], Ws [32][LD], LD = Np + 8 (Np = N rounded up to 16).  LD % 16 == 8 makes both operand
@@ -166,11 +167,11 @@ __device__ __forceinline__ bool all_masked(const int* valid, float* mask_out, in
     return true;
 }
 
-// Launch of a tile kernel instance, 16 rows per workgroup of 256.  Once per instance and device: the dynamic-LDS
+// Launch of a tile kernel instance on `grid` workgroups of 256.  Once per instance and device: the dynamic-LDS
 // limit of the widest shape the instance takes (lds_max; a property of the function, not of a launch; a second
 // thread that gets here first sets the same value again).
 template <auto Kern, class... Args>
-hipError_t launch(int device, size_t lds_max, size_t lds, int64_t rows, hipStream_t stream, Args... args) {
+hipError_t launch_grid(int device, size_t lds_max, size_t lds, dim3 grid, hipStream_t stream, Args... args) {
     static std::atomic<bool> raised[64];
     if (device < 0 || device >= 64 || !raised[device].load(std::memory_order_acquire)) {
         const hipError_t e = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -178,8 +179,14 @@ hipError_t launch(int device, size_t lds_max, size_t lds, int64_t rows, hipStrea
         if (e != hipSuccess) return e;
         if (device >= 0 && device < 64) raised[device].store(true, std::memory_order_release);
     }
-    hipLaunchKernelGGL(Kern, dim3((unsigned)((rows + TR - 1) / TR)), dim3(256), lds, stream, args...);
+    hipLaunchKernelGGL(Kern, grid, dim3(256), lds, stream, args...);
     return hipGetLastError();
+}
+
+// ... 16 rows per workgroup
+template <auto Kern, class... Args>
+hipError_t launch(int device, size_t lds_max, size_t lds, int64_t rows, hipStream_t stream, Args... args) {
+    return launch_grid<Kern>(device, lds_max, lds, dim3((unsigned)((rows + TR - 1) / TR)), stream, args...);
 }
 
 }  // namespace snmf_tile

@@ -2757,10 +2757,19 @@ class SparseNMFModel(_SequenceModel):
     cores with fp32 accumulation (csrc/snmf_f16.hip, ops.snmf_f16_forward; every frame scaled by a power of two of
     its own); the numerator, the update, the master copy of H and the final mask stay float32, and so do the
     weights.  Such a model ALWAYS runs that kernel (the mode is about operand precision, not speed): beta == 2,
-    2r <= 512 and path 'auto' or 'tile' only."""
+    2r <= 512 and path 'auto' or 'tile' only.
+
+    adapt_noise (no counterpart in the reference's inference; its stage two of dictionary training is the same
+    update, enhance.py:110-116): True makes the model semi-supervised.  Every batch row -- one recording, or one cut
+    of it -- keeps the r speech atoms and fits the r noise atoms to its own valid frames during the n_iter
+    iterations (sparse_nmf_gpu.m:232-264 with w_update_ind false on the speech half; csrc/snmf_adapt.hip,
+    ops.snmf_adapt_forward).  The stored dictionary is the starting point and is never modified;
+    forward(x, return_dictionaries=True) also returns the rows' dictionaries [B, F, 2r] (unit-norm columns).  Rows
+    are independent bit for bit, so predict and enhance may regroup them; frames of ONE row are not, so `stream`
+    raises NotImplementedError.  beta == 2, 2r <= 512, float32 operands and path 'auto' or 'tile' only."""
 
     def __init__(self, W, r, sparsity, n_iter=200, beta=2.0, spectrogram_power=1.0, mask_value=-1.0, h_init=None,
-                 random_seed=2016, path='auto', device=None, operand_dtype='float32'):
+                 random_seed=2016, path='auto', device=None, operand_dtype='float32', adapt_noise=False):
         W = np.asarray(W, np.float32)
         r = int(r)
         if W.ndim != 2 or W.shape[1] % 2 or W.shape[1] != 2 * r or r < 1:
@@ -2776,7 +2785,13 @@ class SparseNMFModel(_SequenceModel):
             raise ValueError("SparseNMFModel: operand_dtype='float16' runs one kernel, which takes beta == 2, "
                              "2r <= %d and path 'auto' or 'tile' (beta = %g, 2r = %d, path = %r)" %
                              (_capi.SNMF_F16_MAX_N, float(beta), N, path))
+        if adapt_noise and (operand_dtype == 'float16' or float(beta) != 2.0 or N > _capi.SNMF_ADAPT_MAX_N or
+                            path == 'gemm'):
+            raise ValueError("SparseNMFModel: adapt_noise=True takes operand_dtype='float32', beta == 2, 2r <= %d and "
+                             "path 'auto' or 'tile' (operand_dtype = %r, beta = %g, 2r = %d, path = %r)" %
+                             (_capi.SNMF_ADAPT_MAX_N, operand_dtype, float(beta), N, path))
         self.operand_dtype = operand_dtype
+        self.adapt_noise = bool(adapt_noise)
         if h_init is None:
             h_init = np.random.RandomState(int(random_seed)).rand(N)
         h_init = np.asarray(h_init, np.float32).reshape(-1)
@@ -2836,12 +2851,22 @@ class SparseNMFModel(_SequenceModel):
         self._operands()
         return self._normalised[3]
 
-    def forward(self, x):
-        """x [B,T,F] device float32 -> mask [B,T,F]; nothing is waited for."""
+    def forward(self, x, return_dictionaries=False):
+        """x [B,T,F] device float32 -> mask [B,T,F]; nothing is waited for.  return_dictionaries=True (an adaptive
+        model only): (mask, the rows' dictionaries [B,F,2r])."""
         F = self._input_width()
         if x.dim() != 3 or x.shape[-1] != F:
             raise ValueError('forward: x must be (B, T, %d), got %s' % (F, tuple(x.shape)))
+        if return_dictionaries and not self.adapt_noise:
+            raise ValueError('forward: return_dictionaries=True needs a model built with adapt_noise=True (every '
+                             'row of a fixed model has the stored dictionary)')
         Wn, hn = self._operands()
+        if self.adapt_noise:
+            self._ws = ops.snmf_adapt_workspace(int(x.shape[0]), int(x.shape[1]), F, 2 * self.r, self.r, x.device,
+                                                have=self._ws)
+            return ops.snmf_adapt_forward(x, Wn, hn, self.sparsity, self.n_iter, self.r,
+                                          power=self.spectrogram_power, mask_value=self.mask_value,
+                                          workspace=self._ws, return_dictionaries=return_dictionaries)
         if self.operand_dtype == 'float16':
             return ops.snmf_f16_forward(x, self._dict16(), Wn, hn, self.sparsity, self.n_iter,
                                         power=self.spectrogram_power, mask_value=self.mask_value)
@@ -2853,6 +2878,13 @@ class SparseNMFModel(_SequenceModel):
                                      workspace=self._ws)
 
     __call__ = forward
+
+    def stream(self, *args, **kwargs):
+        if self.adapt_noise:
+            raise NotImplementedError('SparseNMFModel: stream() of an adaptive model (adapt_noise=True) is not '
+                                      'defined -- the noise atoms are fitted to a whole row; online adaptation is '
+                                      'another algorithm')
+        return super(SparseNMFModel, self).stream(*args, **kwargs)
 
     def free_predict_buffers(self):
         super(SparseNMFModel, self).free_predict_buffers()
@@ -2884,7 +2916,10 @@ class SparseNMFModel(_SequenceModel):
 
     def val_loss(self, noisy, clean, N=512, hop=128):
         """enhance.py:855 on waveform pairs: mean((irm * x - y)^2) over the packed frames of both sides raised
-        to spectrogram_power."""
+        to spectrogram_power.  An adaptive model adapts per recording: one row each through the ragged STFT that
+        `enhance` uses, the same mean over the same frames."""
+        if self.adapt_noise:
+            return self._val_loss_per_recording(noisy, clean, N, hop)
         with torch.cuda.device(self.device):
             xf, yf = ops.wavs_to_frames(noisy, clean, N, hop)
             irm = self.forward(xf[None])[0]
@@ -2892,16 +2927,36 @@ class SparseNMFModel(_SequenceModel):
             return float(((irm * xf ** p - yf ** p) ** 2).mean())
 
 
+    def _val_loss_per_recording(self, noisy, clean, N, hop):
+        rx, ry, dt, nf = ops._check_wav_pairs(noisy, clean, N, hop, 'mag', 'val_loss')
+        dev = torch.device('cuda', ops._dev_of(self.device))
+        with torch.cuda.device(dev):
+            pcm_x, len_x = ops._upload_wav_side(rx, dt, dev)
+            pcm_y, len_y = ops._upload_wav_side(ry, dt, dev)
+            x, _, _, nfx = ops.stft_ragged(pcm_x, len_x, N=N, hop=hop, mask_value=self.mask_value)
+            T = int(nfx.max())
+            y, _, _, _ = ops.stft_ragged(pcm_y, len_y, T=T, N=N, hop=hop, mask_value=self.mask_value)
+            # the frames of the pair are the clean side's (ops.wavs_to_frames); a longer noisy side is cut there
+            keep = (torch.arange(T, device=dev)[None, :] < torch.from_numpy(nf).to(dev)[:, None])[..., None]
+            x = torch.where(keep, x, torch.full_like(x, float(self.mask_value))).contiguous()
+            irm = self.forward(x)
+            p = self.spectrogram_power
+            err = torch.where(keep, (irm * x ** p - y ** p) ** 2, torch.zeros_like(x))
+            return float(err.sum() / (int(nf.sum()) * x.shape[-1]))
+
+
 def build_snmf(params_snmf, W, device=None):
     """The sparse-NMF baseline from the reference's params_snmf (enhance.py:590-596, 754-757, 838-845) and a
     trained dictionary W (F, 2r): keys r, sparsity, cf ('ed' / 'kl' / 'is', or 'beta'), random_seed,
     spectrogram_power; max_iter / conv_eps are training settings -- inference runs the reference's 200
     iterations.  Optional keys the reference's dictionaries do not have: 'n_iter', 'mask_value', 'path' and
-    'operand_dtype' ('float32' or 'float16', as build_unfolded_snmf's and build_lstm's)."""
+    'operand_dtype' ('float32' or 'float16', as build_unfolded_snmf's and build_lstm's) and 'adapt_noise' (True: every
+    row fits the noise atoms to its own frames, see SparseNMFModel)."""
     from . import snmf
     p = params_snmf
     return SparseNMFModel(W, int(p['r']), float(p.get('sparsity', 0.0)), n_iter=int(p.get('n_iter', 200)),
                           beta=snmf._beta(p), spectrogram_power=float(p.get('spectrogram_power', 1.0)),
                           mask_value=p.get('mask_value', -1.0), random_seed=int(p.get('random_seed', 2016)),
                           path=p.get('path', 'auto'), device=device,
-                          operand_dtype=p.get('operand_dtype', 'float32'))
+                          operand_dtype=p.get('operand_dtype', 'float32'),
+                          adapt_noise=bool(p.get('adapt_noise', False)))

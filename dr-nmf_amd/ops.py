@@ -917,6 +917,45 @@ def snmf_f16_forward(x, dict16, Wn, h_init, sparsity, n_iter, power=1.0, mask_va
     return out
 
 
+def snmf_adapt_admitted(F, N, beta=2.0):
+    """True when `snmf_adapt_forward` takes the shape (beta == 2, 2 <= N <= 512)."""
+    return bool(_capi.lib().drnmf_snmf_adapt_admitted(int(F), int(N), float(beta)))
+
+
+def snmf_adapt_workspace(B, T, F, N, n_fixed, device, have=None):
+    """The workspace `snmf_adapt_forward` needs for this call: a uint8 tensor of drnmf_snmf_adapt_workspace_bytes --
+    `have` itself when it is large enough and on `device`.  ValueError for a shape the entry point refuses."""
+    need = _capi.lib().drnmf_snmf_adapt_workspace_bytes(int(B), int(T), int(F), int(N), int(n_fixed))
+    if need == 0:
+        raise ValueError("snmf_adapt: shape B=%d T=%d F=%d N=%d n_fixed=%d is not taken (N even, 2 <= N <= %d, "
+                         "0 <= n_fixed <= N)" % (B, T, F, N, n_fixed, _capi.SNMF_ADAPT_MAX_N))
+    if have is not None and have.numel() >= need and have.device == torch.device(device):
+        return have
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def snmf_adapt_forward(x, Wn, hn, sparsity, n_iter, n_fixed, power=1.0, mask_value=None, workspace=None,
+                       return_dictionaries=False, return_activations=False):
+    """The noise-adaptive sparse-NMF baseline on padded sequences (drnmf_snmf_adapt_forward): every row of x [B,T,F]
+    keeps the first n_fixed atoms of Wn [F,N] (unit-norm columns) and fits the others to its own valid frames for
+    n_iter iterations, all frames starting from hn [N] -> mask [B,T,F].  return_dictionaries / return_activations
+    append the rows' dictionaries [B,F,N] / activations [B,T,N] (normalised basis; 0 at masked frames).  beta == 2
+    only; workspace: a uint8 tensor (`snmf_adapt_workspace`; allocated here when None or too small)."""
+    L, h, x, Wn, hn, out = _snmf_args(x, Wn, hn, None)
+    B, T, F = x.shape
+    N = Wn.shape[1]
+    workspace = snmf_adapt_workspace(B, T, F, N, n_fixed, x.device, have=workspace)
+    Wd = torch.empty((B, F, N), dtype=torch.float32, device=x.device) if return_dictionaries else None
+    Ha = torch.empty((B, T, N), dtype=torch.float32, device=x.device) if return_activations else None
+    rc = L.drnmf_snmf_adapt_forward(h, B, T, F, N, int(n_fixed), int(n_iter), float(sparsity), float(power),
+                                    0.0 if mask_value is None else float(mask_value), int(mask_value is not None),
+                                    _capi.ptr(x), _capi.ptr(Wn), _capi.ptr(hn), _capi.ptr(out), _capi.ptr(Wd),
+                                    _capi.ptr(Ha), _capi.ptr(workspace), workspace.numel(), _stream())
+    _capi.check(rc, h, "drnmf_snmf_adapt_forward")
+    ret = (out,) + ((Wd,) if return_dictionaries else ()) + ((Ha,) if return_activations else ())
+    return ret[0] if len(ret) == 1 else ret
+
+
 def stft_frames(nsampl, N, hop):
     return int(_capi.lib().drnmf_stft_frames(int(nsampl), int(N), int(hop)))
 
