@@ -2,7 +2,7 @@
 STOI score's in include/drnmf_score.h; the ragged STFT / iSTFT / int16 stages' in include/drnmf_enhance.h; the
 device-side SDR's in include/drnmf_sdr.h; the training-data front end's in include/drnmf_dataset.h; the streaming
 STFT / iSTFT's in include/drnmf_stream.h; the sparse-NMF baseline's inference in include/drnmf_snmf.h, on fp16
-operands in include/drnmf_snmf_f16.h, with per-row noise atoms in include/drnmf_snmf_adapt.h; ESTOI beside STOI in include/drnmf_estoi.h).
+operands in include/drnmf_snmf_f16.h, with per-row noise atoms in include/drnmf_snmf_adapt.h, under the KL cost in include/drnmf_snmf_kl.h; ESTOI beside STOI in include/drnmf_estoi.h).
 
 The library is the product path: there is NO fallback.  If the shared object is missing or a
 call fails, an exception is raised.
@@ -253,6 +253,17 @@ SNMF_ADAPT_SIGNATURES = {
 }
 SNMF_ADAPT_MAX_N = 512                             # csrc/snmf_adapt.hip MAX_N
 
+# name -> (restype, argtypes); mirrors include/drnmf_snmf_kl.h one to one (a table of its own, like those above)
+SNMF_KL_SIGNATURES = {
+    "drnmf_snmf_kl_admitted": (_i32, [_i32, _i32]),
+    "drnmf_snmf_kl_workspace_bytes": (_sz, []),
+    "drnmf_snmf_kl_auto_max_rows": (_i64, []),
+    "drnmf_snmf_kl_forward": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _f32,
+                                     _vp, _vp, _sz, _vp]),
+}
+SNMF_KL_MAX_N = 512                                # csrc/snmf_kl.hip KL_MAX_N
+SNMF_KL_AUTO_MAX_ROWS = 8192                        # csrc/snmf_kl.hip KL_AUTO_MAX_ROWS: a beta = 1 model's 'auto' takes the KL kernel up to here
+
 _lib = None
 _handles = {}
 
@@ -279,7 +290,8 @@ def lib():
                                   list(SDR_SIGNATURES.items()) + list(DATASET_SIGNATURES.items()) +
                                   list(STREAM_SIGNATURES.items()) + list(SNMF_SIGNATURES.items()) +
                                   list(SNMF_F16_SIGNATURES.items()) + list(TARGET_SIGNATURES.items()) +
-                                  list(ESTOI_SIGNATURES.items()) + list(SNMF_ADAPT_SIGNATURES.items())):
+                                  list(ESTOI_SIGNATURES.items()) + list(SNMF_ADAPT_SIGNATURES.items()) +
+                                  list(SNMF_KL_SIGNATURES.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

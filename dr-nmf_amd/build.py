@@ -44,6 +44,8 @@ NO_SCRATCH = {"lstm.hip": "lstm_step_kernel",
               # the adaptive baseline's H pass keeps num and den in registers, its statistics pass four accumulators per
               # 16-atom tile; the small kernels of the file ride along
               "snmf_adapt.hip": "snmf_adapt_",
+              # the KL tile kernel: H's numerator of its tiles, the column denominators and a chunk of V in registers
+              "snmf_kl.hip": "snmf_kl_",
               # the target kernels keep the noisy member's bins of a frame in registers (up to 27 per lane)
               "stft.hip": "stft_pair_target_",
               # the ESTOI segment kernel holds a 30-frame row, then two 15-band columns, of fp64 per lane
@@ -76,7 +78,8 @@ def _deps():
     return _sources() + glob.glob(os.path.join(CSRC, "*.h")) + \
         [os.path.join(os.path.dirname(HERE), "include", n) for n in ("drnmf.h", "drnmf_lstm.h", "drnmf_score.h", "drnmf_enhance.h", "drnmf_sdr.h",
                                                                      "drnmf_dataset.h", "drnmf_stream.h", "drnmf_snmf.h", "drnmf_snmf_f16.h",
-                                                                     "drnmf_target.h", "drnmf_estoi.h", "drnmf_snmf_adapt.h")] + \
+                                                                     "drnmf_target.h", "drnmf_estoi.h", "drnmf_snmf_adapt.h",
+                                                                     "drnmf_snmf_kl.h")] + \
         [os.path.abspath(__file__)]
 
 

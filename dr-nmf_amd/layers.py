@@ -2739,18 +2739,28 @@ class SparseNMFModel(_SequenceModel):
     (rand('seed', 2016), sparse_nmf_gpu.m), which cannot be reproduced here, and
     any per-frame draw would make a frame's result depend on where the frame sits in a batch.  With a shared
     vector the mask of a frame is a function of that frame alone: predict does not depend on the slabs, and a
-    recording streamed in chunks gives the masks of the whole recording.  (For beta = 2, the reference's 'ed'.  For
-    other beta the update raises zeros of V to the smallest positive entry of the CALL's V, sparse_nmf_gpu.m:201-205:
-    a frame that holds a zero bin then depends on the frames it is run with.)  h_init is given for the dictionary as
-    stored; the kernels work in the column-normalised basis (sparse_nmf_gpu.m:163-166) and receive
-    h_init * column norms.
+    recording streamed in chunks gives the masks of the whole recording.  (For beta = 2, the reference's 'ed', and
+    for beta = 1, its 'kl', with `v_floor` set.  For beta != 2 the reference's update raises zeros of V to the smallest
+    positive entry of the CALL's V, sparse_nmf_gpu.m:201-205: a frame that holds a zero bin then depends on the frames
+    it is run with.  v_floor=None keeps that rule, on every path.)  h_init is given for the dictionary as stored; the
+    kernels work in the column-normalised basis (sparse_nmf_gpu.m:163-166) and receive h_init * column norms.
 
     Streaming.  Frames are independent, so there is no state: _stateful() is True (the streaming contract holds
     trivially, and predict keeps every row at its own frames: a masked frame's mask is 0, not a repeat of the
     frame before it) and reset_states() does nothing.
 
     path: 'auto' (the rule in ops.snmf_mask_forward / DESIGN.md), 'gemm' or 'tile'.  Nothing is compiled or
-    fitted: the dictionary comes from snmf.train_snmf (`from_wavs`).
+    fitted: the dictionary comes from snmf.train_snmf (`from_wavs`).  For beta = 1 the tile kernel is the KL one
+    (csrc/snmf_kl.hip, ops.snmf_kl_forward; 2r <= 512, else 'tile' is a ValueError here) and 'auto' takes it up to
+    _capi.SNMF_KL_AUTO_MAX_ROWS rows of a call, the measured crossover at beta = 1, and the
+    GEMM path beyond; any other beta != 2 runs the GEMM path only.
+
+    v_floor (no counterpart in the reference; beta = 1 only): a positive finite number to which the zeros of V are
+    raised INSTEAD of the call's smallest positive entry.  A frame's mask is then a function of that frame alone again,
+    bit for bit: predict does not depend on batch_size and a streamed recording equals the whole one.  Such a model
+    ALWAYS runs the KL kernel, at any row count (the option is about what is computed, as operand_dtype='float16'
+    is): beta == 1, 2r <= 512 and path 'auto' or 'tile' only.  Choose it below the smallest magnitude that counts as
+    signal (1e-3 of an int16 step's spectrum is far below any recorded bin).
 
     operand_dtype (no counterpart in the reference; as SimpleDeepRNN's and LSTM's): 'float16' rounds the operands of
     the iteration's two products -- the dictionary, H and Lambda -- to fp16 and contracts them on the fp16 matrix
@@ -2769,7 +2779,8 @@ class SparseNMFModel(_SequenceModel):
     raises NotImplementedError.  beta == 2, 2r <= 512, float32 operands and path 'auto' or 'tile' only."""
 
     def __init__(self, W, r, sparsity, n_iter=200, beta=2.0, spectrogram_power=1.0, mask_value=-1.0, h_init=None,
-                 random_seed=2016, path='auto', device=None, operand_dtype='float32', adapt_noise=False):
+                 random_seed=2016, path='auto', device=None, operand_dtype='float32', adapt_noise=False,
+                 v_floor=None):
         W = np.asarray(W, np.float32)
         r = int(r)
         if W.ndim != 2 or W.shape[1] % 2 or W.shape[1] != 2 * r or r < 1:
@@ -2790,8 +2801,25 @@ class SparseNMFModel(_SequenceModel):
             raise ValueError("SparseNMFModel: adapt_noise=True takes operand_dtype='float32', beta == 2, 2r <= %d and "
                              "path 'auto' or 'tile' (operand_dtype = %r, beta = %g, 2r = %d, path = %r)" %
                              (_capi.SNMF_ADAPT_MAX_N, operand_dtype, float(beta), N, path))
+        if v_floor is not None:
+            if not (float(v_floor) > 0 and float(v_floor) < float('inf')):
+                raise ValueError('SparseNMFModel: v_floor must be None or a positive finite number (v_floor = %r)' %
+                                 (v_floor,))
+            if float(beta) != 1.0:
+                raise ValueError('SparseNMFModel: v_floor is the floor of the KL update and takes beta == 1 '
+                                 '(beta = %g)' % float(beta))
+            if N > _capi.SNMF_KL_MAX_N:
+                raise ValueError('SparseNMFModel: v_floor runs the KL kernel, which takes 2r <= %d (2r = %d)' %
+                                 (_capi.SNMF_KL_MAX_N, N))
+            if path == 'gemm':
+                raise ValueError("SparseNMFModel: v_floor runs the KL kernel: path 'auto' or 'tile' (path = %r)" %
+                                 (path,))
+        if float(beta) == 1.0 and path == 'tile' and N > _capi.SNMF_KL_MAX_N:
+            raise ValueError("SparseNMFModel: path='tile' at beta == 1 is the KL kernel, which takes 2r <= %d "
+                             "(2r = %d)" % (_capi.SNMF_KL_MAX_N, N))
         self.operand_dtype = operand_dtype
         self.adapt_noise = bool(adapt_noise)
+        self.v_floor = None if v_floor is None else float(v_floor)
         if h_init is None:
             h_init = np.random.RandomState(int(random_seed)).rand(N)
         h_init = np.asarray(h_init, np.float32).reshape(-1)
@@ -2806,6 +2834,7 @@ class SparseNMFModel(_SequenceModel):
         self.h_init = torch.from_numpy(np.array(h_init, copy=True)).to(self.device)
         self._normalised = None      # (W version, Wn, h_init * column norms[, Wn packed as fp16])
         self._ws = None
+        self._ws_kl = None
 
     @property
     def weights(self):
@@ -2851,6 +2880,15 @@ class SparseNMFModel(_SequenceModel):
         self._operands()
         return self._normalised[3]
 
+    def _takes_kl_kernel(self, rows):
+        """beta == 1 only: does a call of `rows` frame rows run csrc/snmf_kl.hip (else the GEMM path)?  With v_floor
+        always; path 'tile' always; 'auto' up to the measured row count."""
+        if self.beta != 1.0 or self.path == 'gemm':
+            return False
+        if self.v_floor is not None or self.path == 'tile':
+            return True
+        return 2 * self.r <= _capi.SNMF_KL_MAX_N and int(rows) <= _capi.SNMF_KL_AUTO_MAX_ROWS
+
     def forward(self, x, return_dictionaries=False):
         """x [B,T,F] device float32 -> mask [B,T,F]; nothing is waited for.  return_dictionaries=True (an adaptive
         model only): (mask, the rows' dictionaries [B,F,2r])."""
@@ -2871,6 +2909,12 @@ class SparseNMFModel(_SequenceModel):
             return ops.snmf_f16_forward(x, self._dict16(), Wn, hn, self.sparsity, self.n_iter,
                                         power=self.spectrogram_power, mask_value=self.mask_value)
         B, T = int(x.shape[0]), int(x.shape[1])
+        if self._takes_kl_kernel(B * T):
+            if self._ws_kl is None or self._ws_kl.device != x.device:
+                self._ws_kl = torch.empty(_capi.lib().drnmf_snmf_kl_workspace_bytes(), dtype=torch.uint8,
+                                          device=x.device)
+            return ops.snmf_kl_forward(x, Wn, hn, self.sparsity, self.n_iter, power=self.spectrogram_power,
+                                       mask_value=self.mask_value, v_floor=self.v_floor, workspace=self._ws_kl)
         # (kept between calls; ops decides whether the call takes one at all)
         self._ws = ops.snmf_mask_workspace(self.path, B, T, F, 2 * self.r, self.beta, x.device, have=self._ws)
         return ops.snmf_mask_forward(x, Wn, hn, self.sparsity, self.n_iter, beta=self.beta,
@@ -2889,6 +2933,7 @@ class SparseNMFModel(_SequenceModel):
     def free_predict_buffers(self):
         super(SparseNMFModel, self).free_predict_buffers()
         self._ws = None
+        self._ws_kl = None
 
     def compile(self, *args, **kwargs):
         raise NotImplementedError('SparseNMFModel: nothing to compile -- the dictionary is trained by '
@@ -2950,8 +2995,10 @@ def build_snmf(params_snmf, W, device=None):
     trained dictionary W (F, 2r): keys r, sparsity, cf ('ed' / 'kl' / 'is', or 'beta'), random_seed,
     spectrogram_power; max_iter / conv_eps are training settings -- inference runs the reference's 200
     iterations.  Optional keys the reference's dictionaries do not have: 'n_iter', 'mask_value', 'path' and
-    'operand_dtype' ('float32' or 'float16', as build_unfolded_snmf's and build_lstm's) and 'adapt_noise' (True: every
-    row fits the noise atoms to its own frames, see SparseNMFModel)."""
+    'operand_dtype' ('float32' or 'float16', as build_unfolded_snmf's and build_lstm's), 'adapt_noise' (True: every
+    row fits the noise atoms to its own frames, see SparseNMFModel) and 'v_floor' (cf 'kl' only: the constant that
+    zeros of V are raised to, see SparseNMFModel; absent or None: the reference's per-call rule).  cf 'kl' runs the KL
+    tile kernel where 'path' says so, cf 'ed' the Euclidean one."""
     from . import snmf
     p = params_snmf
     return SparseNMFModel(W, int(p['r']), float(p.get('sparsity', 0.0)), n_iter=int(p.get('n_iter', 200)),
@@ -2959,4 +3006,4 @@ def build_snmf(params_snmf, W, device=None):
                           mask_value=p.get('mask_value', -1.0), random_seed=int(p.get('random_seed', 2016)),
                           path=p.get('path', 'auto'), device=device,
                           operand_dtype=p.get('operand_dtype', 'float32'),
-                          adapt_noise=bool(p.get('adapt_noise', False)))
+                          adapt_noise=bool(p.get('adapt_noise', False)), v_floor=p.get('v_floor'))

@@ -917,6 +917,38 @@ def snmf_f16_forward(x, dict16, Wn, h_init, sparsity, n_iter, power=1.0, mask_va
     return out
 
 
+def snmf_kl_admitted(F, N):
+    """True when the KL tile kernel of `snmf_kl_forward` takes the shape (2 <= N <= 512)."""
+    return bool(_capi.lib().drnmf_snmf_kl_admitted(int(F), int(N)))
+
+
+def snmf_kl_forward(x, Wn, h_init, sparsity, n_iter, power=1.0, mask_value=None, v_floor=None, out=None,
+                    workspace=None):
+    """The sparse-NMF baseline's inference under the KL cost (beta == 1) as one launch (drnmf_snmf_kl_forward,
+    csrc/snmf_kl.hip): x [B,T,F], Wn [F,N] with unit-norm columns, h_init [N] in the normalised basis -> mask
+    [B,T,F]; frames whose bins all equal mask_value get a zero mask (None: no frame is masked).  v_floor: None -- the
+    reference's rule, zeros of V = x^power are raised to the smallest positive entry of THIS call's V
+    (sparse_nmf_gpu.m:201-205); a positive finite number -- zeros are raised to that constant, and a frame's mask no
+    longer depends on the frames it is run with.  N even and at most 512: ValueError otherwise.  workspace: a uint8
+    tensor of drnmf_snmf_kl_workspace_bytes (the floor as the kernel reads it; allocated here when None or too
+    small)."""
+    if v_floor is not None and not (float(v_floor) > 0 and float(v_floor) < float("inf")):
+        raise ValueError("v_floor must be None or a positive finite number (got %r)" % (v_floor,))
+    L, h, x, Wn, h_init, out = _snmf_args(x, Wn, h_init, out)
+    B, T, F = x.shape
+    N = Wn.shape[1]
+    need = L.drnmf_snmf_kl_workspace_bytes()
+    if workspace is None or workspace.numel() < need or workspace.device != x.device or workspace.dtype != torch.uint8:
+        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    rc = L.drnmf_snmf_kl_forward(h, B, T, F, N, int(n_iter), float(sparsity), float(power),
+                                 0.0 if mask_value is None else float(mask_value), int(mask_value is not None),
+                                 _capi.ptr(x), _capi.ptr(Wn), _capi.ptr(h_init),
+                                 0.0 if v_floor is None else float(v_floor), _capi.ptr(out), _capi.ptr(workspace),
+                                 workspace.numel(), _stream())
+    _capi.check(rc, h, "drnmf_snmf_kl_forward")
+    return out
+
+
 def snmf_adapt_admitted(F, N, beta=2.0):
     """True when `snmf_adapt_forward` takes the shape (beta == 2, 2 <= N <= 512)."""
     return bool(_capi.lib().drnmf_snmf_adapt_admitted(int(F), int(N), float(beta)))

@@ -1,7 +1,7 @@
 """Wall time of the sparse-NMF baseline's inference, both paths of ops.snmf_mask_forward in one session.
 
     python tools/snmf_bench.py [--iters 200] [--rows 32,4096,262144] [--out profiles/snmf_bench.jsonl]
-                               [--root CHECKOUT] [--label NAME]
+                               [--root CHECKOUT] [--label NAME] [--beta 2|1]
 
 At the shipped dictionary size (F = 257, N = 200) and the reference's 200 iterations (enhance.py:842), for
 n = 32, 4096 and 262144 frame rows: median milliseconds of
@@ -11,6 +11,9 @@ n = 32, 4096 and 262144 frame rows: median milliseconds of
            package has it), with its largest mask difference from the tile path
   mu       ops.mu_forward with want_irm on the same input -- the entry the package had before, measured before and
            after the paths to show drift inside the session.
+--beta 1 measures the KL cost instead: the GEMM path at beta = 1 and the KL tile kernel (ops.snmf_kl_forward, path
+name 'kl', with its largest mask difference from the GEMM path), between the same two `mu` runs at beta = 1; every
+line then carries "beta": 1.0.  _capi.SNMF_KL_AUTO_MAX_ROWS is read off such a session.
 --root measures the package of ANOTHER checkout (built there) with this script -- the parent commit's, in front of
 and behind this one's, is how a session shows that the machine did not drift between two builds; --label names the
 run in the JSON lines.
@@ -52,6 +55,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "snmf_bench.jsonl"))
     ap.add_argument("--root", default=ROOT, help="the checkout whose package is measured (default: this one)")
     ap.add_argument("--label", default=None, help="written into every JSON line as 'label'")
+    ap.add_argument("--beta", type=float, default=2.0, choices=[2.0, 1.0], help="2: 'ed' (default), 1: 'kl'")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.root))
     import __graft_entry__ as G
@@ -74,14 +78,19 @@ def main():
         x = torch.rand((1, n, F), generator=g, device=dev) ** 2 + 1e-3
         ws = torch.empty(max(1, ops._capi.lib().drnmf_snmf_mask_workspace_bytes(1, n, F, N)), dtype=torch.uint8,
                          device=dev)
-        out = {p: torch.empty_like(x) for p in ("gemm", "tile", "f16")}
+        out = {p: torch.empty_like(x) for p in ("gemm", "tile", "f16", "kl")}
         H = torch.empty((n, N), dtype=torch.float32, device=dev)
         fill = lambda: H.copy_(h0[None].expand(n, N))
-        runs = [("mu_before", lambda: ops.mu_forward(x[0], Wd, H, SPARSITY, a.iters, want_irm=True), fill)]
-        for p in ("gemm", "tile"):
-            runs.append((p, (lambda p=p: ops.snmf_mask_forward(x, Wn, hn, SPARSITY, a.iters, mask_value=-1.0, path=p,
-                                                               out=out[p], workspace=ws)), None))
-        if hasattr(ops, "snmf_f16_forward"):
+        runs = [("mu_before", lambda: ops.mu_forward(x[0], Wd, H, SPARSITY, a.iters, beta=a.beta, want_irm=True), fill)]
+        for p in ("gemm", "tile") if a.beta == 2.0 else ("gemm",):
+            runs.append((p, (lambda p=p: ops.snmf_mask_forward(x, Wn, hn, SPARSITY, a.iters, beta=a.beta,
+                                                               mask_value=-1.0, path=p, out=out[p], workspace=ws)),
+                         None))
+        if a.beta == 1.0:
+            wk = torch.empty(ops._capi.lib().drnmf_snmf_kl_workspace_bytes(), dtype=torch.uint8, device=dev)
+            runs.append(("kl", lambda: ops.snmf_kl_forward(x, Wn, hn, SPARSITY, a.iters, mask_value=-1.0,
+                                                           out=out["kl"], workspace=wk), None))
+        elif hasattr(ops, "snmf_f16_forward"):
             d16 = ops.snmf_f16_pack_dict(Wn)
             runs.append(("f16", lambda: ops.snmf_f16_forward(x, d16, Wn, hn, SPARSITY, a.iters, mask_value=-1.0,
                                                              out=out["f16"]), None))
@@ -93,8 +102,10 @@ def main():
                         repeats_ms=[float(v) for v in ms])
             if a.label is not None:
                 line["label"] = a.label
-            if name == "tile":
-                line["max_abs_diff_vs_gemm"] = float((out["tile"] - out["gemm"]).abs().max())
+            if a.beta != 2.0:
+                line["beta"] = a.beta
+            if name in ("tile", "kl"):
+                line["max_abs_diff_vs_gemm"] = float((out[name] - out["gemm"]).abs().max())
             if name == "f16":
                 line["max_abs_diff_vs_tile"] = float((out["f16"] - out["tile"]).abs().max())
             print(json.dumps(line), flush=True)
