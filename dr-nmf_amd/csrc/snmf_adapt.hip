@@ -3,8 +3,8 @@
 // row's frames (sparse_nmf_gpu.m:210-264 with w_update_ind false on the first n0, beta == 2).  Plain launches on
 // the caller's stream, per iteration:
 //
-//  - snmf_adapt_h_kernel: one workgroup owns 16 frames of one row, with snmf_mask_tile_kernel's layout and the
-//    phases of snmf_tile.h.  W_b moves every iteration, so the numerator V W_b is taken again beside the
+//  - snmf_adapt_h_kernel: one workgroup owns 16 frames of one row, with the layout, the stager and the phases of
+//    snmf_tile.h.  W_b moves every iteration, so the numerator V W_b is taken again beside the
 //    denominator: one pass over W_b's chunks serves both.  H <- H num / max(den + sparsity, flr), stored.
 //  - snmf_adapt_stats_kernel: a workgroup owns (a chunk of 32 bins, a block of TB = 64 frames, a row).  Per 16
 //    frames it rebuilds Lambda = max(H W_b^T, flr) on chip from the new H (lambda_partial), then contracts V and
@@ -26,69 +26,15 @@ namespace {
 
 using namespace snmf_tile;
 
-constexpr int MAX_N = 512;
 constexpr int TB = 64;            // frames per statistics block (four 16-frame tiles)
 constexpr int LS = 48;            // row stride of the stats kernel's V / Lambda tiles: rows 4 s + q, q = 0..3, land
                                   // 16 banks apart for the 16-lane reads of the second product
 constexpr float FLR = 1e-9f;      // sparse_nmf_gpu.m:172
 
-// A dictionary chunk on its way global -> registers -> LDS (as snmf_mask_tile_kernel stages it): wave w takes the
-// chunk's rows w, w + 4, ..  VEC: N % 4 == 0, 16-byte loads (a row's dictionary starts 16-byte aligned then).
-template <int NTW, bool VEC>
-struct Chunk {
-    f32x4 v4[VEC ? FC / 4 : 1][VEC ? NTW / 4 : 1];
-    float v1[VEC ? 1 : FC / 4][VEC ? 1 : NTW];
-};
-
-template <int NTW, bool VEC>
-__device__ __forceinline__ void gload(Chunk<NTW, VEC>& p, const float* __restrict__ W, int c, int F, int N, int w,
-                                      int l) {
-#pragma unroll
-    for (int i = 0; i < FC / 4; ++i) {
-        const int bin = c * FC + w + 4 * i;
-        if constexpr (VEC) {
-#pragma unroll
-            for (int k = 0; k < NTW / 4; ++k) {
-                const int col = 4 * (l + 64 * k);
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (bin < F && col < N) v = *(const f32x4*)(W + (size_t)bin * N + col);
-                p.v4[i][k] = v;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < NTW; ++k) {
-                const int col = l + 64 * k;
-                float v = 0.f;
-                if (bin < F && col < N) v = W[(size_t)bin * N + col];
-                p.v1[i][k] = v;
-            }
-        }
-    }
-}
-
-template <int NTW, bool VEC>
-__device__ __forceinline__ void swrite(const Chunk<NTW, VEC>& p, float* Ws, int LD, int Np, int w, int l) {
-#pragma unroll
-    for (int i = 0; i < FC / 4; ++i) {
-        float* dst = Ws + (w + 4 * i) * LD;
-        if constexpr (VEC) {
-#pragma unroll
-            for (int k = 0; k < NTW / 4; ++k) {
-                const int col = 4 * (l + 64 * k);
-                if (col < Np) *(f32x4*)(dst + col) = p.v4[i][k];
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < NTW; ++k) {
-                const int col = l + 64 * k;
-                if (col < Np) dst[col] = p.v1[i][k];
-            }
-        }
-    }
-}
-
 // Hs [16][LD] <- H of the frames t0 .. t0 + 15 of the row (Hrow = the row's [T][N]), 0 behind T and N.  Every
 // lane loads the elements it owns in the update (row 4 q + v, column 16 t + r).
+// (This walk, the H pass's stores and the statistics pass's copy are written out and not through snmf_tile.h's
+// for_own_h: with it the iteration measured 0.5 % slower at B = 16)
 template <int NTW>
 __device__ __forceinline__ void load_h(const float* __restrict__ Hrow, float* Hs, int t0, int T, int N, int LD,
                                        int NT, int w, int r, int q) {
@@ -141,10 +87,10 @@ snmf_adapt_bcast_kernel(const float* __restrict__ Wn, float* __restrict__ Wb, in
     if (i < FN) Wb[(size_t)blockIdx.y * FN + i] = Wn[i];
 }
 
-inline size_t h_lds_bytes(int N) {
-    const int LD = np16(N) + 8;
-    return ((size_t)(TR + FC) * LD + 5 * TR * LLD + TR) * sizeof(float);
-}
+// Dynamic LDS of the H pass (a V chunk buffer behind Lp) and of the statistics pass (its V and Lambda tiles there)
+constexpr size_t h_lds_bytes(int N) { return lds_bytes(N, LLD, TR * LLD + TR); }
+constexpr size_t stats_lds_bytes(int N) { return lds_bytes(N, LLD, 2 * TR * LS); }
+static_assert(h_lds_bytes(200) == 53056 && stats_lds_bytes(200) == 56832, "as before the sizes were shared");
 
 // One H update of 16 frames of row blockIdx.y against the row's dictionary.  NTW, VEC, the layout and the waves per
 // SIMD as in snmf_mask_tile_kernel; Vs is a V chunk buffer of its own because the numerator's chunk and the
@@ -192,18 +138,11 @@ snmf_adapt_h_kernel(const float* __restrict__ x, const float* __restrict__ Wb, f
         lambda_partial<NTW, 0>(Hs, Ws, Lp, LD, NT, w, r, q, 0);
         __syncthreads();
         float aF[2][4];
+        lambda_sum(Lp, r, q, aF);
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const float* p = Lp + r * LLD + 16 * s + bin_base(q) + 4 * hh;
-                f32x2 sum = *(const f32x2*)p;                 // the four waves' partials, in wave order
-                sum += *(const f32x2*)(p + TR * LLD);
-                sum += *(const f32x2*)(p + 2 * TR * LLD);
-                sum += *(const f32x2*)(p + 3 * TR * LLD);
-                aF[s][2 * hh] = fmaxf(sum[0], FLR);
-                aF[s][2 * hh + 1] = fmaxf(sum[1], FLR);
-            }
+            for (int e = 0; e < 4; ++e) aF[s][e] = fmaxf(aF[s][e], FLR);
         accumulate<NTW>(Ws, LD, NT, w, r, q, aF, den);
         __syncthreads();                      // every wave is done with Ws, Vs and Lp
     }
@@ -243,11 +182,6 @@ __device__ __forceinline__ void fetch_tile(const float* __restrict__ Hrow, const
         const int idx = tid + 256 * kk, fr = t0 + (idx >> 5), f = c * FC + (idx & 31);
         vreg[kk] = (fr < T && f < F && vrow[fr]) ? vpow(xrow[(size_t)fr * F + f], power) : 0.f;
     }
-}
-
-inline size_t stats_lds_bytes(int N) {
-    const int LD = np16(N) + 8;
-    return ((size_t)(TR + FC) * LD + 4 * TR * LLD + 2 * TR * LS) * sizeof(float);
 }
 
 // The W update's statistics of (bin chunk blockIdx.x, frame block blockIdx.y, row blockIdx.z): the block's share
@@ -426,11 +360,6 @@ snmf_adapt_col_kernel(float* __restrict__ Wb, float* __restrict__ P, const int* 
         for (int f = fl; f < F; f += CL) W[(size_t)f * N] = Pb[(size_t)f * Nu] / nrm;
 }
 
-inline size_t final_lds_bytes(int N) {
-    const int LD = np16(N) + 8;
-    return ((size_t)(TR + FC) * LD + 4 * TR * LLD + TR) * sizeof(float);
-}
-
 // The mask of 16 frames of row blockIdx.y from the row's last dictionary and H
 template <int NTW, bool VEC>
 __global__ void __launch_bounds__(256, NTW == 4 ? 3 : 1)
@@ -491,7 +420,7 @@ struct Call {
 
 template <int NTW, bool VEC>
 hipError_t run_iterations(const Call& c) {
-    const int wide = NTW == 4 ? 256 : MAX_N;
+    const int wide = widest_n(NTW);
     const dim3 tiles((unsigned)((c.T + TR - 1) / TR), (unsigned)c.B);
     const dim3 sgrid((unsigned)((c.F + FC - 1) / FC), (unsigned)c.nblk, (unsigned)c.B);
     const int Nu = c.N - c.n0;
@@ -513,9 +442,9 @@ hipError_t run_iterations(const Call& c) {
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    return launch_grid<snmf_adapt_final_kernel<NTW, VEC>>(c.device, final_lds_bytes(wide), final_lds_bytes(c.N), tiles,
-                                                          c.stream, (const float*)c.Wb, (const float*)c.H,
-                                                          (const int*)c.valid, c.mask_out, c.T, c.F, c.N);
+    return launch_grid<snmf_adapt_final_kernel<NTW, VEC>>(c.device, lds_bytes(wide), lds_bytes(c.N), tiles, c.stream,
+                                                          (const float*)c.Wb, (const float*)c.H, (const int*)c.valid,
+                                                          c.mask_out, c.T, c.F, c.N);
 }
 
 bool shape_ok(int B, int T, int F, int N, int n0) {
@@ -540,18 +469,12 @@ extern "C" int32_t drnmf_snmf_adapt_forward(drnmf_handle_t h, int32_t B, int32_t
                                             void* workspace, size_t workspace_bytes, void* stream_) {
     DRNMF_LOCK(h);
     if (!h) return DRNMF_ERR_INVALID_ARG;
-    if (B <= 0 || T <= 0 || F <= 0 || N <= 0 || n_iter < 0)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_adapt_forward: bad shape B=%d T=%d F=%d N=%d iters=%d", B, T, F,
-                   N, n_iter);
-    if (N % 2)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_adapt_forward: N = %d must be even (speech and noise halves)", N);
+    if (int32_t rc = check_shape(h, "snmf_adapt_forward", B, T, F, N, n_iter)) return rc;
     if (n0 < 0 || n0 > N)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_adapt_forward: n0 = %d fixed atoms of N = %d", n0, N);
     if (B > 65535) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_adapt_forward: at most 65535 rows per call (B = %d)", B);
-    if (!(sparsity >= 0.f) || (has_mask != 0 && has_mask != 1))
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_adapt_forward: sparsity must be >= 0, has_mask 0 or 1");
-    if (!x || !Wn || !h_init || !mask_out)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_adapt_forward: NULL pointer argument");
+    if (int32_t rc = check_flags(h, "snmf_adapt_forward", sparsity, has_mask)) return rc;
+    if (int32_t rc = check_pointers(h, "snmf_adapt_forward", {x, Wn, h_init, mask_out})) return rc;
     if ((int64_t)B * T > 0x7fffff00)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_adapt_forward: too many frames (%lld)", (long long)B * T);
     if (!drnmf_snmf_adapt_admitted(F, N, 2.f))
@@ -580,12 +503,10 @@ extern "C" int32_t drnmf_snmf_adapt_forward(drnmf_handle_t h, int32_t B, int32_t
     hipLaunchKernelGGL(snmf_adapt_bcast_kernel, dim3((unsigned)((F * N + 255) / 256), (unsigned)B), dim3(256), 0,
                        c.stream, Wn, c.Wb, F * N);
     DRNMF_HIP(h, hipGetLastError());
-    const bool vec = N % 4 == 0;
-    hipError_t e;
-    if (np16(N) <= 256)
-        e = vec ? run_iterations<4, true>(c) : run_iterations<4, false>(c);
-    else
-        e = vec ? run_iterations<8, true>(c) : run_iterations<8, false>(c);
+    // (a row's dictionary starts 16-byte aligned when N % 4 == 0)
+    const hipError_t e = with_instance(N, N % 4 == 0, [&](auto ntw, auto v) {
+        return run_iterations<decltype(ntw)::value, decltype(v)::value>(c);
+    });
     DRNMF_HIP(h, e);
     if (W_out)
         DRNMF_HIP(h, hipMemcpyAsync(W_out, c.Wb, (size_t)B * F * N * 4, hipMemcpyDeviceToDevice, c.stream));

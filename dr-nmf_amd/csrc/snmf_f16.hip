@@ -32,7 +32,7 @@
 // spreads every 16-lane group of the ds_read_b128 (rows 0-3, 12-15 at q and 4-11 at q + 1) over all sixteen
 // 16-byte slots, and puts the eight bin rows of a 32-lane half of the transposing read (32 bytes each) on
 // disjoint banks.  The fp32 partials have LLH = 40 floats per row for the same reason.  The fp32 phases in front
-// of and behind the iterations are snmf_tile.h's, shared with snmf_mask.hip: they use the same memory with the
+// of and behind the iterations are snmf_tile.h's, shared with the fp32 tile kernels: they use the same memory with the
 // strides, the slot order and the bank reasoning written there.
 #include "snmf_tile.h"
 
@@ -43,13 +43,11 @@ namespace {
 using namespace snmf_tile;        // (FC = 32 bins is also one K-step of the second product here)
 
 constexpr int LLH = 40;           // iterations: row stride of the fp32 partials of Lambda_c
-constexpr int MAX_N = 512;
 
 inline int np32(int N) { return (N + 31) & ~31; }
-inline size_t f16_lds_bytes(int N) {
-    const int LD = np16(N) + 8;   // (the fp16 images fit inside the fp32 ones: 2 (Np32 + 16) <= 4 (Np16 + 8))
-    return ((size_t)(TR + FC) * LD + 4 * TR * LLH + 2 * TR) * sizeof(float);
-}
+// (the fp16 images fit inside the fp32 ones: 2 (Np32 + 16) <= 4 (Np16 + 8)); the tail: valid and the row scales
+constexpr size_t f16_lds_bytes(int N) { return lds_bytes(N, LLH, 2 * TR); }
+static_assert(f16_lds_bytes(200) == 51840 && f16_lds_bytes(MAX_N) == 110208, "as before the sizes were shared");
 
 typedef __attribute__((__vector_size__(4 * sizeof(short)))) short s16x4;
 typedef __attribute__((__vector_size__(8 * sizeof(short)))) short s16x8;
@@ -104,7 +102,8 @@ snmf_f16_tile_kernel(const float* __restrict__ x, const f16* __restrict__ dict16
     const int64_t row0 = (int64_t)blockIdx.x * TR;
     const float flr = 1e-9f;                  // sparse_nmf_gpu.m:172
 
-    // keras.layers.Masking (snmf_mask.hip's rule) and the row's scale
+    // keras.layers.Masking (row_validity's rule) and the row's scale.  Not row_validity: the row's maximum rides on
+    // the same read of x, has_mask or not, and is reduced beside __any
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int rl = 4 * w + i;
@@ -293,7 +292,7 @@ template <int NTW>
 hipError_t launch_f16(const float* x, const f16* dict16, const float* Wn, const float* h_init, float* mask_out,
                       int64_t rows, int F, int N, int n_iter, float sparsity, float power, float mask_value,
                       int has_mask, hipStream_t stream, int device) {
-    return launch<snmf_f16_tile_kernel<NTW>>(device, f16_lds_bytes(NTW == 4 ? 256 : MAX_N), f16_lds_bytes(N), rows,
+    return launch<snmf_f16_tile_kernel<NTW>>(device, f16_lds_bytes(widest_n(NTW)), f16_lds_bytes(N), rows,
                                              stream, x, dict16, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity,
                                              power, mask_value, has_mask);
 }
@@ -338,15 +337,9 @@ extern "C" int32_t drnmf_snmf_f16_forward(drnmf_handle_t h, int32_t B, int32_t T
                                           const float* h_init, float* mask_out, void* stream_) {
     DRNMF_LOCK(h);
     if (!h) return DRNMF_ERR_INVALID_ARG;
-    if (B <= 0 || T <= 0 || F <= 0 || N <= 0 || n_iter < 0)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_f16_forward: bad shape B=%d T=%d F=%d N=%d iters=%d", B, T, F, N,
-                   n_iter);
-    if (N % 2)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_f16_forward: N = %d must be even (speech and noise halves)", N);
-    if (!(sparsity >= 0.f) || (has_mask != 0 && has_mask != 1))
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_f16_forward: sparsity must be >= 0, has_mask 0 or 1");
-    if (!x || !dict16 || !Wn || !h_init || !mask_out)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_f16_forward: NULL pointer argument");
+    if (int32_t rc = check_shape(h, "snmf_f16_forward", B, T, F, N, n_iter)) return rc;
+    if (int32_t rc = check_flags(h, "snmf_f16_forward", sparsity, has_mask)) return rc;
+    if (int32_t rc = check_pointers(h, "snmf_f16_forward", {x, dict16, Wn, h_init, mask_out})) return rc;
     if (((uintptr_t)dict16 & 15) || ((uintptr_t)Wn & 7))
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_f16_forward: dict16 must be 16-byte and Wn 8-byte aligned");
     const int64_t rows = (int64_t)B * T;

@@ -31,7 +31,6 @@ namespace {
 
 using namespace snmf_tile;
 
-constexpr int KL_MAX_N = 512;
 // The model's 'auto' takes this kernel up to this many rows: the largest measured row count at which it was faster
 // than the GEMM path at beta == 1.  Measured (tools/snmf_bench.py --beta 1, MI355X, F = 257, N = 200, 200 iterations,
 // this kernel against the GEMM path): 5.08 / 9.35 ms at 32 rows, 5.21 / 10.21 at 4096, 6.90 / 10.42 at 8192, 13.21 /
@@ -39,11 +38,6 @@ constexpr int KL_MAX_N = 512;
 // _capi.SNMF_KL_AUTO_MAX_ROWS.
 constexpr int64_t KL_AUTO_MAX_ROWS = 8192;
 constexpr size_t KL_WS_BYTES = 256;           // the floor scalar
-
-inline size_t kl_lds_bytes(int N) {
-    const int LD = np16(N) + 8;
-    return ((size_t)(TR + FC) * LD + 4 * TR * LLD + TR) * sizeof(float);
-}
 
 // *dst = v: the caller's floor, or +inf in front of the min-positive pass
 __global__ void snmf_kl_floor_init_kernel(float* __restrict__ dst, float v) {
@@ -94,90 +88,18 @@ snmf_kl_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn, c
     const int64_t row0 = (int64_t)blockIdx.x * TR;
     const float flr = 1e-9f;                  // sparse_nmf_gpu.m:172
 
-    // keras.layers.Masking: a frame is masked when every bin equals mask_value
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int rl = 4 * w + i;
-        const int64_t row = row0 + rl;
-        bool any = false;
-        if (row < rows) {
-            if (has_mask) {
-                for (int f = l; f < F; f += 64) any |= (x[row * F + f] != mask_value);
-            } else {
-                any = true;
-            }
-        }
-        any = __any(any);
-        if (l == 0) valid[rl] = any ? 1 : 0;
-    }
+    row_validity(x, valid, row0, rows, F, mask_value, has_mask, w, l);
     __syncthreads();
     if (all_masked(valid, mask_out, row0, rows, F, tid)) return;
 
     float vfl = *v_floor;
     if (!(vfl < __int_as_float(0x7f800000))) vfl = 0.f;          // no positive entry in the call: nothing is raised
 
+    init_h<NTW>(Hs, h_init, valid, N, NT, LD, w, r, q);
     f32x4 num[NTW];
     float den[NTW];
 #pragma unroll
-    for (int i = 0; i < NTW; ++i) {
-        const int t = w + 4 * i, col = 16 * t + r;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int rl = 4 * q + v;
-            float hv = 0.f;
-            if (t < NT && col < N && valid[rl]) hv = h_init[col];
-            num[i][v] = 0.f;
-            if (t < NT) Hs[rl * LD + col] = hv;
-        }
-    }
-
-    // dictionary chunk: global -> registers (in flight under the previous chunk's products) -> LDS, wave w the
-    // chunk's rows w, w + 4, ..  (always_inline: a call would cost scratch)
-    constexpr int NVP = NTW / 4;
-    f32x4 pf4[FC / 4][NVP];
-    float pf1[FC / 4][NTW];
-    auto gload = [&](int c) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < FC / 4; ++i) {
-            const int bin = c * FC + w + 4 * i;
-            if constexpr (VEC) {
-#pragma unroll
-                for (int p = 0; p < NVP; ++p) {
-                    const int col = 4 * (l + 64 * p);
-                    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                    if (bin < F && col < N) v = *(const f32x4*)(Wn + (size_t)bin * N + col);
-                    pf4[i][p] = v;
-                }
-            } else {
-#pragma unroll
-                for (int p = 0; p < NTW; ++p) {
-                    const int col = l + 64 * p;
-                    float v = 0.f;
-                    if (bin < F && col < N) v = Wn[(size_t)bin * N + col];
-                    pf1[i][p] = v;
-                }
-            }
-        }
-    };
-    auto swrite = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < FC / 4; ++i) {
-            float* dst = Ws + (w + 4 * i) * LD;
-            if constexpr (VEC) {
-#pragma unroll
-                for (int p = 0; p < NVP; ++p) {
-                    const int col = 4 * (l + 64 * p);
-                    if (col < Np) *(f32x4*)(dst + col) = pf4[i][p];
-                }
-            } else {
-#pragma unroll
-                for (int p = 0; p < NTW; ++p) {
-                    const int col = l + 64 * p;
-                    if (col < Np) dst[col] = pf1[i][p];
-                }
-            }
-        }
-    };
+    for (int i = 0; i < NTW; ++i) num[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // this lane's eight values of V in chunk c: row r, slots (q, e) of both k-steps
     const bool rv = valid[r] != 0;            // (a valid row lies inside the call)
@@ -197,14 +119,15 @@ snmf_kl_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn, c
             }
     };
 
-    gload(0);
+    Chunk<NTW, VEC> pf;
+    gload(pf, Wn, 0, F, N, w, l);
     // den = max(column sums of Wn + sparsity, flr), once: `accumulate` on an all-ones operand, every row alike
     {
         const float ones[2][4] = {{1.f, 1.f, 1.f, 1.f}, {1.f, 1.f, 1.f, 1.f}};
         for (int c = 0; c < NC; ++c) {
-            swrite();
+            swrite(pf, Ws, LD, Np, w, l);
             __syncthreads();
-            gload(c + 1 < NC ? c + 1 : 0);
+            gload(pf, Wn, c + 1 < NC ? c + 1 : 0, F, N, w, l);
             accumulate<NTW>(Ws, LD, NT, w, r, q, ones, num);
             __syncthreads();
         }
@@ -217,61 +140,39 @@ snmf_kl_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn, c
 #pragma unroll
         for (int i = 0; i < NTW; ++i) num[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int c = 0; c < NC; ++c) {
-            swrite();
+            swrite(pf, Ws, LD, Np, w, l);
             __syncthreads();                  // Ws (and, for c == 0, the new H) visible
-            gload(c + 1 < NC ? c + 1 : 0);
+            gload(pf, Wn, c + 1 < NC ? c + 1 : 0, F, N, w, l);
             lambda_partial<NTW, 0>(Hs, Ws, Lp, LD, NT, w, r, q, 0);
             __syncthreads();
             float aF[2][4];
+            lambda_sum(Lp, r, q, aF);
 #pragma unroll
             for (int s = 0; s < 2; ++s)
 #pragma unroll
-                for (int hh = 0; hh < 2; ++hh) {
-                    const float* p = Lp + r * LLD + 16 * s + bin_base(q) + 4 * hh;
-                    f32x2 sum = *(const f32x2*)p;                 // the four waves' partials, in wave order
-                    sum += *(const f32x2*)(p + TR * LLD);
-                    sum += *(const f32x2*)(p + 2 * TR * LLD);
-                    sum += *(const f32x2*)(p + 3 * TR * LLD);
-                    aF[s][2 * hh] = vF[s][2 * hh] / fmaxf(sum[0], flr);           // sparse_nmf_gpu.m:213
-                    aF[s][2 * hh + 1] = vF[s][2 * hh + 1] / fmaxf(sum[1], flr);
-                }
+                for (int e = 0; e < 4; ++e) aF[s][e] = vF[s][e] / fmaxf(aF[s][e], flr);       // sparse_nmf_gpu.m:213
             accumulate<NTW>(Ws, LD, NT, w, r, q, aF, num);
             vload(c + 1 < NC ? c + 1 : 0);    // the next chunk's V, in flight under that chunk's first product
             __syncthreads();                  // every wave is done with Ws and Lp
         }
-#pragma unroll
-        for (int i = 0; i < NTW; ++i) {       // sparse_nmf_gpu.m:216
-            const int t = w + 4 * i;
-            if (t < NT) {
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    float* hp = Hs + (4 * q + v) * LD + 16 * t + r;      // (this lane's own elements)
-                    *hp = *hp * num[i][v] / den[i];
-                }
-            }
-        }
+        // sparse_nmf_gpu.m:216, on this lane's own elements
+        for_own_h<NTW>(NT, w, r, q, [&](int i, int v, int row, int col) {
+            float* hp = Hs + row * LD + col;
+            *hp = *hp * num[i][v] / den[i];
+        });
     }
 
     final_mask<NTW>(Hs, Ws, Lp, valid, nullptr, mask_out, row0, rows, F, N, LD, tid, w, r, q, [&](int c) {
-        swrite();
+        swrite(pf, Ws, LD, Np, w, l);
         __syncthreads();
-        if (c + 1 < NC) gload(c + 1);
+        if (c + 1 < NC) gload(pf, Wn, c + 1, F, N, w, l);
     });
-}
-
-template <int NTW, bool VEC, bool POW>
-hipError_t launch_kl(int device, hipStream_t stream, const float* x, const float* Wn, const float* h_init,
-                     const float* v_floor, float* mask_out, int64_t rows, int F, int N, int n_iter, float sparsity,
-                     float power, float mask_value, int has_mask) {
-    return launch<snmf_kl_tile_kernel<NTW, VEC, POW>>(device, kl_lds_bytes(NTW == 4 ? 256 : KL_MAX_N),
-                                                      kl_lds_bytes(N), rows, stream, x, Wn, h_init, v_floor, mask_out,
-                                                      rows, F, N, n_iter, sparsity, power, mask_value, has_mask);
 }
 
 }  // namespace
 
 extern "C" int32_t drnmf_snmf_kl_admitted(int32_t F, int32_t N) {
-    return (F > 0 && N >= 2 && N <= KL_MAX_N) ? 1 : 0;
+    return (F > 0 && N >= 2 && N <= MAX_N) ? 1 : 0;
 }
 
 extern "C" size_t drnmf_snmf_kl_workspace_bytes(void) { return KL_WS_BYTES; }
@@ -285,23 +186,17 @@ extern "C" int32_t drnmf_snmf_kl_forward(drnmf_handle_t h, int32_t B, int32_t T,
                                          void* stream_) {
     DRNMF_LOCK(h);
     if (!h) return DRNMF_ERR_INVALID_ARG;
-    if (B <= 0 || T <= 0 || F <= 0 || N <= 0 || n_iter < 0)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_kl_forward: bad shape B=%d T=%d F=%d N=%d iters=%d", B, T, F, N,
-                   n_iter);
-    if (N % 2)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_kl_forward: N = %d must be even (speech and noise halves)", N);
-    if (!(sparsity >= 0.f) || (has_mask != 0 && has_mask != 1))
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_kl_forward: sparsity must be >= 0, has_mask 0 or 1");
+    if (int32_t rc = check_shape(h, "snmf_kl_forward", B, T, F, N, n_iter)) return rc;
+    if (int32_t rc = check_flags(h, "snmf_kl_forward", sparsity, has_mask)) return rc;
     if (!(v_floor >= 0.f) || !(v_floor < __builtin_inff()))
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_kl_forward: v_floor = %g must be 0 (the call's smallest positive "
                    "V) or a positive finite constant", (double)v_floor);
-    if (!x || !Wn || !h_init || !mask_out)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_kl_forward: NULL pointer argument");
+    if (int32_t rc = check_pointers(h, "snmf_kl_forward", {x, Wn, h_init, mask_out})) return rc;
     const int64_t rows = (int64_t)B * T;
     if (rows > 0x7fffff00)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_kl_forward: too many rows (%lld)", (long long)rows);
-    if (N > KL_MAX_N)
-        DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED, "snmf_kl_forward: the kernel takes N <= %d (N = %d)", KL_MAX_N, N);
+    if (N > MAX_N)
+        DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED, "snmf_kl_forward: the kernel takes N <= %d (N = %d)", MAX_N, N);
     if (!workspace || workspace_bytes < KL_WS_BYTES)
         DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "snmf_kl_forward: workspace %zu < required %zu",
                    workspace ? workspace_bytes : (size_t)0, KL_WS_BYTES);
@@ -319,17 +214,16 @@ extern "C" int32_t drnmf_snmf_kl_forward(drnmf_handle_t h, int32_t B, int32_t T,
         DRNMF_HIP(h, hipGetLastError());
     }
     const bool vec = N % 4 == 0 && ((uintptr_t)Wn & 15) == 0, pw = power != 1.f && power != 2.f;
-    auto go = [&](auto kern) {
-        return kern(h->device, stream, x, Wn, h_init, vf, mask_out, rows, F, N, n_iter, sparsity, power, mask_value,
-                    has_mask);
-    };
-    hipError_t e;
-    if (np16(N) <= 256)
-        e = vec ? (pw ? go(launch_kl<4, true, true>) : go(launch_kl<4, true, false>))
-                : (pw ? go(launch_kl<4, false, true>) : go(launch_kl<4, false, false>));
-    else
-        e = vec ? (pw ? go(launch_kl<8, true, true>) : go(launch_kl<8, true, false>))
-                : (pw ? go(launch_kl<8, false, true>) : go(launch_kl<8, false, false>));
+    const hipError_t e = with_instance(N, vec, [&](auto ntw, auto v) {
+        constexpr int NTW = decltype(ntw)::value;
+        constexpr bool VEC = decltype(v)::value;
+        auto go = [&](auto pw_) {
+            return launch<snmf_kl_tile_kernel<NTW, VEC, decltype(pw_)::value>>(
+                h->device, lds_bytes(widest_n(NTW)), lds_bytes(N), rows, stream, x, Wn, h_init, (const float*)vf,
+                mask_out, rows, F, N, n_iter, sparsity, power, mask_value, has_mask);
+        };
+        return pw ? go(std::true_type{}) : go(std::false_type{});      // POW: see the kernel
+    });
     DRNMF_HIP(h, e);
     return DRNMF_OK;
 }

@@ -19,8 +19,8 @@
 // wherever the row sits and whatever its neighbours hold.
 //
 // LDS: Hs [16][LD], Ws [32][LD], LD = Np + 8 (Np = N rounded up to 16).  snmf_tile.h holds the phases this kernel
-// shares with its fp16-operand sibling (snmf_f16.hip), the slot order of the second product and why these strides
-// are free of bank conflicts.
+// shares with its siblings (snmf_kl.hip, snmf_adapt.hip, snmf_f16.hip), the slot order of the second product and
+// why these strides are free of bank conflicts.
 #include "snmf_tile.h"
 
 #include "../../include/drnmf_snmf.h"
@@ -29,17 +29,11 @@ namespace {
 
 using namespace snmf_tile;
 
-constexpr int TILE_MAX_N = 512;
 // path = 0 takes the tile kernel up to this many rows: the largest measured row count at which it was the faster
 // path.  Measured (tools/snmf_bench.py, MI355X, F = 257, N = 200, 200 iterations, tile against GEMM path): 3.9 / 8.8
 // ms at 32 rows, 3.9 / 9.4 at 4096, 5.3 / 9.6 at 8192, 10.35 / 10.18 at 16384, 141.4 / 132.9 at 262144 (DESIGN.md
 // section 6h has the table).  Mirrored by _capi.SNMF_TILE_AUTO_MAX_ROWS.
 constexpr int64_t TILE_AUTO_MAX_ROWS = 8192;
-
-inline size_t tile_lds_bytes(int N) {
-    const int LD = np16(N) + 8;
-    return ((size_t)(TR + FC) * LD + 4 * TR * LLD + TR) * sizeof(float);
-}
 
 // NTW: 16-column tiles of H / num / den per wave (4: N <= 256, 8: N <= 512).  VEC: N % 4 == 0 and Wn 16-byte
 // aligned -- the dictionary is staged with 16-byte loads.  Waves per SIMD: three workgroups of the shipped N = 200
@@ -61,25 +55,13 @@ snmf_mask_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn,
     const int64_t row0 = (int64_t)blockIdx.x * TR;
     const float flr = 1e-9f;                  // sparse_nmf_gpu.m:172
 
-    // keras.layers.Masking: a frame is masked when every bin equals mask_value (lstm_pack_x_kernel's rule)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int rl = 4 * w + i;
-        const int64_t row = row0 + rl;
-        bool any = false;
-        if (row < rows) {
-            if (has_mask) {
-                for (int f = l; f < F; f += 64) any |= (x[row * F + f] != mask_value);
-            } else {
-                any = true;
-            }
-        }
-        any = __any(any);
-        if (l == 0) valid[rl] = any ? 1 : 0;
-    }
+    row_validity(x, valid, row0, rows, F, mask_value, has_mask, w, l);
     __syncthreads();
     if (all_masked(valid, mask_out, row0, rows, F, tid)) return;
 
+    // H = h_init on valid rows and the accumulators' zeros in one loop, the Lambda sum and the update below written
+    // out: init_h, lambda_sum and for_own_h (snmf_tile.h) say the same, and this kernel measured 0.3 to 0.8 % slower
+    // at two workgroups per CU with them
     f32x4 num[NTW], den[NTW];
 #pragma unroll
     for (int i = 0; i < NTW; ++i) {
@@ -95,62 +77,14 @@ snmf_mask_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn,
         }
     }
 
-    // dictionary chunk: global -> registers (in flight under the previous chunk's products) -> LDS.  Wave w
-    // stages the chunk's rows w, w + 4, ..  (always_inline: the inliner's budget for a caller of this size is
-    // spent by the time it gets to these two in the <8, false> instance, and a call costs scratch)
-    constexpr int NVP = NTW / 4;
-    f32x4 pf4[FC / 4][NVP];
-    float pf1[FC / 4][NTW];
-    auto gload = [&](int c) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < FC / 4; ++i) {
-            const int bin = c * FC + w + 4 * i;
-            if constexpr (VEC) {
-#pragma unroll
-                for (int p = 0; p < NVP; ++p) {
-                    const int col = 4 * (l + 64 * p);
-                    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                    if (bin < F && col < N) v = *(const f32x4*)(Wn + (size_t)bin * N + col);
-                    pf4[i][p] = v;
-                }
-            } else {
-#pragma unroll
-                for (int p = 0; p < NTW; ++p) {
-                    const int col = l + 64 * p;
-                    float v = 0.f;
-                    if (bin < F && col < N) v = Wn[(size_t)bin * N + col];
-                    pf1[i][p] = v;
-                }
-            }
-        }
-    };
-    auto swrite = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < FC / 4; ++i) {
-            float* dst = Ws + (w + 4 * i) * LD;
-            if constexpr (VEC) {
-#pragma unroll
-                for (int p = 0; p < NVP; ++p) {
-                    const int col = 4 * (l + 64 * p);
-                    if (col < Np) *(f32x4*)(dst + col) = pf4[i][p];
-                }
-            } else {
-#pragma unroll
-                for (int p = 0; p < NTW; ++p) {
-                    const int col = l + 64 * p;
-                    if (col < Np) dst[col] = pf1[i][p];
-                }
-            }
-        }
-    };
-
-    gload(0);
+    Chunk<NTW, VEC> pf;
+    gload(pf, Wn, 0, F, N, w, l);
     // num = V Wn, once: V = x^power on valid rows, 0 elsewhere
     for (int c = 0; c < NC; ++c) {
-        swrite();
+        swrite(pf, Ws, LD, Np, w, l);
         num_fill(x, Lp, valid, nullptr, row0, F, c, power, tid);
         __syncthreads();
-        gload(c + 1 < NC ? c + 1 : 0);
+        gload(pf, Wn, c + 1 < NC ? c + 1 : 0, F, N, w, l);
         num_accumulate<NTW>(Ws, Lp, LD, NT, w, r, q, num);
         __syncthreads();
     }
@@ -159,9 +93,9 @@ snmf_mask_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn,
 #pragma unroll
         for (int i = 0; i < NTW; ++i) den[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int c = 0; c < NC; ++c) {
-            swrite();
+            swrite(pf, Ws, LD, Np, w, l);
             __syncthreads();                  // Ws (and, for c == 0, the new H) visible
-            gload(c + 1 < NC ? c + 1 : 0);
+            gload(pf, Wn, c + 1 < NC ? c + 1 : 0, F, N, w, l);
             lambda_partial<NTW, 0>(Hs, Ws, Lp, LD, NT, w, r, q, 0);
             __syncthreads();
             float aF[2][4];
@@ -194,9 +128,9 @@ snmf_mask_tile_kernel(const float* __restrict__ x, const float* __restrict__ Wn,
     }
 
     final_mask<NTW>(Hs, Ws, Lp, valid, nullptr, mask_out, row0, rows, F, N, LD, tid, w, r, q, [&](int c) {
-        swrite();
+        swrite(pf, Ws, LD, Np, w, l);
         __syncthreads();
-        if (c + 1 < NC) gload(c + 1);
+        if (c + 1 < NC) gload(pf, Wn, c + 1, F, N, w, l);
     });
 }
 
@@ -250,19 +184,10 @@ MaskWs mask_ws(int64_t rows, int F, int N) {
     return w;
 }
 
-template <int NTW, bool VEC>
-hipError_t launch_tile(int device, hipStream_t stream, const float* x, const float* Wn, const float* h_init,
-                       float* mask_out, int64_t rows, int F, int N, int n_iter, float sparsity, float power,
-                       float mask_value, int has_mask) {
-    return launch<snmf_mask_tile_kernel<NTW, VEC>>(device, tile_lds_bytes(NTW == 4 ? 256 : TILE_MAX_N),
-                                                   tile_lds_bytes(N), rows, stream, x, Wn, h_init, mask_out, rows, F,
-                                                   N, n_iter, sparsity, power, mask_value, has_mask);
-}
-
 }  // namespace
 
 extern "C" int32_t drnmf_snmf_mask_admitted(int32_t F, int32_t N, float beta) {
-    return (F > 0 && N >= 2 && N <= TILE_MAX_N && beta == 2.f) ? 1 : 0;
+    return (F > 0 && N >= 2 && N <= MAX_N && beta == 2.f) ? 1 : 0;
 }
 
 extern "C" size_t drnmf_snmf_mask_workspace_bytes(int32_t B, int32_t T, int32_t F, int32_t N) {
@@ -277,24 +202,18 @@ extern "C" int32_t drnmf_snmf_mask_forward(drnmf_handle_t h, int32_t B, int32_t 
                                            size_t workspace_bytes, void* stream_) {
     DRNMF_LOCK(h);
     if (!h) return DRNMF_ERR_INVALID_ARG;
-    if (B <= 0 || T <= 0 || F <= 0 || N <= 0 || n_iter < 0)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_mask_forward: bad shape B=%d T=%d F=%d N=%d iters=%d", B, T, F,
-                   N, n_iter);
-    if (N % 2)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_mask_forward: N = %d must be even (speech and noise halves)", N);
+    if (int32_t rc = check_shape(h, "snmf_mask_forward", B, T, F, N, n_iter)) return rc;
     if (path < DRNMF_SNMF_PATH_AUTO || path > DRNMF_SNMF_PATH_TILE)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_mask_forward: unknown path %d", path);
-    if (!(sparsity >= 0.f) || (has_mask != 0 && has_mask != 1))
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_mask_forward: sparsity must be >= 0, has_mask 0 or 1");
-    if (!x || !Wn || !h_init || !mask_out)
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_mask_forward: NULL pointer argument");
+    if (int32_t rc = check_flags(h, "snmf_mask_forward", sparsity, has_mask)) return rc;
+    if (int32_t rc = check_pointers(h, "snmf_mask_forward", {x, Wn, h_init, mask_out})) return rc;
     const int64_t rows = (int64_t)B * T;
     if (rows > 0x7fffff00)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "snmf_mask_forward: too many rows (%lld)", (long long)rows);
     const bool admitted = drnmf_snmf_mask_admitted(F, N, beta) != 0;
     if (path == DRNMF_SNMF_PATH_TILE && !admitted)
         DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED, "snmf_mask_forward: the tile kernel takes beta == 2 and N <= %d "
-                   "(beta = %g, N = %d)", TILE_MAX_N, (double)beta, N);
+                   "(beta = %g, N = %d)", MAX_N, (double)beta, N);
     hipStream_t stream = (hipStream_t)stream_;
     const bool gemm = !(path == DRNMF_SNMF_PATH_TILE ||
                         (path == DRNMF_SNMF_PATH_AUTO && admitted && rows <= TILE_AUTO_MAX_ROWS));
@@ -305,17 +224,12 @@ extern "C" int32_t drnmf_snmf_mask_forward(drnmf_handle_t h, int32_t B, int32_t 
     if (h->device < 0) DRNMF_FAIL(h, DRNMF_ERR_HIP, "snmf_mask_forward: the handle is bound to no device");
     if (!gemm) {
         const bool vec = N % 4 == 0 && ((uintptr_t)Wn & 15) == 0;
-        hipError_t e;
-        if (np16(N) <= 256)
-            e = vec ? launch_tile<4, true>(h->device, stream, x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity,
-                                           power, mask_value, has_mask)
-                    : launch_tile<4, false>(h->device, stream, x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity,
-                                            power, mask_value, has_mask);
-        else
-            e = vec ? launch_tile<8, true>(h->device, stream, x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity,
-                                           power, mask_value, has_mask)
-                    : launch_tile<8, false>(h->device, stream, x, Wn, h_init, mask_out, rows, F, N, n_iter, sparsity,
-                                            power, mask_value, has_mask);
+        const hipError_t e = with_instance(N, vec, [&](auto ntw, auto v) {
+            constexpr int NTW = decltype(ntw)::value;
+            return launch<snmf_mask_tile_kernel<NTW, decltype(v)::value>>(
+                h->device, lds_bytes(widest_n(NTW)), lds_bytes(N), rows, stream, x, Wn, h_init, mask_out, rows, F, N,
+                n_iter, sparsity, power, mask_value, has_mask);
+        });
         DRNMF_HIP(h, e);
         return DRNMF_OK;
     }
