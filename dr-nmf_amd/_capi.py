@@ -2,7 +2,8 @@
 STOI score's in include/drnmf_score.h; the ragged STFT / iSTFT / int16 stages' in include/drnmf_enhance.h; the
 device-side SDR's in include/drnmf_sdr.h; the training-data front end's in include/drnmf_dataset.h; the streaming
 STFT / iSTFT's in include/drnmf_stream.h; the sparse-NMF baseline's inference in include/drnmf_snmf.h, on fp16
-operands in include/drnmf_snmf_f16.h, with per-row noise atoms in include/drnmf_snmf_adapt.h, under the KL cost in include/drnmf_snmf_kl.h; ESTOI beside STOI in include/drnmf_estoi.h).
+operands in include/drnmf_snmf_f16.h, with per-row noise atoms in include/drnmf_snmf_adapt.h, their online
+form in include/drnmf_snmf_online.h, under the KL cost in include/drnmf_snmf_kl.h; ESTOI beside STOI in include/drnmf_estoi.h).
 
 The library is the product path: there is NO fallback.  If the shared object is missing or a
 call fails, an exception is raised.
@@ -264,6 +265,19 @@ SNMF_KL_SIGNATURES = {
 SNMF_KL_MAX_N = 512                                # csrc/snmf_kl.hip KL_MAX_N
 SNMF_KL_AUTO_MAX_ROWS = 8192                        # csrc/snmf_kl.hip KL_AUTO_MAX_ROWS: a beta = 1 model's 'auto' takes the KL kernel up to here
 
+# name -> (restype, argtypes); mirrors include/drnmf_snmf_online.h one to one (a table of its own, like those above)
+SNMF_ONLINE_SIGNATURES = {
+    "drnmf_snmf_online_admitted": (_i32, [_i32, _i32, _f32, _i32]),
+    "drnmf_snmf_online_state_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "drnmf_snmf_online_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "drnmf_snmf_online_reset": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "drnmf_snmf_online_forward": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _f32,
+                                         _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "drnmf_snmf_online_read": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+}
+SNMF_ONLINE_MAX_N = 512                            # csrc/snmf_online.hip: snmf_tile.h's MAX_N
+SNMF_ONLINE_BLOCKS = tuple(range(16, 257, 16))     # csrc/snmf_online.hip MIN_BLOCK .. MAX_BLOCK
+
 _lib = None
 _handles = {}
 
@@ -291,7 +305,7 @@ def lib():
                                   list(STREAM_SIGNATURES.items()) + list(SNMF_SIGNATURES.items()) +
                                   list(SNMF_F16_SIGNATURES.items()) + list(TARGET_SIGNATURES.items()) +
                                   list(ESTOI_SIGNATURES.items()) + list(SNMF_ADAPT_SIGNATURES.items()) +
-                                  list(SNMF_KL_SIGNATURES.items())):
+                                  list(SNMF_KL_SIGNATURES.items()) + list(SNMF_ONLINE_SIGNATURES.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

@@ -44,6 +44,9 @@ NO_SCRATCH = {"lstm.hip": "lstm_step_kernel",
               # the adaptive baseline's H pass keeps num and den in registers, its statistics pass four accumulators per
               # 16-atom tile; the small kernels of the file ride along
               "snmf_adapt.hip": "snmf_adapt_",
+              # the online form: the fixed tile kernel's registers in its H kernel, two accumulators per 16-atom tile
+              # in its statistics kernel
+              "snmf_online.hip": "snmf_online_",
               # the KL tile kernel: H's numerator of its tiles, the column denominators and a chunk of V in registers
               "snmf_kl.hip": "snmf_kl_",
               # the target kernels keep the noisy member's bins of a frame in registers (up to 27 per lane)
@@ -79,7 +82,7 @@ def _deps():
         [os.path.join(os.path.dirname(HERE), "include", n) for n in ("drnmf.h", "drnmf_lstm.h", "drnmf_score.h", "drnmf_enhance.h", "drnmf_sdr.h",
                                                                      "drnmf_dataset.h", "drnmf_stream.h", "drnmf_snmf.h", "drnmf_snmf_f16.h",
                                                                      "drnmf_target.h", "drnmf_estoi.h", "drnmf_snmf_adapt.h",
-                                                                     "drnmf_snmf_kl.h")] + \
+                                                                     "drnmf_snmf_kl.h", "drnmf_snmf_online.h")] + \
         [os.path.abspath(__file__)]
 
 

@@ -14,6 +14,8 @@
 //   snmf_adapt.hip  snmf_adapt_h_kernel, snmf_adapt_stats_kernel, snmf_adapt_final_kernel: a dictionary per batch
 //                   row (the stager's W), validity and H from global memory in place of the prologue, an LDS tail
 //                   of their own (a V chunk buffer; the statistics' V / Lambda tiles).
+//   snmf_online.hip snmf_online_h_kernel: snmf_mask_tile_kernel's loop on a dictionary per batch row, the row's block
+//                   buffer as x and its to-do flags as validity, all through the functions here.
 //   snmf_f16.hip    snmf_f16_tile_kernel: the row scale (rs: nullptr = none, and then no multiply either; else
 //                   s[rl] multiplies V and the mask's epsilon), a stager of its own (a callable of final_mask; the
 //                   fp32 dictionary is read twice in all) and fp16 iterations with their own maps and a wider

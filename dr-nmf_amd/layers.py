@@ -2776,11 +2776,22 @@ class SparseNMFModel(_SequenceModel):
     ops.snmf_adapt_forward).  The stored dictionary is the starting point and is never modified;
     forward(x, return_dictionaries=True) also returns the rows' dictionaries [B, F, 2r] (unit-norm columns).  Rows
     are independent bit for bit, so predict and enhance may regroup them; frames of ONE row are not, so `stream`
-    raises NotImplementedError.  beta == 2, 2r <= 512, float32 operands and path 'auto' or 'tile' only."""
+    raises NotImplementedError.  beta == 2, 2r <= 512, float32 operands and path 'auto' or 'tile' only.
+
+    adapt_noise='online' is the online form of the same update (csrc/snmf_online.hip, ops.snmf_online_forward), and
+    the one that streams.  Every batch row is a stream with a state of its own: its dictionary, the sufficient
+    statistics sum H^T H_noise and sum V^T H_noise, and the count of valid frames it has seen.  A frame is decomposed
+    and masked with the dictionary its row had when the frame's block of `adapt_block` valid frames (a multiple of 16
+    in 16..256) began; every full block adds its frames to the statistics, which first decay by `adapt_forget` (in
+    (0, 1]), and moves the r noise atoms `adapt_w_iter` times (0: never).  A frame's mask depends on the row's earlier
+    frames only and not on how the frames were cut into calls, bit for bit: `stream`, `predict` and `predict_on_batch`
+    carry the state from call to call (_carries_state() is True, so `enhance`, which regroups rows, refuses the
+    model), reset_states(batch_size=) binds and resets it, a changed stored dictionary rebuilds it, and
+    dictionaries() returns the streams' dictionaries and counts.  The same construction limits as True."""
 
     def __init__(self, W, r, sparsity, n_iter=200, beta=2.0, spectrogram_power=1.0, mask_value=-1.0, h_init=None,
                  random_seed=2016, path='auto', device=None, operand_dtype='float32', adapt_noise=False,
-                 v_floor=None):
+                 v_floor=None, adapt_block=64, adapt_forget=1.0, adapt_w_iter=1):
         W = np.asarray(W, np.float32)
         r = int(r)
         if W.ndim != 2 or W.shape[1] % 2 or W.shape[1] != 2 * r or r < 1:
@@ -2792,15 +2803,25 @@ class SparseNMFModel(_SequenceModel):
         if operand_dtype not in ('float32', 'float16'):
             raise ValueError("SparseNMFModel: operand_dtype must be 'float32' or 'float16'")
         N = 2 * r
+        if isinstance(adapt_noise, str) and adapt_noise != 'online':
+            raise ValueError("SparseNMFModel: adapt_noise must be False, True or 'online' (got %r)" % (adapt_noise,))
+        if int(adapt_block) not in _capi.SNMF_ONLINE_BLOCKS or int(adapt_block) != adapt_block:
+            raise ValueError('SparseNMFModel: adapt_block must be a multiple of 16 in 16..256 (got %r)' %
+                             (adapt_block,))
+        if not (float(adapt_forget) > 0 and float(adapt_forget) <= 1):
+            raise ValueError('SparseNMFModel: adapt_forget must lie in (0, 1] (got %r)' % (adapt_forget,))
+        if int(adapt_w_iter) < 0 or int(adapt_w_iter) != adapt_w_iter:
+            raise ValueError('SparseNMFModel: adapt_w_iter must be an integer >= 0 (got %r)' % (adapt_w_iter,))
         if operand_dtype == 'float16' and (float(beta) != 2.0 or N > _capi.SNMF_F16_MAX_N or path == 'gemm'):
             raise ValueError("SparseNMFModel: operand_dtype='float16' runs one kernel, which takes beta == 2, "
                              "2r <= %d and path 'auto' or 'tile' (beta = %g, 2r = %d, path = %r)" %
                              (_capi.SNMF_F16_MAX_N, float(beta), N, path))
         if adapt_noise and (operand_dtype == 'float16' or float(beta) != 2.0 or N > _capi.SNMF_ADAPT_MAX_N or
                             path == 'gemm'):
-            raise ValueError("SparseNMFModel: adapt_noise=True takes operand_dtype='float32', beta == 2, 2r <= %d and "
+            raise ValueError("SparseNMFModel: adapt_noise=%r takes operand_dtype='float32', beta == 2, 2r <= %d and "
                              "path 'auto' or 'tile' (operand_dtype = %r, beta = %g, 2r = %d, path = %r)" %
-                             (_capi.SNMF_ADAPT_MAX_N, operand_dtype, float(beta), N, path))
+                             (adapt_noise if adapt_noise == 'online' else True, _capi.SNMF_ADAPT_MAX_N,
+                              operand_dtype, float(beta), N, path))
         if v_floor is not None:
             if not (float(v_floor) > 0 and float(v_floor) < float('inf')):
                 raise ValueError('SparseNMFModel: v_floor must be None or a positive finite number (v_floor = %r)' %
@@ -2818,7 +2839,10 @@ class SparseNMFModel(_SequenceModel):
             raise ValueError("SparseNMFModel: path='tile' at beta == 1 is the KL kernel, which takes 2r <= %d "
                              "(2r = %d)" % (_capi.SNMF_KL_MAX_N, N))
         self.operand_dtype = operand_dtype
-        self.adapt_noise = bool(adapt_noise)
+        self.adapt_noise = 'online' if adapt_noise == 'online' else bool(adapt_noise)
+        self.adapt_block, self.adapt_forget, self.adapt_w_iter = int(adapt_block), float(adapt_forget), \
+            int(adapt_w_iter)
+        self._online = None          # (W version the state was made for, ops.SNMFOnlineState): adapt_noise='online'
         self.v_floor = None if v_floor is None else float(v_floor)
         if h_init is None:
             h_init = np.random.RandomState(int(random_seed)).rand(N)
@@ -2858,11 +2882,47 @@ class SparseNMFModel(_SequenceModel):
     def _stateful(self):
         return True
 
+    def _is_online(self):
+        return self.adapt_noise == 'online'
+
     def _carries_state(self):
-        return False
+        return self._is_online()
 
     def reset_states(self, batch_size=None):
-        """Nothing to reset: no frame depends on another."""
+        """Nothing to reset: no frame depends on another -- except with adapt_noise='online': every stream back to
+        the stored dictionary, zero statistics and count.  batch_size: (re)bind the state to that many streams."""
+        if not self._is_online():
+            return
+        if batch_size is None and self._online is None:
+            return
+        self._online_state(int(batch_size) if batch_size is not None else self._online[1].B, reset=True)
+
+    def _online_state(self, B, reset=False):
+        """The state a call of B rows carries: made (reset) on first use, when the stored dictionary has changed and
+        when reset_states rebinds it; ValueError at another batch size than the one it is bound to."""
+        Wn, _ = self._operands()
+        key = self._normalised[0]
+        cur = self._online
+        if cur is not None and cur[0] == key and cur[1].B == int(B) and cur[1].device == Wn.device:
+            if reset:
+                ops.snmf_online_reset(cur[1], Wn)
+            return cur[1]
+        if cur is not None and cur[0] == key and not reset and cur[1].B != int(B):
+            raise ValueError("SparseNMFModel(adapt_noise='online'): the state belongs to %d streams, this call has "
+                             "%d rows (reset_states(batch_size=%d) starts over at the new size)" %
+                             (cur[1].B, int(B), int(B)))
+        state = ops.snmf_online_state(int(B), self._input_width(), 2 * self.r, self.r, self.adapt_block, Wn,
+                                      Wn.device)
+        self._online = (key, state)
+        return state
+
+    def dictionaries(self):
+        """adapt_noise='online': (the streams' dictionaries [B, F, 2r] with unit-norm columns, the valid frames each
+        stream has seen [B] int64), device tensors; before the first call the state of one stream."""
+        if not self._is_online():
+            raise ValueError("dictionaries: needs a model built with adapt_noise='online' (an adapt_noise=True model "
+                             "returns them from forward(x, return_dictionaries=True))")
+        return ops.snmf_online_dictionaries(self._online_state(self._online[1].B if self._online is not None else 1))
 
     def _operands(self):
         """(Wn, h_init in Wn's basis), remade when W has changed (torch's in-place version counter); with
@@ -2899,6 +2959,17 @@ class SparseNMFModel(_SequenceModel):
             raise ValueError('forward: return_dictionaries=True needs a model built with adapt_noise=True (every '
                              'row of a fixed model has the stored dictionary)')
         Wn, hn = self._operands()
+        if self._is_online():
+            B, T = int(x.shape[0]), int(x.shape[1])
+            state = self._online_state(B)
+            if T:
+                self._ws = ops.snmf_online_workspace(B, T, F, 2 * self.r, self.r, self.adapt_block, x.device,
+                                                     have=self._ws)
+            mask = ops.snmf_online_forward(x, hn, self.sparsity, self.n_iter, self.r, state,
+                                           w_iter=self.adapt_w_iter, forget=self.adapt_forget,
+                                           power=self.spectrogram_power, mask_value=self.mask_value,
+                                           workspace=self._ws)
+            return (mask, ops.snmf_online_dictionaries(state)[0]) if return_dictionaries else mask
         if self.adapt_noise:
             self._ws = ops.snmf_adapt_workspace(int(x.shape[0]), int(x.shape[1]), F, 2 * self.r, self.r, x.device,
                                                 have=self._ws)
@@ -2924,7 +2995,7 @@ class SparseNMFModel(_SequenceModel):
     __call__ = forward
 
     def stream(self, *args, **kwargs):
-        if self.adapt_noise:
+        if self.adapt_noise is True:
             raise NotImplementedError('SparseNMFModel: stream() of an adaptive model (adapt_noise=True) is not '
                                       'defined -- the noise atoms are fitted to a whole row; online adaptation is '
                                       'another algorithm')
@@ -2962,7 +3033,7 @@ class SparseNMFModel(_SequenceModel):
     def val_loss(self, noisy, clean, N=512, hop=128):
         """enhance.py:855 on waveform pairs: mean((irm * x - y)^2) over the packed frames of both sides raised
         to spectrogram_power.  An adaptive model adapts per recording: one row each through the ragged STFT that
-        `enhance` uses, the same mean over the same frames."""
+        `enhance` uses, the same mean over the same frames; an online model's state is reset first."""
         if self.adapt_noise:
             return self._val_loss_per_recording(noisy, clean, N, hop)
         with torch.cuda.device(self.device):
@@ -2984,6 +3055,8 @@ class SparseNMFModel(_SequenceModel):
             # the frames of the pair are the clean side's (ops.wavs_to_frames); a longer noisy side is cut there
             keep = (torch.arange(T, device=dev)[None, :] < torch.from_numpy(nf).to(dev)[:, None])[..., None]
             x = torch.where(keep, x, torch.full_like(x, float(self.mask_value))).contiguous()
+            if self._is_online():
+                self.reset_states(batch_size=int(x.shape[0]))
             irm = self.forward(x)
             p = self.spectrogram_power
             err = torch.where(keep, (irm * x ** p - y ** p) ** 2, torch.zeros_like(x))
@@ -2996,7 +3069,8 @@ def build_snmf(params_snmf, W, device=None):
     spectrogram_power; max_iter / conv_eps are training settings -- inference runs the reference's 200
     iterations.  Optional keys the reference's dictionaries do not have: 'n_iter', 'mask_value', 'path' and
     'operand_dtype' ('float32' or 'float16', as build_unfolded_snmf's and build_lstm's), 'adapt_noise' (True: every
-    row fits the noise atoms to its own frames, see SparseNMFModel) and 'v_floor' (cf 'kl' only: the constant that
+    row fits the noise atoms to its own frames; 'online': block by block on a state that streams, with the optional
+    'adapt_block', 'adapt_forget' and 'adapt_w_iter'; see SparseNMFModel) and 'v_floor' (cf 'kl' only: the constant that
     zeros of V are raised to, see SparseNMFModel; absent or None: the reference's per-call rule).  cf 'kl' runs the KL
     tile kernel where 'path' says so, cf 'ed' the Euclidean one."""
     from . import snmf
@@ -3006,4 +3080,7 @@ def build_snmf(params_snmf, W, device=None):
                           mask_value=p.get('mask_value', -1.0), random_seed=int(p.get('random_seed', 2016)),
                           path=p.get('path', 'auto'), device=device,
                           operand_dtype=p.get('operand_dtype', 'float32'),
-                          adapt_noise=bool(p.get('adapt_noise', False)), v_floor=p.get('v_floor'))
+                          adapt_noise=('online' if p.get('adapt_noise', False) == 'online'
+                                       else bool(p.get('adapt_noise', False))), v_floor=p.get('v_floor'),
+                          adapt_block=p.get('adapt_block', 64), adapt_forget=p.get('adapt_forget', 1.0),
+                          adapt_w_iter=p.get('adapt_w_iter', 1))

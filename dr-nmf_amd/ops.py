@@ -988,6 +988,133 @@ def snmf_adapt_forward(x, Wn, hn, sparsity, n_iter, n_fixed, power=1.0, mask_val
     return ret[0] if len(ret) == 1 else ret
 
 
+class SNMFOnlineState(object):
+    """The caller-owned state of `snmf_online_forward` (include/drnmf_snmf_online.h): `buf`, a uint8 device tensor of
+    drnmf_snmf_online_state_bytes, and the shape it was sized for.  Made by `snmf_online_state`."""
+
+    def __init__(self, buf, B, F, N, n0, block):
+        self.buf, self.B, self.F, self.N, self.n0, self.block = buf, int(B), int(F), int(N), int(n0), int(block)
+
+    @property
+    def device(self):
+        return self.buf.device
+
+    def _shape(self):
+        return self.B, self.F, self.N, self.n0, self.block
+
+
+def snmf_online_admitted(F, N, beta=2.0, block=64):
+    """True when `snmf_online_forward` takes the shape (beta == 2, N even, 2 <= N <= 512, block a multiple of 16 in
+    16..256)."""
+    return bool(_capi.lib().drnmf_snmf_online_admitted(int(F), int(N), float(beta), int(block)))
+
+
+def snmf_online_reset(state, Wn, rows=None):
+    """Every row of `state` -- or, with rows (B booleans), the rows marked -- back to its start: dictionary Wn [F,N]
+    (unit-norm columns), statistics and count 0 (drnmf_snmf_online_reset)."""
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(state.buf))
+    Wn = _f32c(Wn, "Wn")
+    if tuple(Wn.shape) != (state.F, state.N) or Wn.device != state.device:
+        raise ValueError("Wn must be [%d, %d] on %s, got %s on %s" % (state.F, state.N, state.device,
+                                                                      tuple(Wn.shape), Wn.device))
+    flags = None
+    if rows is not None:
+        flags = torch.as_tensor(np.asarray(rows, dtype=bool).astype(np.int32).reshape(-1)).to(state.device)
+        if flags.numel() != state.B:
+            raise ValueError("rows must have %d entries, got %d" % (state.B, flags.numel()))
+    rc = L.drnmf_snmf_online_reset(h, *state._shape(), _capi.ptr(Wn), _capi.ptr(flags), _capi.ptr(state.buf),
+                                   state.buf.numel(), _stream())
+    _capi.check(rc, h, "drnmf_snmf_online_reset")
+    return state
+
+
+def snmf_online_state(B, F, N, n0, block, Wn, device):
+    """A reset state of B streams for `snmf_online_forward`: every row's dictionary is Wn [F,N] (unit-norm columns),
+    of which the first n0 atoms stay fixed; `block` valid frames make one update.  ValueError for a shape the entry
+    points refuse."""
+    need = _capi.lib().drnmf_snmf_online_state_bytes(int(B), int(F), int(N), int(n0), int(block))
+    if need == 0:
+        raise ValueError("snmf_online: shape B=%d F=%d N=%d n0=%d block=%d is not taken (N even, 2 <= N <= %d, "
+                         "0 <= n0 <= N, block a multiple of 16 in 16..256)" %
+                         (B, F, N, n0, block, _capi.SNMF_ONLINE_MAX_N))
+    state = SNMFOnlineState(torch.empty(need, dtype=torch.uint8, device=device), B, F, N, n0, block)
+    return snmf_online_reset(state, Wn)
+
+
+def snmf_online_workspace(B, T, F, N, n0, block, device, have=None):
+    """The workspace a `snmf_online_forward` call of T frames needs: a uint8 tensor of
+    drnmf_snmf_online_workspace_bytes -- `have` itself when it is large enough and on `device`."""
+    need = _capi.lib().drnmf_snmf_online_workspace_bytes(int(B), int(T), int(F), int(N), int(n0), int(block))
+    if need == 0:
+        raise ValueError("snmf_online: shape B=%d T=%d F=%d N=%d n0=%d block=%d is not taken" %
+                         (B, T, F, N, n0, block))
+    if have is not None and have.numel() >= need and have.device == torch.device(device):
+        return have
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def snmf_online_forward(x, h_init, sparsity, n_iter, n0, state, w_iter=1, forget=1.0, power=1.0, mask_value=None,
+                        workspace=None, out=None, return_h=False):
+    """The online noise-adaptive sparse-NMF baseline (drnmf_snmf_online_forward): x [B,T,F] holds the next T frames
+    of the B streams of `state` (masked frames where a stream has fewer) -> mask [B,T,F], and with return_h the
+    activations [B,T,N] (0 at masked frames).  A valid frame is decomposed for n_iter iterations from h_init [N] on
+    the dictionary its row had when the frame's block began; every full block of state.block valid frames moves the
+    row's atoms from n0 on (w_iter updates from the statistics, which decay by `forget` per block).  The masks, the
+    activations and the state do not depend on how a row's frames are cut into calls."""
+    if x.dim() != 3 or tuple(h_init.shape) != (state.N,) or x.shape[2] != state.F or x.shape[0] != state.B:
+        raise ValueError("shape mismatch: x %s h_init %s for a state of B=%d F=%d N=%d" %
+                         (tuple(x.shape), tuple(h_init.shape), state.B, state.F, state.N))
+    if int(n0) != state.n0:
+        raise ValueError("n0 = %d, the state was made for n0 = %d" % (int(n0), state.n0))
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(x))
+    x, h_init = _f32c(x, "x"), _f32c(h_init, "h_init")
+    B, T, F = x.shape
+    if out is None:
+        out = torch.empty((B, T, F), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, T, F) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of shape %s" % ((B, T, F),))
+    Ha = torch.empty((B, T, state.N), dtype=torch.float32, device=x.device) if return_h else None
+    if T == 0:
+        return (out, Ha) if return_h else out
+    workspace = snmf_online_workspace(B, T, F, state.N, state.n0, state.block, x.device, have=workspace)
+    rc = L.drnmf_snmf_online_forward(h, B, T, F, state.N, state.n0, state.block, int(n_iter), int(w_iter),
+                                     float(sparsity), float(forget), float(power),
+                                     0.0 if mask_value is None else float(mask_value), int(mask_value is not None),
+                                     _capi.ptr(x), _capi.ptr(h_init), _capi.ptr(out), _capi.ptr(Ha),
+                                     _capi.ptr(state.buf), state.buf.numel(), _capi.ptr(workspace),
+                                     workspace.numel(), _stream())
+    _capi.check(rc, h, "drnmf_snmf_online_forward")
+    return (out, Ha) if return_h else out
+
+
+def _snmf_online_read(state, want_w, want_stats):
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(state.buf))
+    B, F, N, n0, _ = state._shape()
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=state.device)
+    W = new(B, F, N) if want_w else None
+    counts = torch.empty((B,), dtype=torch.int64, device=state.device) if want_w else None
+    A = new(B, N, N - n0) if want_stats else None
+    Bm = new(B, F, N - n0) if want_stats else None
+    rc = L.drnmf_snmf_online_read(h, *state._shape(), _capi.ptr(state.buf), state.buf.numel(), _capi.ptr(W),
+                                  _capi.ptr(counts), _capi.ptr(A), _capi.ptr(Bm), _stream())
+    _capi.check(rc, h, "drnmf_snmf_online_read")
+    return W, counts, A, Bm
+
+
+def snmf_online_dictionaries(state):
+    """(the streams' dictionaries [B,F,N] float32, the valid frames each has seen [B] int64), copied out of `state`
+    (drnmf_snmf_online_read)."""
+    return _snmf_online_read(state, True, False)[:2]
+
+
+def snmf_online_statistics(state):
+    """(A [B,N,N-n0], Bm [B,F,N-n0]): the streams' sufficient statistics, copied out of `state`."""
+    return _snmf_online_read(state, False, True)[2:]
+
+
 def stft_frames(nsampl, N, hop):
     return int(_capi.lib().drnmf_stft_frames(int(nsampl), int(N), int(hop)))
 
