@@ -541,9 +541,124 @@ static int32_t lstm_store_state(drnmf_handle_t h, const drnmf_lstm_desc_t* d, co
     return DRNMF_OK;
 }
 
-// st == nullptr: drnmf_lstm_forward (zero state in, none out); else drnmf_lstm_forward_stateful.  The state
-// kernels run on the stream before and behind the replayed frames, never inside them: the graphs hold no state
-// pointer (the cache key has none), and both entry points replay the same graphs.
+// Row stride, then params alignment: the order of the head, the loss head and the training forwards (the inference
+// forwards check the workspace size between the two and have one alignment message for workspace and params)
+static int32_t lstm_check_ld_params(drnmf_handle_t h, const drnmf_lstm_desc_t* d, int32_t ld_h, const void* params,
+                                    const char* what) {
+    if (ld_h < d->H) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: ld_h %d < H %d", what, ld_h, d->H);
+    if ((uintptr_t)params & 255) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "params must be 256-byte aligned");
+    return DRNMF_OK;
+}
+
+// A wavefront of T + K - 1 diagonals (the forwards count up, the BPTT counts DOWN: its kernel writes d - 1), two
+// per graph frame: the first launch reads counter 0 and sets counter 1, the second the other way round (nobody
+// reads a counter in the launch that writes it).  An odd diagonal count ends on one launch whose workgroups all
+// exit at once.  Args: LstmStepArgs or LstmBwdArgs.
+template <class Args>
+static int32_t lstm_wavefront(drnmf_handle_t h, hipStream_t stream, GraphKind kind,
+                              const std::vector<uint64_t>& key, int T, int K, const void* kernel, dim3 grid,
+                              const Args& base, int* ctr) {
+    auto frame = [&](Launcher& chain, int) -> int32_t {
+        for (int p = 0; p < 2; ++p) {
+            Args a = base;
+            a.d_rd = ctr + 16 * p;
+            a.d_wr = ctr + 16 * (1 - p);
+            void* kp[1] = {&a};
+            DRNMF_HIP(h, chain.add(kernel, grid, dim3(64 * LSTM_NW), kp));
+        }
+        return DRNMF_OK;
+    };
+    const int diagonals = T + K - 1, frames = (diagonals + 1) / 2;
+    const int fpg = frames < 64 ? frames : 64;
+    return replay_frames(h, stream, kind, key, {fpg, 1}, 0, frames, frame);
+}
+
+namespace {     // (defined with the training kernels below)
+__global__ void lstm_stash_init_kernel(float* __restrict__ zst, float* __restrict__ cst, float* __restrict__ hst,
+                                       int Bp, int T, size_t zk, size_t RS, int NC, int Hc, int Hq);
+}
+
+// One forward's buffers, carved by the entry from its own layout (LstmLayout or LstmTrainLayout)
+struct LstmFwdViews {
+    float* xz;
+    unsigned char* valid;
+    float* xproj;
+    float* hring;
+    float* cring;
+    f16* h16;                  // operand_f16 only, else NULL
+    int* ctr;
+    size_t rows;               // of xz / valid / xproj: B T, or B (T + 1) in the training layout
+    float* zst;                // the training stash (lstm_step_kernel<true>), or all NULL / 0
+    float* cst;
+    float* hst;
+    size_t zk, RS;
+};
+
+// Everything of a forward behind its pack launch: entering state, (training) the stash's zero rows and entering
+// state, input projection, the wavefront and the state behind it.  st == nullptr: zero state in, none out; else a
+// *_stateful entry.  The state kernels run on the stream before and behind the replayed frames, never inside
+// them: the graphs hold no state pointer (the cache key has none), and both entry points of a kind replay the
+// same graphs.  The entering state of a training call also goes into row b (T + 1) of the stash, where the BPTT
+// finds it: a constant of the gradient.
+static int32_t lstm_forward_run(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const LstmLayout& L,
+                                const LstmFwdViews& V, const void* params, float* h_out, int32_t ld_h,
+                                void* workspace, hipStream_t stream, const LstmState* st, const void* step,
+                                GraphKind kind) {
+    const char* pb = (const char*)params;
+    const size_t nring = (size_t)d->K * 2 * L.Bp * L.Hc;
+    if (st)
+        hipLaunchKernelGGL(lstm_state_scatter_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream,
+                           V.hring, V.cring, V.h16, V.ctr, st->initial_h, st->initial_c, nring, d->B, d->H, L.Bp,
+                           L.Hc);
+    else
+        hipLaunchKernelGGL(lstm_init_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream, V.hring,
+                           V.cring, V.h16, V.ctr, nring);
+    if (V.zst) {
+        hipLaunchKernelGGL(lstm_stash_init_kernel, dim3((unsigned)(L.Bp + 1), (unsigned)d->K), dim3(256), 0, stream,
+                           V.zst, V.cst, V.hst, L.Bp, d->T, V.zk, V.RS, L.NC, L.Hc, L.Hq);
+        if (st && (st->initial_h || st->initial_c)) {
+            const size_t ns = (size_t)d->K * d->B * d->H;
+            hipLaunchKernelGGL(lstm_stash_state_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, stream,
+                               V.cst, V.hst, st->initial_h, st->initial_c, ns, d->B, d->H, d->T, V.RS, L.Hc, L.Hq);
+        }
+    }
+    DRNMF_HIP(h, hipGetLastError());
+    {
+        gemm::Operands g;
+        g.A = V.xz;
+        g.Bt = (const float*)(pb + L.off_k0t);
+        g.M = (int64_t)V.rows;
+        g.N = L.NC;
+        g.K = L.Fq;
+        g.lda = g.ldb = L.Fq;
+        DRNMF_HIP(h, gemm::launch(g, EpiLstmXproj{V.xproj, (const float*)(pb + L.off_bias), L.NC}, stream));
+    }
+
+    LstmStepArgs base{};
+    base.M = (const float*)pb;
+    base.bias = (const float*)(pb + L.off_bias);
+    base.xproj = V.xproj;
+    base.valid = V.valid;
+    base.hring = V.hring;
+    base.cring = V.cring;
+    base.out = h_out;
+    base.B = d->B; base.T = d->T; base.H = d->H; base.K = d->K;
+    base.Bp = L.Bp; base.Hc = L.Hc; base.numU = L.numU; base.NC = L.NC;
+    base.act = d->recurrent_activation;
+    base.ld_h = ld_h;
+    base.zst = V.zst; base.cst = V.cst; base.hst = V.hst; base.zk = V.zk; base.Hq = L.Hq;
+    base.h16 = V.h16;
+    const dim3 grid((unsigned)L.numU, (unsigned)(L.Bp / 16), (unsigned)d->K);
+    std::vector<uint64_t> key = {
+        (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->H, (uint64_t)d->K,
+        (uint64_t)d->recurrent_activation, (uint64_t)(uintptr_t)params, (uint64_t)(uintptr_t)h_out, (uint64_t)ld_h,
+        (uint64_t)(uintptr_t)workspace};
+    if (kind == GraphKind::Lstm) key.push_back((uint64_t)d->operand_f16);    // (LstmTrain refuses operand_f16)
+    int32_t rc = lstm_wavefront(h, stream, kind, key, d->T, d->K, step, grid, base, V.ctr);
+    if (rc) return rc;
+    return lstm_store_state(h, d, L, V.hring, V.cring, st, stream);
+}
+
 static int32_t lstm_forward_impl(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x, float mask_value,
                                  const void* params, float* h_out, int32_t ld_h, void* workspace,
                                  size_t workspace_bytes, void* stream_, const LstmState* st, const char* what) {
@@ -562,75 +677,20 @@ static int32_t lstm_forward_impl(drnmf_handle_t h, const drnmf_lstm_desc_t* d, c
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "workspace/params must be 256-byte aligned");
     hipStream_t stream = (hipStream_t)stream_;
     char* ws = (char*)workspace;
-    const char* pb = (const char*)params;
-    float* xz = (float*)(ws + L.off_xz);
-    unsigned char* valid = (unsigned char*)(ws + L.off_valid);
-    float* xproj = (float*)(ws + L.off_xproj);
-    float* hring = (float*)(ws + L.off_h);
-    float* cring = (float*)(ws + L.off_c);
-    f16* h16 = L.half ? (f16*)(ws + L.off_h16) : nullptr;
-    int* ctr = (int*)(ws + L.off_ctr);
-    const size_t rows = (size_t)d->B * d->T;
-
-    hipLaunchKernelGGL(lstm_pack_x_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, xz, valid,
-                       mask_value, rows, d->F, L.Fq);
-    const size_t nring = (size_t)d->K * 2 * L.Bp * L.Hc;
-    if (st)
-        hipLaunchKernelGGL(lstm_state_scatter_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream,
-                           hring, cring, h16, ctr, st->initial_h, st->initial_c, nring, d->B, d->H, L.Bp, L.Hc);
-    else
-        hipLaunchKernelGGL(lstm_init_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream, hring,
-                           cring, h16, ctr, nring);
-    DRNMF_HIP(h, hipGetLastError());
-    {
-        gemm::Operands g;
-        g.A = xz;
-        g.Bt = (const float*)(pb + L.off_k0t);
-        g.M = (int64_t)rows;
-        g.N = L.NC;
-        g.K = L.Fq;
-        g.lda = g.ldb = L.Fq;
-        DRNMF_HIP(h, gemm::launch(g, EpiLstmXproj{xproj, (const float*)(pb + L.off_bias), L.NC}, stream));
-    }
-
-    LstmStepArgs base;
-    base.M = (const float*)pb;
-    base.bias = (const float*)(pb + L.off_bias);
-    base.xproj = xproj;
-    base.valid = valid;
-    base.hring = hring;
-    base.cring = cring;
-    base.out = h_out;
-    base.B = d->B; base.T = d->T; base.H = d->H; base.K = d->K;
-    base.Bp = L.Bp; base.Hc = L.Hc; base.numU = L.numU; base.NC = L.NC;
-    base.act = d->recurrent_activation;
-    base.ld_h = ld_h;
-    base.h16 = h16;
+    LstmFwdViews V{};
+    V.xz = (float*)(ws + L.off_xz);
+    V.valid = (unsigned char*)(ws + L.off_valid);
+    V.xproj = (float*)(ws + L.off_xproj);
+    V.hring = (float*)(ws + L.off_h);
+    V.cring = (float*)(ws + L.off_c);
+    V.h16 = L.half ? (f16*)(ws + L.off_h16) : nullptr;
+    V.ctr = (int*)(ws + L.off_ctr);
+    V.rows = (size_t)d->B * d->T;
+    hipLaunchKernelGGL(lstm_pack_x_kernel, dim3((unsigned)((V.rows + 3) / 4)), dim3(256), 0, stream, x, V.xz,
+                       V.valid, mask_value, V.rows, d->F, L.Fq);
     const void* step = L.half ? (const void*)&lstm_step_kernel<false, true>
                               : (const void*)&lstm_step_kernel<false, false>;
-    const dim3 grid((unsigned)L.numU, (unsigned)(L.Bp / 16), (unsigned)d->K);
-    // one graph frame = two diagonals: the first reads counter 0 and sets counter 1, the second the other way
-    // round (nobody reads a counter in the launch that writes it).  An odd diagonal count ends on one launch
-    // whose workgroups all exit at once.
-    auto frame = [&](Launcher& chain, int) -> int32_t {
-        for (int p = 0; p < 2; ++p) {
-            LstmStepArgs a = base;
-            a.d_rd = ctr + 16 * p;
-            a.d_wr = ctr + 16 * (1 - p);
-            void* kp[1] = {&a};
-            DRNMF_HIP(h, chain.add(step, grid, dim3(64 * LSTM_NW), kp));
-        }
-        return DRNMF_OK;
-    };
-    const int diagonals = d->T + d->K - 1, frames = (diagonals + 1) / 2;
-    const int fpg = frames < 64 ? frames : 64;
-    const std::vector<uint64_t> key = {
-        (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->H, (uint64_t)d->K,
-        (uint64_t)d->recurrent_activation, (uint64_t)(uintptr_t)params, (uint64_t)(uintptr_t)h_out, (uint64_t)ld_h,
-        (uint64_t)(uintptr_t)workspace, (uint64_t)d->operand_f16};
-    rc = replay_frames(h, stream, GraphKind::Lstm, key, {fpg, 1}, 0, frames, frame);
-    if (rc) return rc;
-    return lstm_store_state(h, d, L, hring, cring, st, stream);
+    return lstm_forward_run(h, d, L, V, params, h_out, ld_h, workspace, stream, st, step, GraphKind::Lstm);
 }
 
 extern "C" int32_t drnmf_lstm_forward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x,
@@ -653,8 +713,28 @@ extern "C" int32_t drnmf_lstm_forward_stateful(drnmf_handle_t h, const drnmf_lst
                              "lstm_forward_stateful");
 }
 
-// With ld_h >= round_up(H, 4) the product contracts the padding columns too (against zero rows of W_out^T): K and
-// lda are then multiples of 4 and the gemm takes its vectorised path (and the split-operand one in bf16x3 mode).
+// Columns of a hidden row that the head's products contract.  With ld_h >= round_up(H, 4) they take the padding
+// columns too (against zero rows of W_out^T): K and lda are then multiples of 4 and the gemm takes its vectorised
+// path (and the split-operand one in bf16x3 mode).
+static int lstm_head_k(const drnmf_lstm_desc_t* d, const LstmLayout& L, int32_t ld_h) {
+    return ld_h >= L.Hq ? L.Hq : d->H;
+}
+
+// out [B T][F] = sigmoid(hidden . W_out + b_out)
+static hipError_t lstm_head_product(const drnmf_lstm_desc_t* d, const LstmLayout& L, const float* hidden,
+                                    int32_t ld_h, const void* params, float* out, hipStream_t stream) {
+    const char* pb = (const char*)params;
+    gemm::Operands g;
+    g.A = hidden;
+    g.Bt = (const float*)(pb + L.off_wo);
+    g.M = (int64_t)d->B * d->T;
+    g.N = d->F;
+    g.K = lstm_head_k(d, L, ld_h);
+    g.lda = ld_h;
+    g.ldb = L.Hq;
+    return gemm::launch(g, EpiLstmHead{out, (const float*)(pb + L.off_bo), d->F}, stream);
+}
+
 extern "C" int32_t drnmf_lstm_head_forward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* hidden,
                                            int32_t ld_h, const void* params, float* out, void* stream_) {
     DRNMF_LOCK(h);
@@ -662,19 +742,9 @@ extern "C" int32_t drnmf_lstm_head_forward(drnmf_handle_t h, const drnmf_lstm_de
     int rc = validate_lstm_desc(h, d, true);
     if (rc) return rc;
     if (!hidden || !params || !out) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_head_forward: NULL pointer argument");
-    if (ld_h < d->H) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_head_forward: ld_h %d < H %d", ld_h, d->H);
-    if ((uintptr_t)params & 255) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "params must be 256-byte aligned");
-    const LstmLayout L = lstm_layout(d);
-    const char* pb = (const char*)params;
-    gemm::Operands g;
-    g.A = hidden;
-    g.Bt = (const float*)(pb + L.off_wo);
-    g.M = (int64_t)d->B * d->T;
-    g.N = d->F;
-    g.K = ld_h >= L.Hq ? L.Hq : d->H;
-    g.lda = ld_h;
-    g.ldb = L.Hq;
-    DRNMF_HIP(h, gemm::launch(g, EpiLstmHead{out, (const float*)(pb + L.off_bo), d->F}, (hipStream_t)stream_));
+    rc = lstm_check_ld_params(h, d, ld_h, params, "lstm_head_forward");
+    if (rc) return rc;
+    DRNMF_HIP(h, lstm_head_product(d, lstm_layout(d), hidden, ld_h, params, out, (hipStream_t)stream_));
     return DRNMF_OK;
 }
 
@@ -1100,8 +1170,6 @@ extern "C" size_t drnmf_lstm_train_workspace_bytes(const drnmf_lstm_desc_t* d) {
     return lstm_train_layout(d).total;
 }
 
-// st as in lstm_forward_impl; the entering state also goes into row b (T + 1) of the stash, where the BPTT
-// (drnmf_lstm_backward, unchanged) finds it: a constant of the gradient
 static int32_t lstm_train_forward_impl(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x,
                                        float mask_value, const void* params, float* h_out, int32_t ld_h,
                                        void* workspace, size_t workspace_bytes, void* stream_,
@@ -1112,84 +1180,28 @@ static int32_t lstm_train_forward_impl(drnmf_handle_t h, const drnmf_lstm_desc_t
     if (rc) return rc;
     ++h->call_seq;
     if (!x || !params || !h_out) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: NULL pointer argument", what);
-    if (ld_h < d->H) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: ld_h %d < H %d", what, ld_h, d->H);
-    if ((uintptr_t)params & 255) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "params must be 256-byte aligned");
+    rc = lstm_check_ld_params(h, d, ld_h, params, what);
+    if (rc) return rc;
     const LstmLayout& L = W.L;
     hipStream_t stream = (hipStream_t)stream_;
     char* ws = (char*)workspace;
-    const char* pb = (const char*)params;
-    float* xz = (float*)(ws + W.off_xz);
-    unsigned char* valid = (unsigned char*)(ws + W.off_valid);
-    float* xproj = (float*)(ws + W.off_xproj);
-    float* hring = (float*)(ws + W.off_h);
-    float* cring = (float*)(ws + W.off_c);
-    int* ctr = (int*)(ws + W.off_ctr);
-    float* zst = (float*)(ws + W.off_z);
-    float* cst = (float*)(ws + W.off_cst);
-    float* hst = (float*)(ws + W.off_hst);
-
-    hipLaunchKernelGGL(lstm_pack_x_train_kernel, dim3((unsigned)((W.R1 + 3) / 4)), dim3(256), 0, stream, x, xz,
-                       valid, mask_value, W.R1, d->T, d->F, L.Fq);
-    const size_t nring = (size_t)d->K * 2 * L.Bp * L.Hc;
-    if (st)
-        hipLaunchKernelGGL(lstm_state_scatter_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream,
-                           hring, cring, (f16*)nullptr, ctr, st->initial_h, st->initial_c, nring, d->B, d->H, L.Bp,
-                           L.Hc);
-    else
-        hipLaunchKernelGGL(lstm_init_kernel, dim3((unsigned)((nring + 255) / 256)), dim3(256), 0, stream, hring,
-                           cring, (f16*)nullptr, ctr, nring);
-    hipLaunchKernelGGL(lstm_stash_init_kernel, dim3((unsigned)(L.Bp + 1), (unsigned)d->K), dim3(256), 0, stream,
-                       zst, cst, hst, L.Bp, d->T, W.zk, W.RS, L.NC, L.Hc, L.Hq);
-    if (st && (st->initial_h || st->initial_c)) {
-        const size_t ns = (size_t)d->K * d->B * d->H;
-        hipLaunchKernelGGL(lstm_stash_state_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, stream, cst,
-                           hst, st->initial_h, st->initial_c, ns, d->B, d->H, d->T, W.RS, L.Hc, L.Hq);
-    }
-    DRNMF_HIP(h, hipGetLastError());
-    {
-        gemm::Operands g;
-        g.A = xz;
-        g.Bt = (const float*)(pb + L.off_k0t);
-        g.M = (int64_t)W.R1;
-        g.N = L.NC;
-        g.K = L.Fq;
-        g.lda = g.ldb = L.Fq;
-        DRNMF_HIP(h, gemm::launch(g, EpiLstmXproj{xproj, (const float*)(pb + L.off_bias), L.NC}, stream));
-    }
-    LstmStepArgs base;
-    base.M = (const float*)pb;
-    base.bias = (const float*)(pb + L.off_bias);
-    base.xproj = xproj;
-    base.valid = valid;
-    base.hring = hring;
-    base.cring = cring;
-    base.out = h_out;
-    base.B = d->B; base.T = d->T; base.H = d->H; base.K = d->K;
-    base.Bp = L.Bp; base.Hc = L.Hc; base.numU = L.numU; base.NC = L.NC;
-    base.act = d->recurrent_activation;
-    base.ld_h = ld_h;
-    base.zst = zst; base.cst = cst; base.hst = hst; base.zk = W.zk; base.Hq = L.Hq;
-    base.h16 = nullptr;
-    const dim3 grid((unsigned)L.numU, (unsigned)(L.Bp / 16), (unsigned)d->K);
-    auto frame = [&](Launcher& chain, int) -> int32_t {      // two diagonals, as drnmf_lstm_forward
-        for (int p = 0; p < 2; ++p) {
-            LstmStepArgs a = base;
-            a.d_rd = ctr + 16 * p;
-            a.d_wr = ctr + 16 * (1 - p);
-            void* kp[1] = {&a};
-            DRNMF_HIP(h, chain.add((const void*)&lstm_step_kernel<true, false>, grid, dim3(64 * LSTM_NW), kp));
-        }
-        return DRNMF_OK;
-    };
-    const int diagonals = d->T + d->K - 1, frames = (diagonals + 1) / 2;
-    const int fpg = frames < 64 ? frames : 64;
-    const std::vector<uint64_t> key = {
-        (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->H, (uint64_t)d->K,
-        (uint64_t)d->recurrent_activation, (uint64_t)(uintptr_t)params, (uint64_t)(uintptr_t)h_out, (uint64_t)ld_h,
-        (uint64_t)(uintptr_t)workspace};
-    rc = replay_frames(h, stream, GraphKind::LstmTrain, key, {fpg, 1}, 0, frames, frame);
-    if (rc) return rc;
-    return lstm_store_state(h, d, L, hring, cring, st, stream);
+    LstmFwdViews V{};
+    V.xz = (float*)(ws + W.off_xz);
+    V.valid = (unsigned char*)(ws + W.off_valid);
+    V.xproj = (float*)(ws + W.off_xproj);
+    V.hring = (float*)(ws + W.off_h);
+    V.cring = (float*)(ws + W.off_c);
+    V.ctr = (int*)(ws + W.off_ctr);
+    V.rows = W.R1;
+    V.zst = (float*)(ws + W.off_z);
+    V.cst = (float*)(ws + W.off_cst);
+    V.hst = (float*)(ws + W.off_hst);
+    V.zk = W.zk;
+    V.RS = W.RS;
+    hipLaunchKernelGGL(lstm_pack_x_train_kernel, dim3((unsigned)((W.R1 + 3) / 4)), dim3(256), 0, stream, x, V.xz,
+                       V.valid, mask_value, W.R1, d->T, d->F, L.Fq);
+    return lstm_forward_run(h, d, L, V, params, h_out, ld_h, workspace, stream, st,
+                            (const void*)&lstm_step_kernel<true, false>, GraphKind::LstmTrain);
 }
 
 extern "C" int32_t drnmf_lstm_train_forward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* x,
@@ -1223,28 +1235,17 @@ extern "C" int32_t drnmf_lstm_loss_head_backward(drnmf_handle_t h, const drnmf_l
     if (rc) return rc;
     if (!y || !w || !hidden || !params || !w_out || !sums || !d_hidden || !d_w_out || !d_b_out)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_loss_head_backward: NULL pointer argument");
-    if (ld_h < d->H) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_loss_head_backward: ld_h %d < H %d", ld_h, d->H);
-    if ((uintptr_t)params & 255) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "params must be 256-byte aligned");
+    rc = lstm_check_ld_params(h, d, ld_h, params, "lstm_loss_head_backward");
+    if (rc) return rc;
     const LstmLayout& L = W.L;
     hipStream_t stream = (hipStream_t)stream_;
     char* ws = (char*)workspace;
-    const char* pb = (const char*)params;
     const int64_t rows = (int64_t)d->B * d->T;
     float* S = (float*)(ws + W.off_s);
     float* dpre = (float*)(ws + W.off_dpre);
     float* wop = (float*)(ws + W.off_wop);
     float* lpart = (float*)(ws + W.off_lpart);
-    {   // sigmoid head (as drnmf_lstm_head_forward)
-        gemm::Operands g;
-        g.A = hidden;
-        g.Bt = (const float*)(pb + L.off_wo);
-        g.M = rows;
-        g.N = d->F;
-        g.K = ld_h >= L.Hq ? L.Hq : d->H;
-        g.lda = ld_h;
-        g.ldb = L.Hq;
-        DRNMF_HIP(h, gemm::launch(g, EpiLstmHead{S, (const float*)(pb + L.off_bo), d->F}, stream));
-    }
+    DRNMF_HIP(h, lstm_head_product(d, L, hidden, ld_h, params, S, stream));
     const int64_t nblocks = (rows + 3) / 4;
     hipLaunchKernelGGL(lstm_loss_rows_kernel, dim3((unsigned)nblocks), dim3(256), 0, stream,
                        (const float*)(ws + W.off_xz), S, y, w, dpre, lpart, (size_t)rows, d->T, d->F, L.Fq);
@@ -1263,8 +1264,8 @@ extern "C" int32_t drnmf_lstm_loss_head_backward(drnmf_handle_t h, const drnmf_l
         g.lda = g.ldb = L.Fq;
         DRNMF_HIP(h, gemm::launch(g, EpiLstmDh{d_hidden, d->H}, stream));
     }
-    const int Mh = ld_h >= L.Hq ? L.Hq : d->H;
-    DRNMF_HIP(h, lstm_tn_product(W, ws, hidden, ld_h, Mh, dpre, L.Fq, L.Fq, rows, d_w_out, d->H, d->F, 0, stream));
+    DRNMF_HIP(h, lstm_tn_product(W, ws, hidden, ld_h, lstm_head_k(d, L, ld_h), dpre, L.Fq, L.Fq, rows, d_w_out,
+                                 d->H, d->F, 0, stream));
     DRNMF_HIP(h, lstm_colsum(W, ws, dpre, L.Fq, L.Fq, rows, d_b_out, d->F, 0, stream));
     return DRNMF_OK;
 }
@@ -1318,23 +1319,11 @@ extern "C" int32_t drnmf_lstm_backward(drnmf_handle_t h, const drnmf_lstm_desc_t
     base.Bp = L.Bp; base.Hc = L.Hc; base.NB = W.NB; base.NC = L.NC;
     base.act = d->recurrent_activation;
     const dim3 grid((unsigned)W.NB, (unsigned)(L.Bp / 16), (unsigned)d->K);
-    // two diagonals per graph frame, the counter going DOWN (lstm_bwd_step_kernel writes d - 1)
-    auto frame = [&](Launcher& chain, int) -> int32_t {
-        for (int p = 0; p < 2; ++p) {
-            LstmBwdArgs a = base;
-            a.d_rd = ctr + 16 * p;
-            a.d_wr = ctr + 16 * (1 - p);
-            void* kp[1] = {&a};
-            DRNMF_HIP(h, chain.add((const void*)&lstm_bwd_step_kernel, grid, dim3(64 * LSTM_NW), kp));
-        }
-        return DRNMF_OK;
-    };
-    const int diagonals = d->T + d->K - 1, frames = (diagonals + 1) / 2;
-    const int fpg = frames < 64 ? frames : 64;
     const std::vector<uint64_t> key = {
         (uint64_t)d->B, (uint64_t)d->T, (uint64_t)d->F, (uint64_t)d->H, (uint64_t)d->K,
         (uint64_t)d->recurrent_activation, (uint64_t)(uintptr_t)d_hidden, (uint64_t)(uintptr_t)workspace};
-    rc = replay_frames(h, stream, GraphKind::LstmBackward, key, {fpg, 1}, 0, frames, frame);
+    rc = lstm_wavefront(h, stream, GraphKind::LstmBackward, key, d->T, d->K, (const void*)&lstm_bwd_step_kernel,
+                        grid, base, ctr);
     if (rc) return rc;
 
     // time-batched weight gradients, unnormalised sums, Keras layouts

@@ -1430,8 +1430,64 @@ class _SequenceModel(object):
     def _after_step(self):
         pass
 
+    def _weights_replaced(self):
+        """sync_replicas wrote every weight in place: drop whatever was derived from them."""
+        raise NotImplementedError
+
     def _regularized_items(self):
         return []
+
+    def _init_trainer(self, items, device, loss, optimizer, lr, clipnorm, decay, beta_1, beta_2, epsilon,
+                      sample_weight_mode, loss_norm):
+        """The state of the trainer below, set up by a subclass's compile(): the shared argument checks, then
+        items() = [(name, weight tensor)] in flat-buffer order (called behind those checks: it may refuse the
+        model)."""
+        if loss != 'mse' or optimizer != 'adam' or sample_weight_mode != 'temporal':
+            raise NotImplementedError("only loss='mse', optimizer='adam', temporal sample weights "
+                                      "(the reference's training configuration)")
+        if loss_norm not in ('masked_mean', 'keras204'):
+            raise ValueError("loss_norm must be 'masked_mean' or 'keras204'")
+        self.loss_norm = loss_norm
+        self.opt = dict(lr=float(lr), clipnorm=float(clipnorm), decay=float(decay),
+                        b1=float(beta_1), b2=float(beta_2), eps=float(epsilon), iterations=0)
+        self._train_items = items()
+        total = sum(int(t.numel()) for _, t in self._train_items)
+        # the kernels write their gradients straight into views of the flat buffer (the weights in item order,
+        # then the 4-float tail [sum w*mse, count, frames, fault])
+        self._flat = torch.zeros(total + self.N_SCALARS, dtype=torch.float32, device=device)
+        # Adam moments as flat buffers parallel to the gradient (ONE fused launch per step,
+        # ops.adam_step_flat); _opt_state keeps per-weight views of them
+        self._mflat = torch.zeros(total, dtype=torch.float32, device=device)
+        self._vflat = torch.zeros(total, dtype=torch.float32, device=device)
+        self._gview, self._opt_state, o = {}, {}, 0
+        for n, t in self._train_items:
+            self._gview[n] = self._flat[o:o + t.numel()].view(t.shape)
+            self._opt_state[n] = (self._mflat[o:o + t.numel()].view(t.shape),
+                                  self._vflat[o:o + t.numel()].view(t.shape))
+            o += t.numel()
+        self._adam_table = None          # (table, n_blocks, storage pointers it was built for)
+        self._sumsq = torch.zeros(256, dtype=torch.float32, device=device)
+        self._pending = []               # DeviceLoss of recent steps, oldest first
+        self._step_no = 0
+        # applied optimiser steps, ON THE DEVICE (ping-pong pair: launch n reads [n & 1], writes [(n + 1) & 1];
+        # drnmf_adam_step_flat_counted): a step the fault word skipped is not counted, identically on every rank
+        self._step_dev = torch.zeros((2,), dtype=torch.float32, device=device)
+
+    def sync_replicas(self, root=0):
+        """Data parallelism: every weight of the model (trainable or not) is replaced by rank
+        `root`'s, in one broadcast of a flat buffer -- replicas must not depend on every rank
+        having drawn the same random initial log_h0.  No-op for a single rank."""
+        from . import dp
+        if dp.world_size() <= 1:
+            return
+        ws = self.weights
+        flat = torch.cat([w.reshape(-1) for w in ws]).contiguous()
+        dp.broadcast_(flat, root)
+        o = 0
+        for w in ws:
+            w.copy_(flat[o:o + w.numel()].view(w.shape))
+            o += w.numel()
+        self._weights_replaced()
 
     def _drop_stale_fault(self):
         """Stream-ordered read-and-clear of the handle's fault word into a scratch, at the START of a
@@ -1918,14 +1974,15 @@ class UnfoldedSNMFModel(_SequenceModel):
         does propagate (the sample weights are the mask itself, enhance.py:1148-1152).  The two
         differ by the per-batch factor 1/p on loss and gradients (Adam largely cancels it).
         Under torch.distributed rank 0's weights are broadcast so that all replicas start equal."""
-        if loss != 'mse' or optimizer != 'adam' or sample_weight_mode != 'temporal':
-            raise NotImplementedError("only loss='mse', optimizer='adam', temporal sample weights "
-                                      "(the reference's training configuration)")
-        if loss_norm not in ('masked_mean', 'keras204'):
-            raise ValueError("loss_norm must be 'masked_mean' or 'keras204'")
-        self.loss_norm = loss_norm
-        self.opt = dict(lr=float(lr), clipnorm=float(clipnorm), decay=float(decay),
-                        b1=float(beta_1), b2=float(beta_2), eps=float(epsilon), iterations=0)
+        self._init_trainer(self._choose_train_items, self.cell.device, loss, optimizer, lr, clipnorm, decay, beta_1,
+                           beta_2, epsilon, sample_weight_mode, loss_norm)
+        self._grad_targets = self._make_grad_targets()
+        self.sync_replicas()
+        return self
+
+    def _choose_train_items(self):
+        """compile(): what this cell cannot train is refused, the fused or the dense-matrix BPTT chosen
+        (cell._train_dense), and the trained weights returned in flat-buffer order."""
         cell = self.cell
         if cell.divergence != 'ed' and any(k in ('log_U1', 'log_Uk') for k in cell.keys_trainable):
             raise NotImplementedError('the KL / beta variant of the cell has no U term to train')
@@ -1949,7 +2006,7 @@ class UnfoldedSNMFModel(_SequenceModel):
         if cell.dropout_U:
             cell._train_dense = True
         if cell._train_dense:
-            self._train_items = cell.trainable_weight_items()
+            items = cell.trainable_weight_items()
         else:
             # flat-buffer order = the order of the BPTT's stacked outputs (d_log_D [n_D,F,N], d_log_h0,
             # d_log_alph, d_log_lam1), so that the kernels write their gradients straight into the flat
@@ -1958,31 +2015,9 @@ class UnfoldedSNMFModel(_SequenceModel):
             names = [w for w, gk, _ in sl if gk == 'd_log_D'] + ['log_h0'] + \
                     [w for w, gk, _ in sl if gk != 'd_log_D']
             names += [k for k in cell._alt if k not in names]
-            self._train_items = [(k, cell.log_h0 if k == 'log_h0' else cell._alt[k]) for k in names
-                                 if k == 'log_h0' or k in cell.keys_trainable]
-        self._train_items += [('kernel_clean', self.clean.kernel), ('kernel_noise', self.noise.kernel)]
-        total = sum(int(t.numel()) for _, t in self._train_items)
-        self._flat = torch.zeros(total + self.N_SCALARS, dtype=torch.float32, device=cell.device)
-        # Adam moments as flat buffers parallel to the gradient (ONE fused launch per step,
-        # ops.adam_step_flat); _opt_state keeps per-weight views of them
-        self._mflat = torch.zeros(total, dtype=torch.float32, device=cell.device)
-        self._vflat = torch.zeros(total, dtype=torch.float32, device=cell.device)
-        self._gview, self._opt_state, o = {}, {}, 0
-        for n, t in self._train_items:
-            self._gview[n] = self._flat[o:o + t.numel()].view(t.shape)
-            self._opt_state[n] = (self._mflat[o:o + t.numel()].view(t.shape),
-                                  self._vflat[o:o + t.numel()].view(t.shape))
-            o += t.numel()
-        self._grad_targets = self._make_grad_targets()
-        self._adam_table = None          # (table, n_blocks, storage pointers it was built for)
-        self._sumsq = torch.zeros(256, dtype=torch.float32, device=cell.device)
-        self._pending = []               # DeviceLoss of recent steps, oldest first
-        self._step_no = 0
-        # applied optimiser steps, ON THE DEVICE (ping-pong pair: launch n reads [n & 1], writes [(n + 1) & 1];
-        # drnmf_adam_step_flat_counted): a step the fault word skipped is not counted, identically on every rank
-        self._step_dev = torch.zeros((2,), dtype=torch.float32, device=cell.device)
-        self.sync_replicas()
-        return self
+            items = [(k, cell.log_h0 if k == 'log_h0' else cell._alt[k]) for k in names
+                     if k == 'log_h0' or k in cell.keys_trainable]
+        return items + [('kernel_clean', self.clean.kernel), ('kernel_noise', self.noise.kernel)]
 
     def _make_grad_targets(self):
         """Views of the flat gradient buffer the kernels write into: (`grads` of cell.backward -- a
@@ -2021,20 +2056,7 @@ class UnfoldedSNMFModel(_SequenceModel):
             if wname in gv and gkey not in direct:
                 gv[wname].copy_(g[gkey][idx].reshape(gv[wname].shape))
 
-    def sync_replicas(self, root=0):
-        """Data parallelism: every weight of the model (trainable or not) is replaced by rank
-        `root`'s, in one broadcast of a flat buffer -- replicas must not depend on every rank
-        having drawn the same random initial log_h0.  No-op for a single rank."""
-        from . import dp
-        if dp.world_size() <= 1:
-            return
-        ws = self.weights
-        flat = torch.cat([w.reshape(-1) for w in ws]).contiguous()
-        dp.broadcast_(flat, root)
-        o = 0
-        for w in ws:
-            w.copy_(flat[o:o + w.numel()].view(w.shape))
-            o += w.numel()
+    def _weights_replaced(self):
         for l in (self.cell, self.clean, self.noise):
             l._weights_changed()
 
@@ -2528,33 +2550,8 @@ class LSTMModel(_SequenceModel):
                                       "model, then set_weights / load_weights its weights into a float16 model")
         if self.device.type != 'cuda':
             raise NotImplementedError('LSTMModel: training runs on the GPU kernels only (device %s)' % self.device)
-        if loss != 'mse' or optimizer != 'adam' or sample_weight_mode != 'temporal':
-            raise NotImplementedError("only loss='mse', optimizer='adam', temporal sample weights "
-                                      "(the reference's training configuration)")
-        if loss_norm not in ('masked_mean', 'keras204'):
-            raise ValueError("loss_norm must be 'masked_mean' or 'keras204'")
-        self.loss_norm = loss_norm
-        self.opt = dict(lr=float(lr), clipnorm=float(clipnorm), decay=float(decay),
-                        b1=float(beta_1), b2=float(beta_2), eps=float(epsilon), iterations=0)
-        self._train_items = self.flat_layout_items()
-        total = sum(int(t.numel()) for _, t in self._train_items)
-        dev = self.device
-        # the kernels write their gradients straight into views of the flat buffer (Keras weight order, then the
-        # 4-float tail [sum w*mse, count, frames, fault])
-        self._flat = torch.zeros(total + self.N_SCALARS, dtype=torch.float32, device=dev)
-        self._mflat = torch.zeros(total, dtype=torch.float32, device=dev)
-        self._vflat = torch.zeros(total, dtype=torch.float32, device=dev)
-        self._gview, self._opt_state, o = {}, {}, 0
-        for n, t in self._train_items:
-            self._gview[n] = self._flat[o:o + t.numel()].view(t.shape)
-            self._opt_state[n] = (self._mflat[o:o + t.numel()].view(t.shape),
-                                  self._vflat[o:o + t.numel()].view(t.shape))
-            o += t.numel()
-        self._adam_table = None
-        self._sumsq = torch.zeros(256, dtype=torch.float32, device=dev)
-        self._pending = []
-        self._step_no = 0
-        self._step_dev = torch.zeros((2,), dtype=torch.float32, device=dev)
+        self._init_trainer(self.flat_layout_items, self.device, loss, optimizer, lr, clipnorm, decay, beta_1,
+                           beta_2, epsilon, sample_weight_mode, loss_norm)
         self._train_ws = None
         self._d_hidden = None
         self.sync_replicas()
@@ -2569,18 +2566,7 @@ class LSTMModel(_SequenceModel):
         items += list(zip(self.dense.weight_names, self.dense.weights))
         return items
 
-    def sync_replicas(self, root=0):
-        """Data parallelism: rank `root`'s weights everywhere (one broadcast); no-op for a single rank."""
-        from . import dp
-        if dp.world_size() <= 1:
-            return
-        ws = self.weights
-        flat = torch.cat([w.reshape(-1) for w in ws]).contiguous()
-        dp.broadcast_(flat, root)
-        o = 0
-        for w in ws:
-            w.copy_(flat[o:o + w.numel()].view(w.shape))
-            o += w.numel()
+    def _weights_replaced(self):
         self._prepared = None
 
     def loss_and_grads(self, x, y, sample_weight, live=True):

@@ -2149,13 +2149,8 @@ def _lstm_state_pair(state, desc, what, device):
     return state[0], state[1]
 
 
-def lstm_forward(x, mask_value, params, desc, out=None, workspace=None, *, initial_state=None, final_state=None):
-    """K stacked Keras LSTM layers (return_sequences=True) behind Masking(mask_value): x [B,T,F] -> the last
-    layer's outputs [B,T,H], by default a view of a [B,T,lstm_hidden_ld(H)] buffer whose padding columns the
-    kernel zeroes (`out`: any (B,T,H) tensor with strides (T*ld, ld, 1)).  mask_value None: no frame is masked.
-    initial_state / final_state: (h, c) pairs of [K,B,H] tensors, the state entering frame 0 (None: zeros) and the
-    one leaving frame T-1, written in place (None: not wanted); the same pair may be passed as both
-    (drnmf_lstm_forward_stateful).  Both None: drnmf_lstm_forward."""
+def _lstm_forward_call(entry, x, mask_value, params, desc, out, workspace, initial_state, final_state):
+    """lstm_forward and lstm_train_forward: the C entry `entry`, or `entry`_stateful when a state is given."""
     L = _capi.lib()
     h = _capi.handle(_dev_index(x))
     x = _f32c(x, "x")
@@ -2166,21 +2161,31 @@ def lstm_forward(x, mask_value, params, desc, out=None, workspace=None, *, initi
         out = torch.empty((desc.B, desc.T, ld), dtype=torch.float32, device=x.device)[..., :desc.H]
     else:
         ld = _hidden_ld(out, desc, "out")
-    if workspace is None:
-        workspace = lstm_workspace(desc, x.device)
     mv = float("nan") if mask_value is None else float(mask_value)
+    tail = (_capi.ptr(out), ld, _capi.ptr(workspace), workspace.numel(), _stream())
     if initial_state is not None or final_state is not None:
+        entry += "_stateful"
         ih, ic = _lstm_state_pair(initial_state, desc, "initial_state", x.device)
         fh, fc = _lstm_state_pair(final_state, desc, "final_state", x.device)
-        rc = L.drnmf_lstm_forward_stateful(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), _capi.ptr(ih),
-                                           _capi.ptr(ic), _capi.ptr(fh), _capi.ptr(fc), _capi.ptr(out), ld,
-                                           _capi.ptr(workspace), workspace.numel(), _stream())
-        _capi.check(rc, h, "drnmf_lstm_forward_stateful")
-        return out
-    rc = L.drnmf_lstm_forward(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), _capi.ptr(out), ld,
-                              _capi.ptr(workspace), workspace.numel(), _stream())
-    _capi.check(rc, h, "drnmf_lstm_forward")
+        rc = getattr(L, entry)(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), _capi.ptr(ih), _capi.ptr(ic),
+                               _capi.ptr(fh), _capi.ptr(fc), *tail)
+    else:
+        rc = getattr(L, entry)(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), *tail)
+    _capi.check(rc, h, entry)
     return out
+
+
+def lstm_forward(x, mask_value, params, desc, out=None, workspace=None, *, initial_state=None, final_state=None):
+    """K stacked Keras LSTM layers (return_sequences=True) behind Masking(mask_value): x [B,T,F] -> the last
+    layer's outputs [B,T,H], by default a view of a [B,T,lstm_hidden_ld(H)] buffer whose padding columns the
+    kernel zeroes (`out`: any (B,T,H) tensor with strides (T*ld, ld, 1)).  mask_value None: no frame is masked.
+    initial_state / final_state: (h, c) pairs of [K,B,H] tensors, the state entering frame 0 (None: zeros) and the
+    one leaving frame T-1, written in place (None: not wanted); the same pair may be passed as both
+    (drnmf_lstm_forward_stateful).  Both None: drnmf_lstm_forward."""
+    if workspace is None:
+        workspace = lstm_workspace(desc, x.device)
+    return _lstm_forward_call("drnmf_lstm_forward", x, mask_value, params, desc, out, workspace, initial_state,
+                              final_state)
 
 
 def lstm_head_forward(hidden, params, desc, out=None):
@@ -2211,30 +2216,8 @@ def lstm_train_forward(x, mask_value, params, desc, workspace, out=None, *, init
     lstm_loss_head_backward and lstm_backward need.  initial_state / final_state as in lstm_forward
     (drnmf_lstm_train_forward_stateful): the entering state is kept in the workspace as a constant of the gradient,
     which lstm_backward then reads there."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(x))
-    x = _f32c(x, "x")
-    if tuple(x.shape) != (desc.B, desc.T, desc.F):
-        raise ValueError("x has shape %s, descriptor says (%d,%d,%d)" % (tuple(x.shape), desc.B, desc.T, desc.F))
-    if out is None:
-        ld = lstm_hidden_ld(desc.H)
-        out = torch.empty((desc.B, desc.T, ld), dtype=torch.float32, device=x.device)[..., :desc.H]
-    else:
-        ld = _hidden_ld(out, desc, "out")
-    mv = float("nan") if mask_value is None else float(mask_value)
-    if initial_state is not None or final_state is not None:
-        ih, ic = _lstm_state_pair(initial_state, desc, "initial_state", x.device)
-        fh, fc = _lstm_state_pair(final_state, desc, "final_state", x.device)
-        rc = L.drnmf_lstm_train_forward_stateful(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params),
-                                                 _capi.ptr(ih), _capi.ptr(ic), _capi.ptr(fh), _capi.ptr(fc),
-                                                 _capi.ptr(out), ld, _capi.ptr(workspace), workspace.numel(),
-                                                 _stream())
-        _capi.check(rc, h, "drnmf_lstm_train_forward_stateful")
-        return out
-    rc = L.drnmf_lstm_train_forward(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), _capi.ptr(out), ld,
-                                    _capi.ptr(workspace), workspace.numel(), _stream())
-    _capi.check(rc, h, "drnmf_lstm_train_forward")
-    return out
+    return _lstm_forward_call("drnmf_lstm_train_forward", x, mask_value, params, desc, out, workspace, initial_state,
+                              final_state)
 
 
 def lstm_loss_head_backward(y, w, hidden, params, w_out, desc, workspace, sums, d_hidden, d_w_out, d_b_out):

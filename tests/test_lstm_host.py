@@ -273,5 +273,42 @@ def test_lstm_entry_points_validate_without_a_gpu(capi):
         assert rc == -4, rc                          # params buffer too short
         assert L.drnmf_lstm_prepare_params(None, ctypes.byref(good), fake, fake, fake, fake, fake, fake,
                                            fake, pneed, None) == -1
+        # Two faults at once: the inference and the training entries order their checks differently, and each keeps
+        # its order (codes and texts as the library gave them before its host drivers were folded).
+        dp = ctypes.byref(good)
+        tneed = L.drnmf_lstm_train_workspace_bytes(dp)
+        off = ctypes.c_void_p(0x100010)
+        # fault -> (x, params, ld_h, workspace, bytes short of the full size)
+        faults = {"NULL x, short workspace": (None, fake, 16, fake, 1),
+                  "NULL workspace, NULL x": (None, fake, 16, None, 0),
+                  "params off by 16, ld_h < H": (fake, off, 12, fake, 0),
+                  "workspace and params off by 16": (fake, off, 16, off, 0)}
+        expected = {"forward": (need, {
+                        "NULL x, short workspace": (-1, "%s: NULL pointer argument"),
+                        "NULL workspace, NULL x": (-1, "%s: NULL pointer argument"),
+                        "params off by 16, ld_h < H": (-1, "%s: ld_h 12 < H 13"),
+                        "workspace and params off by 16": (-1, "workspace/params must be 256-byte aligned")}),
+                    "train_forward": (tneed, {
+                        "NULL x, short workspace": (-4, "%%s: workspace %d < required %d" % (tneed - 1, tneed)),
+                        "NULL workspace, NULL x": (-1, "%s: NULL workspace"),
+                        "params off by 16, ld_h < H": (-1, "%s: ld_h 12 < H 13"),
+                        "workspace and params off by 16": (-1, "workspace must be 256-byte aligned")})}
+        for stem, (full, want) in expected.items():
+            for suffix, state in (("", ()), ("_stateful", (fake, None, None, fake))):
+                what = "lstm_" + stem + suffix
+                fn = getattr(L, "drnmf_" + what)
+                for name, (x, params, ld, ws, less) in faults.items():
+                    code, text = want[name]
+                    rc = fn(h, dp, x, -1.0, params, *state, fake, ld, ws, full - less, None)
+                    assert rc == code, (what, name, rc)
+                    assert L.drnmf_last_error(h).decode() == (text % what if "%s" in text else text), (what, name)
+        rc = L.drnmf_lstm_loss_head_backward(h, dp, fake, fake, fake, 12, off, fake, fake, fake, fake, fake, fake,
+                                             tneed, None)
+        assert rc == -1 and L.drnmf_last_error(h) == b"lstm_loss_head_backward: ld_h 12 < H 13"
+        rc = L.drnmf_lstm_loss_head_backward(h, dp, fake, fake, fake, 16, off, fake, fake, fake, fake, fake, off,
+                                             tneed, None)
+        assert rc == -1 and L.drnmf_last_error(h) == b"workspace must be 256-byte aligned"
+        assert L.drnmf_lstm_head_forward(h, dp, fake, 12, off, fake, None) == -1
+        assert L.drnmf_last_error(h) == b"lstm_head_forward: ld_h 12 < H 13"
     finally:
         L.drnmf_destroy(h)
