@@ -3,7 +3,8 @@ STOI score's in include/drnmf_score.h; the ragged STFT / iSTFT / int16 stages' i
 device-side SDR's in include/drnmf_sdr.h; the training-data front end's in include/drnmf_dataset.h; the streaming
 STFT / iSTFT's in include/drnmf_stream.h; the sparse-NMF baseline's inference in include/drnmf_snmf.h, on fp16
 operands in include/drnmf_snmf_f16.h, with per-row noise atoms in include/drnmf_snmf_adapt.h, their online
-form in include/drnmf_snmf_online.h, under the KL cost in include/drnmf_snmf_kl.h; ESTOI beside STOI in include/drnmf_estoi.h).
+form in include/drnmf_snmf_online.h, under the KL cost in include/drnmf_snmf_kl.h; ESTOI beside STOI in include/drnmf_estoi.h;
+the device-side mixer's in include/drnmf_mix.h).
 
 The library is the product path: there is NO fallback.  If the shared object is missing or a
 call fails, an exception is raised.
@@ -278,6 +279,15 @@ SNMF_ONLINE_SIGNATURES = {
 SNMF_ONLINE_MAX_N = 512                            # csrc/snmf_online.hip: snmf_tile.h's MAX_N
 SNMF_ONLINE_BLOCKS = tuple(range(16, 257, 16))     # csrc/snmf_online.hip MIN_BLOCK .. MAX_BLOCK
 
+# name -> (restype, argtypes); mirrors include/drnmf_mix.h one to one (a table of its own, like those above)
+MIX_SIGNATURES = {
+    "drnmf_mix_workspace_bytes": (_sz, [_i32, _i64]),
+    "drnmf_mix_energy": (_i32, [_vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "drnmf_mix_forward": (_i32, [_vp, _i32, _i64, _vp, _i32, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, _sz, _vp]),
+}
+MIX_BLOCK = 4096                                   # DRNMF_MIX_BLOCK
+
 _lib = None
 _handles = {}
 
@@ -305,7 +315,8 @@ def lib():
                                   list(STREAM_SIGNATURES.items()) + list(SNMF_SIGNATURES.items()) +
                                   list(SNMF_F16_SIGNATURES.items()) + list(TARGET_SIGNATURES.items()) +
                                   list(ESTOI_SIGNATURES.items()) + list(SNMF_ADAPT_SIGNATURES.items()) +
-                                  list(SNMF_KL_SIGNATURES.items()) + list(SNMF_ONLINE_SIGNATURES.items())):
+                                  list(SNMF_KL_SIGNATURES.items()) + list(SNMF_ONLINE_SIGNATURES.items()) +
+                                  list(MIX_SIGNATURES.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

@@ -52,7 +52,9 @@ NO_SCRATCH = {"lstm.hip": "lstm_step_kernel",
               # the target kernels keep the noisy member's bins of a frame in registers (up to 27 per lane)
               "stft.hip": "stft_pair_target_",
               # the ESTOI segment kernel holds a 30-frame row, then two 15-band columns, of fp64 per lane
-              "stoi.hip": "estoi_"}
+              "stoi.hip": "estoi_",
+              # the mixer's sample passes hold four quads and an fp64 accumulator per lane; its gain kernel calls pow
+              "mix.hip": "mix_"}
 
 
 def _check_no_scratch(src, remarks):
@@ -82,7 +84,7 @@ def _deps():
         [os.path.join(os.path.dirname(HERE), "include", n) for n in ("drnmf.h", "drnmf_lstm.h", "drnmf_score.h", "drnmf_enhance.h", "drnmf_sdr.h",
                                                                      "drnmf_dataset.h", "drnmf_stream.h", "drnmf_snmf.h", "drnmf_snmf_f16.h",
                                                                      "drnmf_target.h", "drnmf_estoi.h", "drnmf_snmf_adapt.h",
-                                                                     "drnmf_snmf_kl.h", "drnmf_snmf_online.h")] + \
+                                                                     "drnmf_snmf_kl.h", "drnmf_snmf_online.h", "drnmf_mix.h")] + \
         [os.path.abspath(__file__)]
 
 

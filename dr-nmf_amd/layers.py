@@ -1779,6 +1779,60 @@ class _SequenceModel(object):
         x, y, w = build(noisy, clean)
         return self.fit(x, y, sample_weight=w, validation_data=val, **fit_kwargs)
 
+    def fit_mixtures(self, clean, noise, snr_db=None, snr_choices=None, seed=0, N=512, hop=128, maxlen=None,
+                     transform='mag', target='mag', validation_wavs=None, shuffle_seed=None, **fit_kwargs):
+        """`fit` on mixtures made on the device, a fresh draw every epoch (multi-condition training): clean and
+        noise, lists of 1-D int16 / float32 arrays, go up once (ops.MixBank); before epoch ep's first batch the
+        training tensors are rewritten in place with bank.tensors(bank.draw(snr_db, snr_choices, seed, epoch=ep)),
+        noisy = clean + g * noise at the drawn noise, offset and SNR.  snr_db=(lo, hi): uniform in dB (default
+        ops.MIX_SNR_DB = (-6, 9)); snr_choices=[...]: one of a list; both: ValueError.  SNRs are over the whole
+        utterance (no speech-activity weighting).  validation_wavs=(noisy_v, clean_v): ready-made pairs, built once
+        as in fit_wavs and the same for every epoch -- bank.wavs(draw) of a bank of held-out recordings makes
+        one.  N, hop, maxlen, transform, target and the checks as in fit_wavs; everything else goes to fit
+        unchanged (shuffle_seed, if given, as fit's own `seed`, the one that shuffles the batches), callbacks after
+        the one that redraws.  Under torch.distributed every rank passes ITS shard of clean and draws with
+        seed + 104729 * rank."""
+        from . import data, dp
+        ops._check_target(target, transform, 'fit_mixtures')
+        for k in ('sample_weight', 'validation_data'):
+            if k in fit_kwargs:
+                raise ValueError('fit_mixtures: %s is built from the waveforms (validation_wavs=)' % k)
+        ops._check_mix_snr(snr_db, snr_choices, 'fit_mixtures')
+        mv = float(data.get_mask_value(dict(transform_x=transform, transform_y=transform)))
+        if mv != float(self.mask_value):
+            raise ValueError("fit_mixtures: transform %r pads with %g, the model masks %g"
+                             % (transform, mv, float(self.mask_value)))
+        if int(N) // 2 + 1 != self._input_width():
+            raise ValueError('fit_mixtures: N = %d gives %d bins, the model takes %d'
+                             % (N, int(N) // 2 + 1, self._input_width()))
+        ops._check_wav_side(clean, 'fit_mixtures', 'clean')
+        ops._check_wav_side(noise, 'fit_mixtures', 'noise')
+        val = None
+        if validation_wavs is not None:
+            noisy_v, clean_v = validation_wavs
+            val = ops.wavs_to_tensors(noisy_v, clean_v, N=N, hop=hop, maxlen=maxlen, transform=transform,
+                                      mask_value=mv, device=self._device(), target=target)
+        bank = ops.MixBank(clean, noise, device=self._device())
+        seed_eff = int(seed) + 104729 * dp.rank()
+        kw = dict(N=N, hop=hop, maxlen=maxlen, transform=transform, mask_value=mv, target=target)
+        draw = lambda ep: bank.draw(snr_db=snr_db, snr_choices=snr_choices, seed=seed_eff, epoch=ep)
+        tensors = bank.tensors(draw(0), **kw)
+
+        class Redraw(object):
+            """Rewrites the training tensors on the current stream before the epoch's first batch is taken."""
+            drawn = 0
+
+            def on_epoch_begin(self, ep, logs=None):
+                if ep != self.drawn:
+                    bank.tensors(draw(ep), out=tensors, **kw)
+                    self.drawn = ep
+
+        callbacks = [Redraw()] + list(fit_kwargs.pop('callbacks', None) or [])
+        if shuffle_seed is not None:
+            fit_kwargs['seed'] = shuffle_seed
+        x, y, w = tensors
+        return self.fit(x, y, sample_weight=w, validation_data=val, callbacks=callbacks, **fit_kwargs)
+
     def _validate(self, validation_data, batch_size, take):
         """Validation loss of fit(), evaluated in mini-batches of `batch_size` sequences as Keras'
         test loop does (enhance.py:1152-1157: model.fit(..., validation_data=...)); the reference's
@@ -3011,6 +3065,31 @@ class SparseNMFModel(_SequenceModel):
         p = float(params_snmf.get('spectrogram_power', 1.0))
         with torch.cuda.device(dev):
             xf, yf = ops.wavs_to_frames(noisy, clean, N, hop)
+            x_frames = (xf ** p).t().cpu().numpy()
+            y_frames = (yf ** p).t().cpu().numpy()
+        W, _, _ = snmf.train_snmf(y_frames, x_frames, params_snmf, save_H=False, device=dev)
+        return build_snmf(params_snmf, W, device=dev)
+
+    def fit_mixtures(self, *args, **kwargs):
+        raise NotImplementedError('SparseNMFModel: nothing to fit -- the dictionary is trained by '
+                                  'SparseNMFModel.from_mixtures (snmf.train_snmf)')
+
+    @classmethod
+    def from_mixtures(cls, clean, noise, params_snmf, snr_db=None, snr_choices=None, seed=0, N=512, hop=128,
+                      device=None):
+        """from_wavs on ONE draw of mixtures made on the device (ops.MixBank: clean + g * noise at SNRs uniform in
+        snr_db=(lo, hi), default ops.MIX_SNR_DB, or taken from snr_choices): the packed frames of
+        bank.frames(bank.draw(snr_db, snr_choices, seed)), then the training of from_wavs."""
+        from . import snmf
+        ops._check_mix_snr(snr_db, snr_choices, 'from_mixtures')
+        ops._check_wav_side(clean, 'from_mixtures', 'clean')
+        ops._check_wav_side(noise, 'from_mixtures', 'noise')
+        dev = torch.device(device if device is not None else 'cuda')
+        dev = torch.device('cuda', ops._dev_of(dev))
+        p = float(params_snmf.get('spectrogram_power', 1.0))
+        with torch.cuda.device(dev):
+            bank = ops.MixBank(clean, noise, device=dev)
+            xf, yf = bank.frames(bank.draw(snr_db=snr_db, snr_choices=snr_choices, seed=seed), N, hop)
             x_frames = (xf ** p).t().cpu().numpy()
             y_frames = (yf ** p).t().cpu().numpy()
         W, _, _ = snmf.train_snmf(y_frames, x_frames, params_snmf, save_H=False, device=dev)

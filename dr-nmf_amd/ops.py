@@ -1627,6 +1627,290 @@ def wavs_to_frames(noisy, clean, N, hop, transform='mag'):
     return xf, yf
 
 
+# ---- mixtures of a speech bank and a noise bank on the device (include/drnmf_mix.h) -------------------------
+def _mix_pcm(t, name):
+    if t.dim() != 2 or t.dtype not in (torch.int16, torch.float32) or not t.is_contiguous() or t.shape[0] < 1 \
+            or t.shape[1] < 1:
+        raise ValueError("%s must be a contiguous 2-D int16 or float32 tensor [n][stride] (got %s %s)"
+                         % (name, t.dtype, tuple(t.shape)))
+    return t
+
+
+def _mix_table(t, n, dtype, name):
+    if t.dtype != dtype or t.dim() != 1 or t.shape[0] != n or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous %s tensor [%d] (got %s %s)" % (name, dtype, n, t.dtype,
+                                                                                 tuple(t.shape)))
+    return t
+
+
+def mix_workspace(n_sig, stride, device, have=None):
+    """The workspace of mix_energy / mix_forward for n_sig signals of `stride` samples (`have`: kept if it is
+    large enough)."""
+    need = int(_capi.lib().drnmf_mix_workspace_bytes(int(n_sig), int(stride)))
+    if have is not None and have.numel() >= need and have.dtype == torch.uint8:
+        return have
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def mix_energy(pcm, lengths, out=None, workspace=None):
+    """drnmf_mix_energy: the fp64 sum of squares of every row of pcm [n][stride] (int16, scaled by 1/32768, or
+    float32) over its own length (int64 [n] on the device), in the fixed order of include/drnmf_mix.h.  Enqueues
+    only."""
+    _mix_pcm(pcm, "pcm")
+    n, stride = pcm.shape
+    _mix_table(lengths, n, torch.int64, "lengths")
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(pcm))
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=pcm.device)
+    _mix_table(out, n, torch.float64, "out")
+    ws = mix_workspace(n, stride, pcm.device, workspace)
+    rc = L.drnmf_mix_energy(h, n, stride, _capi.ptr(lengths), int(pcm.dtype == torch.int16), _capi.ptr(pcm),
+                            _capi.ptr(out), _capi.ptr(ws), ws.numel(), _stream())
+    _capi.check(rc, h, "drnmf_mix_energy")
+    return out
+
+
+def mix_forward(speech, len_s, noise, len_n, noise_index, offset, snr_db, speech_energy=None, out=None,
+                workspace=None, return_gain=False):
+    """drnmf_mix_forward: noisy[i] = speech[i] + g_i * (noise[noise_index[i]] read from offset[i], wrapped), with
+    g_i the gain that realises snr_db[i] over the whole signal (no speech-activity weighting); see
+    include/drnmf_mix.h for the definition, the degenerate rows (g = 0) and the order of the sums.  speech
+    [n][stride_s] and noise [m][stride_n] int16 or float32 (independently), len_s / len_n int64, noise_index int32,
+    offset int64, snr_db float32, all on the device.  speech_energy: mix_energy(speech, len_s) if the caller keeps
+    it.  Returns noisy float32 [n][stride_s] (`out` if given), and the gains [n] with return_gain.  Enqueues
+    only."""
+    _mix_pcm(speech, "speech")
+    _mix_pcm(noise, "noise")
+    n, stride_s = speech.shape
+    m, stride_n = noise.shape
+    _mix_table(len_s, n, torch.int64, "len_s")
+    _mix_table(len_n, m, torch.int64, "len_n")
+    _mix_table(noise_index, n, torch.int32, "noise_index")
+    _mix_table(offset, n, torch.int64, "offset")
+    _mix_table(snr_db, n, torch.float32, "snr_db")
+    if speech_energy is not None:
+        _mix_table(speech_energy, n, torch.float64, "speech_energy")
+    dev = speech.device
+    if out is None:
+        out = torch.empty((n, stride_s), dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or tuple(out.shape) != (n, stride_s) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor %s" % ((n, stride_s),))
+    for t in (len_s, noise, len_n, noise_index, offset, snr_db, speech_energy, out):
+        if t is not None and t.device != dev:
+            raise ValueError("mix_forward: every tensor must be on %s" % dev)
+    gain = torch.empty(n, dtype=torch.float32, device=dev) if return_gain else None
+    L = _capi.lib()
+    h = _capi.handle(_dev_index(speech))
+    ws = mix_workspace(n, stride_s, dev, workspace)
+    rc = L.drnmf_mix_forward(h, n, stride_s, _capi.ptr(len_s), int(speech.dtype == torch.int16), _capi.ptr(speech),
+                             m, stride_n, _capi.ptr(len_n), int(noise.dtype == torch.int16), _capi.ptr(noise),
+                             _capi.ptr(noise_index), _capi.ptr(offset), _capi.ptr(snr_db),
+                             _capi.ptr(speech_energy), _capi.ptr(out), _capi.ptr(gain), _capi.ptr(ws), ws.numel(),
+                             _stream())
+    _capi.check(rc, h, "drnmf_mix_forward")
+    return (out, gain) if return_gain else out
+
+
+MIX_SNR_DB = (-6.0, 9.0)      # the SNR range of a draw that names neither snr_db nor snr_choices (CHiME2's)
+
+
+def _check_mix_snr(snr_db, snr_choices, what):
+    """(lo, hi, None) or (None, None, choices float32) of a draw, before anything else happens."""
+    if snr_db is not None and snr_choices is not None:
+        raise ValueError("%s: give snr_db=(lo, hi) or snr_choices=[...], not both" % what)
+    if snr_choices is not None:
+        c = np.asarray(snr_choices, dtype=np.float32)
+        if c.ndim != 1 or c.size < 1 or not np.isfinite(c).all():
+            raise ValueError("%s: snr_choices must be a non-empty list of finite values" % what)
+        return None, None, c
+    lo, hi = MIX_SNR_DB if snr_db is None else snr_db
+    lo, hi = float(lo), float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi)) or lo > hi:
+        raise ValueError("%s: snr_db = (%r, %r) must be finite with lo <= hi" % (what, lo, hi))
+    return lo, hi, None
+
+
+def mix_draw(n, len_noise, snr_db=None, snr_choices=None, seed=0, epoch=0):
+    """One epoch's mixing tables for n signals over noise recordings of len_noise samples, on the host and a pure
+    function of its arguments: (noise_index int32 [n], offset int64 [n], snr float32 [n]).  With
+    rs = np.random.RandomState((seed * 1000003 + epoch) % 2**32): noise_index = rs.randint(0, n_noise, n); offset
+    = min(floor(rs.random_sample(n) * len_noise[noise_index]), len - 1); snr = lo + (hi - lo) * rs.random_sample(n)
+    for snr_db=(lo, hi) (default MIX_SNR_DB) or choices[rs.randint(0, len(choices), n)] for snr_choices.  Giving
+    both raises ValueError."""
+    lo, hi, choices = _check_mix_snr(snr_db, snr_choices, "mix_draw")
+    len_noise = np.asarray(len_noise, dtype=np.int64)
+    if int(n) < 1 or len_noise.ndim != 1 or len_noise.size < 1 or (len_noise < 1).any():
+        raise ValueError("mix_draw: n = %r signals and %d noise lengths, every one positive, are needed"
+                         % (n, len_noise.size))
+    n = int(n)
+    rs = np.random.RandomState((int(seed) * 1000003 + int(epoch)) % 2 ** 32)
+    idx = rs.randint(0, len_noise.size, n).astype(np.int32)
+    ln = len_noise[idx]
+    off = np.minimum(np.floor(rs.random_sample(n) * ln).astype(np.int64), ln - 1)
+    if choices is None:
+        snr = (lo + (hi - lo) * rs.random_sample(n)).astype(np.float32)
+    else:
+        snr = choices[rs.randint(0, choices.size, n)]
+    return idx, off, snr
+
+
+def _check_wav_side(rows, what, side):
+    """Host-side checks of one side of a bank: a non-empty list of non-empty 1-D arrays of ONE type, int16 or
+    float32.  Returns (rows, numpy dtype)."""
+    rows = [np.asarray(v) for v in rows]
+    if not rows:
+        raise ValueError("%s: no %s waveforms" % (what, side))
+    dt = rows[0].dtype
+    if dt not in (np.dtype('int16'), np.dtype('float32')):
+        raise ValueError("%s: %s waveforms must be int16 or float32 (got %s)" % (what, side, dt))
+    for v in rows:
+        if v.ndim != 1 or v.dtype != dt or v.shape[0] < 1:
+            raise ValueError("%s: every %s waveform must be a non-empty 1-D %s array" % (what, side, dt))
+    return rows, dt
+
+
+class MixBank(object):
+    """Clean speech and noise recordings, uploaded once, from which every epoch's noisy training data is mixed on
+    the device: noisy = speech + g * noise at a drawn SNR (mix_forward), then the pair kernels of
+    wavs_to_tensors on (noisy, clean).  A new draw costs three small index tables and two passes over samples
+    already in device memory; the clean side decides the frame counts, so the shapes of (x, y, w) are the same
+    for every draw and a draw can be rewritten into the same tensors (out=).
+
+    clean, noise: lists of 1-D int16 or float32 arrays, one type per side (the sides may differ).  The clean
+    side is kept as float32 (int16 converted once, v / 32768: the pair kernels take both members of a pair in one
+    type), the noise side in the type it came in.  SNRs are over the whole utterance (no speech-activity
+    weighting); mixtures are not clipped and may exceed +-1."""
+
+    def __init__(self, clean, noise, device=None):
+        ry, dty = _check_wav_side(clean, "MixBank", "clean")
+        rn, dtn = _check_wav_side(noise, "MixBank", "noise")
+        if dty == np.dtype('int16'):
+            ry = [v.astype(np.float32) / np.float32(32768.0) for v in ry]
+        self.n, self.n_noise = len(ry), len(rn)
+        self.len_clean = np.array([v.shape[0] for v in ry], dtype=np.int64)
+        self.len_noise = np.array([v.shape[0] for v in rn], dtype=np.int64)
+        dev = torch.device('cuda' if device is None else device)
+        self.device = torch.device('cuda', _dev_of(dev))
+        with torch.cuda.device(self.device):
+            self.clean, self.len_clean_dev = _upload_wav_side(ry, np.dtype('float32'), self.device)
+            self.noise, self.len_noise_dev = _upload_wav_side(rn, dtn, self.device)
+            self.workspace = mix_workspace(self.n, self.clean.shape[1], self.device)
+            self.energy = mix_energy(self.clean, self.len_clean_dev, workspace=self.workspace)
+            self.noisy = torch.empty(tuple(self.clean.shape), dtype=torch.float32, device=self.device)
+        self._tables = {}
+
+    def draw(self, snr_db=None, snr_choices=None, seed=0, epoch=0):
+        """mix_draw for this bank: (noise_index, offset, snr) on the host, a pure function of the arguments."""
+        return mix_draw(self.n, self.len_noise, snr_db=snr_db, snr_choices=snr_choices, seed=seed, epoch=epoch)
+
+    def _check_draw(self, draw):
+        try:
+            idx, off, snr = draw
+        except (TypeError, ValueError):
+            raise ValueError("MixBank: a draw is (noise_index, offset, snr)")
+        idx, off, snr = np.asarray(idx), np.asarray(off), np.asarray(snr)
+        for a, dt, name in ((idx, np.int32, "noise_index"), (off, np.int64, "offset"), (snr, np.float32, "snr")):
+            if a.dtype != np.dtype(dt) or a.shape != (self.n,):
+                raise ValueError("MixBank: %s must be %s [%d] (got %s %s)" % (name, np.dtype(dt), self.n, a.dtype,
+                                                                              a.shape))
+        if idx.min() < 0 or idx.max() >= self.n_noise:
+            raise ValueError("MixBank: noise_index outside [0, %d)" % self.n_noise)
+        return idx, off, snr
+
+    def mix(self, draw):
+        """(noisy float32 [n][stride], lengths int64 [n]) on the device.  noisy is the bank's own buffer: the next
+        mix overwrites it."""
+        idx, off, snr = self._check_draw(draw)
+        with torch.cuda.device(self.device):
+            # one pinned upload: offset [n] int64 | noise_index [n] int32 | snr [n] float32
+            n = self.n
+            host = torch.empty(16 * n, dtype=torch.uint8, pin_memory=True)
+            hn = host.numpy()
+            hn[:8 * n].view(np.int64)[:] = off
+            hn[8 * n:12 * n].view(np.int32)[:] = idx
+            hn[12 * n:].view(np.float32)[:] = snr
+            d = host.to(self.device, non_blocking=True)
+            mix_forward(self.clean, self.len_clean_dev, self.noise, self.len_noise_dev, d[8 * n:12 * n].view(torch.int32),
+                        d[:8 * n].view(torch.int64), d[12 * n:].view(torch.float32), speech_energy=self.energy,
+                        out=self.noisy, workspace=self.workspace)
+        return self.noisy, self.len_clean_dev
+
+    def _frame_counts(self, N, hop, transform, what):
+        N, hop = int(N), int(hop)
+        if transform not in _capi.TRANSFORMS:
+            raise ValueError("%s: transform must be 'mag' or 'logmag' (got %r)" % (what, transform))
+        if N < 64 or N > 4096 or N & (N - 1) or hop < 1:
+            raise ValueError("%s: N = %d must be a power of two in [64, 4096] and hop = %d positive" % (what, N, hop))
+        return -(-self.len_clean // hop) + N // hop + 1               # drnmf_stft_frames
+
+    def _table(self, kind, N, hop, maxlen, build):
+        key = (kind, int(N), int(hop), maxlen)
+        if key not in self._tables:
+            self._tables[key] = build()
+        return self._tables[key]
+
+    def tensors(self, draw, N=512, hop=128, maxlen=None, transform='mag', mask_value=None, target='mag', out=None):
+        """(x, y, w) of one draw, exactly what wavs_to_tensors(self.wavs(draw), clean as float32, ...) returns, by
+        the same launches on (noisy, clean) without the download and the two uploads.  The sequence table is
+        uploaded once per (N, hop, maxlen).  out=(x, y, w): tensors of an earlier call with the same arguments,
+        rewritten in place and returned.  Enqueues only."""
+        from . import data
+        _check_target(target, transform, "MixBank.tensors")
+        nf = self._frame_counts(N, hop, transform, "MixBank.tensors")
+        self._check_draw(draw)
+
+        def build():
+            table, T = data.sequence_table_from_lengths(nf, maxlen)
+            return _upload_pinned(table, self.device), T
+        with torch.cuda.device(self.device):
+            table_d, T = self._table('seq', N, hop, maxlen, build)
+            if mask_value is None:
+                mask_value = data.get_mask_value(dict(transform_x=transform, transform_y=transform))
+            n_seq, F = table_d.shape[0], int(N) // 2 + 1
+            if out is None:
+                x = torch.empty((n_seq, T, F), dtype=torch.float32, device=self.device)
+                out = (x, torch.empty_like(x), torch.empty((n_seq, T), dtype=torch.float32, device=self.device))
+            x, y, w = out
+            for t, shape in ((x, (n_seq, T, F)), (y, (n_seq, T, F)), (w, (n_seq, T))):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape or \
+                        not t.is_contiguous() or t.device != self.device:
+                    raise ValueError("MixBank.tensors: out must be contiguous float32 tensors %s, %s, %s on %s"
+                                     % ((n_seq, T, F), (n_seq, T, F), (n_seq, T), self.device))
+            noisy, ln = self.mix(draw)
+            if target == 'mag':
+                stft_pair_chunks_enqueue(noisy, self.clean, ln, ln, table_d, T, N, hop, transform, mask_value, x, y, w)
+            else:
+                stft_pair_target_enqueue(noisy, self.clean, ln, ln, table_d, T, N, hop, transform, target,
+                                         mask_value, x, y, w)
+        return x, y, w
+
+    def frames(self, draw, N, hop, transform='mag'):
+        """(x_frames, y_frames) of one draw: the packed rows wavs_to_frames gives for (self.wavs(draw), clean)."""
+        nf = self._frame_counts(N, hop, transform, "MixBank.frames")
+        self._check_draw(draw)
+        with torch.cuda.device(self.device):
+            row0 = self._table('row0', N, hop, None, lambda: _upload_pinned(np.cumsum(nf) - nf, self.device))
+            xf = torch.empty((int(nf.sum()), int(N) // 2 + 1), dtype=torch.float32, device=self.device)
+            yf = torch.empty_like(xf)
+            noisy, ln = self.mix(draw)
+            stft_pair_frames_enqueue(noisy, self.clean, ln, ln, row0, N, hop, transform, xf, yf)
+        return xf, yf
+
+    def _download(self, pcm):
+        host = pcm.cpu().numpy()
+        return [host[i, :int(k)].copy() for i, k in enumerate(self.len_clean)]
+
+    def wavs(self, draw):
+        """The mixtures of one draw as a list of float32 numpy arrays: the one call that downloads (a fixed
+        validation set, listening)."""
+        return self._download(self.mix(draw)[0])
+
+    def clean_wavs(self):
+        """The clean side as the bank holds it: a list of float32 numpy arrays (downloads)."""
+        return self._download(self.clean)
+
+
 def istft_ragged_enqueue(re, im, mask, lengths_dev, sig_index_dev, N, hop, y, crop, workspace=None):
     """drnmf_istft_ragged on tensors the caller owns and has checked: enqueues, reads nothing back."""
     L = _capi.lib()
