@@ -381,7 +381,56 @@ stft_real_kernel(const void* __restrict__ pcm, int is_int16, int64_t nsampl, int
                           ((size_t)sig * nf + frame) * (N / 2 + 1), mag, re, im, tw, bufs[wv], j);
 }
 
-static bool stft_fast(int N) { return N == 512 || N == 1024; }
+// ---------------------------------------------------------------------------------------------
+// The host half.  Every entry that launches an FFT kernel takes its size from three shared pieces:
+// check_fft_size (one predicate, one message), fft_call (log2 N, the generic kernels' dynamic LDS, the tables
+// on the caller's stream) and with_fft_size (which kernel of a family runs a size).  What an entry keeps for
+// itself is the ORDER of its checks and the CODE of its size check -- callers see which error wins when two
+// apply, and tests/test_stft_args_host.py pins it:
+//   drnmf_stft_mag                  shape, N (UNSUPPORTED), NULL
+//   drnmf_stft                      "bad argument" (shape or NULL), N (UNSUPPORTED); is_int16 is not checked
+//   drnmf_istft_masked              "bad argument", N (UNSUPPORTED), workspace
+//   drnmf_stft_ragged               shape, N, NULL
+//   drnmf_istft_ragged              shape, N, NULL, ld_mask, workspace
+//   drnmf_stft_pair_chunks          n_seq / T, then check_stft_pair (shape, N, transform, frame overflow), NULL
+//   drnmf_stft_pair_chunks_target   target, the chunks' checks, target needs TRANSFORM_MAG, unbound handle (the
+//                                   only entry that tests h->device)
+//   drnmf_stft_pair_frames          total_frames, check_stft_pair, NULL
+//   drnmf_stream_reset              check_stream (B, N, hop, NULL state, state bytes)
+//   drnmf_stream_forward            shape, NULL, check_stream
+//   drnmf_stream_inverse            shape, NULL, check_stream, ld_mask
+// N is INVALID_ARG where no code is named.  drnmf_stream_state_bytes answers 0 from the same predicate.
+static_assert(TAB_LOG_MIN == 6 && TAB_LOG_MAX == 12, "check_fft_size's message says [64,4096]");
+
+static bool fft_size_ok(int N) { return N >= (1 << TAB_LOG_MIN) && N <= TAB_N_MAX && (N & (N - 1)) == 0; }
+
+static int32_t check_fft_size(drnmf_handle_t h, const char* who, int N, int32_t code) {
+    if (!fft_size_ok(N)) DRNMF_FAIL(h, code, "%s: N=%d must be a power of two in [64,4096]", who, N);
+    return DRNMF_OK;
+}
+
+// Which kernel of a family runs size N: f(FftSize<8, 3>) for N = 1024 and f(FftSize<4, 4>) for N = 512, the
+// RealFft<R, P> kernels (one wave per frame, static LDS); f(AnySize) for every other size, the radix-2 kernels (one
+// workgroup per frame, FftCall::lds of dynamic LDS).  A third fast size is a line here.
+template <int R_, int P_>
+struct FftSize {
+    static constexpr int R = R_, P = P_;
+    static constexpr bool fast = R_ != 0;
+};
+using AnySize = FftSize<0, 0>;
+
+template <class Fn>
+static void with_fft_size(int N, Fn&& f) {
+    if (N == RealFft<8, 3>::N) f(FftSize<8, 3>{});
+    else if (N == RealFft<4, 4>::N) f(FftSize<4, 4>{});
+    else f(AnySize{});
+}
+
+static bool stft_fast(int N) {
+    bool fast = false;
+    with_fft_size(N, [&](auto s) { fast = decltype(s)::fast; });
+    return fast;
+}
 
 // The window / twiddle tables of a size are filled once per handle (= per device); later calls on
 // any stream only wait for the event recorded behind that fill.
@@ -399,15 +448,21 @@ static int32_t ensure_fft_tables(drnmf_handle_t h, int N, int logN, hipStream_t 
     }
     return DRNMF_OK;
 }
-static void launch_stft_real(int N, int logN, const void* pcm, int is_int16, int64_t nsampl, int hop,
-                             int nf, int n_sig, float* mag, float* re, float* im, hipStream_t st) {
-    const dim3 grid((unsigned)((nf + 3) / 4), (unsigned)n_sig);
-    if (N == 1024)
-        hipLaunchKernelGGL((stft_real_kernel<8, 3>), grid, dim3(256), 0, st, pcm, is_int16, nsampl,
-                           logN, hop, nf, mag, re, im);
-    else
-        hipLaunchKernelGGL((stft_real_kernel<4, 4>), grid, dim3(256), 0, st, pcm, is_int16, nsampl,
-                           logN, hop, nf, mag, re, im);
+
+// What every launch of an FFT kernel needs of a checked size; filled by fft_call and by nothing else.
+struct FftCall {
+    int N, logN;
+    size_t lds;                   // dynamic LDS of the AnySize kernels: N points and N/2 twiddles
+    hipStream_t stream;
+};
+
+static int32_t fft_call(drnmf_handle_t h, int N, void* stream_, FftCall* c) {
+    c->N = N;
+    c->logN = 0;
+    while ((1 << c->logN) < N) ++c->logN;
+    c->lds = (size_t)(N + N / 2) * sizeof(float2);
+    c->stream = (hipStream_t)stream_;
+    return ensure_fft_tables(h, N, c->logN, c->stream);
 }
 
 // one workgroup per (signal, frame): masked spectrum -> Hermitian extension -> inverse FFT -> real
@@ -495,6 +550,13 @@ snr_kernel(const float* __restrict__ est, const float* __restrict__ ref, int64_t
     if (threadIdx.x == 0) out_db[sig] = (float)(10.0 * log10(s0[0] / s1[0]));
 }
 
+// Frames of a signal of len samples: stft_mc pads it to a multiple of hop (util.py:183) and puts N zeros on both
+// sides, and librosa frames that with center=False.  drnmf_stft_frames and drnmf_stream_counts on the host,
+// ragged_row on the device; pair_row and stream_push keep the rule written out (see there).
+__host__ __device__ inline int64_t stft_frame_count(int64_t len, int N, int hop) {
+    const int64_t nfram = (len + hop - 1) / hop;
+    return 1 + (nfram * hop + (int64_t)N) / hop;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Ragged batches (include/drnmf_enhance.h): the signals of a slab have their own lengths, read on the device;
@@ -519,8 +581,7 @@ __device__ __forceinline__ RaggedRow ragged_row(const int64_t* __restrict__ leng
     int64_t len = lengths[r.sig];
     len = len < 0 ? 0 : (len > cap ? cap : len);
     r.len = len;
-    const int64_t nfram = (len + hop - 1) / hop;                 // as drnmf_stft_frames
-    r.nf = 1 + (nfram * hop + (int64_t)N) / hop;
+    r.nf = stft_frame_count(len, N, hop);
     return r;
 }
 
@@ -787,6 +848,7 @@ __device__ __forceinline__ PairRow pair_row(const PairArgs& a, int k, int N) {
     int64_t ly = a.len_y[r.sig], lx = a.len_x[r.sig];
     r.len_y = ly < 0 ? 0 : (ly > a.stride_y ? a.stride_y : ly);
     r.len_x = lx < 0 ? 0 : (lx > a.stride_x ? a.stride_x : lx);
+    // written out, not stft_frame_count: through the call the PACKED kernels come out with other instructions
     const int64_t nfram = (r.len_y + a.hop - 1) / a.hop;          // as drnmf_stft_frames
     r.nf = 1 + (nfram * a.hop + (int64_t)N) / a.hop;
     if (PACKED) {
@@ -926,8 +988,26 @@ __global__ void __launch_bounds__(256) stft_pair_target_kernel(const PairArgs a,
 
 extern "C" int32_t drnmf_stft_frames(int64_t nsampl, int32_t N, int32_t hop) {
     if (nsampl < 0 || N <= 0 || hop <= 0) return -1;
-    const int64_t nfram = (nsampl + hop - 1) / hop;               // util.py:183
-    return (int32_t)(1 + (nfram * hop + 2 * (int64_t)N - N) / hop);   // librosa framing
+    return (int32_t)stft_frame_count(nsampl, N, hop);
+}
+
+// drnmf_stft_mag (re = im = NULL) and drnmf_stft (mag may be NULL) behind their own checks
+static int32_t enqueue_stft(drnmf_handle_t h, int32_t n_sig, int64_t nsampl, int32_t N, int32_t hop,
+                            int32_t is_int16, const void* pcm, float* mag, float* re, float* im, void* stream_) {
+    FftCall c;
+    if (const int32_t rc = fft_call(h, N, stream_, &c)) return rc;
+    const int nf = drnmf_stft_frames(nsampl, N, hop);
+    with_fft_size(N, [&](auto s) {
+        using S = decltype(s);
+        if constexpr (S::fast)
+            hipLaunchKernelGGL((stft_real_kernel<S::R, S::P>), dim3((unsigned)((nf + 3) / 4), (unsigned)n_sig),
+                               dim3(256), 0, c.stream, pcm, is_int16, nsampl, c.logN, hop, nf, mag, re, im);
+        else
+            hipLaunchKernelGGL(stft_kernel, dim3((unsigned)nf, (unsigned)n_sig), dim3(256), c.lds, c.stream, pcm,
+                               is_int16, nsampl, N, c.logN, hop, nf, mag, re, im);
+    });
+    DRNMF_HIP(h, hipGetLastError());
+    return DRNMF_OK;
 }
 
 extern "C" int32_t drnmf_stft_mag(drnmf_handle_t h, int32_t n_sig, int64_t nsampl, int32_t N,
@@ -938,33 +1018,9 @@ extern "C" int32_t drnmf_stft_mag(drnmf_handle_t h, int32_t n_sig, int64_t nsamp
     if (n_sig <= 0 || nsampl <= 0 || hop <= 0)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stft_mag: bad shape n_sig=%d nsampl=%lld hop=%d",
                    n_sig, (long long)nsampl, hop);
-    if (N < 64 || N > 4096 || (N & (N - 1)))
-        DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED, "stft_mag: N=%d must be a power of two in [64,4096]",
-                   N);
+    if (const int32_t rc = check_fft_size(h, "stft_mag", N, DRNMF_ERR_UNSUPPORTED)) return rc;
     if (!pcm || !mag) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stft_mag: NULL pointer argument");
-    int logN = 0;
-    while ((1 << logN) < N) ++logN;
-    const int nf = drnmf_stft_frames(nsampl, N, hop);
-    const size_t shmem = (size_t)(N + N / 2) * sizeof(float2);
-    {
-        const int32_t trc = ensure_fft_tables(h, N, logN, (hipStream_t)stream_);
-        if (trc) return trc;
-    }
-    if (stft_fast(N))
-        launch_stft_real(N, logN, pcm, is_int16, nsampl, hop, nf, n_sig, mag, nullptr, nullptr,
-                         (hipStream_t)stream_);
-    else
-        hipLaunchKernelGGL(stft_kernel, dim3((unsigned)nf, (unsigned)n_sig), dim3(256), shmem,
-                           (hipStream_t)stream_, pcm, is_int16, nsampl, N, logN, hop, nf, mag,
-                           (float*)nullptr, (float*)nullptr);
-    DRNMF_HIP(h, hipGetLastError());
-    return DRNMF_OK;
-}
-
-static int check_fft_size(drnmf_handle_t h, int N, const char* who) {
-    if (N < 64 || N > 4096 || (N & (N - 1)))
-        DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED, "%s: N=%d must be a power of two in [64,4096]", who, N);
-    return DRNMF_OK;
+    return enqueue_stft(h, n_sig, nsampl, N, hop, is_int16, pcm, mag, nullptr, nullptr, stream_);
 }
 
 extern "C" int32_t drnmf_stft(drnmf_handle_t h, int32_t n_sig, int64_t nsampl, int32_t N,
@@ -974,25 +1030,8 @@ extern "C" int32_t drnmf_stft(drnmf_handle_t h, int32_t n_sig, int64_t nsampl, i
     if (!h) return DRNMF_ERR_INVALID_ARG;
     if (n_sig <= 0 || nsampl <= 0 || hop <= 0 || !pcm || !re || !im)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stft: bad argument");
-    int rc = check_fft_size(h, N, "stft");
-    if (rc) return rc;
-    int logN = 0;
-    while ((1 << logN) < N) ++logN;
-    const int nf = drnmf_stft_frames(nsampl, N, hop);
-    const size_t shmem = (size_t)(N + N / 2) * sizeof(float2);
-    {
-        const int32_t trc = ensure_fft_tables(h, N, logN, (hipStream_t)stream_);
-        if (trc) return trc;
-    }
-    if (stft_fast(N))
-        launch_stft_real(N, logN, pcm, is_int16, nsampl, hop, nf, n_sig, mag, re, im,
-                         (hipStream_t)stream_);
-    else
-        hipLaunchKernelGGL(stft_kernel, dim3((unsigned)nf, (unsigned)n_sig), dim3(256), shmem,
-                           (hipStream_t)stream_, pcm, is_int16, nsampl, N, logN, hop, nf, mag, re,
-                           im);
-    DRNMF_HIP(h, hipGetLastError());
-    return DRNMF_OK;
+    if (const int32_t rc = check_fft_size(h, "stft", N, DRNMF_ERR_UNSUPPORTED)) return rc;
+    return enqueue_stft(h, n_sig, nsampl, N, hop, is_int16, pcm, mag, re, im, stream_);
 }
 
 extern "C" size_t drnmf_istft_workspace_bytes(int32_t n_sig, int32_t n_frames, int32_t N) {
@@ -1008,23 +1047,17 @@ extern "C" int32_t drnmf_istft_masked(drnmf_handle_t h, int32_t n_sig, int32_t n
     if (!h) return DRNMF_ERR_INVALID_ARG;
     if (n_sig <= 0 || n_frames <= 0 || nsampl <= 0 || hop <= 0 || !re || !im || !y || !workspace)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "istft_masked: bad argument");
-    int rc = check_fft_size(h, N, "istft_masked");
-    if (rc) return rc;
+    if (const int32_t rc = check_fft_size(h, "istft_masked", N, DRNMF_ERR_UNSUPPORTED)) return rc;
     if (workspace_bytes < drnmf_istft_workspace_bytes(n_sig, n_frames, N))
         DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "istft_masked: workspace too small");
-    int logN = 0;
-    while ((1 << logN) < N) ++logN;
-    hipStream_t stream = (hipStream_t)stream_;
+    FftCall c;
+    if (const int32_t rc = fft_call(h, N, stream_, &c)) return rc;
     float* frames = (float*)workspace;
-    const size_t shmem = (size_t)(N + N / 2) * sizeof(float2);
-    {
-        const int32_t trc = ensure_fft_tables(h, N, logN, stream);
-        if (trc) return trc;
-    }
-    hipLaunchKernelGGL(istft_frames_kernel, dim3((unsigned)n_frames, (unsigned)n_sig), dim3(256),
-                       shmem, stream, re, im, mask, N, logN, hop, n_frames, frames);
+    // every size takes the radix-2 inverse: this entry has no fused kernel
+    hipLaunchKernelGGL(istft_frames_kernel, dim3((unsigned)n_frames, (unsigned)n_sig), dim3(256), c.lds, c.stream,
+                       re, im, mask, N, c.logN, hop, n_frames, frames);
     hipLaunchKernelGGL(overlap_add_kernel, dim3((unsigned)((nsampl + 255) / 256), (unsigned)n_sig),
-                       dim3(256), 0, stream, frames, N, hop, n_frames, nsampl, y);
+                       dim3(256), 0, c.stream, frames, N, hop, n_frames, nsampl, y);
     DRNMF_HIP(h, hipGetLastError());
     return DRNMF_OK;
 }
@@ -1059,31 +1092,22 @@ extern "C" int32_t drnmf_stft_ragged(drnmf_handle_t h, int32_t n_sig, int64_t st
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG,
                    "stft_ragged: bad shape n_sig=%d stride=%lld b=%d (1..65535) T=%d hop=%d", n_sig,
                    (long long)stride, b, T, hop);
-    if (N < 64 || N > 4096 || (N & (N - 1)))
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stft_ragged: N=%d must be a power of two in [64,4096]", N);
+    if (const int32_t rc = check_fft_size(h, "stft_ragged", N, DRNMF_ERR_INVALID_ARG)) return rc;
     if (!lengths || !sig_index || !pcm || !x || !re || !im)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stft_ragged: NULL pointer argument");
-    int logN = 0;
-    while ((1 << logN) < N) ++logN;
-    hipStream_t stream = (hipStream_t)stream_;
-    {
-        const int32_t trc = ensure_fft_tables(h, N, logN, stream);
-        if (trc) return trc;
-    }
-    if (stft_fast(N)) {
-        const dim3 grid((unsigned)((T + 3) / 4), (unsigned)b);
-        if (N == 1024)
-            hipLaunchKernelGGL((stft_real_ragged_kernel<8, 3>), grid, dim3(256), 0, stream, pcm, is_int16,
-                               stride, lengths, sig_index, n_sig, T, logN, hop, mask_value, x, re, im);
+    FftCall c;
+    if (const int32_t rc = fft_call(h, N, stream_, &c)) return rc;
+    with_fft_size(N, [&](auto s) {
+        using S = decltype(s);
+        if constexpr (S::fast)
+            hipLaunchKernelGGL((stft_real_ragged_kernel<S::R, S::P>), dim3((unsigned)((T + 3) / 4), (unsigned)b),
+                               dim3(256), 0, c.stream, pcm, is_int16, stride, lengths, sig_index, n_sig, T, c.logN,
+                               hop, mask_value, x, re, im);
         else
-            hipLaunchKernelGGL((stft_real_ragged_kernel<4, 4>), grid, dim3(256), 0, stream, pcm, is_int16,
-                               stride, lengths, sig_index, n_sig, T, logN, hop, mask_value, x, re, im);
-    } else {
-        const size_t shmem = (size_t)(N + N / 2) * sizeof(float2);
-        hipLaunchKernelGGL(stft_ragged_kernel, dim3((unsigned)T, (unsigned)b), dim3(256), shmem, stream, pcm,
-                           is_int16, stride, lengths, sig_index, n_sig, T, N, logN, hop, mask_value, x, re,
-                           im);
-    }
+            hipLaunchKernelGGL(stft_ragged_kernel, dim3((unsigned)T, (unsigned)b), dim3(256), c.lds, c.stream, pcm,
+                               is_int16, stride, lengths, sig_index, n_sig, T, N, c.logN, hop, mask_value, x, re,
+                               im);
+    });
     DRNMF_HIP(h, hipGetLastError());
     return DRNMF_OK;
 }
@@ -1104,8 +1128,7 @@ extern "C" int32_t drnmf_istft_ragged(drnmf_handle_t h, int32_t n_sig, int32_t b
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG,
                    "istft_ragged: bad shape n_sig=%d b=%d (1..65535) T=%d hop=%d stride_y=%lld crop=%d", n_sig,
                    b, T, hop, (long long)stride_y, crop);
-    if (N < 64 || N > 4096 || (N & (N - 1)))
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "istft_ragged: N=%d must be a power of two in [64,4096]", N);
+    if (const int32_t rc = check_fft_size(h, "istft_ragged", N, DRNMF_ERR_INVALID_ARG)) return rc;
     if (!lengths || !sig_index || !re || !im || !y)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "istft_ragged: NULL pointer argument");
     if (mask && ld_mask < N / 2 + 1)
@@ -1115,31 +1138,27 @@ extern "C" int32_t drnmf_istft_ragged(drnmf_handle_t h, int32_t n_sig, int32_t b
     if (need && (!workspace || workspace_bytes < need))
         DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "istft_ragged: workspace too small (%zu < %zu bytes)",
                    workspace ? workspace_bytes : (size_t)0, need);
-    int logN = 0;
-    while ((1 << logN) < N) ++logN;
-    hipStream_t stream = (hipStream_t)stream_;
-    {
-        const int32_t trc = ensure_fft_tables(h, N, logN, stream);
-        if (trc) return trc;
-    }
-    if (istft_ragged_fused(N, hop)) {
-        const int run = ragged_run(hop);
-        const dim3 grid((unsigned)((stride_y + run - 1) / run), (unsigned)b);
-        if (N == 1024)
-            hipLaunchKernelGGL((istft_real_ragged_kernel<8, 3>), grid, dim3(256), 0, stream, re, im, mask,
-                               ld_mask, lengths, sig_index, n_sig, T, logN, hop, run, crop, y, stride_y);
-        else
-            hipLaunchKernelGGL((istft_real_ragged_kernel<4, 4>), grid, dim3(256), 0, stream, re, im, mask,
-                               ld_mask, lengths, sig_index, n_sig, T, logN, hop, run, crop, y, stride_y);
-    } else {
+    FftCall c;
+    if (const int32_t rc = fft_call(h, N, stream_, &c)) return rc;
+    const bool fused = istft_ragged_fused(N, hop);        // the rule drnmf_istft_ragged_workspace_bytes answers from
+    with_fft_size(N, [&](auto s) {
+        using S = decltype(s);
+        if constexpr (S::fast) {
+            if (fused) {
+                const int run = ragged_run(hop);
+                hipLaunchKernelGGL((istft_real_ragged_kernel<S::R, S::P>),
+                                   dim3((unsigned)((stride_y + run - 1) / run), (unsigned)b), dim3(256), 0, c.stream,
+                                   re, im, mask, ld_mask, lengths, sig_index, n_sig, T, c.logN, hop, run, crop, y,
+                                   stride_y);
+                return;
+            }
+        }
         float* frames = (float*)workspace;
-        const size_t shmem = (size_t)(N + N / 2) * sizeof(float2);
-        hipLaunchKernelGGL(istft_frames_ragged_kernel, dim3((unsigned)T, (unsigned)b), dim3(256), shmem,
-                           stream, re, im, mask, ld_mask, lengths, sig_index, n_sig, T, N, logN, hop, frames);
+        hipLaunchKernelGGL(istft_frames_ragged_kernel, dim3((unsigned)T, (unsigned)b), dim3(256), c.lds, c.stream,
+                           re, im, mask, ld_mask, lengths, sig_index, n_sig, T, N, c.logN, hop, frames);
         hipLaunchKernelGGL(overlap_add_ragged_kernel, dim3((unsigned)((stride_y + 255) / 256), (unsigned)b),
-                           dim3(256), 0, stream, frames, lengths, sig_index, n_sig, T, N, hop, crop, y,
-                           stride_y);
-    }
+                           dim3(256), 0, c.stream, frames, lengths, sig_index, n_sig, T, N, hop, crop, y, stride_y);
+    });
     DRNMF_HIP(h, hipGetLastError());
     return DRNMF_OK;
 }
@@ -1148,31 +1167,29 @@ extern "C" int32_t drnmf_istft_ragged(drnmf_handle_t h, int32_t n_sig, int32_t b
 // Rows (sequences, or signals in the packed mode) go on grid.y in slices of at most 65535 and frame tiles on
 // grid.x in slices of at most 2^23, so neither count is bounded by a grid dimension.
 template <bool PACKED>
-static void launch_stft_pair(PairArgs a, int N, int64_t n_rows, hipStream_t stream,
-                             int target = DRNMF_TARGET_MAG) {
-    const bool fast = stft_fast(N);
-    const int64_t tiles = fast ? ((int64_t)a.T + 3) / 4 : (int64_t)a.T;
+static void launch_stft_pair(PairArgs a, const FftCall& c, int64_t n_rows, int target = DRNMF_TARGET_MAG) {
+    const int N = c.N;
+    const int64_t tiles = stft_fast(N) ? ((int64_t)a.T + 3) / 4 : (int64_t)a.T;
     const int64_t max_y = 65535, max_x = (int64_t)1 << 23;
-    const size_t shmem = (size_t)(N + N / 2) * sizeof(float2);
     for (int64_t r0 = 0; r0 < n_rows; r0 += max_y)
         for (int64_t x0 = 0; x0 < tiles; x0 += max_x) {
             a.row_base = (int)r0;
             a.tile_base = (int)x0;
             const dim3 grid((unsigned)(tiles - x0 < max_x ? tiles - x0 : max_x),
                             (unsigned)(n_rows - r0 < max_y ? n_rows - r0 : max_y));
-            if (!PACKED && target != DRNMF_TARGET_MAG) {
-                if (N == 1024)
-                    hipLaunchKernelGGL((stft_pair_target_real_kernel<8, 3>), grid, dim3(256), 0, stream, a, target);
-                else if (N == 512)
-                    hipLaunchKernelGGL((stft_pair_target_real_kernel<4, 4>), grid, dim3(256), 0, stream, a, target);
+            with_fft_size(N, [&](auto s) {
+                using S = decltype(s);
+                if (!PACKED && target != DRNMF_TARGET_MAG) {
+                    if constexpr (S::fast)
+                        hipLaunchKernelGGL((stft_pair_target_real_kernel<S::R, S::P>), grid, dim3(256), 0, c.stream,
+                                           a, target);
+                    else
+                        hipLaunchKernelGGL(stft_pair_target_kernel, grid, dim3(256), c.lds, c.stream, a, N, target);
+                } else if constexpr (S::fast)
+                    hipLaunchKernelGGL((stft_pair_real_kernel<S::R, S::P, PACKED>), grid, dim3(256), 0, c.stream, a);
                 else
-                    hipLaunchKernelGGL(stft_pair_target_kernel, grid, dim3(256), shmem, stream, a, N, target);
-            } else if (N == 1024)
-                hipLaunchKernelGGL((stft_pair_real_kernel<8, 3, PACKED>), grid, dim3(256), 0, stream, a);
-            else if (N == 512)
-                hipLaunchKernelGGL((stft_pair_real_kernel<4, 4, PACKED>), grid, dim3(256), 0, stream, a);
-            else
-                hipLaunchKernelGGL((stft_pair_kernel<PACKED>), grid, dim3(256), shmem, stream, a, N);
+                    hipLaunchKernelGGL((stft_pair_kernel<PACKED>), grid, dim3(256), c.lds, c.stream, a, N);
+            });
         }
 }
 
@@ -1183,8 +1200,7 @@ static int32_t check_stft_pair(drnmf_handle_t h, const char* who, int32_t n_sig,
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG,
                    "%s: bad shape n_sig=%d stride_x=%lld stride_y=%lld hop=%d is_int16=%d", who, n_sig,
                    (long long)stride_x, (long long)stride_y, hop, is_int16);
-    if (N < 64 || N > 4096 || (N & (N - 1)))
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: N=%d must be a power of two in [64,4096]", who, N);
+    if (const int32_t rc = check_fft_size(h, who, N, DRNMF_ERR_INVALID_ARG)) return rc;
     if (transform != DRNMF_TRANSFORM_MAG && transform != DRNMF_TRANSFORM_LOGMAG)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: transform=%d is neither DRNMF_TRANSFORM_MAG nor _LOGMAG", who,
                    transform);
@@ -1213,16 +1229,12 @@ static int32_t enqueue_stft_pair_chunks(drnmf_handle_t h, int32_t n_sig, int64_t
                                         const int32_t* seq_table, int32_t T, int32_t N, int32_t hop,
                                         int32_t is_int16, int32_t transform, int32_t target, float mask_value,
                                         const void* pcm_x, const void* pcm_y, float* x, float* y, float* w,
-                                        hipStream_t stream) {
-    int logN = 0;
-    while ((1 << logN) < N) ++logN;
-    {
-        const int32_t trc = ensure_fft_tables(h, N, logN, stream);
-        if (trc) return trc;
-    }
+                                        void* stream_) {
+    FftCall c;
+    if (const int32_t rc = fft_call(h, N, stream_, &c)) return rc;
     PairArgs a = {pcm_x, pcm_y, len_x, len_y, stride_x, stride_y, seq_table, nullptr, 0, x, y, w,
-                  nullptr, nullptr, n_sig, T, hop, logN, is_int16, transform, mask_value, 0, 0};
-    launch_stft_pair<false>(a, N, n_seq, stream, target);
+                  nullptr, nullptr, n_sig, T, hop, c.logN, is_int16, transform, mask_value, 0, 0};
+    launch_stft_pair<false>(a, c, n_seq, target);
     DRNMF_HIP(h, hipGetLastError());
     return DRNMF_OK;
 }
@@ -1239,8 +1251,7 @@ extern "C" int32_t drnmf_stft_pair_chunks(drnmf_handle_t h, int32_t n_sig, int64
                                               seq_table, T, N, hop, is_int16, transform, pcm_x, pcm_y, x, y, w);
     if (rc) return rc;
     return enqueue_stft_pair_chunks(h, n_sig, stride_x, stride_y, len_x, len_y, n_seq, seq_table, T, N, hop,
-                                    is_int16, transform, DRNMF_TARGET_MAG, mask_value, pcm_x, pcm_y, x, y, w,
-                                    (hipStream_t)stream_);
+                                    is_int16, transform, DRNMF_TARGET_MAG, mask_value, pcm_x, pcm_y, x, y, w, stream_);
 }
 
 // include/drnmf_target.h
@@ -1263,8 +1274,7 @@ extern "C" int32_t drnmf_stft_pair_chunks_target(drnmf_handle_t h, int32_t n_sig
                    who, target, transform);
     if (h->device < 0) DRNMF_FAIL(h, DRNMF_ERR_HIP, "%s: the handle is bound to no device", who);
     return enqueue_stft_pair_chunks(h, n_sig, stride_x, stride_y, len_x, len_y, n_seq, seq_table, T, N, hop,
-                                    is_int16, transform, target, mask_value, pcm_x, pcm_y, x, y, w,
-                                    (hipStream_t)stream_);
+                                    is_int16, transform, target, mask_value, pcm_x, pcm_y, x, y, w, stream_);
 }
 
 extern "C" int32_t drnmf_stft_pair_frames(drnmf_handle_t h, int32_t n_sig, int64_t stride_x, int64_t stride_y,
@@ -1282,18 +1292,13 @@ extern "C" int32_t drnmf_stft_pair_frames(drnmf_handle_t h, int32_t n_sig, int64
     if (rc) return rc;
     if (!len_x || !len_y || !row0 || !pcm_x || !pcm_y || !x_frames || !y_frames)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stft_pair_frames: NULL pointer argument");
-    int logN = 0;
-    while ((1 << logN) < N) ++logN;
-    hipStream_t stream = (hipStream_t)stream_;
-    {
-        const int32_t trc = ensure_fft_tables(h, N, logN, stream);
-        if (trc) return trc;
-    }
+    FftCall c;
+    if (const int32_t rc = fft_call(h, N, stream_, &c)) return rc;
     // the grid spans the frames the longest signal can have; a signal's own count is evaluated on the device
     const int T = drnmf_stft_frames(stride_y, N, hop);
     PairArgs a = {pcm_x, pcm_y, len_x, len_y, stride_x, stride_y, nullptr, row0, total_frames, x_frames,
-                  y_frames, nullptr, nullptr, nullptr, n_sig, T, hop, logN, is_int16, transform, 0.f, 0, 0};
-    launch_stft_pair<true>(a, N, n_sig, stream);
+                  y_frames, nullptr, nullptr, nullptr, n_sig, T, hop, c.logN, is_int16, transform, 0.f, 0, 0};
+    launch_stft_pair<true>(a, c, n_sig);
     DRNMF_HIP(h, hipGetLastError());
     return DRNMF_OK;
 }

@@ -59,7 +59,8 @@ __device__ __forceinline__ StreamPush stream_push(const StreamHdr* h, int64_t le
     if (closed0) len = 0;
     p.n1 = p.n0 + len;
     p.closed = closed0 || fin != 0;
-    p.f1 = p.closed ? (p.n1 + hop - 1) / hop + N / hop + 1      // drnmf_stft_frames
+    // written out in its own form (hop divides N), not stft_frame_count: the kernels' instructions stay as they were
+    p.f1 = p.closed ? (p.n1 + hop - 1) / hop + N / hop + 1      // as drnmf_stft_frames
                     : p.n1 / hop + 1;
     if (p.f1 < p.f0) p.f1 = p.f0;
     const int64_t d = p.f1 - p.f0;
@@ -336,8 +337,7 @@ static int32_t check_stream(drnmf_handle_t h, const char* who, int32_t B, int32_
                             const void* state, size_t state_bytes) {
     if (B <= 0 || B > 65535)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: B=%d must lie in [1,65535]", who, B);
-    if (N < 64 || N > 4096 || (N & (N - 1)))
-        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: N=%d must be a power of two in [64,4096]", who, N);
+    if (const int32_t rc = check_fft_size(h, who, N, DRNMF_ERR_INVALID_ARG)) return rc;
     if (hop <= 0 || hop > N || N % hop)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: hop=%d must divide N=%d", who, hop, N);
     if (!state) DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: NULL state", who);
@@ -361,8 +361,7 @@ extern "C" int32_t drnmf_stream_counts(int64_t n_samples, int32_t closed, int32_
         *samples = n > 0 ? n : 0;
         return DRNMF_OK;
     }
-    const int64_t nfram = (n_samples + hop - 1) / hop;            // as drnmf_stft_frames
-    *frames = 1 + (nfram * hop + (int64_t)N) / hop;
+    *frames = stft_frame_count(n_samples, N, hop);
     int64_t n = (int64_t)hop * (*frames - 1) - N;
     if (crop && n_samples < n) n = n_samples;
     *samples = n;
@@ -370,7 +369,7 @@ extern "C" int32_t drnmf_stream_counts(int64_t n_samples, int32_t closed, int32_
 }
 
 extern "C" size_t drnmf_stream_state_bytes(int32_t B, int32_t N, int32_t hop) {
-    if (B <= 0 || B > 65535 || N < 64 || N > 4096 || (N & (N - 1)) || hop <= 0 || hop > N || N % hop) return 0;
+    if (B <= 0 || B > 65535 || !fft_size_ok(N) || hop <= 0 || hop > N || N % hop) return 0;
     return (size_t)B * stream_state_stride(N, hop);
 }
 
@@ -400,28 +399,21 @@ extern "C" int32_t drnmf_stream_forward(drnmf_handle_t h, int32_t B, int64_t str
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stream_forward: NULL pointer argument");
     const int32_t rc = check_stream(h, "stream_forward", B, N, hop, state, state_bytes);
     if (rc) return rc;
-    int logN = 0;
-    while ((1 << logN) < N) ++logN;
-    hipStream_t stream = (hipStream_t)stream_;
-    {
-        const int32_t trc = ensure_fft_tables(h, N, logN, stream);
-        if (trc) return trc;
-    }
+    FftCall c;
+    if (const int32_t trc = fft_call(h, N, stream_, &c)) return trc;
     const size_t per = stream_state_stride(N, hop);
-    if (stft_fast(N)) {
-        const dim3 grid((unsigned)((T + 3) / 4), (unsigned)B);
-        if (N == 1024)
-            hipLaunchKernelGGL((stream_fwd_real_kernel<8, 3>), grid, dim3(256), 0, stream, chunk, is_int16, stride,
-                               chunk_len, final, T, logN, hop, mask_value, x, re, im, state, per);
-        else
-            hipLaunchKernelGGL((stream_fwd_real_kernel<4, 4>), grid, dim3(256), 0, stream, chunk, is_int16, stride,
-                               chunk_len, final, T, logN, hop, mask_value, x, re, im, state, per);
-    } else {
-        const size_t shmem = (size_t)(N + N / 2) * sizeof(float2) + (size_t)N * sizeof(int32_t);
-        hipLaunchKernelGGL(stream_fwd_kernel, dim3((unsigned)T, (unsigned)B), dim3(256), shmem, stream, chunk,
-                           is_int16, stride, chunk_len, final, T, N, logN, hop, mask_value, x, re, im, state, per);
-    }
-    hipLaunchKernelGGL(stream_fwd_commit_kernel, dim3((unsigned)B), dim3(256), 0, stream, chunk, is_int16, stride,
+    with_fft_size(N, [&](auto s) {
+        using S = decltype(s);
+        if constexpr (S::fast)
+            hipLaunchKernelGGL((stream_fwd_real_kernel<S::R, S::P>), dim3((unsigned)((T + 3) / 4), (unsigned)B),
+                               dim3(256), 0, c.stream, chunk, is_int16, stride, chunk_len, final, T, c.logN, hop,
+                               mask_value, x, re, im, state, per);
+        else                                  // behind the points and the twiddles: N words of stage
+            hipLaunchKernelGGL(stream_fwd_kernel, dim3((unsigned)T, (unsigned)B), dim3(256),
+                               c.lds + (size_t)N * sizeof(int32_t), c.stream, chunk, is_int16, stride, chunk_len,
+                               final, T, N, c.logN, hop, mask_value, x, re, im, state, per);
+    });
+    hipLaunchKernelGGL(stream_fwd_commit_kernel, dim3((unsigned)B), dim3(256), 0, c.stream, chunk, is_int16, stride,
                        chunk_len, final, T, N, hop, state, per);
     DRNMF_HIP(h, hipGetLastError());
     return DRNMF_OK;
@@ -442,25 +434,19 @@ extern "C" int32_t drnmf_stream_inverse(drnmf_handle_t h, int32_t B, int32_t T, 
     if (mask && ld_mask < N / 2 + 1)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stream_inverse: ld_mask=%lld is below N/2+1=%d", (long long)ld_mask,
                    N / 2 + 1);
-    int logN = 0;
-    while ((1 << logN) < N) ++logN;
-    hipStream_t stream = (hipStream_t)stream_;
-    {
-        const int32_t trc = ensure_fft_tables(h, N, logN, stream);
-        if (trc) return trc;
-    }
+    FftCall c;
+    if (const int32_t trc = fft_call(h, N, stream_, &c)) return trc;
     const size_t per = stream_state_stride(N, hop);
-    if (N == 1024)
-        hipLaunchKernelGGL((stream_inv_real_kernel<8, 3>), dim3((unsigned)B), dim3(256), 0, stream, re, im, mask,
-                           ld_mask, T, logN, hop, crop, out_int16, y, stride_y, state, per);
-    else if (N == 512)
-        hipLaunchKernelGGL((stream_inv_real_kernel<4, 4>), dim3((unsigned)B), dim3(256), 0, stream, re, im, mask,
-                           ld_mask, T, logN, hop, crop, out_int16, y, stride_y, state, per);
-    else {
-        const size_t shmem = (size_t)(N + N / 2) * sizeof(float2) + (size_t)N * sizeof(float);
-        hipLaunchKernelGGL(stream_inv_kernel, dim3((unsigned)B), dim3(256), shmem, stream, re, im, mask, ld_mask, T,
-                           N, logN, hop, crop, out_int16, y, stride_y, state, per);
-    }
+    with_fft_size(N, [&](auto s) {
+        using S = decltype(s);
+        if constexpr (S::fast)
+            hipLaunchKernelGGL((stream_inv_real_kernel<S::R, S::P>), dim3((unsigned)B), dim3(256), 0, c.stream, re,
+                               im, mask, ld_mask, T, c.logN, hop, crop, out_int16, y, stride_y, state, per);
+        else                                  // behind the points and the twiddles: N floats of overlap-add
+            hipLaunchKernelGGL(stream_inv_kernel, dim3((unsigned)B), dim3(256), c.lds + (size_t)N * sizeof(float),
+                               c.stream, re, im, mask, ld_mask, T, N, c.logN, hop, crop, out_int16, y, stride_y,
+                               state, per);
+    });
     DRNMF_HIP(h, hipGetLastError());
     return DRNMF_OK;
 }
