@@ -288,6 +288,12 @@ MIX_SIGNATURES = {
 }
 MIX_BLOCK = 4096                                   # DRNMF_MIX_BLOCK
 
+# every table above, one per header: lib() binds them all (a new header adds its table's name here)
+SIGNATURE_TABLES = (SIGNATURES, LSTM_SIGNATURES, SCORE_SIGNATURES, ENHANCE_SIGNATURES, SDR_SIGNATURES,
+                    DATASET_SIGNATURES, STREAM_SIGNATURES, SNMF_SIGNATURES, SNMF_F16_SIGNATURES, TARGET_SIGNATURES,
+                    ESTOI_SIGNATURES, SNMF_ADAPT_SIGNATURES, SNMF_KL_SIGNATURES, SNMF_ONLINE_SIGNATURES,
+                    MIX_SIGNATURES)
+
 _lib = None
 _handles = {}
 
@@ -309,16 +315,10 @@ def lib():
         # to initialise reports "no ROCm-capable device".
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in (list(SIGNATURES.items()) + list(LSTM_SIGNATURES.items()) +
-                                  list(SCORE_SIGNATURES.items()) + list(ENHANCE_SIGNATURES.items()) +
-                                  list(SDR_SIGNATURES.items()) + list(DATASET_SIGNATURES.items()) +
-                                  list(STREAM_SIGNATURES.items()) + list(SNMF_SIGNATURES.items()) +
-                                  list(SNMF_F16_SIGNATURES.items()) + list(TARGET_SIGNATURES.items()) +
-                                  list(ESTOI_SIGNATURES.items()) + list(SNMF_ADAPT_SIGNATURES.items()) +
-                                  list(SNMF_KL_SIGNATURES.items()) + list(SNMF_ONLINE_SIGNATURES.items()) +
-                                  list(MIX_SIGNATURES.items())):
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
+        for table in SIGNATURE_TABLES:
+            for name, (res, args) in table.items():
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = res, args
         _lib = L
     return _lib
 

@@ -40,7 +40,62 @@ def _f32c(t, name):
     return t if t.is_contiguous() else t.contiguous()
 
 
-DIVERGENCES = {"ed": _capi.DIV_ED, "kl": _capi.DIV_KL, "beta": _capi.DIV_BETA}
+# ---- the argument rules every wrapper below shares: one call sequence, one output check, one workspace rule ----
+def _call(name, dev, *args, stream=True):
+    """The C entry `name` on device index `dev`'s handle: name(handle, *args[, torch's current stream]), then
+    _capi.check.  Arguments are passed as they are (the site converts them, in the header's order)."""
+    L = _capi.lib()
+    h = _capi.handle(dev)
+    rc = getattr(L, name)(h, *args, _stream()) if stream else getattr(L, name)(h, *args)
+    _capi.check(rc, h, name)
+
+
+def _given(t, shape, dtype, device, name):
+    """The one test of a tensor the caller supplies for a kernel to write: contiguous, `dtype`, exactly `shape`
+    (a tuple), on `device` (a tensor's .device) -- ValueError otherwise.  Returns t."""
+    if tuple(t.shape) != shape or t.dtype != dtype or t.device != device or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous %s tensor of shape %s on %s (got %s %s on %s)" %
+                         (name, dtype, shape, device, t.dtype, tuple(t.shape), t.device))
+    return t
+
+
+def _out(out, shape, dtype, device, name="out"):
+    """Allocate or check: a new tensor when `out` is None, else `out` itself if it passes `_given`."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    return _given(out, shape, dtype, device, name)
+
+
+def _check_state(t, shape, device, name):
+    """A float32 state the caller may leave out: None passes, anything else must pass `_given`."""
+    if t is not None:
+        _given(t, shape, torch.float32, device, name)
+
+
+def _workspace(need, device, have=None):
+    """`have` itself when it is a uint8 tensor of at least `need` bytes on `device`, else a new one."""
+    if have is not None and have.dtype == torch.uint8 and have.numel() >= need and \
+            have.device == torch.device(device):
+        return have
+    return torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+
+
+def _mask_pair(mask_value):
+    """(value, given) as the SNMF family's entries take a mask value."""
+    return (0.0, 0) if mask_value is None else (float(mask_value), 1)
+
+
+def _mask_nan(mask_value):
+    """The cell family's convention: NaN means no masking."""
+    return float("nan") if mask_value is None else float(mask_value)
+
+
+def _hidden_width(desc):
+    """Last dimension of a cell's output: every layer's state with return_all_hidden, else the last one's."""
+    return desc.N * (desc.K if desc.return_all_hidden else 1)
+
+
+DIVERGENCES ={"ed": _capi.DIV_ED, "kl": _capi.DIV_KL, "beta": _capi.DIV_BETA}
 
 
 def make_desc(B, T, F, N, K, n_D=1, n_alph=1, alph_len=1, n_lam=1, return_all_hidden=False,
@@ -54,9 +109,7 @@ def make_desc(B, T, F, N, K, n_D=1, n_alph=1, alph_len=1, n_lam=1, return_all_hi
 
 def prepare_params(desc, log_D, log_alph, log_lam1, out=None):
     """log_D [n_D,F,N], log_alph [n_alph,alph_len], log_lam1 [n_lam] -> prepared block (uint8)."""
-    L = _capi.lib()
     dev = _dev_index(log_D)
-    h = _capi.handle(dev)
     log_D, log_alph, log_lam1 = (_f32c(log_D, "log_D"), _f32c(log_alph, "log_alph"),
                                  _f32c(log_lam1, "log_lam1"))
     if log_D.numel() != desc.n_D * desc.F * desc.N:
@@ -64,12 +117,9 @@ def prepare_params(desc, log_D, log_alph, log_lam1, out=None):
                          (log_D.numel(), desc.n_D * desc.F * desc.N))
     if log_alph.numel() != desc.n_alph * desc.alph_len or log_lam1.numel() != desc.n_lam:
         raise ValueError("log_alph/log_lam1 sizes do not match the descriptor")
-    nbytes = L.drnmf_params_bytes(C.byref(desc))
-    if out is None or out.numel() < nbytes:
-        out = torch.empty(nbytes, dtype=torch.uint8, device=log_D.device)
-    rc = L.drnmf_prepare_params(h, C.byref(desc), _capi.ptr(log_D), _capi.ptr(log_alph),
-                                _capi.ptr(log_lam1), _capi.ptr(out), _stream())
-    _capi.check(rc, h, "drnmf_prepare_params")
+    out = _workspace(_capi.lib().drnmf_params_bytes(C.byref(desc)), log_D.device, out)
+    _call("drnmf_prepare_params", dev, C.byref(desc), _capi.ptr(log_D), _capi.ptr(log_alph),
+          _capi.ptr(log_lam1), _capi.ptr(out))
     return out
 
 
@@ -107,9 +157,7 @@ def cell_forward(x, mask_value, params, desc, log_h0, u, out=None, workspace=Non
                  initial_state=None, final_state=None):
     """x [B,T,F] -> h [B,T,N] (or [B,T,K*N]).  mask_value None = no masking.
     u = (u0_diag, u0_off, uk_off).  initial_state / final_state [B,N]: stateful mode."""
-    L = _capi.lib()
     dev = _dev_index(x)
-    h = _capi.handle(dev)
     x = _f32c(x, "x")
     log_h0 = _f32c(log_h0, "log_h0")
     if tuple(x.shape) != (desc.B, desc.T, desc.F):
@@ -117,30 +165,19 @@ def cell_forward(x, mask_value, params, desc, log_h0, u, out=None, workspace=Non
                          (tuple(x.shape), desc.B, desc.T, desc.F))
     if log_h0.numel() != desc.N:
         raise ValueError("log_h0 must have N=%d elements" % desc.N)
-    width = desc.N * (desc.K if desc.return_all_hidden else 1)
-    if out is None:
-        out = torch.empty((desc.B, desc.T, width), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (desc.B, desc.T, width) or not out.is_contiguous():
-        raise ValueError("out must be a contiguous (B,T,%d) float32 tensor" % width)
+    out = _out(out, (desc.B, desc.T, _hidden_width(desc)), torch.float32, x.device)
     if workspace is None:
         workspace = cell_workspace(desc, x.device)
-    mv = float("nan") if mask_value is None else float(mask_value)
+    mv = _mask_nan(mask_value)
     if initial_state is not None or final_state is not None:
-        for st in (initial_state, final_state):
-            if st is not None and (tuple(st.shape) != (desc.B, desc.N) or st.dtype != torch.float32
-                                   or not st.is_contiguous()):
-                raise ValueError("states must be contiguous float32 (B,N) tensors")
-        rc = L.drnmf_cell_forward_stateful(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params),
-                                           _capi.ptr(log_h0), float(u[0]), float(u[1]),
-                                           float(u[2]), _capi.ptr(initial_state),
-                                           _capi.ptr(final_state), _capi.ptr(out),
-                                           _capi.ptr(workspace), workspace.numel(), _stream())
-        _capi.check(rc, h, "drnmf_cell_forward_stateful")
+        _check_state(initial_state, (desc.B, desc.N), x.device, "initial_state")
+        _check_state(final_state, (desc.B, desc.N), x.device, "final_state")
+        _call("drnmf_cell_forward_stateful", dev, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params),
+              _capi.ptr(log_h0), float(u[0]), float(u[1]), float(u[2]), _capi.ptr(initial_state),
+              _capi.ptr(final_state), _capi.ptr(out), _capi.ptr(workspace), workspace.numel())
         return out
-    rc = L.drnmf_cell_forward(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params),
-                              _capi.ptr(log_h0), float(u[0]), float(u[1]), float(u[2]),
-                              _capi.ptr(out), _capi.ptr(workspace), workspace.numel(), _stream())
-    _capi.check(rc, h, "drnmf_cell_forward")
+    _call("drnmf_cell_forward", dev, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), _capi.ptr(log_h0),
+          float(u[0]), float(u[1]), float(u[2]), _capi.ptr(out), _capi.ptr(workspace), workspace.numel())
     return out
 
 
@@ -157,8 +194,7 @@ def make_dense_desc(B, T, F, N, K, connect_input=True, activation="relu",
 def dense_prepare_params(desc, U, S, W, b, out=None):
     """U [K,N,N], S [K-1,N,N] (None when K == 1), W [K,F,N] (None without the input connection),
     b [K,N] -- the reference's Uk/Sk/Wk/bk lists stacked -> prepared block (uint8)."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(U))
+    dev = _dev_index(U)
     K, N, F = desc.K, desc.N, desc.F
     U, b = _f32c(U, "U"), _f32c(b, "b")
     if tuple(U.shape) != (K, N, N) or tuple(b.shape) != (K, N):
@@ -175,12 +211,9 @@ def dense_prepare_params(desc, U, S, W, b, out=None):
             raise ValueError("W must have shape (K,F,N) = (%d,%d,%d)" % (K, F, N))
     else:
         W = None
-    nbytes = L.drnmf_dense_params_bytes(C.byref(desc))
-    if out is None or out.numel() < nbytes:
-        out = torch.empty(nbytes, dtype=torch.uint8, device=U.device)
-    rc = L.drnmf_dense_prepare_params(h, C.byref(desc), _capi.ptr(U), _capi.ptr(S), _capi.ptr(W),
-                                      _capi.ptr(b), _capi.ptr(out), _stream())
-    _capi.check(rc, h, "drnmf_dense_prepare_params")
+    out = _workspace(_capi.lib().drnmf_dense_params_bytes(C.byref(desc)), U.device, out)
+    _call("drnmf_dense_prepare_params", dev, C.byref(desc), _capi.ptr(U), _capi.ptr(S), _capi.ptr(W),
+          _capi.ptr(b), _capi.ptr(out))
     return out
 
 
@@ -201,47 +234,34 @@ def dense_cell_forward(x, mask_value, params, desc, h0, out=None, workspace=None
     """General SimpleDeepRNN.step on dense per-layer matrices: x [B,T,F] -> h [B,T,N] (or
     [B,T,K*N]).  h0 [N] is the initial state itself.  drop_u [B,N]: the training phase's recurrent
     dropout mask B_U (custom_layers.py:377-384), 0 or 1/(1-p)."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(x))
+    dev = _dev_index(x)
     x, h0 = _f32c(x, "x"), _f32c(h0, "h0")
     if tuple(x.shape) != (desc.B, desc.T, desc.F):
         raise ValueError("x has shape %s, descriptor says (%d,%d,%d)" %
                          (tuple(x.shape), desc.B, desc.T, desc.F))
     if h0.numel() != desc.N:
         raise ValueError("h0 must have N=%d elements" % desc.N)
-    width = desc.N * (desc.K if desc.return_all_hidden else 1)
-    if out is None:
-        out = torch.empty((desc.B, desc.T, width), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (desc.B, desc.T, width) or not out.is_contiguous():
-        raise ValueError("out must be a contiguous (B,T,%d) float32 tensor" % width)
+    out = _out(out, (desc.B, desc.T, _hidden_width(desc)), torch.float32, x.device)
     if workspace is None:
         workspace = dense_workspace(desc, x.device)
-    for st in (initial_state, final_state):
-        if st is not None and (tuple(st.shape) != (desc.B, desc.N) or st.dtype != torch.float32
-                               or not st.is_contiguous()):
-            raise ValueError("states must be contiguous float32 (B,N) tensors")
-    mv = float("nan") if mask_value is None else float(mask_value)
+    _check_state(initial_state, (desc.B, desc.N), x.device, "initial_state")
+    _check_state(final_state, (desc.B, desc.N), x.device, "final_state")
+    mv = _mask_nan(mask_value)
     if drop_u is not None and (initial_state is not None or final_state is not None):
         # a stateful layer in its training phase (custom_layers.py:296-318 with 377-384)
         drop_u = _check_drop_u(drop_u, desc)
-        rc = L.drnmf_dense_cell_forward_dropout_stateful(
-            h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), _capi.ptr(h0),
-            _capi.ptr(initial_state), _capi.ptr(final_state), _capi.ptr(drop_u), _capi.ptr(out),
-            _capi.ptr(workspace), workspace.numel(), _stream())
-        _capi.check(rc, h, "drnmf_dense_cell_forward_dropout_stateful")
+        _call("drnmf_dense_cell_forward_dropout_stateful", dev, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params),
+              _capi.ptr(h0), _capi.ptr(initial_state), _capi.ptr(final_state), _capi.ptr(drop_u), _capi.ptr(out),
+              _capi.ptr(workspace), workspace.numel())
         return out
     if drop_u is not None:
         drop_u = _check_drop_u(drop_u, desc)
-        rc = L.drnmf_dense_cell_forward_dropout(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params),
-                                                _capi.ptr(h0), _capi.ptr(drop_u), _capi.ptr(out),
-                                                _capi.ptr(workspace), workspace.numel(), _stream())
-        _capi.check(rc, h, "drnmf_dense_cell_forward_dropout")
+        _call("drnmf_dense_cell_forward_dropout", dev, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params),
+              _capi.ptr(h0), _capi.ptr(drop_u), _capi.ptr(out), _capi.ptr(workspace), workspace.numel())
         return out
-    rc = L.drnmf_dense_cell_forward(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params),
-                                    _capi.ptr(h0), _capi.ptr(initial_state),
-                                    _capi.ptr(final_state), _capi.ptr(out), _capi.ptr(workspace),
-                                    workspace.numel(), _stream())
-    _capi.check(rc, h, "drnmf_dense_cell_forward")
+    _call("drnmf_dense_cell_forward", dev, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), _capi.ptr(h0),
+          _capi.ptr(initial_state), _capi.ptr(final_state), _capi.ptr(out), _capi.ptr(workspace),
+          workspace.numel())
     return out
 
 
@@ -252,12 +272,11 @@ def dense_cell_backward(x, mask_value, desc, U, S, W, b, h0, hall, d_out, worksp
     desc.return_all_hidden).  Returns dict(dU [K,N,N], dS [K-1,N,N] | None, dW [K,F,N] | None,
     db [K,N], dh0 [N]).  initial_state [B,N]: the state a stateful layer's batch entered with
     (drnmf_dense_cell_backward_stateful: a constant of the gradient, dh0 = 0)."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(x))
+    di = _dev_index(x)
     B, T, F, N, K = desc.B, desc.T, desc.F, desc.N, desc.K
     x, U, b, h0 = _f32c(x, "x"), _f32c(U, "U"), _f32c(b, "b"), _f32c(h0, "h0")
     hall, d_out = _f32c(hall, "hall"), _f32c(d_out, "d_out")
-    width = N * (K if desc.return_all_hidden else 1)
+    width = _hidden_width(desc)
     if tuple(x.shape) != (B, T, F) or tuple(hall.shape) != (B, T, K * N) or \
             tuple(d_out.shape) != (B, T, width):
         raise ValueError("x / hall / d_out must have shapes (B,T,F) / (B,T,K*N) / (B,T,%d)" % width)
@@ -272,42 +291,28 @@ def dense_cell_backward(x, mask_value, desc, U, S, W, b, h0, hall, d_out, worksp
              else None,
              db=torch.empty((K, N), dtype=torch.float32, device=dev),
              dh0=torch.empty((N,), dtype=torch.float32, device=dev))
-    nbytes = L.drnmf_dense_backward_workspace_bytes(C.byref(desc))
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    mv = float("nan") if mask_value is None else float(mask_value)
+    g["workspace"] = workspace = _workspace(_capi.lib().drnmf_dense_backward_workspace_bytes(C.byref(desc)), dev,
+                                            workspace)
+    mv = _mask_nan(mask_value)
+    head = (C.byref(desc), _capi.ptr(x), mv, _capi.ptr(U), _capi.ptr(S), _capi.ptr(W), _capi.ptr(b))
     if initial_state is not None:
-        if tuple(initial_state.shape) != (B, N) or initial_state.dtype != torch.float32 or \
-                not initial_state.is_contiguous():
-            raise ValueError("initial_state must be a contiguous float32 (B,N) tensor")
+        _check_state(initial_state, (B, N), dev, "initial_state")
         if drop_u is not None:
             drop_u = _check_drop_u(drop_u, desc)
-        rc = L.drnmf_dense_cell_backward_stateful(
-            h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(U), _capi.ptr(S), _capi.ptr(W), _capi.ptr(b),
-            _capi.ptr(initial_state), _capi.ptr(drop_u), _capi.ptr(hall), _capi.ptr(d_out),
-            _capi.ptr(g["dU"]), _capi.ptr(g["dS"]), _capi.ptr(g["dW"]), _capi.ptr(g["db"]),
-            _capi.ptr(workspace), workspace.numel(), _stream())
-        _capi.check(rc, h, "drnmf_dense_cell_backward_stateful")
+        _call("drnmf_dense_cell_backward_stateful", di, *head, _capi.ptr(initial_state), _capi.ptr(drop_u),
+              _capi.ptr(hall), _capi.ptr(d_out), _capi.ptr(g["dU"]), _capi.ptr(g["dS"]), _capi.ptr(g["dW"]),
+              _capi.ptr(g["db"]), _capi.ptr(workspace), workspace.numel())
         g["dh0"].zero_()
-        g["workspace"] = workspace
         return g
     if drop_u is not None:
         drop_u = _check_drop_u(drop_u, desc)
-        rc = L.drnmf_dense_cell_backward_dropout(
-            h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(U), _capi.ptr(S), _capi.ptr(W), _capi.ptr(b),
-            _capi.ptr(h0), _capi.ptr(drop_u), _capi.ptr(hall), _capi.ptr(d_out), _capi.ptr(g["dU"]),
-            _capi.ptr(g["dS"]), _capi.ptr(g["dW"]), _capi.ptr(g["db"]), _capi.ptr(g["dh0"]),
-            _capi.ptr(workspace), workspace.numel(), _stream())
-        _capi.check(rc, h, "drnmf_dense_cell_backward_dropout")
-        g["workspace"] = workspace
+        _call("drnmf_dense_cell_backward_dropout", di, *head, _capi.ptr(h0), _capi.ptr(drop_u), _capi.ptr(hall),
+              _capi.ptr(d_out), _capi.ptr(g["dU"]), _capi.ptr(g["dS"]), _capi.ptr(g["dW"]), _capi.ptr(g["db"]),
+              _capi.ptr(g["dh0"]), _capi.ptr(workspace), workspace.numel())
         return g
-    rc = L.drnmf_dense_cell_backward(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(U), _capi.ptr(S),
-                                     _capi.ptr(W), _capi.ptr(b), _capi.ptr(h0), _capi.ptr(hall),
-                                     _capi.ptr(d_out), _capi.ptr(g["dU"]), _capi.ptr(g["dS"]),
-                                     _capi.ptr(g["dW"]), _capi.ptr(g["db"]), _capi.ptr(g["dh0"]),
-                                     _capi.ptr(workspace), workspace.numel(), _stream())
-    _capi.check(rc, h, "drnmf_dense_cell_backward")
-    g["workspace"] = workspace
+    _call("drnmf_dense_cell_backward", di, *head, _capi.ptr(h0), _capi.ptr(hall), _capi.ptr(d_out),
+          _capi.ptr(g["dU"]), _capi.ptr(g["dS"]), _capi.ptr(g["dW"]), _capi.ptr(g["db"]), _capi.ptr(g["dh0"]),
+          _capi.ptr(workspace), workspace.numel())
     return g
 
 
@@ -316,55 +321,39 @@ def cell_forward_ista(x, mask_value, params, desc, log_h0, beta=1.5, out=None, w
     """KL / beta variant of the cell (desc.divergence = 'kl' | 'beta'): every frame runs K full
     ISTA steps of the reference's ista_kl / ista_beta warm-started from the previous frame's
     output.  x [B,T,F] -> h [B,T,N] (or [B,T,K*N])."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(x))
+    dev = _dev_index(x)
     x, log_h0 = _f32c(x, "x"), _f32c(log_h0, "log_h0")
     if tuple(x.shape) != (desc.B, desc.T, desc.F):
         raise ValueError("x has shape %s, descriptor says (%d,%d,%d)" %
                          (tuple(x.shape), desc.B, desc.T, desc.F))
     if log_h0.numel() != desc.N:
         raise ValueError("log_h0 must have N=%d elements" % desc.N)
-    width = desc.N * (desc.K if desc.return_all_hidden else 1)
-    if out is None:
-        out = torch.empty((desc.B, desc.T, width), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (desc.B, desc.T, width) or not out.is_contiguous():
-        raise ValueError("out must be a contiguous (B,T,%d) float32 tensor" % width)
+    out = _out(out, (desc.B, desc.T, _hidden_width(desc)), torch.float32, x.device)
     if workspace is None:
         workspace = cell_workspace(desc, x.device)
-    for st in (initial_state, final_state):
-        if st is not None and (tuple(st.shape) != (desc.B, desc.N) or st.dtype != torch.float32
-                               or not st.is_contiguous()):
-            raise ValueError("states must be contiguous float32 (B,N) tensors")
-    mv = float("nan") if mask_value is None else float(mask_value)
-    rc = L.drnmf_cell_forward_ista(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params),
-                                   _capi.ptr(log_h0), float(beta), _capi.ptr(initial_state),
-                                   _capi.ptr(final_state), _capi.ptr(out), _capi.ptr(workspace),
-                                   workspace.numel(), _stream())
-    _capi.check(rc, h, "drnmf_cell_forward_ista")
+    _check_state(initial_state, (desc.B, desc.N), x.device, "initial_state")
+    _check_state(final_state, (desc.B, desc.N), x.device, "final_state")
+    _call("drnmf_cell_forward_ista", dev, C.byref(desc), _capi.ptr(x), _mask_nan(mask_value), _capi.ptr(params),
+          _capi.ptr(log_h0), float(beta), _capi.ptr(initial_state), _capi.ptr(final_state), _capi.ptr(out),
+          _capi.ptr(workspace), workspace.numel())
     return out
 
 
 def cell_profile(x, mask_value, params, desc, log_h0, u, out, workspace, frames=8):
     """Measurement aid: per-kernel mean durations (us) of the first `frames` frames, HIP events on
     the launch stream.  Returns dict(cell_a_us, cell_b_us, frame_us)."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(x))
     res = (C.c_float * 3)()
-    mv = float("nan") if mask_value is None else float(mask_value)
-    rc = L.drnmf_cell_profile(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params),
-                              _capi.ptr(log_h0), float(u[0]), float(u[1]), float(u[2]),
-                              _capi.ptr(out), _capi.ptr(workspace), workspace.numel(), _stream(),
-                              int(frames), res)
-    _capi.check(rc, h, "drnmf_cell_profile")
+    # (the stream is not this entry's last argument)
+    _call("drnmf_cell_profile", _dev_index(x), C.byref(desc), _capi.ptr(x), _mask_nan(mask_value), _capi.ptr(params),
+          _capi.ptr(log_h0), float(u[0]), float(u[1]), float(u[2]), _capi.ptr(out), _capi.ptr(workspace),
+          workspace.numel(), _stream(), int(frames), res, stream=False)
     return {"cell_a_us": float(res[0]), "cell_b_us": float(res[1]), "frame_us": float(res[2])}
 
 
 def head_forward(hidden, kernel_clean, kernel_noise, square=False, want_ab=False, h_off=0,
                  out=None):
     """hidden [..., ld] (uses columns h_off .. h_off+2r) -> mask [..., F] (and A, Bn)."""
-    L = _capi.lib()
     dev = _dev_index(hidden)
-    h = _capi.handle(dev)
     hidden = _f32c(hidden, "hidden")
     kc, kn = _f32c(kernel_clean, "kernel_clean"), _f32c(kernel_noise, "kernel_noise")
     r, F = kc.shape
@@ -374,31 +363,23 @@ def head_forward(hidden, kernel_clean, kernel_noise, square=False, want_ab=False
     ld = hidden.shape[-1]
     rows = hidden.numel() // ld
     shape = tuple(hidden.shape[:-1]) + (F,)
-    mask = out if out is not None else torch.empty(shape, dtype=torch.float32,
-                                                   device=hidden.device)
+    mask = _out(out, shape, torch.float32, hidden.device)
     A = torch.empty(shape, dtype=torch.float32, device=hidden.device) if want_ab else None
     Bn = torch.empty(shape, dtype=torch.float32, device=hidden.device) if want_ab else None
-    Fp = L.drnmf_padded_f(F)
+    Fp = _capi.lib().drnmf_padded_f(F)
     ecat = torch.empty(2 * ((r + 15) // 16 * 16) * Fp, dtype=torch.float32, device=hidden.device)
-    rc = L.drnmf_head_forward(h, rows, F, r, _capi.ptr(hidden), ld, int(h_off), _capi.ptr(kc),
-                              _capi.ptr(kn), int(bool(square)), _capi.ptr(mask), _capi.ptr(A),
-                              _capi.ptr(Bn), _capi.ptr(ecat), _stream())
-    _capi.check(rc, h, "drnmf_head_forward")
+    _call("drnmf_head_forward", dev, rows, F, r, _capi.ptr(hidden), ld, int(h_off), _capi.ptr(kc), _capi.ptr(kn),
+          int(bool(square)), _capi.ptr(mask), _capi.ptr(A), _capi.ptr(Bn), _capi.ptr(ecat))
     return (mask, A, Bn) if want_ab else mask
 
 
 def _head_grad_outputs(out, kc, kn, dev):
     """(sums[2], d_kernel_clean, d_kernel_noise): the caller's `out` triple (contiguous fp32 device
     tensors of those sizes, e.g. views of a flat gradient buffer) or fresh tensors."""
-    if out is None:
-        return (torch.empty(2, dtype=torch.float32, device=dev), torch.empty_like(kc),
-                torch.empty_like(kn))
-    sums, dkc, dkn = out
-    for t, n, ref in ((sums, 2, None), (dkc, kc.numel(), kc), (dkn, kn.numel(), kn)):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n or t.device != dev:
-            raise ValueError("head gradient outputs must be contiguous float32 device tensors of the "
-                             "sizes of sums[2] / kernel_clean / kernel_noise")
-    return sums, dkc, dkn
+    sums, dkc, dkn = (None, None, None) if out is None else out
+    return (_out(sums, (2,), torch.float32, dev, "sums"),
+            _out(dkc, tuple(kc.shape), torch.float32, dev, "d_kernel_clean"),
+            _out(dkn, tuple(kn.shape), torch.float32, dev, "d_kernel_noise"))
 
 
 def loss_head_backward(x_raw, hidden, kernel_clean, kernel_noise, mask, A, Bn, y, w, square=False,
@@ -406,8 +387,7 @@ def loss_head_backward(x_raw, hidden, kernel_clean, kernel_noise, mask, A, Bn, y
     """Unnormalised loss + gradients of the mask head (see drnmf_loss_head_backward).
     Returns (sums[2] device tensor, d_hidden [..., 2r], d_kernel_clean, d_kernel_noise); `out` =
     (sums, d_kernel_clean, d_kernel_noise) to write into."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(hidden))
+    di = _dev_index(hidden)
     x_raw, hidden, mask, A, Bn, y = (_f32c(t, n) for t, n in
                                      ((x_raw, "x_raw"), (hidden, "hidden"), (mask, "mask"),
                                       (A, "A"), (Bn, "Bn"), (y, "y")))
@@ -421,15 +401,12 @@ def loss_head_backward(x_raw, hidden, kernel_clean, kernel_noise, mask, A, Bn, y
     dev = hidden.device
     sums, dkc, dkn = _head_grad_outputs(out, kc, kn, dev)
     d_hidden = torch.empty(tuple(hidden.shape[:-1]) + (2 * r,), dtype=torch.float32, device=dev)
-    nbytes = L.drnmf_loss_head_workspace_bytes(rows, F, r)
+    nbytes = _capi.lib().drnmf_loss_head_workspace_bytes(rows, F, r)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    rc = L.drnmf_loss_head_backward(h, rows, F, r, _capi.ptr(x_raw), _capi.ptr(hidden), ld,
-                                    int(h_off), _capi.ptr(kc), _capi.ptr(kn), int(bool(square)),
-                                    _capi.ptr(mask), _capi.ptr(A), _capi.ptr(Bn), _capi.ptr(y),
-                                    _capi.ptr(w), _capi.ptr(sums), _capi.ptr(d_hidden),
-                                    _capi.ptr(dkc), _capi.ptr(dkn), _capi.ptr(ws), nbytes,
-                                    _stream())
-    _capi.check(rc, h, "drnmf_loss_head_backward")
+    _call("drnmf_loss_head_backward", di, rows, F, r, _capi.ptr(x_raw), _capi.ptr(hidden), ld, int(h_off),
+          _capi.ptr(kc), _capi.ptr(kn), int(bool(square)), _capi.ptr(mask), _capi.ptr(A), _capi.ptr(Bn),
+          _capi.ptr(y), _capi.ptr(w), _capi.ptr(sums), _capi.ptr(d_hidden), _capi.ptr(dkc), _capi.ptr(dkn),
+          _capi.ptr(ws), nbytes)
     return sums, d_hidden, dkc, dkn
 
 
@@ -437,8 +414,7 @@ def snmf_cost_head_backward(x_raw, hidden, kernel_clean, kernel_noise, A, Bn, w,
                             h_off=0, out=None):
     """Unnormalised SNMF-cost pretraining loss + head gradients (drnmf_snmf_cost_head_backward):
     per frame 0.5*mean_f (A+Bn-x)^2 + l1_weight*mean_n |h|.  Same returns as loss_head_backward."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(hidden))
+    di = _dev_index(hidden)
     x_raw, hidden, A, Bn, w = (_f32c(t, n) for t, n in
                                ((x_raw, "x_raw"), (hidden, "hidden"), (A, "A"), (Bn, "Bn"),
                                 (w, "w")))
@@ -451,14 +427,11 @@ def snmf_cost_head_backward(x_raw, hidden, kernel_clean, kernel_noise, A, Bn, w,
     dev = hidden.device
     sums, dkc, dkn = _head_grad_outputs(out, kc, kn, dev)
     d_hidden = torch.empty(tuple(hidden.shape[:-1]) + (2 * r,), dtype=torch.float32, device=dev)
-    nbytes = L.drnmf_loss_head_workspace_bytes(rows, F, r)
+    nbytes = _capi.lib().drnmf_loss_head_workspace_bytes(rows, F, r)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    rc = L.drnmf_snmf_cost_head_backward(h, rows, F, r, _capi.ptr(x_raw), _capi.ptr(hidden), ld,
-                                         int(h_off), _capi.ptr(kc), _capi.ptr(kn), _capi.ptr(A),
-                                         _capi.ptr(Bn), _capi.ptr(w), float(l1_weight),
-                                         _capi.ptr(sums), _capi.ptr(d_hidden), _capi.ptr(dkc),
-                                         _capi.ptr(dkn), _capi.ptr(ws), nbytes, _stream())
-    _capi.check(rc, h, "drnmf_snmf_cost_head_backward")
+    _call("drnmf_snmf_cost_head_backward", di, rows, F, r, _capi.ptr(x_raw), _capi.ptr(hidden), ld, int(h_off),
+          _capi.ptr(kc), _capi.ptr(kn), _capi.ptr(A), _capi.ptr(Bn), _capi.ptr(w), float(l1_weight),
+          _capi.ptr(sums), _capi.ptr(d_hidden), _capi.ptr(dkc), _capi.ptr(dkn), _capi.ptr(ws), nbytes)
     return sums, d_hidden, dkc, dkn
 
 
@@ -472,8 +445,7 @@ def cell_backward(x, params, desc, log_h0, u, hall, d_out, fwd_workspace, grads=
     batched_ms / chain_launches.  initial_state [B,N]: stateful training -- the forward was
     cell_forward(..., initial_state=...), the supplied state is a constant of the gradient
     (drnmf_cell_backward_stateful; d_log_h0 comes back zero)."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(x))
+    di = _dev_index(x)
     x, hall, d_out = _f32c(x, "x"), _f32c(hall, "hall"), _f32c(d_out, "d_out")
     if tuple(hall.shape) != (desc.B, desc.T, desc.K * desc.N):
         raise ValueError("hall must be (B,T,K*N) = (%d,%d,%d)" % (desc.B, desc.T, desc.K * desc.N))
@@ -491,80 +463,55 @@ def cell_backward(x, params, desc, log_h0, u, hall, d_out, fwd_workspace, grads=
         "d_log_h0": g.get("d_log_h0") if g.get("d_log_h0") is not None else
         torch.empty((desc.N,), dtype=torch.float32, device=dev),
     }
-    nbytes = L.drnmf_cell_backward_workspace_bytes(C.byref(desc))
+    nbytes = _capi.lib().drnmf_cell_backward_workspace_bytes(C.byref(desc))
     bws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    args = (h, C.byref(desc), _capi.ptr(x), _capi.ptr(params),
-            _capi.ptr(log_h0), float(u[0]), float(u[1]), float(u[2]),
-            _capi.ptr(hall), _capi.ptr(d_out), _capi.ptr(fwd_workspace),
-            fwd_workspace.numel(), _capi.ptr(bws), nbytes,
-            _capi.ptr(out["d_log_D"]), _capi.ptr(out["d_log_alph"]),
-            _capi.ptr(out["d_log_lam1"]), _capi.ptr(out["d_log_h0"]), _stream())
+    # every entry: head, its step parameters (u, or beta for the KL / beta cell), [the entering state], tail
+    head = (C.byref(desc), _capi.ptr(x), _capi.ptr(params), _capi.ptr(log_h0))
+    step = (float(u[0]), float(u[1]), float(u[2]))
+    tail = (_capi.ptr(hall), _capi.ptr(d_out), _capi.ptr(fwd_workspace), fwd_workspace.numel(), _capi.ptr(bws),
+            nbytes, _capi.ptr(out["d_log_D"]), _capi.ptr(out["d_log_alph"]), _capi.ptr(out["d_log_lam1"]),
+            _capi.ptr(out["d_log_h0"]))
+    ista = desc.divergence != _capi.DIV_ED
+    if ista:
+        step = (float(1.5 if beta is None else beta),)
     if initial_state is not None:
         if profile is not None:
             raise NotImplementedError("stateful BPTT: unprofiled")
-        if tuple(initial_state.shape) != (desc.B, desc.N) or initial_state.dtype != torch.float32 \
-                or not initial_state.is_contiguous():
-            raise ValueError("initial_state must be a contiguous float32 (B,N) tensor")
-        if desc.divergence != _capi.DIV_ED:
-            rc = L.drnmf_cell_backward_ista_stateful(
-                h, C.byref(desc), _capi.ptr(x), _capi.ptr(params), _capi.ptr(log_h0),
-                float(1.5 if beta is None else beta), _capi.ptr(initial_state), _capi.ptr(hall),
-                _capi.ptr(d_out), _capi.ptr(fwd_workspace), fwd_workspace.numel(), _capi.ptr(bws), nbytes,
-                _capi.ptr(out["d_log_D"]), _capi.ptr(out["d_log_alph"]), _capi.ptr(out["d_log_lam1"]),
-                _capi.ptr(out["d_log_h0"]), _stream())
-            _capi.check(rc, h, "drnmf_cell_backward_ista_stateful")
-        else:
-            rc = L.drnmf_cell_backward_stateful(*(args[:8] + (_capi.ptr(initial_state),) + args[8:]))
-            _capi.check(rc, h, "drnmf_cell_backward_stateful")
-    elif desc.divergence != _capi.DIV_ED:
-        rc = L.drnmf_cell_backward_ista(
-            h, C.byref(desc), _capi.ptr(x), _capi.ptr(params), _capi.ptr(log_h0),
-            float(1.5 if beta is None else beta), _capi.ptr(hall), _capi.ptr(d_out),
-            _capi.ptr(fwd_workspace), fwd_workspace.numel(), _capi.ptr(bws), nbytes,
-            _capi.ptr(out["d_log_D"]), _capi.ptr(out["d_log_alph"]), _capi.ptr(out["d_log_lam1"]),
-            _capi.ptr(out["d_log_h0"]), _stream())
-        _capi.check(rc, h, "drnmf_cell_backward_ista")
+        _check_state(initial_state, (desc.B, desc.N), dev, "initial_state")
+        _call("drnmf_cell_backward_ista_stateful" if ista else "drnmf_cell_backward_stateful", di, *head, *step,
+              _capi.ptr(initial_state), *tail)
+    elif ista:
+        _call("drnmf_cell_backward_ista", di, *head, *step, *tail)
     elif profile is not None:
         res = (C.c_float * 3)()
-        rc = L.drnmf_cell_backward_profile(*(args + (res,)))
-        _capi.check(rc, h, "drnmf_cell_backward_profile")
+        # (the stream is not this entry's last argument)
+        _call("drnmf_cell_backward_profile", di, *head, *step, *tail, _stream(), res, stream=False)
         profile.update(chain_ms=float(res[0]), batched_ms=float(res[1]),
                        chain_launches=int(res[2]))
     else:
-        rc = L.drnmf_cell_backward(*args)
-        _capi.check(rc, h, "drnmf_cell_backward")
+        _call("drnmf_cell_backward", di, *head, *step, *tail)
     return out
 
 
 def adam_step(param, grad, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(param))
+    dev = _dev_index(param)
     for t in (param, grad, m, v):
         if t.dtype != torch.float32 or not t.is_contiguous():
             raise ValueError("adam_step needs contiguous float32 tensors")
-    rc = L.drnmf_adam_step(h, param.numel(), _capi.ptr(param), _capi.ptr(grad), _capi.ptr(m),
-                           _capi.ptr(v), float(lr_t), float(beta1), float(beta2), float(eps),
-                           float(grad_scale), _stream())
-    _capi.check(rc, h, "drnmf_adam_step")
+    _call("drnmf_adam_step", dev, param.numel(), _capi.ptr(param), _capi.ptr(grad), _capi.ptr(m), _capi.ptr(v),
+          float(lr_t), float(beta1), float(beta2), float(eps), float(grad_scale))
 
 
 def sumsq(g):
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(g))
-    out = torch.empty(256, dtype=torch.float32, device=g.device)
-    rc = L.drnmf_sumsq(h, g.numel(), _capi.ptr(_f32c(g, "g")), _capi.ptr(out), _stream())
-    _capi.check(rc, h, "drnmf_sumsq")
-    return float(out.cpu().numpy().astype(np.float64).sum())     # 256 partials, summed on the host
+    # 256 partials, summed on the host
+    return float(sumsq_partials(g).cpu().numpy().astype(np.float64).sum())
 
 
 def sumsq_partials(g, out=None):
     """256 partial sums of g^2 left ON THE DEVICE (the global-norm clip of adam_step_flat reads them)."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(g))
-    if out is None:
-        out = torch.empty(256, dtype=torch.float32, device=g.device)
-    rc = L.drnmf_sumsq(h, g.numel(), _capi.ptr(_f32c(g, "g")), _capi.ptr(out), _stream())
-    _capi.check(rc, h, "drnmf_sumsq")
+    dev = _dev_index(g)
+    out = _out(out, (256,), torch.float32, g.device)
+    _call("drnmf_sumsq", dev, g.numel(), _capi.ptr(_f32c(g, "g")), _capi.ptr(out))
     return out
 
 
@@ -597,14 +544,10 @@ def adam_step_flat(table, n_blocks, flat_grad, flat_m, flat_v, scalars4, lr_t, b
     """ONE launch for the whole optimiser step; scale, clip and the fault guard are evaluated on the
     device from `scalars4` = [sum w*mse, count, frames, fault] (see include/drnmf.h).  `report`: 4 floats
     of device-accessible memory (e.g. a pinned host tensor) that receive [loss, fault, scale, count]."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(flat_grad))
-    rc = L.drnmf_adam_step_flat(h, int(n_blocks), _capi.ptr(table), _capi.ptr(flat_grad),
-                                _capi.ptr(flat_m), _capi.ptr(flat_v), _capi.ptr(scalars4),
-                                _capi.ptr(sumsq256), float(lr_t), float(beta1), float(beta2),
-                                float(eps), float(clipnorm), 1 if keras204 else 0, float(reg_loss),
-                                report if isinstance(report, int) else _capi.ptr(report), _stream())
-    _capi.check(rc, h, "drnmf_adam_step_flat")
+    _call("drnmf_adam_step_flat", _dev_index(flat_grad), int(n_blocks), _capi.ptr(table), _capi.ptr(flat_grad),
+          _capi.ptr(flat_m), _capi.ptr(flat_v), _capi.ptr(scalars4), _capi.ptr(sumsq256), float(lr_t), float(beta1),
+          float(beta2), float(eps), float(clipnorm), 1 if keras204 else 0, float(reg_loss),
+          report if isinstance(report, int) else _capi.ptr(report))
 
 
 def adam_step_flat_counted(table, n_blocks, flat_grad, flat_m, flat_v, scalars4, lr, decay, step_in, step_out,
@@ -612,15 +555,11 @@ def adam_step_flat_counted(table, n_blocks, flat_grad, flat_m, flat_v, scalars4,
                            sumsq256=None, report=None):
     """adam_step_flat with the step count on the device: `step_in` / `step_out` are two DIFFERENT one-element
     float32 device tensors (applied steps before / after this launch); lr_t is evaluated by the launch."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(flat_grad))
-    rc = L.drnmf_adam_step_flat_counted(h, int(n_blocks), _capi.ptr(table), _capi.ptr(flat_grad),
-                                        _capi.ptr(flat_m), _capi.ptr(flat_v), _capi.ptr(scalars4),
-                                        _capi.ptr(sumsq256), float(lr), float(decay), float(beta1), float(beta2),
-                                        float(eps), float(clipnorm), 1 if keras204 else 0, float(reg_loss),
-                                        _capi.ptr(step_in), _capi.ptr(step_out),
-                                        report if isinstance(report, int) else _capi.ptr(report), _stream())
-    _capi.check(rc, h, "drnmf_adam_step_flat_counted")
+    _call("drnmf_adam_step_flat_counted", _dev_index(flat_grad), int(n_blocks), _capi.ptr(table),
+          _capi.ptr(flat_grad), _capi.ptr(flat_m), _capi.ptr(flat_v), _capi.ptr(scalars4), _capi.ptr(sumsq256),
+          float(lr), float(decay), float(beta1), float(beta2), float(eps), float(clipnorm), 1 if keras204 else 0,
+          float(reg_loss), _capi.ptr(step_in), _capi.ptr(step_out),
+          report if isinstance(report, int) else _capi.ptr(report))
 
 
 _report_rings = {}
@@ -631,11 +570,9 @@ def host_report_ring(device):
     address is a valid `report` argument of adam_step_flat."""
     dev = _dev_of(device)
     if dev not in _report_rings:
-        L = _capi.lib()
-        h = _capi.handle(dev)
         p = C.POINTER(C.c_float)()
         n = C.c_int32(0)
-        _capi.check(L.drnmf_host_report_ring(h, C.byref(p), C.byref(n)), h, "drnmf_host_report_ring")
+        _call("drnmf_host_report_ring", dev, C.byref(p), C.byref(n), stream=False)
         arr = np.ctypeslib.as_array(p, shape=(int(n.value), 4))
         _report_rings[dev] = (arr, C.addressof(p.contents))
     return _report_rings[dev]
@@ -644,9 +581,7 @@ def host_report_ring(device):
 def check_status(device):
     """Raise if an EARLIER, already synchronised call on this device's handle suffered an asynchronous
     fault (a persistent chain that timed out: its output is invalid).  Reads and clears the flag."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_of(device))
-    _capi.check(L.drnmf_check_status(h), h, "drnmf_check_status")
+    _call("drnmf_check_status", _dev_of(device), stream=False)
 
 
 def persist_admitted(device):
@@ -665,9 +600,7 @@ def persist_admit_reason(device):
 def status_take(dst):
     """Stream-ordered: adds 1.0 to the one-element device tensor `dst` if the handle's fault word is
     raised, and clears it (no synchronisation)."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(dst))
-    _capi.check(L.drnmf_status_take_device(h, _capi.ptr(dst), _stream()), h, "drnmf_status_take_device")
+    _call("drnmf_status_take_device", _dev_index(dst), _capi.ptr(dst))
 
 
 def reload_env():
@@ -684,11 +617,10 @@ def set_matrix_mode(mode, device=None):
     per operand, six bf16 MFMAs per product, fp32 accumulate).  Returns the previous mode's name."""
     if mode not in MATRIX_MODES:
         raise ValueError("matrix mode must be one of %s" % sorted(MATRIX_MODES))
-    L = _capi.lib()
-    h = _capi.handle(torch.cuda.current_device() if device is None else _dev_of(device))
-    prev = L.drnmf_get_matrix_mode(h)
-    _capi.check(L.drnmf_set_matrix_mode(h, MATRIX_MODES[mode]), h, "drnmf_set_matrix_mode")
-    return {v: k for k, v in MATRIX_MODES.items()}[prev]
+    dev = torch.cuda.current_device() if device is None else _dev_of(device)
+    prev = get_matrix_mode(dev)
+    _call("drnmf_set_matrix_mode", dev, MATRIX_MODES[mode], stream=False)
+    return prev
 
 
 def get_matrix_mode(device=None):
@@ -699,27 +631,22 @@ def get_matrix_mode(device=None):
 
 def divide_a_by_aplusb(A, B):
     """exp(log(1e-7+A) - log(1e-7+A+B)) (custom_layers.py:41-45), elementwise."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(A))
+    dev = _dev_index(A)
     A, B = _f32c(A, "A"), _f32c(B, "B")
     if A.shape != B.shape:
         raise ValueError("A and B must have the same shape")
     out = torch.empty_like(A)
-    rc = L.drnmf_divide_a_by_aplusb(h, A.numel(), _capi.ptr(A), _capi.ptr(B), _capi.ptr(out),
-                                    _stream())
-    _capi.check(rc, h, "drnmf_divide_a_by_aplusb")
+    _call("drnmf_divide_a_by_aplusb", dev, A.numel(), _capi.ptr(A), _capi.ptr(B), _capi.ptr(out))
     return out
 
 
 def add(a, b):
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(a))
+    dev = _dev_index(a)
     a, b = _f32c(a, "a"), _f32c(b, "b")
     if a.shape != b.shape:
         raise ValueError("a and b must have the same shape")
     out = torch.empty_like(a)
-    rc = L.drnmf_add(h, a.numel(), _capi.ptr(a), _capi.ptr(b), _capi.ptr(out), _stream())
-    _capi.check(rc, h, "drnmf_add")
+    _call("drnmf_add", dev, a.numel(), _capi.ptr(a), _capi.ptr(b), _capi.ptr(out))
     return out
 
 
@@ -727,51 +654,41 @@ def loss_forward(y, w, x_raw=None, mask=None, A=None, Bn=None, hidden=None, l1_w
     """Validation loss sums {sum_rows w*loss_row, #rows with w != 0} (device tensor of 2 floats).
     mask given: mean_F (x_raw*mask - y)^2;  A, Bn, hidden given: the SNMF pretraining cost
     0.5 mean_F (A+Bn-y)^2 + l1_weight * mean_N |hidden| (enhance.py:1027-1035)."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(y))
+    dev = _dev_index(y)
     F = y.shape[-1]
     rows = y.numel() // F
     y, w = _f32c(y, "y"), _f32c(w, "w")
     if w.numel() != rows:
         raise ValueError("w must have one weight per row")
     sums = torch.empty(2, dtype=torch.float32, device=y.device)
-    ws = torch.empty(L.drnmf_loss_forward_workspace_bytes(rows), dtype=torch.uint8, device=y.device)
+    ws = torch.empty(_capi.lib().drnmf_loss_forward_workspace_bytes(rows), dtype=torch.uint8, device=y.device)
     if mask is not None:
         x_raw, mask = _f32c(x_raw, "x_raw"), _f32c(mask, "mask")
-        rc = L.drnmf_loss_forward(h, rows, F, 0, _capi.ptr(x_raw), _capi.ptr(mask), None,
-                                  _capi.ptr(y), _capi.ptr(w), None, 0, 0, 0.0, _capi.ptr(sums),
-                                  _capi.ptr(ws), ws.numel(), _stream())
+        _call("drnmf_loss_forward", dev, rows, F, 0, _capi.ptr(x_raw), _capi.ptr(mask), None, _capi.ptr(y),
+              _capi.ptr(w), None, 0, 0, 0.0, _capi.ptr(sums), _capi.ptr(ws), ws.numel())
     else:
         A, Bn, hidden = _f32c(A, "A"), _f32c(Bn, "Bn"), _f32c(hidden, "hidden")
         N2 = hidden.shape[-1]
-        rc = L.drnmf_loss_forward(h, rows, F, 1, None, _capi.ptr(A), _capi.ptr(Bn), _capi.ptr(y),
-                                  _capi.ptr(w), _capi.ptr(hidden), N2, N2, float(l1_weight),
-                                  _capi.ptr(sums), _capi.ptr(ws), ws.numel(), _stream())
-    _capi.check(rc, h, "drnmf_loss_forward")
+        _call("drnmf_loss_forward", dev, rows, F, 1, None, _capi.ptr(A), _capi.ptr(Bn), _capi.ptr(y), _capi.ptr(w),
+              _capi.ptr(hidden), N2, N2, float(l1_weight), _capi.ptr(sums), _capi.ptr(ws), ws.numel())
     return sums
 
 
 def ista_forward(X, W, H, lam1, alph, K, divergence="ed", beta=2.0):
     """Frame-parallel ISTA (enhance.py:402-456) in row layout: X [n,F], W [F,N], H [n,N] updated
     IN PLACE and returned."""
-    L = _capi.lib()
     dev = _dev_index(X)
-    h = _capi.handle(dev)
     X, W = _f32c(X, "X"), _f32c(W, "W")
-    if H.dtype != torch.float32 or not H.is_contiguous():
-        raise ValueError("H must be a contiguous float32 tensor (updated in place)")
     n, F = X.shape
     N = W.shape[1]
-    if W.shape[0] != F or tuple(H.shape) != (n, N):
+    _given(H, (n, N), torch.float32, X.device, "H (updated in place)")
+    if W.shape[0] != F:
         raise ValueError("shape mismatch: X %s W %s H %s" % (tuple(X.shape), tuple(W.shape),
                                                               tuple(H.shape)))
-    div = {"ed": _capi.DIV_ED, "kl": _capi.DIV_KL, "beta": _capi.DIV_BETA}[divergence]
-    nbytes = L.drnmf_ista_workspace_bytes(n, F, N)
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=X.device)
-    rc = L.drnmf_ista_forward(h, n, F, N, int(K), div, float(beta), float(lam1), float(alph),
-                              _capi.ptr(X), _capi.ptr(W), _capi.ptr(H), _capi.ptr(ws), nbytes,
-                              _stream())
-    _capi.check(rc, h, "drnmf_ista_forward")
+    nbytes = _capi.lib().drnmf_ista_workspace_bytes(n, F, N)
+    ws = _workspace(nbytes, X.device)
+    _call("drnmf_ista_forward", dev, n, F, N, int(K), DIVERGENCES[divergence], float(beta), float(lam1),
+          float(alph), _capi.ptr(X), _capi.ptr(W), _capi.ptr(H), _capi.ptr(ws), nbytes)
     return H
 
 
@@ -779,25 +696,20 @@ def mu_forward(V, W, H, sparsity, n_iter, beta=2.0, want_irm=False):
     """SNMF inference by multiplicative updates, W fixed (sparse_nmf_gpu.m:163-173, 210-229) in
     row layout: V [n,F], W [F,N], H [n,N] (initial value in, result out, in place).
     Returns (H, Wn[, irm])."""
-    L = _capi.lib()
     dev = _dev_index(V)
-    h = _capi.handle(dev)
     V, W = _f32c(V, "V"), _f32c(W, "W")
-    if H.dtype != torch.float32 or not H.is_contiguous():
-        raise ValueError("H must be a contiguous float32 tensor (updated in place)")
     n, F = V.shape
     N = W.shape[1]
-    if W.shape[0] != F or tuple(H.shape) != (n, N):
+    _given(H, (n, N), torch.float32, V.device, "H (updated in place)")
+    if W.shape[0] != F:
         raise ValueError("shape mismatch: V %s W %s H %s" % (tuple(V.shape), tuple(W.shape),
                                                               tuple(H.shape)))
     Wn = torch.empty_like(W)
     irm = torch.empty((n, F), dtype=torch.float32, device=V.device) if want_irm else None
-    nbytes = L.drnmf_mu_workspace_bytes(n, F, N)
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=V.device)
-    rc = L.drnmf_mu_forward(h, n, F, N, int(n_iter), float(beta), float(sparsity), _capi.ptr(V),
-                            _capi.ptr(W), _capi.ptr(Wn), _capi.ptr(H), _capi.ptr(irm),
-                            _capi.ptr(ws), nbytes, _stream())
-    _capi.check(rc, h, "drnmf_mu_forward")
+    nbytes = _capi.lib().drnmf_mu_workspace_bytes(n, F, N)
+    ws = _workspace(nbytes, V.device)
+    _call("drnmf_mu_forward", dev, n, F, N, int(n_iter), float(beta), float(sparsity), _capi.ptr(V), _capi.ptr(W),
+          _capi.ptr(Wn), _capi.ptr(H), _capi.ptr(irm), _capi.ptr(ws), nbytes)
     return (H, Wn, irm) if want_irm else (H, Wn)
 
 
@@ -823,15 +735,12 @@ def snmf_mask_workspace(path, B, T, F, N, beta, device, have=None):
     path decision meets the sizing."""
     if snmf_mask_path(path, int(B) * int(T), F, N, beta) == "tile":
         return None
-    need = _capi.lib().drnmf_snmf_mask_workspace_bytes(int(B), int(T), int(F), int(N))
-    if have is not None and have.numel() >= need and have.device == torch.device(device):
-        return have
-    return torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    return _workspace(_capi.lib().drnmf_snmf_mask_workspace_bytes(int(B), int(T), int(F), int(N)), device, have)
 
 
 def _snmf_args(x, Wn, h_init, out, dict16=None):
-    """The argument checks `snmf_mask_forward` and `snmf_f16_forward` share -> (lib, handle, x, Wn, h_init, out) with
-    the three inputs contiguous float32 and out [B,T,F] (allocated when None).  dict16: checked against Wn when given."""
+    """The argument checks the SNMF family's forwards share -> (device index, x, Wn, h_init, out) with the three
+    inputs contiguous float32 and out [B,T,F] (allocated when None).  dict16: checked against Wn when given."""
     if x.dim() != 3 or Wn.dim() != 2 or Wn.shape[0] != x.shape[2] or tuple(h_init.shape) != (Wn.shape[1],):
         raise ValueError("shape mismatch: x %s Wn %s h_init %s" % (tuple(x.shape), tuple(Wn.shape),
                                                                     tuple(h_init.shape)))
@@ -843,14 +752,9 @@ def _snmf_args(x, Wn, h_init, out, dict16=None):
                                not dict16.is_contiguous()):
         raise ValueError("dict16 must be snmf_f16_pack_dict(Wn): contiguous float16 %s, got %s %s" %
                          ((F, (N + 31) // 32 * 32), dict16.dtype, tuple(dict16.shape)))
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(x))
+    dev = _dev_index(x)
     x, Wn, h_init = _f32c(x, "x"), _f32c(Wn, "Wn"), _f32c(h_init, "h_init")
-    if out is None:
-        out = torch.empty((B, T, F), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, T, F) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous float32 tensor of shape %s" % ((B, T, F),))
-    return L, h, x, Wn, h_init, out
+    return dev, x, Wn, h_init, _out(out, (B, T, F), torch.float32, x.device)
 
 
 def snmf_mask_forward(x, Wn, h_init, sparsity, n_iter, beta=2.0, power=1.0, mask_value=None, path="auto",
@@ -863,16 +767,13 @@ def snmf_mask_forward(x, Wn, h_init, sparsity, n_iter, beta=2.0, power=1.0, mask
     here when None or too small)."""
     if path not in _capi.SNMF_PATHS:
         raise ValueError("path must be 'auto', 'gemm' or 'tile' (got %r)" % (path,))
-    L, h, x, Wn, h_init, out = _snmf_args(x, Wn, h_init, out)
+    dev, x, Wn, h_init, out = _snmf_args(x, Wn, h_init, out)
     B, T, F = x.shape
     N = Wn.shape[1]
     workspace = snmf_mask_workspace(path, B, T, F, N, beta, x.device, have=workspace)
-    rc = L.drnmf_snmf_mask_forward(h, B, T, F, N, int(n_iter), float(beta), float(sparsity), float(power),
-                                   0.0 if mask_value is None else float(mask_value), int(mask_value is not None),
-                                   _capi.ptr(x), _capi.ptr(Wn), _capi.ptr(h_init), _capi.ptr(out),
-                                   _capi.SNMF_PATHS[path], _capi.ptr(workspace),
-                                   0 if workspace is None else workspace.numel(), _stream())
-    _capi.check(rc, h, "drnmf_snmf_mask_forward")
+    _call("drnmf_snmf_mask_forward", dev, B, T, F, N, int(n_iter), float(beta), float(sparsity), float(power),
+          *_mask_pair(mask_value), _capi.ptr(x), _capi.ptr(Wn), _capi.ptr(h_init), _capi.ptr(out),
+          _capi.SNMF_PATHS[path], _capi.ptr(workspace), 0 if workspace is None else workspace.numel())
     return out
 
 
@@ -884,20 +785,13 @@ def snmf_f16_admitted(F, N, beta=2.0):
 def snmf_f16_pack_dict(Wn, out=None):
     """Wn [F,N] float32 -> the dictionary as `snmf_f16_forward` reads it: float16 [F, N rounded up to 32], zero
     behind N (drnmf_snmf_f16_pack_dict)."""
-    L = _capi.lib()
     dev = _dev_index(Wn)
-    h = _capi.handle(dev)
     Wn = _f32c(Wn, "Wn")
     if Wn.dim() != 2:
         raise ValueError("Wn must be [F, N], got %s" % (tuple(Wn.shape),))
     F, N = Wn.shape
-    shape = (F, (N + 31) // 32 * 32)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float16, device=Wn.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float16 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous float16 tensor of shape %s" % (shape,))
-    rc = L.drnmf_snmf_f16_pack_dict(h, F, N, _capi.ptr(Wn), _capi.ptr(out), out.numel() * 2, _stream())
-    _capi.check(rc, h, "drnmf_snmf_f16_pack_dict")
+    out = _out(out, (F, (N + 31) // 32 * 32), torch.float16, Wn.device)
+    _call("drnmf_snmf_f16_pack_dict", dev, F, N, _capi.ptr(Wn), _capi.ptr(out), out.numel() * 2)
     return out
 
 
@@ -906,14 +800,11 @@ def snmf_f16_forward(x, dict16, Wn, h_init, sparsity, n_iter, power=1.0, mask_va
     (drnmf_snmf_f16_forward): x [B,T,F], dict16 = snmf_f16_pack_dict(Wn), Wn [F,N] float32 with unit-norm columns
     (the numerator and the final mask read it), h_init [N] -> mask [B,T,F].  N even and at most 512: ValueError
     otherwise."""
-    L, h, x, Wn, h_init, out = _snmf_args(x, Wn, h_init, out, dict16=dict16)
+    dev, x, Wn, h_init, out = _snmf_args(x, Wn, h_init, out, dict16=dict16)
     B, T, F = x.shape
     N = Wn.shape[1]
-    rc = L.drnmf_snmf_f16_forward(h, B, T, F, N, int(n_iter), float(sparsity), float(power),
-                                  0.0 if mask_value is None else float(mask_value), int(mask_value is not None),
-                                  _capi.ptr(x), _capi.ptr(dict16), _capi.ptr(Wn), _capi.ptr(h_init), _capi.ptr(out),
-                                  _stream())
-    _capi.check(rc, h, "drnmf_snmf_f16_forward")
+    _call("drnmf_snmf_f16_forward", dev, B, T, F, N, int(n_iter), float(sparsity), float(power),
+          *_mask_pair(mask_value), _capi.ptr(x), _capi.ptr(dict16), _capi.ptr(Wn), _capi.ptr(h_init), _capi.ptr(out))
     return out
 
 
@@ -934,18 +825,13 @@ def snmf_kl_forward(x, Wn, h_init, sparsity, n_iter, power=1.0, mask_value=None,
     small)."""
     if v_floor is not None and not (float(v_floor) > 0 and float(v_floor) < float("inf")):
         raise ValueError("v_floor must be None or a positive finite number (got %r)" % (v_floor,))
-    L, h, x, Wn, h_init, out = _snmf_args(x, Wn, h_init, out)
+    dev, x, Wn, h_init, out = _snmf_args(x, Wn, h_init, out)
     B, T, F = x.shape
     N = Wn.shape[1]
-    need = L.drnmf_snmf_kl_workspace_bytes()
-    if workspace is None or workspace.numel() < need or workspace.device != x.device or workspace.dtype != torch.uint8:
-        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
-    rc = L.drnmf_snmf_kl_forward(h, B, T, F, N, int(n_iter), float(sparsity), float(power),
-                                 0.0 if mask_value is None else float(mask_value), int(mask_value is not None),
-                                 _capi.ptr(x), _capi.ptr(Wn), _capi.ptr(h_init),
-                                 0.0 if v_floor is None else float(v_floor), _capi.ptr(out), _capi.ptr(workspace),
-                                 workspace.numel(), _stream())
-    _capi.check(rc, h, "drnmf_snmf_kl_forward")
+    workspace = _workspace(_capi.lib().drnmf_snmf_kl_workspace_bytes(), x.device, workspace)
+    _call("drnmf_snmf_kl_forward", dev, B, T, F, N, int(n_iter), float(sparsity), float(power),
+          *_mask_pair(mask_value), _capi.ptr(x), _capi.ptr(Wn), _capi.ptr(h_init),
+          0.0 if v_floor is None else float(v_floor), _capi.ptr(out), _capi.ptr(workspace), workspace.numel())
     return out
 
 
@@ -961,9 +847,7 @@ def snmf_adapt_workspace(B, T, F, N, n_fixed, device, have=None):
     if need == 0:
         raise ValueError("snmf_adapt: shape B=%d T=%d F=%d N=%d n_fixed=%d is not taken (N even, 2 <= N <= %d, "
                          "0 <= n_fixed <= N)" % (B, T, F, N, n_fixed, _capi.SNMF_ADAPT_MAX_N))
-    if have is not None and have.numel() >= need and have.device == torch.device(device):
-        return have
-    return torch.empty(need, dtype=torch.uint8, device=device)
+    return _workspace(need, device, have)
 
 
 def snmf_adapt_forward(x, Wn, hn, sparsity, n_iter, n_fixed, power=1.0, mask_value=None, workspace=None,
@@ -973,17 +857,15 @@ def snmf_adapt_forward(x, Wn, hn, sparsity, n_iter, n_fixed, power=1.0, mask_val
     n_iter iterations, all frames starting from hn [N] -> mask [B,T,F].  return_dictionaries / return_activations
     append the rows' dictionaries [B,F,N] / activations [B,T,N] (normalised basis; 0 at masked frames).  beta == 2
     only; workspace: a uint8 tensor (`snmf_adapt_workspace`; allocated here when None or too small)."""
-    L, h, x, Wn, hn, out = _snmf_args(x, Wn, hn, None)
+    dev, x, Wn, hn, out = _snmf_args(x, Wn, hn, None)
     B, T, F = x.shape
     N = Wn.shape[1]
     workspace = snmf_adapt_workspace(B, T, F, N, n_fixed, x.device, have=workspace)
     Wd = torch.empty((B, F, N), dtype=torch.float32, device=x.device) if return_dictionaries else None
     Ha = torch.empty((B, T, N), dtype=torch.float32, device=x.device) if return_activations else None
-    rc = L.drnmf_snmf_adapt_forward(h, B, T, F, N, int(n_fixed), int(n_iter), float(sparsity), float(power),
-                                    0.0 if mask_value is None else float(mask_value), int(mask_value is not None),
-                                    _capi.ptr(x), _capi.ptr(Wn), _capi.ptr(hn), _capi.ptr(out), _capi.ptr(Wd),
-                                    _capi.ptr(Ha), _capi.ptr(workspace), workspace.numel(), _stream())
-    _capi.check(rc, h, "drnmf_snmf_adapt_forward")
+    _call("drnmf_snmf_adapt_forward", dev, B, T, F, N, int(n_fixed), int(n_iter), float(sparsity), float(power),
+          *_mask_pair(mask_value), _capi.ptr(x), _capi.ptr(Wn), _capi.ptr(hn), _capi.ptr(out), _capi.ptr(Wd),
+          _capi.ptr(Ha), _capi.ptr(workspace), workspace.numel())
     ret = (out,) + ((Wd,) if return_dictionaries else ()) + ((Ha,) if return_activations else ())
     return ret[0] if len(ret) == 1 else ret
 
@@ -1012,8 +894,7 @@ def snmf_online_admitted(F, N, beta=2.0, block=64):
 def snmf_online_reset(state, Wn, rows=None):
     """Every row of `state` -- or, with rows (B booleans), the rows marked -- back to its start: dictionary Wn [F,N]
     (unit-norm columns), statistics and count 0 (drnmf_snmf_online_reset)."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(state.buf))
+    dev = _dev_index(state.buf)
     Wn = _f32c(Wn, "Wn")
     if tuple(Wn.shape) != (state.F, state.N) or Wn.device != state.device:
         raise ValueError("Wn must be [%d, %d] on %s, got %s on %s" % (state.F, state.N, state.device,
@@ -1023,9 +904,8 @@ def snmf_online_reset(state, Wn, rows=None):
         flags = torch.as_tensor(np.asarray(rows, dtype=bool).astype(np.int32).reshape(-1)).to(state.device)
         if flags.numel() != state.B:
             raise ValueError("rows must have %d entries, got %d" % (state.B, flags.numel()))
-    rc = L.drnmf_snmf_online_reset(h, *state._shape(), _capi.ptr(Wn), _capi.ptr(flags), _capi.ptr(state.buf),
-                                   state.buf.numel(), _stream())
-    _capi.check(rc, h, "drnmf_snmf_online_reset")
+    _call("drnmf_snmf_online_reset", dev, *state._shape(), _capi.ptr(Wn), _capi.ptr(flags), _capi.ptr(state.buf),
+          state.buf.numel())
     return state
 
 
@@ -1049,9 +929,7 @@ def snmf_online_workspace(B, T, F, N, n0, block, device, have=None):
     if need == 0:
         raise ValueError("snmf_online: shape B=%d T=%d F=%d N=%d n0=%d block=%d is not taken" %
                          (B, T, F, N, n0, block))
-    if have is not None and have.numel() >= need and have.device == torch.device(device):
-        return have
-    return torch.empty(need, dtype=torch.uint8, device=device)
+    return _workspace(need, device, have)
 
 
 def snmf_online_forward(x, h_init, sparsity, n_iter, n0, state, w_iter=1, forget=1.0, power=1.0, mask_value=None,
@@ -1067,40 +945,31 @@ def snmf_online_forward(x, h_init, sparsity, n_iter, n0, state, w_iter=1, forget
                          (tuple(x.shape), tuple(h_init.shape), state.B, state.F, state.N))
     if int(n0) != state.n0:
         raise ValueError("n0 = %d, the state was made for n0 = %d" % (int(n0), state.n0))
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(x))
+    dev = _dev_index(x)
     x, h_init = _f32c(x, "x"), _f32c(h_init, "h_init")
     B, T, F = x.shape
-    if out is None:
-        out = torch.empty((B, T, F), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, T, F) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous float32 tensor of shape %s" % ((B, T, F),))
+    out = _out(out, (B, T, F), torch.float32, x.device)
     Ha = torch.empty((B, T, state.N), dtype=torch.float32, device=x.device) if return_h else None
     if T == 0:
         return (out, Ha) if return_h else out
     workspace = snmf_online_workspace(B, T, F, state.N, state.n0, state.block, x.device, have=workspace)
-    rc = L.drnmf_snmf_online_forward(h, B, T, F, state.N, state.n0, state.block, int(n_iter), int(w_iter),
-                                     float(sparsity), float(forget), float(power),
-                                     0.0 if mask_value is None else float(mask_value), int(mask_value is not None),
-                                     _capi.ptr(x), _capi.ptr(h_init), _capi.ptr(out), _capi.ptr(Ha),
-                                     _capi.ptr(state.buf), state.buf.numel(), _capi.ptr(workspace),
-                                     workspace.numel(), _stream())
-    _capi.check(rc, h, "drnmf_snmf_online_forward")
+    _call("drnmf_snmf_online_forward", dev, B, T, F, state.N, state.n0, state.block, int(n_iter), int(w_iter),
+          float(sparsity), float(forget), float(power), *_mask_pair(mask_value), _capi.ptr(x), _capi.ptr(h_init),
+          _capi.ptr(out), _capi.ptr(Ha), _capi.ptr(state.buf), state.buf.numel(), _capi.ptr(workspace),
+          workspace.numel())
     return (out, Ha) if return_h else out
 
 
 def _snmf_online_read(state, want_w, want_stats):
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(state.buf))
+    dev = _dev_index(state.buf)
     B, F, N, n0, _ = state._shape()
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=state.device)
     W = new(B, F, N) if want_w else None
     counts = torch.empty((B,), dtype=torch.int64, device=state.device) if want_w else None
     A = new(B, N, N - n0) if want_stats else None
     Bm = new(B, F, N - n0) if want_stats else None
-    rc = L.drnmf_snmf_online_read(h, *state._shape(), _capi.ptr(state.buf), state.buf.numel(), _capi.ptr(W),
-                                  _capi.ptr(counts), _capi.ptr(A), _capi.ptr(Bm), _stream())
-    _capi.check(rc, h, "drnmf_snmf_online_read")
+    _call("drnmf_snmf_online_read", dev, *state._shape(), _capi.ptr(state.buf), state.buf.numel(), _capi.ptr(W),
+          _capi.ptr(counts), _capi.ptr(A), _capi.ptr(Bm))
     return W, counts, A, Bm
 
 
@@ -1122,9 +991,7 @@ def stft_frames(nsampl, N, hop):
 def stft_mag(pcm, N=1024, hop=None):
     """pcm [n_sig, nsampl] int16 (scaled by 1/32768, util.py:29-35) or float32 ->
     |STFT| [n_sig, n_frames, N/2+1] with the sqrt-Hann window (audio_dataset.py:194)."""
-    L = _capi.lib()
     dev = _dev_index(pcm)
-    h = _capi.handle(dev)
     if hop is None:
         hop = N // 2
     if pcm.dim() == 1:
@@ -1135,9 +1002,8 @@ def stft_mag(pcm, N=1024, hop=None):
     n_sig, nsampl = pcm.shape
     nf = stft_frames(nsampl, N, hop)
     mag = torch.empty((n_sig, nf, N // 2 + 1), dtype=torch.float32, device=pcm.device)
-    rc = L.drnmf_stft_mag(h, n_sig, nsampl, int(N), int(hop), int(pcm.dtype == torch.int16),
-                          _capi.ptr(pcm), _capi.ptr(mag), _stream())
-    _capi.check(rc, h, "drnmf_stft_mag")
+    _call("drnmf_stft_mag", dev, n_sig, nsampl, int(N), int(hop), int(pcm.dtype == torch.int16), _capi.ptr(pcm),
+          _capi.ptr(mag))
     return mag
 
 
@@ -1147,8 +1013,7 @@ class SnmfTrainer(object):
     tensor obj = [div, cost]."""
 
     def __init__(self, V, W, H, beta=2.0):
-        self.L = _capi.lib()
-        self.h = _capi.handle(_dev_index(V))
+        self.dev = _dev_index(V)
         self.V, self.W, self.H = _f32c(V, "V"), _f32c(W, "W").clone(), _f32c(H, "H").clone()
         self.n, self.F = self.V.shape
         self.N = self.W.shape[1]
@@ -1156,38 +1021,30 @@ class SnmfTrainer(object):
             raise ValueError("shape mismatch: V %s W %s H %s" % (tuple(V.shape), tuple(W.shape),
                                                                   tuple(H.shape)))
         self.beta = float(beta)
-        self.nbytes = self.L.drnmf_snmf_train_workspace_bytes(self.n, self.F, self.N)
+        self.nbytes = _capi.lib().drnmf_snmf_train_workspace_bytes(self.n, self.F, self.N)
         self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device=V.device)
-        rc = self.L.drnmf_snmf_train_init(self.h, self.n, self.F, self.N, self.beta,
-                                          _capi.ptr(self.V), _capi.ptr(self.W), _capi.ptr(self.H),
-                                          _capi.ptr(self.ws), self.nbytes, _stream())
-        _capi.check(rc, self.h, "drnmf_snmf_train_init")
+        _call("drnmf_snmf_train_init", self.dev, self.n, self.F, self.N, self.beta, _capi.ptr(self.V),
+              _capi.ptr(self.W), _capi.ptr(self.H), _capi.ptr(self.ws), self.nbytes)
 
     def step(self, sparsity, w_update_mask=None, update_w=True, obj=None):
         """obj: a 2-element float32 device tensor (e.g. a row of a preallocated [max_iter, 2] log)
         that receives [div, cost]; allocated here when None.  Nothing is synchronised."""
-        if obj is None:
-            obj = torch.empty(2, dtype=torch.float32, device=self.V.device)
-        elif obj.numel() != 2 or obj.dtype != torch.float32 or not obj.is_contiguous():
-            raise ValueError("obj must be a contiguous float32 tensor of 2 elements")
+        obj = _out(obj, (2,), torch.float32, self.V.device, "obj")
         m = None
         if w_update_mask is not None:
             m = w_update_mask.to(device=self.V.device, dtype=torch.uint8).contiguous()
             if m.numel() != self.N:
                 raise ValueError("w_update_mask must have N entries")
-        rc = self.L.drnmf_snmf_train_step(self.h, self.n, self.F, self.N, self.beta,
-                                          float(sparsity), _capi.ptr(self.W), _capi.ptr(self.H),
-                                          _capi.ptr(m), int(bool(update_w)), _capi.ptr(obj),
-                                          _capi.ptr(self.ws), self.nbytes, _stream())
-        _capi.check(rc, self.h, "drnmf_snmf_train_step")
+        _call("drnmf_snmf_train_step", self.dev, self.n, self.F, self.N, self.beta, float(sparsity),
+              _capi.ptr(self.W), _capi.ptr(self.H), _capi.ptr(m), int(bool(update_w)), _capi.ptr(obj),
+              _capi.ptr(self.ws), self.nbytes)
         return obj
 
 
 def stft(pcm, N=1024, hop=None, want_mag=False):
     """Complex STFT (reference stack convention: conjugated spectrum, util.py:195,351).
     Returns (re, im[, mag]) each [n_sig, n_frames, N/2+1]."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(pcm))
+    dev = _dev_index(pcm)
     if hop is None:
         hop = N // 2
     if pcm.dim() == 1:
@@ -1201,17 +1058,15 @@ def stft(pcm, N=1024, hop=None, want_mag=False):
     re = torch.empty(shape, dtype=torch.float32, device=pcm.device)
     im = torch.empty(shape, dtype=torch.float32, device=pcm.device)
     mag = torch.empty(shape, dtype=torch.float32, device=pcm.device) if want_mag else None
-    rc = L.drnmf_stft(h, n_sig, nsampl, int(N), int(hop), int(pcm.dtype == torch.int16),
-                      _capi.ptr(pcm), _capi.ptr(re), _capi.ptr(im), _capi.ptr(mag), _stream())
-    _capi.check(rc, h, "drnmf_stft")
+    _call("drnmf_stft", dev, n_sig, nsampl, int(N), int(hop), int(pcm.dtype == torch.int16), _capi.ptr(pcm),
+          _capi.ptr(re), _capi.ptr(im), _capi.ptr(mag))
     return (re, im, mag) if want_mag else (re, im)
 
 
 def istft_masked(re, im, mask, nsampl, N, hop):
     """y [n_sig, nsampl] = istft_noDiv(mask * (re + i im)) with the sqrt-Hann synthesis window
     (audio_dataset.py:267-278; util.py:48-169, 203-226).  mask may be None."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(re))
+    dev = _dev_index(re)
     re, im = _f32c(re, "re"), _f32c(im, "im")
     n_sig, nf, F = re.shape
     if F != N // 2 + 1:
@@ -1222,26 +1077,22 @@ def istft_masked(re, im, mask, nsampl, N, hop):
             raise ValueError("mask shape %s != spectrum shape %s" % (tuple(mask.shape),
                                                                      tuple(re.shape)))
     y = torch.empty((n_sig, int(nsampl)), dtype=torch.float32, device=re.device)
-    nbytes = L.drnmf_istft_workspace_bytes(n_sig, nf, int(N))
+    nbytes = _capi.lib().drnmf_istft_workspace_bytes(n_sig, nf, int(N))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=re.device)
-    rc = L.drnmf_istft_masked(h, n_sig, nf, int(nsampl), int(N), int(hop), _capi.ptr(re),
-                              _capi.ptr(im), _capi.ptr(mask), _capi.ptr(y), _capi.ptr(ws), nbytes,
-                              _stream())
-    _capi.check(rc, h, "drnmf_istft_masked")
+    _call("drnmf_istft_masked", dev, n_sig, nf, int(nsampl), int(N), int(hop), _capi.ptr(re), _capi.ptr(im),
+          _capi.ptr(mask), _capi.ptr(y), _capi.ptr(ws), nbytes)
     return y
 
 
 def snr_db(est, ref):
     """Raw SNR per signal (score_audio.m:209)."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(est))
+    dev = _dev_index(est)
     est, ref = _f32c(est, "est"), _f32c(ref, "ref")
     if est.dim() == 1:
         est, ref = est[None], ref[None]
     n_sig, nsampl = est.shape
     out = torch.empty(n_sig, dtype=torch.float32, device=est.device)
-    rc = L.drnmf_snr(h, n_sig, nsampl, _capi.ptr(est), _capi.ptr(ref), _capi.ptr(out), _stream())
-    _capi.check(rc, h, "drnmf_snr")
+    _call("drnmf_snr", dev, n_sig, nsampl, _capi.ptr(est), _capi.ptr(ref), _capi.ptr(out))
     return out
 
 
@@ -1249,8 +1100,7 @@ def toeplitz_solve(r, d):
     """Solve the symmetric Toeplitz systems Toeplitz(r[k]) c[k] = d[k] on the device (Levinson-Durbin, fp64;
     include/drnmf_sdr.h).  r, d: device float64 [n_sys, n] (or 1-D), n <= 2048.  Returns (c, info): c like r,
     info int32 [n_sys] -- 0 solved, 1 r[0] <= 0 or not finite (c = 0), 2 + k the recursion stopped at step k."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(r))
+    dev = _dev_index(r)
     if r.dtype != torch.float64 or d.dtype != torch.float64 or r.shape != d.shape or r.device != d.device:
         raise ValueError("toeplitz_solve: r and d must be float64 tensors of one shape on one device")
     one = r.dim() == 1
@@ -1261,8 +1111,7 @@ def toeplitz_solve(r, d):
     n_sys, n = r2.shape
     c = torch.empty_like(r2)
     info = torch.empty(n_sys, dtype=torch.int32, device=r2.device)
-    rc = L.drnmf_toeplitz_solve(h, n_sys, n, _capi.ptr(r2), _capi.ptr(d2), _capi.ptr(c), _capi.ptr(info), _stream())
-    _capi.check(rc, h, "drnmf_toeplitz_solve")
+    _call("drnmf_toeplitz_solve", dev, n_sys, n, _capi.ptr(r2), _capi.ptr(d2), _capi.ptr(c), _capi.ptr(info))
     return (c[0] if one else c), info
 
 
@@ -1291,16 +1140,13 @@ def _sdr_lengths(lengths, n_sig, width, dev):
 def sdr_ragged_enqueue(est, ref, lengths_dev, flen, out, coef=None, energies=None, r=None, d=None, info=None,
                        workspace=None):
     """drnmf_sdr_ragged on tensors the caller owns and has checked: enqueues, reads nothing back."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(est))
+    dev = _dev_index(est)
     n_sig, stride = est.shape
-    nbytes = L.drnmf_sdr_ragged_workspace_bytes(n_sig, stride, int(flen))
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=est.device)
-    rc = L.drnmf_sdr_ragged(h, n_sig, stride, _capi.ptr(lengths_dev), int(flen), _capi.ptr(est), _capi.ptr(ref),
-                            _capi.ptr(out), _capi.ptr(coef), _capi.ptr(energies), _capi.ptr(r), _capi.ptr(d),
-                            _capi.ptr(info), _capi.ptr(workspace), workspace.numel(), _stream())
-    _capi.check(rc, h, "drnmf_sdr_ragged")
+    nbytes = _capi.lib().drnmf_sdr_ragged_workspace_bytes(n_sig, stride, int(flen))
+    workspace = _workspace(max(nbytes, 256), est.device, workspace)
+    _call("drnmf_sdr_ragged", dev, n_sig, stride, _capi.ptr(lengths_dev), int(flen), _capi.ptr(est), _capi.ptr(ref),
+          _capi.ptr(out), _capi.ptr(coef), _capi.ptr(energies), _capi.ptr(r), _capi.ptr(d), _capi.ptr(info),
+          _capi.ptr(workspace), workspace.numel())
 
 
 def sdr_db(est, ref, flen=512, return_parts=False, lengths=None, solver="host"):
@@ -1318,8 +1164,7 @@ def sdr_db(est, ref, flen=512, return_parts=False, lengths=None, solver="host"):
         raise ValueError("sdr_db: solver must be one of %s (got %r)" % (SDR_SOLVERS, solver))
     if lengths is not None and solver == "host":
         raise ValueError("sdr_db: lengths= needs solver='device' (the host solver scores whole rows)")
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(est))
+    di = _dev_index(est)
     est, ref = _f32c(est, "est"), _f32c(ref, "ref")
     if est.dim() == 1:
         est, ref = est[None], ref[None]
@@ -1343,11 +1188,9 @@ def sdr_db(est, ref, flen=512, return_parts=False, lengths=None, solver="host"):
     f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
     r, d, coef, en = f64(n_sig, flen), f64(n_sig, flen), f64(n_sig, flen), f64(n_sig, 2)
     out = torch.empty(n_sig, dtype=torch.float32, device=dev)
-    nbytes = L.drnmf_sdr_workspace_bytes(n_sig, nsampl, flen)
-    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-    rc = L.drnmf_sdr_corr(h, n_sig, nsampl, flen, _capi.ptr(est), _capi.ptr(ref), _capi.ptr(r),
-                          _capi.ptr(d), _capi.ptr(ws), ws.numel(), _stream())
-    _capi.check(rc, h, "drnmf_sdr_corr")
+    ws = _workspace(max(_capi.lib().drnmf_sdr_workspace_bytes(n_sig, nsampl, flen), 256), dev)
+    _call("drnmf_sdr_corr", di, n_sig, nsampl, flen, _capi.ptr(est), _capi.ptr(ref), _capi.ptr(r), _capi.ptr(d),
+          _capi.ptr(ws), ws.numel())
     rh, dh = r.cpu().numpy(), d.cpu().numpy()
     idx = np.abs(np.arange(flen)[:, None] - np.arange(flen)[None, :])
     ch = np.empty_like(dh)
@@ -1358,24 +1201,19 @@ def sdr_db(est, ref, flen=512, return_parts=False, lengths=None, solver="host"):
         except np.linalg.LinAlgError:          # silent reference: any solution of G c = d
             ch[i] = np.linalg.lstsq(G, dh[i], rcond=None)[0]
     coef.copy_(torch.from_numpy(ch))
-    rc = L.drnmf_sdr_project(h, n_sig, nsampl, flen, _capi.ptr(est), _capi.ptr(ref),
-                             _capi.ptr(coef), _capi.ptr(en), _capi.ptr(out), _capi.ptr(ws),
-                             ws.numel(), _stream())
-    _capi.check(rc, h, "drnmf_sdr_project")
+    _call("drnmf_sdr_project", di, n_sig, nsampl, flen, _capi.ptr(est), _capi.ptr(ref), _capi.ptr(coef),
+          _capi.ptr(en), _capi.ptr(out), _capi.ptr(ws), ws.numel())
     return (out, coef, en) if return_parts else out
 
 
 def to_int16_wav(x):
     """util.wavwrite's float32 -> int16 conversion (util.py:37-45): divide by max|x| if it exceeds
     1, scale by 32767, truncate toward zero (numpy int16 cast)."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(x))
+    dev = _dev_index(x)
     x = _f32c(x, "x")
     out = torch.empty(x.shape, dtype=torch.int16, device=x.device)
-    ws = torch.empty(L.drnmf_wav_int16_workspace_bytes(), dtype=torch.uint8, device=x.device)
-    rc = L.drnmf_wav_int16(h, x.numel(), _capi.ptr(x), _capi.ptr(out), _capi.ptr(ws), ws.numel(),
-                           _stream())
-    _capi.check(rc, h, "drnmf_wav_int16")
+    ws = torch.empty(_capi.lib().drnmf_wav_int16_workspace_bytes(), dtype=torch.uint8, device=x.device)
+    _call("drnmf_wav_int16", dev, x.numel(), _capi.ptr(x), _capi.ptr(out), _capi.ptr(ws), ws.numel())
     return out
 
 
@@ -1424,14 +1262,11 @@ def ragged_out_lengths(lengths, N, hop, crop=False):
 
 def stft_ragged_enqueue(pcm, lengths_dev, sig_index_dev, T, N, hop, mask_value, x, re, im):
     """drnmf_stft_ragged on tensors the caller owns and has checked: enqueues, reads nothing back."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(pcm))
+    dev = _dev_index(pcm)
     n_sig, stride = pcm.shape
-    rc = L.drnmf_stft_ragged(h, n_sig, stride, _capi.ptr(lengths_dev), sig_index_dev.numel(),
-                             _capi.ptr(sig_index_dev), int(T), int(N), int(hop), int(pcm.dtype == torch.int16),
-                             float(mask_value), _capi.ptr(pcm), _capi.ptr(x), _capi.ptr(re), _capi.ptr(im),
-                             _stream())
-    _capi.check(rc, h, "drnmf_stft_ragged")
+    _call("drnmf_stft_ragged", dev, n_sig, stride, _capi.ptr(lengths_dev), sig_index_dev.numel(),
+          _capi.ptr(sig_index_dev), int(T), int(N), int(hop), int(pcm.dtype == torch.int16), float(mask_value),
+          _capi.ptr(pcm), _capi.ptr(x), _capi.ptr(re), _capi.ptr(im))
 
 
 def stft_ragged(pcm, lengths, sig_index=None, T=None, N=512, hop=None, mask_value=-1.0):
@@ -1472,42 +1307,29 @@ def stft_ragged(pcm, lengths, sig_index=None, T=None, N=512, hop=None, mask_valu
 def stft_pair_chunks_enqueue(pcm_x, pcm_y, len_x_dev, len_y_dev, table_dev, T, N, hop, transform, mask_value,
                              x, y, w):
     """drnmf_stft_pair_chunks on tensors the caller owns and has checked: enqueues, reads nothing back."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(pcm_x))
-    rc = L.drnmf_stft_pair_chunks(h, pcm_x.shape[0], pcm_x.shape[1], pcm_y.shape[1], _capi.ptr(len_x_dev),
-                                  _capi.ptr(len_y_dev), table_dev.shape[0], _capi.ptr(table_dev), int(T), int(N),
-                                  int(hop), int(pcm_x.dtype == torch.int16), _capi.TRANSFORMS[transform],
-                                  float(mask_value), _capi.ptr(pcm_x), _capi.ptr(pcm_y), _capi.ptr(x),
-                                  _capi.ptr(y), _capi.ptr(w), _stream())
-    _capi.check(rc, h, "drnmf_stft_pair_chunks")
+    _call("drnmf_stft_pair_chunks", _dev_index(pcm_x), pcm_x.shape[0], pcm_x.shape[1], pcm_y.shape[1],
+          _capi.ptr(len_x_dev), _capi.ptr(len_y_dev), table_dev.shape[0], _capi.ptr(table_dev), int(T), int(N),
+          int(hop), int(pcm_x.dtype == torch.int16), _capi.TRANSFORMS[transform], float(mask_value),
+          _capi.ptr(pcm_x), _capi.ptr(pcm_y), _capi.ptr(x), _capi.ptr(y), _capi.ptr(w))
 
 
 def stft_pair_target_enqueue(pcm_x, pcm_y, len_x_dev, len_y_dev, table_dev, T, N, hop, transform, target,
                               mask_value, x, y, w):
     """drnmf_stft_pair_chunks_target (include/drnmf_target.h) on tensors the caller owns and has checked:
     stft_pair_chunks_enqueue with y = the 'mag' / 'psa' / 'tpsa' target.  Enqueues, reads nothing back."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(pcm_x))
-    rc = L.drnmf_stft_pair_chunks_target(h, pcm_x.shape[0], pcm_x.shape[1], pcm_y.shape[1], _capi.ptr(len_x_dev),
-                                         _capi.ptr(len_y_dev), table_dev.shape[0], _capi.ptr(table_dev), int(T),
-                                         int(N), int(hop), int(pcm_x.dtype == torch.int16),
-                                         _capi.TRANSFORMS[transform], _capi.TARGETS[target], float(mask_value),
-                                         _capi.ptr(pcm_x), _capi.ptr(pcm_y), _capi.ptr(x), _capi.ptr(y),
-                                         _capi.ptr(w), _stream())
-    _capi.check(rc, h, "drnmf_stft_pair_chunks_target")
+    _call("drnmf_stft_pair_chunks_target", _dev_index(pcm_x), pcm_x.shape[0], pcm_x.shape[1], pcm_y.shape[1],
+          _capi.ptr(len_x_dev), _capi.ptr(len_y_dev), table_dev.shape[0], _capi.ptr(table_dev), int(T), int(N),
+          int(hop), int(pcm_x.dtype == torch.int16), _capi.TRANSFORMS[transform], _capi.TARGETS[target],
+          float(mask_value), _capi.ptr(pcm_x), _capi.ptr(pcm_y), _capi.ptr(x), _capi.ptr(y), _capi.ptr(w))
 
 
 def stft_pair_frames_enqueue(pcm_x, pcm_y, len_x_dev, len_y_dev, row0_dev, N, hop, transform, x_frames,
                              y_frames):
     """drnmf_stft_pair_frames on tensors the caller owns and has checked: enqueues, reads nothing back."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(pcm_x))
-    rc = L.drnmf_stft_pair_frames(h, pcm_x.shape[0], pcm_x.shape[1], pcm_y.shape[1], _capi.ptr(len_x_dev),
-                                  _capi.ptr(len_y_dev), _capi.ptr(row0_dev), x_frames.shape[0], int(N), int(hop),
-                                  int(pcm_x.dtype == torch.int16), _capi.TRANSFORMS[transform],
-                                  _capi.ptr(pcm_x), _capi.ptr(pcm_y), _capi.ptr(x_frames), _capi.ptr(y_frames),
-                                  _stream())
-    _capi.check(rc, h, "drnmf_stft_pair_frames")
+    _call("drnmf_stft_pair_frames", _dev_index(pcm_x), pcm_x.shape[0], pcm_x.shape[1], pcm_y.shape[1],
+          _capi.ptr(len_x_dev), _capi.ptr(len_y_dev), _capi.ptr(row0_dev), x_frames.shape[0], int(N), int(hop),
+          int(pcm_x.dtype == torch.int16), _capi.TRANSFORMS[transform], _capi.ptr(pcm_x), _capi.ptr(pcm_y),
+          _capi.ptr(x_frames), _capi.ptr(y_frames))
 
 
 def _check_wav_pairs(noisy, clean, N, hop, transform, what):
@@ -1646,10 +1468,7 @@ def _mix_table(t, n, dtype, name):
 def mix_workspace(n_sig, stride, device, have=None):
     """The workspace of mix_energy / mix_forward for n_sig signals of `stride` samples (`have`: kept if it is
     large enough)."""
-    need = int(_capi.lib().drnmf_mix_workspace_bytes(int(n_sig), int(stride)))
-    if have is not None and have.numel() >= need and have.dtype == torch.uint8:
-        return have
-    return torch.empty(need, dtype=torch.uint8, device=device)
+    return _workspace(int(_capi.lib().drnmf_mix_workspace_bytes(int(n_sig), int(stride))), device, have)
 
 
 def mix_energy(pcm, lengths, out=None, workspace=None):
@@ -1659,15 +1478,11 @@ def mix_energy(pcm, lengths, out=None, workspace=None):
     _mix_pcm(pcm, "pcm")
     n, stride = pcm.shape
     _mix_table(lengths, n, torch.int64, "lengths")
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(pcm))
-    if out is None:
-        out = torch.empty(n, dtype=torch.float64, device=pcm.device)
-    _mix_table(out, n, torch.float64, "out")
+    dev = _dev_index(pcm)
+    out = _out(out, (n,), torch.float64, pcm.device)
     ws = mix_workspace(n, stride, pcm.device, workspace)
-    rc = L.drnmf_mix_energy(h, n, stride, _capi.ptr(lengths), int(pcm.dtype == torch.int16), _capi.ptr(pcm),
-                            _capi.ptr(out), _capi.ptr(ws), ws.numel(), _stream())
-    _capi.check(rc, h, "drnmf_mix_energy")
+    _call("drnmf_mix_energy", dev, n, stride, _capi.ptr(lengths), int(pcm.dtype == torch.int16), _capi.ptr(pcm),
+          _capi.ptr(out), _capi.ptr(ws), ws.numel())
     return out
 
 
@@ -1692,23 +1507,17 @@ def mix_forward(speech, len_s, noise, len_n, noise_index, offset, snr_db, speech
     if speech_energy is not None:
         _mix_table(speech_energy, n, torch.float64, "speech_energy")
     dev = speech.device
-    if out is None:
-        out = torch.empty((n, stride_s), dtype=torch.float32, device=dev)
-    if out.dtype != torch.float32 or tuple(out.shape) != (n, stride_s) or not out.is_contiguous():
-        raise ValueError("out must be a contiguous float32 tensor %s" % ((n, stride_s),))
-    for t in (len_s, noise, len_n, noise_index, offset, snr_db, speech_energy, out):
+    out = _out(out, (n, stride_s), torch.float32, dev)
+    for t in (len_s, noise, len_n, noise_index, offset, snr_db, speech_energy):
         if t is not None and t.device != dev:
             raise ValueError("mix_forward: every tensor must be on %s" % dev)
     gain = torch.empty(n, dtype=torch.float32, device=dev) if return_gain else None
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(speech))
+    di = _dev_index(speech)
     ws = mix_workspace(n, stride_s, dev, workspace)
-    rc = L.drnmf_mix_forward(h, n, stride_s, _capi.ptr(len_s), int(speech.dtype == torch.int16), _capi.ptr(speech),
-                             m, stride_n, _capi.ptr(len_n), int(noise.dtype == torch.int16), _capi.ptr(noise),
-                             _capi.ptr(noise_index), _capi.ptr(offset), _capi.ptr(snr_db),
-                             _capi.ptr(speech_energy), _capi.ptr(out), _capi.ptr(gain), _capi.ptr(ws), ws.numel(),
-                             _stream())
-    _capi.check(rc, h, "drnmf_mix_forward")
+    _call("drnmf_mix_forward", di, n, stride_s, _capi.ptr(len_s), int(speech.dtype == torch.int16),
+          _capi.ptr(speech), m, stride_n, _capi.ptr(len_n), int(noise.dtype == torch.int16), _capi.ptr(noise),
+          _capi.ptr(noise_index), _capi.ptr(offset), _capi.ptr(snr_db), _capi.ptr(speech_energy), _capi.ptr(out),
+          _capi.ptr(gain), _capi.ptr(ws), ws.numel())
     return (out, gain) if return_gain else out
 
 
@@ -1868,15 +1677,10 @@ class MixBank(object):
             if mask_value is None:
                 mask_value = data.get_mask_value(dict(transform_x=transform, transform_y=transform))
             n_seq, F = table_d.shape[0], int(N) // 2 + 1
-            if out is None:
-                x = torch.empty((n_seq, T, F), dtype=torch.float32, device=self.device)
-                out = (x, torch.empty_like(x), torch.empty((n_seq, T), dtype=torch.float32, device=self.device))
-            x, y, w = out
-            for t, shape in ((x, (n_seq, T, F)), (y, (n_seq, T, F)), (w, (n_seq, T))):
-                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape or \
-                        not t.is_contiguous() or t.device != self.device:
-                    raise ValueError("MixBank.tensors: out must be contiguous float32 tensors %s, %s, %s on %s"
-                                     % ((n_seq, T, F), (n_seq, T, F), (n_seq, T), self.device))
+            x, y, w = (None, None, None) if out is None else out
+            x = _out(x, (n_seq, T, F), torch.float32, self.device, "MixBank.tensors: out[0] (x)")
+            y = _out(y, (n_seq, T, F), torch.float32, self.device, "MixBank.tensors: out[1] (y)")
+            w = _out(w, (n_seq, T), torch.float32, self.device, "MixBank.tensors: out[2] (w)")
             noisy, ln = self.mix(draw)
             if target == 'mag':
                 stft_pair_chunks_enqueue(noisy, self.clean, ln, ln, table_d, T, N, hop, transform, mask_value, x, y, w)
@@ -1913,17 +1717,15 @@ class MixBank(object):
 
 def istft_ragged_enqueue(re, im, mask, lengths_dev, sig_index_dev, N, hop, y, crop, workspace=None):
     """drnmf_istft_ragged on tensors the caller owns and has checked: enqueues, reads nothing back."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(re))
+    dev = _dev_index(re)
     b, T, F = re.shape
-    nbytes = L.drnmf_istft_ragged_workspace_bytes(b, T, int(N), int(hop))
-    if nbytes and (workspace is None or workspace.numel() < nbytes):
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=re.device)
-    rc = L.drnmf_istft_ragged(h, y.shape[0], b, T, int(N), int(hop), _capi.ptr(lengths_dev),
-                              _capi.ptr(sig_index_dev), _capi.ptr(re), _capi.ptr(im), _capi.ptr(mask),
-                              0 if mask is None else mask.stride(1), _capi.ptr(y), y.shape[1], int(bool(crop)),
-                              _capi.ptr(workspace), 0 if workspace is None else workspace.numel(), _stream())
-    _capi.check(rc, h, "drnmf_istft_ragged")
+    nbytes = _capi.lib().drnmf_istft_ragged_workspace_bytes(b, T, int(N), int(hop))
+    if nbytes:                      # (0: the entry needs none, and takes the caller's, or NULL, as it is)
+        workspace = _workspace(nbytes, re.device, workspace)
+    _call("drnmf_istft_ragged", dev, y.shape[0], b, T, int(N), int(hop), _capi.ptr(lengths_dev),
+          _capi.ptr(sig_index_dev), _capi.ptr(re), _capi.ptr(im), _capi.ptr(mask),
+          0 if mask is None else mask.stride(1), _capi.ptr(y), y.shape[1], int(bool(crop)), _capi.ptr(workspace),
+          0 if workspace is None else workspace.numel())
 
 
 def istft_ragged(re, im, mask, lengths, N, hop, sig_index=None, out=None, crop=False):
@@ -1949,8 +1751,8 @@ def istft_ragged(re, im, mask, lengths, N, hop, sig_index=None, out=None, crop=F
     if int(hop) < 1:
         raise ValueError("istft_ragged: hop < 1")
     if out is not None:
-        if out.dim() != 2 or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
-            raise ValueError("istft_ragged: out must be a contiguous float32 [n_sig, width] tensor on %s" % dev)
+        # any [n_sig, width] is taken: (-1, -1) stands for that in the message, and matches no other rank
+        _given(out, tuple(out.shape) if out.dim() == 2 else (-1, -1), torch.float32, dev, "istft_ragged: out")
         n_sig = out.shape[0]
     else:
         n_sig = lengths.numel() if isinstance(lengths, torch.Tensor) else np.asarray(lengths).size
@@ -1966,15 +1768,11 @@ def istft_ragged(re, im, mask, lengths, N, hop, sig_index=None, out=None, crop=F
 
 
 def to_int16_wav_rows_enqueue(y, lengths_dev, out, workspace=None):
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(y))
+    dev = _dev_index(y)
     n_sig, stride = y.shape
-    nbytes = L.drnmf_wav_int16_rows_workspace_bytes(n_sig)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=y.device)
-    rc = L.drnmf_wav_int16_rows(h, n_sig, stride, _capi.ptr(lengths_dev), _capi.ptr(y), _capi.ptr(out),
-                                _capi.ptr(workspace), workspace.numel(), _stream())
-    _capi.check(rc, h, "drnmf_wav_int16_rows")
+    workspace = _workspace(_capi.lib().drnmf_wav_int16_rows_workspace_bytes(n_sig), y.device, workspace)
+    _call("drnmf_wav_int16_rows", dev, n_sig, stride, _capi.ptr(lengths_dev), _capi.ptr(y), _capi.ptr(out),
+          _capi.ptr(workspace), workspace.numel())
 
 
 def to_int16_wav_rows(y, lengths):
@@ -2019,35 +1817,26 @@ def stream_state(B, N, hop, device):
 
 
 def stream_reset_enqueue(state, B, N, hop):
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(state))
-    rc = L.drnmf_stream_reset(h, int(B), int(N), int(hop), _capi.ptr(state), state.numel(), _stream())
-    _capi.check(rc, h, "drnmf_stream_reset")
+    _call("drnmf_stream_reset", _dev_index(state), int(B), int(N), int(hop), _capi.ptr(state), state.numel())
 
 
 def stream_forward_enqueue(chunk, chunk_len_dev, final_dev, N, hop, mask_value, x, re, im, state):
     """drnmf_stream_forward on tensors the caller owns and has checked: enqueues, reads nothing back."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(chunk))
+    dev = _dev_index(chunk)
     B, stride = chunk.shape
-    rc = L.drnmf_stream_forward(h, B, stride, x.shape[1], int(N), int(hop), int(chunk.dtype == torch.int16),
-                                float(mask_value), _capi.ptr(chunk), _capi.ptr(chunk_len_dev),
-                                _capi.ptr(final_dev), _capi.ptr(x), _capi.ptr(re), _capi.ptr(im), _capi.ptr(state),
-                                state.numel(), _stream())
-    _capi.check(rc, h, "drnmf_stream_forward")
+    _call("drnmf_stream_forward", dev, B, stride, x.shape[1], int(N), int(hop), int(chunk.dtype == torch.int16),
+          float(mask_value), _capi.ptr(chunk), _capi.ptr(chunk_len_dev), _capi.ptr(final_dev), _capi.ptr(x),
+          _capi.ptr(re), _capi.ptr(im), _capi.ptr(state), state.numel())
 
 
 def stream_inverse_enqueue(re, im, mask, N, hop, crop, y, state):
     """drnmf_stream_inverse on tensors the caller owns and has checked (y float32 or int16 [B, stride_y]):
     enqueues, reads nothing back."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(re))
+    dev = _dev_index(re)
     B, T, F = re.shape
-    rc = L.drnmf_stream_inverse(h, B, T, int(N), int(hop), _capi.ptr(re), _capi.ptr(im), _capi.ptr(mask),
-                                0 if mask is None else mask.stride(1), int(bool(crop)),
-                                int(y.dtype == torch.int16), _capi.ptr(y), y.shape[1], _capi.ptr(state),
-                                state.numel(), _stream())
-    _capi.check(rc, h, "drnmf_stream_inverse")
+    _call("drnmf_stream_inverse", dev, B, T, int(N), int(hop), _capi.ptr(re), _capi.ptr(im), _capi.ptr(mask),
+          0 if mask is None else mask.stride(1), int(bool(crop)), int(y.dtype == torch.int16), _capi.ptr(y),
+          y.shape[1], _capi.ptr(state), state.numel())
 
 
 class WaveStream(object):
@@ -2219,25 +2008,22 @@ def stoi(est, ref, fs=16000, lengths=None, return_parts=False, extended=False):
     extended=True is `estoi` with the same arguments: ESTOI, not STOI, comes back."""
     if extended:
         return estoi(est, ref, fs, lengths=lengths, return_parts=return_parts)
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(est))
+    di = _dev_index(est)
     est, ref, lh = _stoi_pair_args(est, ref, lengths)
     n_sig, n = est.shape
     max_len = int(lh.max()) if n_sig else 0
     V = stoi_vad_frames(max_len, fs)
     dev = est.device
-    nbytes = L.drnmf_stoi_workspace_bytes(n_sig, max_len, int(fs))
-    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    ws = _workspace(max(_capi.lib().drnmf_stoi_workspace_bytes(n_sig, max_len, int(fs)), 256), dev)
     out = torch.empty(n_sig, dtype=torch.float32, device=dev)
     keep = env_r = env_e = None
     if return_parts:
         keep = torch.zeros((n_sig, V), dtype=torch.uint8, device=dev)
         env_r = torch.zeros((n_sig, max(V - 1, 1), STOI_BANDS), dtype=torch.float32, device=dev)
         env_e = torch.zeros_like(env_r)
-    rc = L.drnmf_stoi(h, n_sig, n, lh.ctypes.data_as(C.POINTER(C.c_int64)), int(fs), _capi.ptr(est),
-                      _capi.ptr(ref), _capi.ptr(out), _capi.ptr(keep if V > 0 else None), _capi.ptr(env_r),
-                      _capi.ptr(env_e), _capi.ptr(ws), ws.numel(), _stream())
-    _capi.check(rc, h, "drnmf_stoi")
+    _call("drnmf_stoi", di, n_sig, n, lh.ctypes.data_as(C.POINTER(C.c_int64)), int(fs), _capi.ptr(est),
+          _capi.ptr(ref), _capi.ptr(out), _capi.ptr(keep if V > 0 else None), _capi.ptr(env_r), _capi.ptr(env_e),
+          _capi.ptr(ws), ws.numel())
     if not return_parts:
         return out
     kb = keep.bool()
@@ -2252,15 +2038,13 @@ def stoi_ext(est, ref, fs=16000, lengths=None, return_parts=False, want_stoi=Tru
     each 30-frame segment (entries past a signal's own n_kept - 30 segments are unspecified)."""
     if not (want_stoi or want_estoi):
         raise ValueError("stoi_ext: nothing to compute (want_stoi and want_estoi are both False)")
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(est))
+    di = _dev_index(est)
     est, ref, lh = _stoi_pair_args(est, ref, lengths)
     n_sig, n = est.shape
     max_len = int(lh.max()) if n_sig else 0
     V = stoi_vad_frames(max_len, fs)
     dev = est.device
-    nbytes = L.drnmf_stoi_ext_workspace_bytes(n_sig, max_len, int(fs))
-    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    ws = _workspace(max(_capi.lib().drnmf_stoi_ext_workspace_bytes(n_sig, max_len, int(fs)), 256), dev)
     out_s = torch.empty(n_sig, dtype=torch.float32, device=dev) if want_stoi else None
     out_e = torch.empty(n_sig, dtype=torch.float32, device=dev) if want_estoi else None
     keep = env_r = env_e = d_ext = None
@@ -2269,10 +2053,9 @@ def stoi_ext(est, ref, fs=16000, lengths=None, return_parts=False, want_stoi=Tru
         env_r = torch.zeros((n_sig, max(V - 1, 1), STOI_BANDS), dtype=torch.float32, device=dev)
         env_e = torch.zeros_like(env_r)
         d_ext = torch.zeros((n_sig, max(V - 30, 1)), dtype=torch.float64, device=dev)
-    rc = L.drnmf_stoi_ext(h, n_sig, n, lh.ctypes.data_as(C.POINTER(C.c_int64)), int(fs), _capi.ptr(est),
-                          _capi.ptr(ref), _capi.ptr(out_s), _capi.ptr(out_e), _capi.ptr(keep if V > 0 else None),
-                          _capi.ptr(env_r), _capi.ptr(env_e), _capi.ptr(d_ext), _capi.ptr(ws), ws.numel(), _stream())
-    _capi.check(rc, h, "drnmf_stoi_ext")
+    _call("drnmf_stoi_ext", di, n_sig, n, lh.ctypes.data_as(C.POINTER(C.c_int64)), int(fs), _capi.ptr(est),
+          _capi.ptr(ref), _capi.ptr(out_s), _capi.ptr(out_e), _capi.ptr(keep if V > 0 else None), _capi.ptr(env_r),
+          _capi.ptr(env_e), _capi.ptr(d_ext), _capi.ptr(ws), ws.numel())
     if not return_parts:
         return out_s, out_e
     kb = keep.bool()
@@ -2366,12 +2149,11 @@ def make_lstm_desc(B, T, F, H, K, recurrent_activation="hard_sigmoid", *, operan
 def lstm_prepare_params(desc, kernels, recurrents, biases, w_out, b_out, out=None):
     """Keras layouts: kernels = [kernel_0 [F,4H], kernel_1..K-1 [H,4H]], recurrents [K] x [H,4H], biases [K] x [4H],
     w_out [H,F], b_out [F] (device tensors) -> prepared block (uint8)."""
-    L = _capi.lib()
     K, H, F = desc.K, desc.H, desc.F
     if len(kernels) != K or len(recurrents) != K or len(biases) != K:
         raise ValueError("lstm_prepare_params: K = %d kernels / recurrent kernels / biases expected" % K)
     k0 = _f32c(kernels[0], "kernel_0")
-    h = _capi.handle(_dev_index(k0))
+    dev = _dev_index(k0)
     if tuple(k0.shape) != (F, 4 * H):
         raise ValueError("kernel_0 must have shape (F,4H) = (%d,%d)" % (F, 4 * H))
     for k in range(1, K):
@@ -2386,13 +2168,9 @@ def lstm_prepare_params(desc, kernels, recurrents, biases, w_out, b_out, out=Non
     w_out, b_out = _f32c(w_out, "w_out"), _f32c(b_out, "b_out")
     if tuple(w_out.shape) != (H, F) or tuple(b_out.shape) != (F,):
         raise ValueError("w_out / b_out must have shapes (H,F) / (F,) = (%d,%d) / (%d,)" % (H, F, F))
-    nbytes = L.drnmf_lstm_params_bytes(C.byref(desc))
-    if out is None or out.numel() < nbytes:
-        out = torch.empty(nbytes, dtype=torch.uint8, device=k0.device)
-    rc = L.drnmf_lstm_prepare_params(h, C.byref(desc), _capi.ptr(k0), _capi.ptr(rest), _capi.ptr(rec),
-                                     _capi.ptr(bias), _capi.ptr(w_out), _capi.ptr(b_out), _capi.ptr(out),
-                                     out.numel(), _stream())
-    _capi.check(rc, h, "drnmf_lstm_prepare_params")
+    out = _workspace(_capi.lib().drnmf_lstm_params_bytes(C.byref(desc)), k0.device, out)
+    _call("drnmf_lstm_prepare_params", dev, C.byref(desc), _capi.ptr(k0), _capi.ptr(rest), _capi.ptr(rec),
+          _capi.ptr(bias), _capi.ptr(w_out), _capi.ptr(b_out), _capi.ptr(out), out.numel())
     return out
 
 
@@ -2423,20 +2201,15 @@ def _lstm_state_pair(state, desc, what, device):
         return None, None
     if not isinstance(state, (tuple, list)) or len(state) != 2:
         raise ValueError("%s must be a pair (h, c)" % what)
-    for t, n in zip(state, ("h", "c")):
-        if t is None:
-            continue
-        if t.dtype != torch.float32 or tuple(t.shape) != (desc.K, desc.B, desc.H) or not t.is_contiguous() or \
-                t.device != device:
-            raise ValueError("%s %s must be a contiguous float32 (K,B,H) = (%d,%d,%d) tensor on %s"
-                             % (what, n, desc.K, desc.B, desc.H, device))
+    # (h and c go by the pair's name: no string is built per call on the streaming path)
+    _check_state(state[0], (desc.K, desc.B, desc.H), device, what)
+    _check_state(state[1], (desc.K, desc.B, desc.H), device, what)
     return state[0], state[1]
 
 
 def _lstm_forward_call(entry, x, mask_value, params, desc, out, workspace, initial_state, final_state):
     """lstm_forward and lstm_train_forward: the C entry `entry`, or `entry`_stateful when a state is given."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(x))
+    dev = _dev_index(x)
     x = _f32c(x, "x")
     if tuple(x.shape) != (desc.B, desc.T, desc.F):
         raise ValueError("x has shape %s, descriptor says (%d,%d,%d)" % (tuple(x.shape), desc.B, desc.T, desc.F))
@@ -2444,18 +2217,16 @@ def _lstm_forward_call(entry, x, mask_value, params, desc, out, workspace, initi
         ld = lstm_hidden_ld(desc.H)
         out = torch.empty((desc.B, desc.T, ld), dtype=torch.float32, device=x.device)[..., :desc.H]
     else:
-        ld = _hidden_ld(out, desc, "out")
-    mv = float("nan") if mask_value is None else float(mask_value)
-    tail = (_capi.ptr(out), ld, _capi.ptr(workspace), workspace.numel(), _stream())
+        ld = _hidden_ld(out, desc, "out")       # (rows may be padded: not `_out`'s contiguous test)
+    mv = _mask_nan(mask_value)
+    tail = (_capi.ptr(out), ld, _capi.ptr(workspace), workspace.numel())
     if initial_state is not None or final_state is not None:
-        entry += "_stateful"
         ih, ic = _lstm_state_pair(initial_state, desc, "initial_state", x.device)
         fh, fc = _lstm_state_pair(final_state, desc, "final_state", x.device)
-        rc = getattr(L, entry)(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), _capi.ptr(ih), _capi.ptr(ic),
-                               _capi.ptr(fh), _capi.ptr(fc), *tail)
+        _call(entry + "_stateful", dev, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), _capi.ptr(ih),
+              _capi.ptr(ic), _capi.ptr(fh), _capi.ptr(fc), *tail)
     else:
-        rc = getattr(L, entry)(h, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), *tail)
-    _capi.check(rc, h, entry)
+        _call(entry, dev, C.byref(desc), _capi.ptr(x), mv, _capi.ptr(params), *tail)
     return out
 
 
@@ -2475,16 +2246,10 @@ def lstm_forward(x, mask_value, params, desc, out=None, workspace=None, *, initi
 def lstm_head_forward(hidden, params, desc, out=None):
     """TimeDistributed(Dense(F)) + sigmoid on every frame: hidden [B,T,H] -> [B,T,F].  hidden: contiguous, or
     rows padded to a stride ld as lstm_forward returns them (padding columns finite)."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(hidden))
+    dev = _dev_index(hidden)
     ld = _hidden_ld(hidden, desc, "hidden")
-    if out is None:
-        out = torch.empty((desc.B, desc.T, desc.F), dtype=torch.float32, device=hidden.device)
-    elif tuple(out.shape) != (desc.B, desc.T, desc.F) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous (B,T,F) float32 tensor")
-    rc = L.drnmf_lstm_head_forward(h, C.byref(desc), _capi.ptr(hidden), ld, _capi.ptr(params), _capi.ptr(out),
-                                   _stream())
-    _capi.check(rc, h, "drnmf_lstm_head_forward")
+    out = _out(out, (desc.B, desc.T, desc.F), torch.float32, hidden.device)
+    _call("drnmf_lstm_head_forward", dev, C.byref(desc), _capi.ptr(hidden), ld, _capi.ptr(params), _capi.ptr(out))
     return out
 
 
@@ -2508,21 +2273,17 @@ def lstm_loss_head_backward(y, w, hidden, params, w_out, desc, workspace, sums, 
     """Loss 'mse_of_masked' and the head's backward after lstm_train_forward on the same workspace: writes
     sums [2] = {sum w * mean_F (xm*s - y)^2, #frames with w != 0} (unnormalised), d_hidden [B,T,H], d_w_out [H,F],
     d_b_out [F] (device tensors, overwritten)."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(hidden))
+    dev = _dev_index(hidden)
     y, w, w_out = _f32c(y, "y"), _f32c(w, "sample_weight"), _f32c(w_out, "w_out")
     if tuple(y.shape) != (desc.B, desc.T, desc.F) or tuple(w.shape) != (desc.B, desc.T):
         raise ValueError("y / sample_weight must have shapes (B,T,F) / (B,T)")
     ld = _hidden_ld(hidden, desc, "hidden")
     for t, shp, what in ((sums, (2,), "sums"), (d_hidden, (desc.B, desc.T, desc.H), "d_hidden"),
                          (d_w_out, (desc.H, desc.F), "d_w_out"), (d_b_out, (desc.F,), "d_b_out")):
-        if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous float32 tensor of shape %s" % (what, shp))
-    rc = L.drnmf_lstm_loss_head_backward(h, C.byref(desc), _capi.ptr(y), _capi.ptr(w), _capi.ptr(hidden), ld,
-                                         _capi.ptr(params), _capi.ptr(w_out), _capi.ptr(sums), _capi.ptr(d_hidden),
-                                         _capi.ptr(d_w_out), _capi.ptr(d_b_out), _capi.ptr(workspace),
-                                         workspace.numel(), _stream())
-    _capi.check(rc, h, "drnmf_lstm_loss_head_backward")
+        _given(t, shp, torch.float32, hidden.device, what)
+    _call("drnmf_lstm_loss_head_backward", dev, C.byref(desc), _capi.ptr(y), _capi.ptr(w), _capi.ptr(hidden), ld,
+          _capi.ptr(params), _capi.ptr(w_out), _capi.ptr(sums), _capi.ptr(d_hidden), _capi.ptr(d_w_out),
+          _capi.ptr(d_b_out), _capi.ptr(workspace), workspace.numel())
 
 
 def _ptr_array(ts):
@@ -2532,20 +2293,19 @@ def _ptr_array(ts):
 def lstm_backward(kernels, recurrents, d_hidden, d_kernels, d_recurrents, d_biases, desc, workspace):
     """BPTT after lstm_loss_head_backward on the same workspace: the unnormalised gradients of every layer's
     kernel, recurrent_kernel and bias, written in Keras layout into the given (contiguous float32) tensors."""
-    L = _capi.lib()
-    h = _capi.handle(_dev_index(d_hidden))
+    dev = _dev_index(d_hidden)
     K, H, F = desc.K, desc.H, desc.F
     if not (len(kernels) == len(recurrents) == len(d_kernels) == len(d_recurrents) == len(d_biases) == K):
         raise ValueError("lstm_backward: K = %d tensors per list expected" % K)
     for k in range(K):
         fin = F if k == 0 else H
-        for t, shp in ((kernels[k], (fin, 4 * H)), (recurrents[k], (H, 4 * H)), (d_kernels[k], (fin, 4 * H)),
-                       (d_recurrents[k], (H, 4 * H)), (d_biases[k], (4 * H,))):
-            if tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError("lstm_backward: layer %d expects contiguous float32 %s" % (k, shp))
-    if tuple(d_hidden.shape) != (desc.B, desc.T, H) or not d_hidden.is_contiguous():
-        raise ValueError("d_hidden must be a contiguous (B,T,H) tensor")
-    rc = L.drnmf_lstm_backward(h, C.byref(desc), _ptr_array(kernels), _ptr_array(recurrents), _capi.ptr(d_hidden),
-                               _ptr_array(d_kernels), _ptr_array(d_recurrents), _ptr_array(d_biases),
-                               _capi.ptr(workspace), workspace.numel(), _stream())
-    _capi.check(rc, h, "drnmf_lstm_backward")
+        for t, shp, what in ((kernels[k], (fin, 4 * H), "lstm_backward: kernels[k]"),
+                             (recurrents[k], (H, 4 * H), "lstm_backward: recurrents[k]"),
+                             (d_kernels[k], (fin, 4 * H), "lstm_backward: d_kernels[k]"),
+                             (d_recurrents[k], (H, 4 * H), "lstm_backward: d_recurrents[k]"),
+                             (d_biases[k], (4 * H,), "lstm_backward: d_biases[k]")):
+            _given(t, shp, torch.float32, d_hidden.device, what)
+    _given(d_hidden, (desc.B, desc.T, H), torch.float32, d_hidden.device, "d_hidden")
+    _call("drnmf_lstm_backward", dev, C.byref(desc), _ptr_array(kernels), _ptr_array(recurrents),
+          _capi.ptr(d_hidden), _ptr_array(d_kernels), _ptr_array(d_recurrents), _ptr_array(d_biases),
+          _capi.ptr(workspace), workspace.numel())
