@@ -4,7 +4,7 @@ device-side SDR's in include/drnmf_sdr.h; the training-data front end's in inclu
 STFT / iSTFT's in include/drnmf_stream.h; the sparse-NMF baseline's inference in include/drnmf_snmf.h, on fp16
 operands in include/drnmf_snmf_f16.h, with per-row noise atoms in include/drnmf_snmf_adapt.h, their online
 form in include/drnmf_snmf_online.h, under the KL cost in include/drnmf_snmf_kl.h; ESTOI beside STOI in include/drnmf_estoi.h;
-the device-side mixer's in include/drnmf_mix.h).
+the device-side mixer's in include/drnmf_mix.h; the waveform losses' in include/drnmf_waveloss.h).
 
 The library is the product path: there is NO fallback.  If the shared object is missing or a
 call fails, an exception is raised.
@@ -288,11 +288,24 @@ MIX_SIGNATURES = {
 }
 MIX_BLOCK = 4096                                   # DRNMF_MIX_BLOCK
 
+# name -> (restype, argtypes); mirrors include/drnmf_waveloss.h one to one (a table of its own, like those above)
+WAVELOSS_SIGNATURES = {
+    "drnmf_istft_ragged_vjp": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp,
+                                      _i64, _vp]),
+    "drnmf_wave_loss_workspace_bytes": (_sz, [_i32, _i64]),
+    "drnmf_wave_loss": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "drnmf_head_backward_cot": (_i32, [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64,
+                                       _vp, _vp, _vp, _vp, _sz, _vp]),
+    "drnmf_lstm_head_backward_cot": (_i32, [_vp, _LDP, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+WAVE_LOSSES = {"wave_mse": 0, "si_sdr": 1}     # DRNMF_WAVE_LOSS_*
+WAVE_LOSS_BLOCK = 4096                         # DRNMF_WAVE_LOSS_BLOCK
+
 # every table above, one per header: lib() binds them all (a new header adds its table's name here)
 SIGNATURE_TABLES = (SIGNATURES, LSTM_SIGNATURES, SCORE_SIGNATURES, ENHANCE_SIGNATURES, SDR_SIGNATURES,
                     DATASET_SIGNATURES, STREAM_SIGNATURES, SNMF_SIGNATURES, SNMF_F16_SIGNATURES, TARGET_SIGNATURES,
                     ESTOI_SIGNATURES, SNMF_ADAPT_SIGNATURES, SNMF_KL_SIGNATURES, SNMF_ONLINE_SIGNATURES,
-                    MIX_SIGNATURES)
+                    MIX_SIGNATURES, WAVELOSS_SIGNATURES)
 
 _lib = None
 _handles = {}

@@ -34,9 +34,10 @@ FLAGS = ARCH + (["-DDRNMF_TIMELINE"] if os.environ.get("DRNMF_TIMELINE") else []
          "-mllvm", "-pragma-unroll-threshold=262144"]
 
 
-# Kernels that must not spill: source -> kernel name.  These sources are compiled with
+# Kernels that must not spill: source -> kernel name, or a tuple of names (each must be seen).  These sources are compiled with
 # -Rpass-analysis=kernel-resource-usage and the build fails if a matching kernel reports scratch.
-NO_SCRATCH = {"lstm.hip": "lstm_step_kernel",
+NO_SCRATCH = {# (lstm_cot_rows_kernel: the head's backward for a given mask cotangent, include/drnmf_waveloss.h)
+              "lstm.hip": ("lstm_step_kernel", "lstm_cot_rows_kernel"),
               # the tile kernel keeps H, num and den of its tiles in registers; the pack / zero kernels ride along
               "snmf_mask.hip": "snmf_mask_",
               # its fp16-operand sibling: H (fp32 master), num and den of its tiles in registers as well
@@ -50,7 +51,12 @@ NO_SCRATCH = {"lstm.hip": "lstm_step_kernel",
               # the KL tile kernel: H's numerator of its tiles, the column denominators and a chunk of V in registers
               "snmf_kl.hip": "snmf_kl_",
               # the target kernels keep the noisy member's bins of a frame in registers (up to 27 per lane)
-              "stft.hip": "stft_pair_target_",
+              # (the transposed inverse runs the frame bodies with a register-only epilogue)
+              "stft.hip": ("stft_pair_target_", "istft_vjp_"),
+              # the mask head's backward for a given cotangent
+              "train.hip": "cot_grad_kernel",
+              # the waveform losses: four fp64 accumulators per lane
+              "waveloss.hip": "wave_loss_",
               # the ESTOI segment kernel holds a 30-frame row, then two 15-band columns, of fp64 per lane
               "stoi.hip": "estoi_",
               # the mixer's sample passes hold four quads and an fp64 accumulator per lane; its gain kernel calls pow
@@ -59,20 +65,23 @@ NO_SCRATCH = {"lstm.hip": "lstm_step_kernel",
 
 def _check_no_scratch(src, remarks):
     """remarks: the compiler's stderr of `src`.  Raises if a NO_SCRATCH kernel uses scratch (or none was seen)."""
-    want = NO_SCRATCH[os.path.basename(src)]
-    seen, name = 0, None
+    wants = NO_SCRATCH[os.path.basename(src)]
+    wants = (wants,) if isinstance(wants, str) else wants
+    seen, name = dict.fromkeys(wants, 0), None
     for line in remarks.splitlines():
         m = re.search(r"remark: Function Name: (\S+)", line)
         if m:
             name = m.group(1)
             continue
         m = re.search(r"remark:\s+ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name and want in name:
-            seen += 1
-            if int(m.group(1)) != 0:
-                raise RuntimeError("%s: kernel %s uses %s bytes of scratch per lane" % (src, name, m.group(1)))
-    if not seen:
-        raise RuntimeError("%s: no resource-usage remark for %s" % (src, want))
+        for want in wants:
+            if m and name and want in name:
+                seen[want] += 1
+                if int(m.group(1)) != 0:
+                    raise RuntimeError("%s: kernel %s uses %s bytes of scratch per lane" % (src, name, m.group(1)))
+    for want in wants:
+        if not seen[want]:
+            raise RuntimeError("%s: no resource-usage remark for %s" % (src, want))
 
 
 def _sources():
@@ -84,7 +93,8 @@ def _deps():
         [os.path.join(os.path.dirname(HERE), "include", n) for n in ("drnmf.h", "drnmf_lstm.h", "drnmf_score.h", "drnmf_enhance.h", "drnmf_sdr.h",
                                                                      "drnmf_dataset.h", "drnmf_stream.h", "drnmf_snmf.h", "drnmf_snmf_f16.h",
                                                                      "drnmf_target.h", "drnmf_estoi.h", "drnmf_snmf_adapt.h",
-                                                                     "drnmf_snmf_kl.h", "drnmf_snmf_online.h", "drnmf_mix.h")] + \
+                                                                     "drnmf_snmf_kl.h", "drnmf_snmf_online.h", "drnmf_mix.h",
+                                                                     "drnmf_waveloss.h")] + \
         [os.path.abspath(__file__)]
 
 

@@ -29,6 +29,7 @@
 #include "gemm_nt.h"
 #include "gemm_tn.h"
 #include "../../include/drnmf_lstm.h"
+#include "../../include/drnmf_waveloss.h"
 
 namespace {
 
@@ -906,6 +907,20 @@ lstm_loss_rows_kernel(const float* __restrict__ xz, const float* __restrict__ S,
     }
 }
 
+// lstm_loss_rows_kernel's dpre for a GIVEN cotangent of the head's output (drnmf_lstm_head_backward_cot):
+// dpre = d_mask s (1 - s), zeros in the padding bins; one wave per frame
+__global__ void __launch_bounds__(256)
+lstm_cot_rows_kernel(const float* __restrict__ d_mask, int64_t ld_dm, const float* __restrict__ S,
+                     float* __restrict__ dpre, size_t rows, int F, int Fq) {
+    const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const size_t row = (size_t)blockIdx.x * 4 + wv;
+    if (row >= rows) return;
+    const float* dm = d_mask + row * (size_t)ld_dm;
+    const float* s = S + row * F;
+    float* dp = dpre + row * Fq;
+    for (int f = l; f < Fq; f += 64) dp[f] = f < F ? dm[f] * s[f] * (1.f - s[f]) : 0.f;
+}
+
 // fixed-order fp64 sum of the block partials (deterministic)
 __global__ void __launch_bounds__(256)
 lstm_loss_final_kernel(const float* __restrict__ part, int64_t nblocks, float* __restrict__ sums) {
@@ -1223,6 +1238,35 @@ extern "C" int32_t drnmf_lstm_train_forward_stateful(drnmf_handle_t h, const drn
                                    &st, "lstm_train_forward_stateful");
 }
 
+// The three products behind dpre (W.off_dpre, [B T][Fq] with zero padding bins), shared by the fused loss head and
+// drnmf_lstm_head_backward_cot: d_hidden = dpre . w_out^T, d_w_out = hidden^T dpre, d_b_out = column sums of dpre
+static int32_t lstm_head_products(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const LstmTrainLayout& W, char* ws,
+                                  const float* hidden, int32_t ld_h, const float* w_out, float* d_hidden,
+                                  float* d_w_out, float* d_b_out, hipStream_t stream) {
+    const LstmLayout& L = W.L;
+    const int64_t rows = (int64_t)d->B * d->T;
+    float* dpre = (float*)(ws + W.off_dpre);
+    float* wop = (float*)(ws + W.off_wop);
+    const size_t nw = (size_t)d->H * L.Fq;
+    hipLaunchKernelGGL(lstm_pad_wo_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, stream, w_out, wop,
+                       d->F, L.Fq, nw);
+    DRNMF_HIP(h, hipGetLastError());
+    {   // d_hidden [B T][H] = dpre . w_out^T
+        gemm::Operands g;
+        g.A = dpre;
+        g.Bt = wop;
+        g.M = rows;
+        g.N = d->H;
+        g.K = L.Fq;
+        g.lda = g.ldb = L.Fq;
+        DRNMF_HIP(h, gemm::launch(g, EpiLstmDh{d_hidden, d->H}, stream));
+    }
+    DRNMF_HIP(h, lstm_tn_product(W, ws, hidden, ld_h, lstm_head_k(d, L, ld_h), dpre, L.Fq, L.Fq, rows, d_w_out,
+                                 d->H, d->F, 0, stream));
+    DRNMF_HIP(h, lstm_colsum(W, ws, dpre, L.Fq, L.Fq, rows, d_b_out, d->F, 0, stream));
+    return DRNMF_OK;
+}
+
 extern "C" int32_t drnmf_lstm_loss_head_backward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* y,
                                                  const float* w, const float* hidden, int32_t ld_h,
                                                  const void* params, const float* w_out, float* sums,
@@ -1243,31 +1287,41 @@ extern "C" int32_t drnmf_lstm_loss_head_backward(drnmf_handle_t h, const drnmf_l
     const int64_t rows = (int64_t)d->B * d->T;
     float* S = (float*)(ws + W.off_s);
     float* dpre = (float*)(ws + W.off_dpre);
-    float* wop = (float*)(ws + W.off_wop);
     float* lpart = (float*)(ws + W.off_lpart);
     DRNMF_HIP(h, lstm_head_product(d, L, hidden, ld_h, params, S, stream));
     const int64_t nblocks = (rows + 3) / 4;
     hipLaunchKernelGGL(lstm_loss_rows_kernel, dim3((unsigned)nblocks), dim3(256), 0, stream,
                        (const float*)(ws + W.off_xz), S, y, w, dpre, lpart, (size_t)rows, d->T, d->F, L.Fq);
     hipLaunchKernelGGL(lstm_loss_final_kernel, dim3(1), dim3(256), 0, stream, lpart, nblocks, sums);
-    const size_t nw = (size_t)d->H * L.Fq;
-    hipLaunchKernelGGL(lstm_pad_wo_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, stream, w_out, wop,
-                       d->F, L.Fq, nw);
-    DRNMF_HIP(h, hipGetLastError());
-    {   // d_hidden [B T][H] = dpre . w_out^T
-        gemm::Operands g;
-        g.A = dpre;
-        g.Bt = wop;
-        g.M = rows;
-        g.N = d->H;
-        g.K = L.Fq;
-        g.lda = g.ldb = L.Fq;
-        DRNMF_HIP(h, gemm::launch(g, EpiLstmDh{d_hidden, d->H}, stream));
-    }
-    DRNMF_HIP(h, lstm_tn_product(W, ws, hidden, ld_h, lstm_head_k(d, L, ld_h), dpre, L.Fq, L.Fq, rows, d_w_out,
-                                 d->H, d->F, 0, stream));
-    DRNMF_HIP(h, lstm_colsum(W, ws, dpre, L.Fq, L.Fq, rows, d_b_out, d->F, 0, stream));
-    return DRNMF_OK;
+    return lstm_head_products(h, d, W, ws, hidden, ld_h, w_out, d_hidden, d_w_out, d_b_out, stream);
+}
+
+// include/drnmf_waveloss.h: the same head backward for a given cotangent of the sigmoid output
+extern "C" int32_t drnmf_lstm_head_backward_cot(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* d_mask,
+                                                int64_t ld_dm, const float* hidden, int32_t ld_h,
+                                                const void* params, const float* w_out, float* d_hidden,
+                                                float* d_w_out, float* d_b_out, void* workspace,
+                                                size_t workspace_bytes, void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    LstmTrainLayout W;
+    int rc = validate_train_call(h, d, workspace, workspace_bytes, "lstm_head_backward_cot", &W);
+    if (rc) return rc;
+    if (!d_mask || !hidden || !params || !w_out || !d_hidden || !d_w_out || !d_b_out)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_head_backward_cot: NULL pointer argument");
+    rc = lstm_check_ld_params(h, d, ld_h, params, "lstm_head_backward_cot");
+    if (rc) return rc;
+    if (ld_dm < d->F)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "lstm_head_backward_cot: ld_dm %lld < F %d", (long long)ld_dm, d->F);
+    const LstmLayout& L = W.L;
+    hipStream_t stream = (hipStream_t)stream_;
+    char* ws = (char*)workspace;
+    const int64_t rows = (int64_t)d->B * d->T;
+    float* S = (float*)(ws + W.off_s);
+    DRNMF_HIP(h, lstm_head_product(d, L, hidden, ld_h, params, S, stream));
+    hipLaunchKernelGGL(lstm_cot_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, d_mask, ld_dm,
+                       (const float*)S, (float*)(ws + W.off_dpre), (size_t)rows, d->F, L.Fq);
+    return lstm_head_products(h, d, W, ws, hidden, ld_h, w_out, d_hidden, d_w_out, d_b_out, stream);
 }
 
 extern "C" int32_t drnmf_lstm_backward(drnmf_handle_t h, const drnmf_lstm_desc_t* d, const float* const* kernel,

@@ -17,6 +17,7 @@
 #include "../../include/drnmf_dataset.h"
 #include "../../include/drnmf_target.h"
 #include "../../include/drnmf_stream.h"
+#include "../../include/drnmf_waveloss.h"
 
 namespace {
 
@@ -392,6 +393,7 @@ stft_real_kernel(const void* __restrict__ pcm, int is_int16, int64_t nsampl, int
 //   drnmf_istft_masked              "bad argument", N (UNSUPPORTED), workspace
 //   drnmf_stft_ragged               shape, N, NULL
 //   drnmf_istft_ragged              shape, N, NULL, ld_mask, workspace
+//   drnmf_istft_ragged_vjp          shape, N, NULL, ld_dm
 //   drnmf_stft_pair_chunks          n_seq / T, then check_stft_pair (shape, N, transform, frame overflow), NULL
 //   drnmf_stft_pair_chunks_target   target, the chunks' checks, target needs TRANSFORM_MAG, unbound handle (the
 //                                   only entry that tests h->device)
@@ -984,6 +986,93 @@ __global__ void __launch_bounds__(256) stft_pair_target_kernel(const PairArgs a,
     pair_frame<false>(a, N, smem, &tg);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Transpose of the ragged masked inverse (include/drnmf_waveloss.h): the frame bodies above run on the waveform
+// cotangent g, and the epilogue multiplies each bin of G with the stored spectrum instead of writing it:
+//   d_mask[k] = (c_k / N) (2 hop / N) (re[k] Re G[k] + im[k] Im G[k]),  c_0 = c_{N/2} = 1, else 2.
+// The bodies hand a bin over as PairTarget receives it (re_k, im_k in the stored, conjugated convention); a lane's
+// slot s is bin lane + STEP s in both bodies (the wave body's extra slot M/64 of lane 0 is bin M).  Nothing of G
+// goes through memory, and the magnitude the bodies compute beside it is dead code here.
+template <int SLOTS, int STEP>
+struct VjpBin {
+    static constexpr bool on = true;
+    static constexpr int slots = SLOTS;
+    const float* re;              // the frame's stored spectrum rows
+    const float* im;
+    int lane, half;               // half = N/2
+    float coef;                   // (1 / N) (2 hop / N)
+    __device__ __forceinline__ float bin(int s, float re_k, float im_k, float, float) const {
+        const int k = lane + STEP * s;
+        const float c = (k == 0 || k == half) ? coef : 2.f * coef;
+        return c * (re[k] * re_k + im[k] * im_k);
+    }
+};
+
+// what a workgroup of either kernel knows of slab row k: the row, the samples of g that count and the frames
+struct VjpRow {
+    RaggedRow row;
+    int64_t nout, nfe;
+};
+
+__device__ __forceinline__ VjpRow vjp_row(const int64_t* __restrict__ lengths, const int* __restrict__ sig_index,
+                                          int n_sig, int k, int T, int N, int hop, int crop, int64_t ld_g) {
+    VjpRow v;
+    v.row = ragged_row(lengths, sig_index, n_sig, k, (int64_t)1 << 40, N, hop);      // as the inverse clamps
+    v.nout = v.row.sig < 0 ? 0 : ragged_nout(v.row, N, hop, crop, ld_g);
+    v.nfe = v.row.nf < T ? v.row.nf : T;
+    return v;
+}
+
+template <int R, int P>
+__global__ void __launch_bounds__(256)
+istft_vjp_real_kernel(const float* __restrict__ g, int64_t ld_g, const int64_t* __restrict__ lengths,
+                      const int* __restrict__ sig_index, int n_sig, int T, int logN, int hop, int crop,
+                      const float* __restrict__ re, const float* __restrict__ im, float* __restrict__ d_mask,
+                      int64_t ld_dm) {
+    constexpr int M = RealFft<R, P>::M, N = 2 * M, F = M + 1;
+    __shared__ float2 tw[N / 2];
+    __shared__ float2 bufs[4][RealFft<R, P>::MP];
+    const int tid = threadIdx.x, wv = tid >> 6, j = tid & 63;
+    const int frame = blockIdx.x * 4 + wv, k = blockIdx.y;
+    for (int i = tid; i < N / 2; i += 256) tw[i] = g_twiddle[logN - TAB_LOG_MIN][i];
+    __syncthreads();
+    if (frame >= T) return;                   // (whole waves: no barrier below)
+    const VjpRow v = vjp_row(lengths, sig_index, n_sig, k, T, N, hop, crop, ld_g);
+    const size_t fr = (size_t)k * T + frame, o = fr * (size_t)ld_dm;
+    if (frame >= v.nfe) {                     // no frame of this row: its mask never reached a sample
+        for (int64_t i = j; i < ld_dm; i += 64) d_mask[o + i] = 0.f;
+        return;
+    }
+    for (int64_t i = F + j; i < ld_dm; i += 64) d_mask[o + i] = 0.f;
+    VjpBin<M / 64 + 1, 64> tg{re + fr * F, im + fr * F, j, M,
+                              (2.0f / ((float)N / (float)hop)) / (float)N};
+    stft_real_frame<R, P>(g, 0, (size_t)v.row.sig * ld_g, v.nout, logN, hop, frame, o, d_mask, nullptr, nullptr,
+                          tw, bufs[wv], j, 0, &tg);
+}
+
+// other sizes: one workgroup per (row, frame); thread tid holds bins tid + 256 s, s < 9 (F <= 2049)
+__global__ void __launch_bounds__(256)
+istft_vjp_kernel(const float* __restrict__ g, int64_t ld_g, const int64_t* __restrict__ lengths,
+                 const int* __restrict__ sig_index, int n_sig, int T, int N, int logN, int hop, int crop,
+                 const float* __restrict__ re, const float* __restrict__ im, float* __restrict__ d_mask,
+                 int64_t ld_dm) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float2* buf = (float2*)smem;
+    float2* tw = buf + N;
+    const int tid = threadIdx.x, frame = blockIdx.x, k = blockIdx.y, F = N / 2 + 1;
+    const VjpRow v = vjp_row(lengths, sig_index, n_sig, k, T, N, hop, crop, ld_g);
+    const size_t fr = (size_t)k * T + frame, o = fr * (size_t)ld_dm;
+    if (frame >= v.nfe) {                     // (the whole workgroup: no barrier is skipped by a part of it)
+        for (int64_t i = tid; i < ld_dm; i += 256) d_mask[o + i] = 0.f;
+        return;
+    }
+    for (int64_t i = F + tid; i < ld_dm; i += 256) d_mask[o + i] = 0.f;
+    VjpBin<TAB_N_MAX / 2 / 256 + 1, 256> tg{re + fr * F, im + fr * F, tid, N / 2,
+                                            (2.0f / ((float)N / (float)hop)) / (float)N};
+    stft_frame(g, 0, (size_t)v.row.sig * ld_g, v.nout, N, logN, hop, frame, o, d_mask, nullptr, nullptr, buf, tw,
+               tid, 0, true, &tg);
+}
+
 }  // namespace
 
 extern "C" int32_t drnmf_stft_frames(int64_t nsampl, int32_t N, int32_t hop) {
@@ -1158,6 +1247,39 @@ extern "C" int32_t drnmf_istft_ragged(drnmf_handle_t h, int32_t n_sig, int32_t b
                            re, im, mask, ld_mask, lengths, sig_index, n_sig, T, N, c.logN, hop, frames);
         hipLaunchKernelGGL(overlap_add_ragged_kernel, dim3((unsigned)((stride_y + 255) / 256), (unsigned)b),
                            dim3(256), 0, c.stream, frames, lengths, sig_index, n_sig, T, N, hop, crop, y, stride_y);
+    });
+    DRNMF_HIP(h, hipGetLastError());
+    return DRNMF_OK;
+}
+
+// include/drnmf_waveloss.h: every size is one launch of a frame body with the VjpBin epilogue
+extern "C" int32_t drnmf_istft_ragged_vjp(drnmf_handle_t h, int32_t n_sig, int32_t b, int32_t T, int32_t N,
+                                          int32_t hop, const int64_t* lengths, const int32_t* sig_index,
+                                          const float* re, const float* im, const float* g, int64_t ld_g,
+                                          int32_t crop, float* d_mask, int64_t ld_dm, void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    if (n_sig <= 0 || b <= 0 || b > 65535 || T <= 0 || hop <= 0 || ld_g <= 0 || (crop != 0 && crop != 1))
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG,
+                   "istft_ragged_vjp: bad shape n_sig=%d b=%d (1..65535) T=%d hop=%d ld_g=%lld crop=%d", n_sig, b,
+                   T, hop, (long long)ld_g, crop);
+    if (const int32_t rc = check_fft_size(h, "istft_ragged_vjp", N, DRNMF_ERR_INVALID_ARG)) return rc;
+    if (!lengths || !sig_index || !re || !im || !g || !d_mask)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "istft_ragged_vjp: NULL pointer argument");
+    if (ld_dm < N / 2 + 1)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "istft_ragged_vjp: ld_dm=%lld is below N/2+1=%d", (long long)ld_dm,
+                   N / 2 + 1);
+    FftCall c;
+    if (const int32_t rc = fft_call(h, N, stream_, &c)) return rc;
+    with_fft_size(N, [&](auto s) {
+        using S = decltype(s);
+        if constexpr (S::fast)
+            hipLaunchKernelGGL((istft_vjp_real_kernel<S::R, S::P>), dim3((unsigned)((T + 3) / 4), (unsigned)b),
+                               dim3(256), 0, c.stream, g, ld_g, lengths, sig_index, n_sig, T, c.logN, hop, crop, re,
+                               im, d_mask, ld_dm);
+        else
+            hipLaunchKernelGGL(istft_vjp_kernel, dim3((unsigned)T, (unsigned)b), dim3(256), c.lds, c.stream, g, ld_g,
+                               lengths, sig_index, n_sig, T, N, c.logN, hop, crop, re, im, d_mask, ld_dm);
     });
     DRNMF_HIP(h, hipGetLastError());
     return DRNMF_OK;

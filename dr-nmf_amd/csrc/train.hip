@@ -8,6 +8,7 @@
 // per-rank normalised gradients would be wrong when ranks hold different numbers of valid frames).
 #include "gemm_nt.h"
 #include "gemm_tn.h"
+#include "../../include/drnmf_waveloss.h"
 
 namespace {
 
@@ -70,6 +71,34 @@ loss_grad_kernel(const float* __restrict__ x, const float* __restrict__ mask,
     if (threadIdx.x == 0) {
         part[2 * (size_t)blockIdx.x + 0] = (ssum[0] + ssum[1]) + (ssum[2] + ssum[3]);
         part[2 * (size_t)blockIdx.x + 1] = (scnt[0] + scnt[1]) + (scnt[2] + scnt[3]);
+    }
+}
+
+// loss_grad_kernel's dA, dBn for a GIVEN cotangent of the mask (drnmf_head_backward_cot): a sibling, so that the
+// fused kernel above keeps its instructions; one wave per row, the padding bins zeroed
+__global__ void __launch_bounds__(256)
+cot_grad_kernel(const float* __restrict__ d_mask, int64_t ld_dm, const float* __restrict__ A,
+                const float* __restrict__ Bn, float* __restrict__ dA, float* __restrict__ dBn, int64_t rows,
+                int F, int Fp4, int square) {
+    const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + wv;
+    if (row >= rows) return;
+    for (int f = l; f < Fp4; f += 64) {
+        float da = 0.f, db = 0.f;
+        if (f < F) {
+            const size_t o = (size_t)row * F + f;
+            const float dm = d_mask[(size_t)row * ld_dm + f], a = A[o], b = Bn[o];
+            const float S = 1e-7f + a + b;
+            const float iS2 = 1.f / (S * S);
+            da = dm * b * iS2;                 // d mask / dA  =  Bn / S^2
+            db = -dm * (1e-7f + a) * iS2;      // d mask / dBn = -(eps + A) / S^2
+            if (square) {                      // A = A0^2 (enhance.py:298-299)
+                da *= 2.f * sqrtf(a);
+                db *= 2.f * sqrtf(b);
+            }
+        }
+        dA[(size_t)row * Fp4 + f] = da;
+        dBn[(size_t)row * Fp4 + f] = db;
     }
 }
 
@@ -370,6 +399,44 @@ extern "C" int32_t drnmf_loss_head_backward(drnmf_handle_t h, int64_t rows, int3
     hipLaunchKernelGGL(loss_grad_kernel, dim3((unsigned)L.nblocks), dim3(256), 0, stream, x_raw,
                        mask, A, Bn, y, w, dA, dB, part, rows, F, Fp4, square);
     hipLaunchKernelGGL(final_sums_kernel, dim3(1), dim3(256), 0, stream, part, L.nblocks, sums);
+    DRNMF_HIP(h, hipGetLastError());
+    return head_backward_gemms(h, rows, F, r, hidden, ld_h, h_off, dA, dB, E, P, Fp4, d_hidden,
+                               d_kernel_clean, d_kernel_noise, stream);
+}
+
+// include/drnmf_waveloss.h: the head's backward for a given d_mask; the workspace and the three products of the
+// fused entry (the partial-sum slots of its loss stay unused)
+extern "C" int32_t drnmf_head_backward_cot(drnmf_handle_t h, int64_t rows, int32_t F, int32_t r,
+                                           const float* hidden, int64_t ld_h, int32_t h_off,
+                                           const float* kernel_clean, const float* kernel_noise, int32_t square,
+                                           const float* A, const float* Bn, const float* d_mask, int64_t ld_dm,
+                                           float* d_hidden, float* d_kernel_clean, float* d_kernel_noise,
+                                           void* workspace, size_t workspace_bytes, void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    if (rows <= 0 || F <= 0 || r <= 0 || h_off < 0 || ld_h < h_off + 2 * (int64_t)r || ld_dm < F)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "head_backward_cot: bad shape");
+    if (!hidden || !kernel_clean || !kernel_noise || !A || !Bn || !d_mask || !d_hidden || !d_kernel_clean ||
+        !d_kernel_noise || !workspace)
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "head_backward_cot: NULL pointer argument");
+    const LhWs L = lh_layout(rows, F, r);
+    if (workspace_bytes < L.total)
+        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "head_backward_cot: workspace %zu < required %zu", workspace_bytes,
+                   L.total);
+    hipStream_t stream = (hipStream_t)stream_;
+    char* ws = (char*)workspace;
+    float* E = (float*)(ws + L.off_E);
+    float* dA = (float*)(ws + L.off_dA);
+    float* dB = (float*)(ws + L.off_dB);
+    float* P = (float*)(ws + L.off_P);
+    const int Fp4 = L.Fp4;
+    {
+        const size_t tot = (size_t)2 * r * Fp4;
+        hipLaunchKernelGGL(exp_pad_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
+                           stream, kernel_clean, kernel_noise, E, r, F, Fp4);
+    }
+    hipLaunchKernelGGL(cot_grad_kernel, dim3((unsigned)L.nblocks), dim3(256), 0, stream, d_mask, ld_dm, A, Bn,
+                       dA, dB, rows, F, Fp4, square);
     DRNMF_HIP(h, hipGetLastError());
     return head_backward_gemms(h, rows, F, r, hidden, ld_h, h_off, dA, dB, E, P, Fp4, d_hidden,
                                d_kernel_clean, d_kernel_noise, stream);

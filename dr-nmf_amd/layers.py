@@ -1833,6 +1833,234 @@ class _SequenceModel(object):
         x, y, w = tensors
         return self.fit(x, y, sample_weight=w, validation_data=val, callbacks=callbacks, **fit_kwargs)
 
+    # -- waveform criteria (include/drnmf_waveloss.h): any loss on the mask through loss_and_grads_cot, and the
+    #    SI-SDR / waveform MSE of the masked inverse STFT on top of it.  Whole recordings per row, stateless
+    #    models, float32 operands.
+    def _check_cot(self, what):
+        """What every entry of this section refuses before anything is enqueued."""
+        if self._carries_state():
+            raise NotImplementedError('%s: a stateful model is not trained on a mask cotangent' % what)
+        if not hasattr(self, '_flat'):
+            raise ValueError('%s: compile() the model first' % what)
+
+    def _cot_head_and_bptt(self, x, cot_fn):
+        """Training forward, head, cot_fn, the head's backward for its d_mask and the BPTT into the flat buffer."""
+        raise NotImplementedError('%s has no trainer for a mask cotangent' % type(self).__name__)
+
+    def loss_and_grads_cot(self, x, cot_fn, live=True):
+        """`loss_and_grads` for any criterion on the mask: the training forward and the head, then cot_fn(mask) ->
+        (sums2, d_mask) -- device tensors, sums2 [2] = {sum of the counted losses, their number}, d_mask [B,T,F]
+        the gradient of that SUM with respect to the mask -- then the head's backward for d_mask
+        (ops.head_backward_cot / ops.lstm_head_backward_cot) and the existing BPTT.  The flat buffer's tail becomes
+        [sums2[0], sums2[1], sums2[1], fault]: the optimiser divides by the count, and loss_norm='keras204' is the
+        identity.  Returns the flat buffer."""
+        self._check_cot('loss_and_grads_cot')
+        self._drop_stale_fault()
+        sums2 = self._cot_head_and_bptt(x, cot_fn)
+        ns = self.N_SCALARS
+        if live:
+            self._flat[-ns:-ns + 2].copy_(sums2)
+            self._flat[-2:-1].copy_(sums2[1:2])
+        else:
+            # (a rank whose shard has run out replays a batch: it must add nothing to the all-reduce)
+            self._flat.zero_()
+        self._flat[-1:].fill_(0.0)
+        ops.status_take(self._flat[-1:])
+        return self._flat
+
+    def train_on_batch_custom(self, x, cot_fn):
+        """One optimiser step on a criterion of the caller's: loss_and_grads_cot(x, cot_fn), the all-reduce of
+        `train_on_batch`, the fused Adam.  x [B,T,F] (device tensor or numpy); returns a DeviceLoss, the sum of the
+        counted losses over their number."""
+        from . import dp
+        self._check_cot('train_on_batch_custom')
+        x = x if isinstance(x, torch.Tensor) else \
+            torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self._device())
+        flat = self.loss_and_grads_cot(x, cot_fn)
+        dp.allreduce_sum_(flat)
+        return self.apply_gradients(flat)
+
+    def _check_wave_args(self, what, loss, N, hop):
+        self._check_cot(what)
+        ops._wave_kind(loss, what)
+        if int(N) // 2 + 1 != self._input_width():
+            raise ValueError('%s: N = %d gives %d bins, the model takes %d' % (what, N, int(N) // 2 + 1,
+                                                                              self._input_width()))
+
+    @staticmethod
+    def _wave_pieces(noisy, clean, N, hop, max_samples, what):
+        """The checked pairs, each clipped to its shorter side and cut every max_samples samples (the same places
+        on both sides) into recordings of their own: (noisy rows, clean rows, numpy dtype)."""
+        rx, ry = [np.asarray(v) for v in noisy], [np.asarray(v) for v in clean]
+        if len(rx) == len(ry):
+            for i in range(len(rx)):
+                if rx[i].ndim == 1 and ry[i].ndim == 1:
+                    n = min(rx[i].shape[0], ry[i].shape[0])
+                    rx[i], ry[i] = rx[i][:n], ry[i][:n]
+        rx, ry, dt, _ = ops._check_wav_pairs(rx, ry, N, hop, 'mag', what)
+        if max_samples is not None:
+            m = int(max_samples)
+            if m < 1:
+                raise ValueError('%s: max_samples must be positive' % what)
+            rx = [v[o:o + m] for v in rx for o in range(0, v.shape[0], m)]
+            ry = [v[o:o + m] for v in ry for o in range(0, v.shape[0], m)]
+        return rx, ry, dt
+
+    def _wave_bank(self, noisy, clean, N, hop, max_samples, what):
+        """One upload of both sides: (noisy pcm [n, stride] as given, clean [n, stride] float32 (int16 scaled by
+        1/32768), lengths on the device, lengths on the host)."""
+        rx, ry, dt = self._wave_pieces(noisy, clean, N, hop, max_samples, what)
+        dev = torch.device(self._device())
+        pcm, lens_d = ops._upload_wav_side(rx, dt, dev)
+        ref, _ = ops._upload_wav_side(ry, dt, dev)
+        ref = ref.to(torch.float32) / 32768.0 if ref.dtype == torch.int16 else ref
+        return pcm, ref, lens_d, np.array([v.shape[0] for v in rx], dtype=np.int64)
+
+    def _wave_batch(self, bank, b, N, hop, kind):
+        """Recordings `b` (host indices) of a bank as one batch: (x [b,T,F], cot_fn).  cot_fn(mask) runs the cropped
+        inverse, the loss against the clean rows and the inverse's transpose, and returns (sums2, d_mask);
+        backward=False stops behind the loss (d_mask None)."""
+        pcm, ref, lens_d, lens = bank
+        dev = pcm.device
+        sel = torch.as_tensor(np.asarray(b), dtype=torch.long, device=dev)
+        lb = lens[np.asarray(b)]
+        W = int(lb.max())
+        pcm_b = pcm.index_select(0, sel)[:, :W].contiguous()
+        ref_b = ref.index_select(0, sel)[:, :W].contiguous()
+        len_b = lens_d.index_select(0, sel)
+        nout_b = torch.from_numpy(ops.ragged_out_lengths(lb, N, hop, True)).to(dev)
+        nb, F = len(b), N // 2 + 1
+        T = int(max(ops.stft_frames(int(l), N, hop) for l in lb))
+        idx = torch.arange(nb, dtype=torch.int32, device=dev)
+        x, re, im = (torch.empty((nb, T, F), dtype=torch.float32, device=dev) for _ in range(3))
+        ops.stft_ragged_enqueue(pcm_b, len_b, idx, T, N, hop, self.mask_value, x, re, im)
+
+        def cot_fn(mask, backward=True):
+            if tuple(mask.shape) != (nb, T, F):
+                raise ValueError('the model returns a mask of shape %s for %s' % (tuple(mask.shape), (nb, T, F)))
+            y = torch.empty((nb, W), dtype=torch.float32, device=dev)
+            ops.istft_ragged_enqueue(re, im, mask, len_b, idx, N, hop, y, True)
+            lo, co = (torch.empty((nb,), dtype=torch.float32, device=dev) for _ in range(2))
+            g, sums = torch.empty_like(y), torch.empty((2,), dtype=torch.float32, device=dev)
+            ops.wave_loss_enqueue(y, ref_b, nout_b, ops.WAVE_LOSSES[kind], lo, co, g, sums,
+                                  ops.wave_loss_workspace(nb, W, dev))
+            if not backward:
+                return sums, None
+            d_mask = torch.empty((nb, T, F), dtype=torch.float32, device=dev)
+            ops.istft_ragged_vjp_enqueue(g, re, im, len_b, idx, N, hop, True, d_mask)
+            return sums, d_mask
+        return x, cot_fn
+
+    def train_on_wavs(self, noisy, clean, loss='si_sdr', N=512, hop=128, max_samples=None):
+        """One optimiser step on a waveform criterion.  noisy, clean: lists of 1-D int16 (scaled by 1/32768) or
+        float32 recordings, each pair clipped to its shorter side; recordings longer than max_samples are cut at
+        the same places on both sides into pieces that count as recordings of their own.  One row per recording:
+        ops.stft_ragged prepared as `enhance` prepares it, the training forward, ops.istft_ragged(crop=True),
+        ops.wave_loss ('si_sdr': minus the SI-SDR in dB; 'wave_mse'), ops.istft_ragged_vjp, then
+        train_on_batch_custom's step -- nothing returns to the host.  Returns a DeviceLoss: the mean of the counted
+        recordings' losses.  No enhancement quality is claimed for either criterion."""
+        from . import dp
+        self._check_wave_args('train_on_wavs', loss, N, hop)
+        bank = self._wave_bank(noisy, clean, int(N), int(hop), max_samples, 'train_on_wavs')
+        x, cot_fn = self._wave_batch(bank, np.arange(bank[3].shape[0]), int(N), int(hop), loss)
+        flat = self.loss_and_grads_cot(x, cot_fn)
+        dp.allreduce_sum_(flat)
+        return self.apply_gradients(flat)
+
+    def _test_on_wave_bank(self, bank, batch_size, N, hop, loss, what):
+        from . import dp
+        dev = bank[0].device
+        s4 = torch.zeros(4, dtype=torch.float32, device=dev)
+        self._drop_stale_fault()
+        n = bank[3].shape[0]
+        for lo in range(0, n, int(batch_size)):
+            x, cot_fn = self._wave_batch(bank, np.arange(lo, min(n, lo + int(batch_size))), N, hop, loss)
+            s4[:2].add_(cot_fn(self.forward(x), backward=False)[0])
+        ops.status_take(s4[3:])
+        dp.allreduce_sum_(s4)
+        sse, cnt, _, fault = s4.tolist()
+        if fault != 0.0:
+            raise _capi.DrnmfError('%s: a persistent small-shape chain timed out on at least one rank '
+                                   '(DRNMF_ERR_TIMEOUT); rerun, or set DRNMF_PERSIST=0' % what)
+        return sse / max(cnt, 1.0)
+
+    def test_on_wavs(self, noisy, clean, loss='si_sdr', N=512, hop=128, max_samples=None, batch_size=8):
+        """The criterion of `train_on_wavs` without a step: the mean over the counted recordings of minus the
+        SI-SDR in dB, or of the waveform MSE, of the model's cropped reconstructions (a float)."""
+        what = 'test_on_wavs'
+        if self._carries_state():
+            raise NotImplementedError('%s: a stateful model needs its rows in order and at one length' % what)
+        ops._wave_kind(loss, what)
+        if int(N) // 2 + 1 != self._input_width():
+            raise ValueError('%s: N = %d gives %d bins, the model takes %d' % (what, N, int(N) // 2 + 1,
+                                                                              self._input_width()))
+        if int(batch_size) < 1:
+            raise ValueError('%s: batch_size must be positive' % what)
+        bank = self._wave_bank(noisy, clean, int(N), int(hop), max_samples, what)
+        return self._test_on_wave_bank(bank, batch_size, int(N), int(hop), loss, what)
+
+    def fit_waveform(self, noisy, clean, loss='si_sdr', batch_size=8, epochs=1, validation_wavs=None, callbacks=None,
+                     shuffle=True, seed=0, N=512, hop=128, max_samples=None, verbose=0):
+        """The epoch loop of `fit` over recordings and a waveform criterion: the recordings (and validation_wavs =
+        (noisy, clean), if given) go up once, every step is train_on_wavs' on batch_size of them, val_loss is
+        test_on_wavs' value (minus the mean SI-SDR in dB, or the waveform MSE).  Callbacks and the returned history
+        as `fit`."""
+        from . import dp
+        what = 'fit_waveform'
+        self._check_wave_args(what, loss, N, hop)
+        N, hop, bs = int(N), int(hop), int(batch_size)
+        if bs < 1 or int(epochs) < 0:
+            raise ValueError('%s: batch_size must be positive and epochs not negative' % what)
+        bank = self._wave_bank(noisy, clean, N, hop, max_samples, what)
+        vbank = None if validation_wavs is None else \
+            self._wave_bank(validation_wavs[0], validation_wavs[1], N, hop, max_samples, what)
+        n = bank[3].shape[0]
+        rng = np.random.RandomState(seed)
+        hist = {'loss': [], 'val_loss': []}
+        callbacks = [cb for cb in (callbacks or []) if dp.rank() == 0 or not getattr(cb, 'rank0_only', False)]
+        self.stop_training = False
+        for cb in callbacks:
+            if hasattr(cb, 'set_model'):
+                cb.set_model(self)
+            else:
+                cb.model = self
+            if hasattr(cb, 'on_train_begin'):
+                cb.on_train_begin({})
+        per_batch_cbs = [cb for cb in callbacks if hasattr(cb, 'on_batch_end')]
+        steps = dp.max_over_ranks(epoch_steps(n, bs))
+        for ep in range(int(epochs)):
+            for cb in callbacks:
+                if hasattr(cb, 'on_epoch_begin'):
+                    cb.on_epoch_begin(ep, {})
+            idx = rng.permutation(n) if shuffle else np.arange(n)
+            ep_losses, cnt = [], 0
+            for b, live in epoch_batches(idx, bs, steps):
+                x, cot_fn = self._wave_batch(bank, b, N, hop, loss)
+                flat = self.loss_and_grads_cot(x, cot_fn, live=live)
+                dp.allreduce_sum_(flat)
+                step_loss = self.apply_gradients(flat)
+                ep_losses.append(step_loss)
+                for cb in per_batch_cbs:
+                    cb.on_batch_end(cnt, {'batch': cnt, 'size': len(b), 'loss': float(step_loss)})
+                cnt += 1
+            logs = {'loss': sum(float(l) for l in ep_losses) / max(cnt, 1)}
+            hist['loss'].append(logs['loss'])
+            if vbank is not None:
+                logs['val_loss'] = self._test_on_wave_bank(vbank, bs, N, hop, loss, what)
+                hist['val_loss'].append(logs['val_loss'])
+            if verbose and dp.rank() == 0:
+                print('epoch %d loss %.6f%s' % (ep + 1, logs['loss'],
+                      (' val_loss %.6f' % logs['val_loss']) if vbank is not None else ''))
+            for cb in callbacks:
+                if hasattr(cb, 'on_epoch_end'):
+                    cb.on_epoch_end(ep, logs)
+            if self.stop_training:
+                break
+        for cb in callbacks:
+            if hasattr(cb, 'on_train_end'):
+                cb.on_train_end({})
+        return hist
+
     def _validate(self, validation_data, batch_size, take):
         """Validation loss of fit(), evaluated in mini-batches of `batch_size` sequences as Keras'
         test loop does (enhance.py:1152-1157: model.fit(..., validation_data=...)); the reference's
@@ -2148,6 +2376,20 @@ class UnfoldedSNMFModel(_SequenceModel):
         self._collect_grads(g)
         self._set_scalars(x, live)
         return self._flat
+
+    def _cot_head_and_bptt(self, x, cot_fn):
+        cell = self.cell
+        N, K = cell.output_dim, cell.K_layers
+        hall = cell.forward_train(x, mask_value=self.mask_value)
+        h_off = (K - 1) * N
+        mask, A, Bn = ops.head_forward(hall, self.clean.kernel, self.noise.kernel, square=self.square,
+                                       want_ab=True, h_off=h_off)
+        sums2, d_mask = cot_fn(mask)
+        grads, head_out = self._grad_targets
+        d_hidden, _, _ = ops.head_backward_cot(d_mask, hall, self.clean.kernel, self.noise.kernel, A, Bn,
+                                               square=self.square, h_off=h_off, out=head_out[1:])
+        self._collect_grads(cell.backward(x, hall, d_hidden, grads=grads))
+        return sums2
 
     @staticmethod
     def _reg_coeffs(reg):
@@ -2655,6 +2897,27 @@ class LSTMModel(_SequenceModel):
         self._set_scalars(x, live)
         return self._flat
 
+    def _cot_head_and_bptt(self, x, cot_fn):
+        x = x.float().contiguous()
+        B, T = int(x.shape[0]), int(x.shape[1])
+        desc = self._desc(B, T)
+        params = self._params(desc)
+        need = _capi.lib().drnmf_lstm_train_workspace_bytes(ctypes.byref(desc))
+        if self._train_ws is None or self._train_ws.numel() < need:
+            self._train_ws = None
+            self._train_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if self._d_hidden is None or tuple(self._d_hidden.shape) != (B, T, desc.H):
+            self._d_hidden = torch.empty((B, T, desc.H), dtype=torch.float32, device=self.device)
+        ws, gv, d, ls = self._train_ws, self._gview, self.dense, self.lstms
+        h = ops.lstm_train_forward(x, self.mask_value, params, desc, ws)
+        sums2, d_mask = cot_fn(ops.lstm_head_forward(h, params, desc))
+        ops.lstm_head_backward_cot(d_mask, h, params, d.kernel, desc, ws, self._d_hidden, gv[d.weight_names[0]],
+                                   gv[d.weight_names[1]])
+        ops.lstm_backward([l.kernel for l in ls], [l.recurrent_kernel for l in ls], self._d_hidden,
+                          [gv[l.weight_names[0]] for l in ls], [gv[l.weight_names[1]] for l in ls],
+                          [gv[l.weight_names[2]] for l in ls], desc, ws)
+        return sums2
+
     def _after_step(self):
         self._prepared = None       # Adam moved the weights behind torch's back: repack before the next use
 
@@ -3053,6 +3316,13 @@ class SparseNMFModel(_SequenceModel):
     def fit(self, *args, **kwargs):
         raise NotImplementedError('SparseNMFModel: nothing to fit -- the dictionary is trained by '
                                   'SparseNMFModel.from_wavs (snmf.train_snmf)')
+
+    def _check_cot(self, what):
+        raise NotImplementedError('SparseNMFModel: %s has nothing to train -- the dictionary is trained by '
+                                  'SparseNMFModel.from_wavs (snmf.train_snmf)' % what)
+
+    def test_on_wavs(self, *args, **kwargs):
+        self._check_cot('test_on_wavs')
 
     @classmethod
     def from_wavs(cls, noisy, clean, params_snmf, N=512, hop=128, device=None):

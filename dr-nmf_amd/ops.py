@@ -2309,3 +2309,149 @@ def lstm_backward(kernels, recurrents, d_hidden, d_kernels, d_recurrents, d_bias
     _call("drnmf_lstm_backward", dev, C.byref(desc), _ptr_array(kernels), _ptr_array(recurrents),
           _capi.ptr(d_hidden), _ptr_array(d_kernels), _ptr_array(d_recurrents), _ptr_array(d_biases),
           _capi.ptr(workspace), workspace.numel())
+
+
+# ---- waveform losses (include/drnmf_waveloss.h) ----------------------------------------------------------------
+WAVE_LOSSES = _capi.WAVE_LOSSES
+
+
+def _wave_kind(loss, what):
+    if loss not in WAVE_LOSSES:
+        raise ValueError("%s: loss must be one of %s (got %r)" % (what, sorted(WAVE_LOSSES), loss))
+    return WAVE_LOSSES[loss]
+
+
+def istft_ragged_vjp_enqueue(g, re, im, lengths_dev, sig_index_dev, N, hop, crop, d_mask):
+    """drnmf_istft_ragged_vjp on tensors the caller owns and has checked: enqueues, reads nothing back."""
+    dev = _dev_index(re)
+    b, T, F = re.shape
+    _call("drnmf_istft_ragged_vjp", dev, g.shape[0], b, T, int(N), int(hop), _capi.ptr(lengths_dev),
+          _capi.ptr(sig_index_dev), _capi.ptr(re), _capi.ptr(im), _capi.ptr(g), g.shape[1], int(bool(crop)),
+          _capi.ptr(d_mask), d_mask.stride(1))
+
+
+def istft_ragged_vjp(g, re, im, lengths, N, hop, sig_index=None, crop=False, out=None):
+    """Transpose of `istft_ragged` with respect to its mask: g [n_sig, width] float32, row sig_index[k] the cotangent
+    of slab row k's reconstruction (samples at or behind ragged_out_lengths(lengths, N, hop, crop) count as 0 and
+    are not read); re, im [b, T, N/2+1] as `stft_ragged` returned them.  Returns d_mask [b, T, N/2+1] (`out`: a
+    contiguous tensor of that shape): zeros in the frames behind a row's own.  A row's result is bitwise the same
+    in any batch."""
+    F = N // 2 + 1
+    if re.dim() != 3 or re.shape != im.shape or re.shape[2] != F:
+        raise ValueError("istft_ragged_vjp: re, im must be [b, T, %d] (got %s, %s)" % (F, tuple(re.shape),
+                                                                                      tuple(im.shape)))
+    dev = re.device
+    _dev_index(re)
+    re, im = _f32c(re, "re"), _f32c(im, "im")
+    if g.dim() != 2 or g.dtype != torch.float32 or g.device != dev or im.device != dev:
+        raise ValueError("istft_ragged_vjp: g must be [n_sig, width] float32 on %s" % (dev,))
+    if int(hop) < 1:
+        raise ValueError("istft_ragged_vjp: hop < 1")
+    g = g.contiguous()
+    n_sig = g.shape[0]
+    b, T, _ = re.shape
+    _, ld = _ragged_lengths(lengths, n_sig, 1 << 40, dev, "istft_ragged_vjp")
+    idx = _ragged_index(sig_index, n_sig, dev, "istft_ragged_vjp")
+    if idx.numel() != b:
+        raise ValueError("istft_ragged_vjp: %d slab rows but sig_index names %d" % (b, idx.numel()))
+    out = _out(out, (b, T, F), torch.float32, dev, "istft_ragged_vjp: out")
+    istft_ragged_vjp_enqueue(g, re, im, ld, idx, N, hop, crop, out)
+    return out
+
+
+def wave_loss_workspace(n_sig, width, device, have=None):
+    return _workspace(_capi.lib().drnmf_wave_loss_workspace_bytes(int(n_sig), int(width)), device, have)
+
+
+def wave_loss_enqueue(est, ref, lengths_dev, kind, loss, counted, g, sums, workspace):
+    """drnmf_wave_loss on tensors the caller owns and has checked: enqueues, reads nothing back."""
+    n_sig, width = est.shape
+    _call("drnmf_wave_loss", _dev_index(est), n_sig, width, _capi.ptr(lengths_dev), _capi.ptr(est), _capi.ptr(ref),
+          int(kind), _capi.ptr(loss), _capi.ptr(counted), _capi.ptr(g), _capi.ptr(sums), _capi.ptr(workspace),
+          workspace.numel())
+
+
+def wave_loss(est, ref, lengths, loss='si_sdr', out=None, workspace=None):
+    """Per-row waveform loss between est and ref [n_sig, width] float32, row i valid up to lengths[i] (host ints
+    or a tensor, each in [1, width]).  loss 'wave_mse': mean (est - ref)^2 over the row; 'si_sdr': minus the
+    scale-invariant SDR in dB, -10 log10((p^2/q + eps) / (e - p^2/q + eps)), a row whose reference is digitally
+    silent not counted (loss 0, gradient 0).  Returns (loss [n_sig], counted [n_sig] (1 / 0), g [n_sig, width],
+    sums [2] = {sum of counted losses, their number}) on the device; g is the gradient of that SUM with respect
+    to est, zeros behind a row's length.  `out`: that 4-tuple to write into."""
+    kind = _wave_kind(loss, "wave_loss")
+    if est.dim() != 2 or est.shape != ref.shape or est.dtype != torch.float32 or ref.dtype != torch.float32 or \
+            est.device != ref.device:
+        raise ValueError("wave_loss: est, ref must be float32 [n_sig, width] on one device (got %s %s, %s %s)" %
+                         (est.dtype, tuple(est.shape), ref.dtype, tuple(ref.shape)))
+    dev = est.device
+    _dev_index(est)
+    est, ref = est.contiguous(), ref.contiguous()
+    n_sig, width = est.shape
+    if n_sig < 1 or width < 1:
+        raise ValueError("wave_loss: empty batch")
+    _, ld = _ragged_lengths(lengths, n_sig, width, dev, "wave_loss")
+    lo, co, g, sums = (None, None, None, None) if out is None else out
+    lo = _out(lo, (n_sig,), torch.float32, dev, "wave_loss: loss")
+    co = _out(co, (n_sig,), torch.float32, dev, "wave_loss: counted")
+    g = _out(g, (n_sig, width), torch.float32, dev, "wave_loss: g")
+    sums = _out(sums, (2,), torch.float32, dev, "wave_loss: sums")
+    wave_loss_enqueue(est, ref, ld, kind, lo, co, g, sums, wave_loss_workspace(n_sig, width, dev, workspace))
+    return lo, co, g, sums
+
+
+def _cot_ld(d_mask, shape, dev, what):
+    """Row stride of a mask cotangent [..., F] whose rows may be padded (strides (.., ld, 1), ld >= F)."""
+    if d_mask.dtype != torch.float32 or tuple(d_mask.shape) != shape or d_mask.device != dev:
+        raise ValueError("%s: d_mask must be a float32 tensor of shape %s on %s (got %s %s on %s)" %
+                         (what, shape, dev, d_mask.dtype, tuple(d_mask.shape), d_mask.device))
+    ld = d_mask.stride(-2) if d_mask.dim() >= 2 else shape[-1]
+    ok = d_mask.stride(-1) == 1 and ld >= shape[-1]
+    for i in range(d_mask.dim() - 3, -1, -1):
+        ok = ok and (d_mask.shape[i] == 1 or d_mask.stride(i) == d_mask.stride(i + 1) * d_mask.shape[i + 1])
+    return (d_mask, int(ld)) if ok else (d_mask.contiguous(), shape[-1])
+
+
+def head_backward_cot(d_mask, hidden, kernel_clean, kernel_noise, A, Bn, square=False, h_off=0, out=None,
+                      workspace=None):
+    """The mask head's backward for a given cotangent of the mask (drnmf_head_backward_cot): d_mask [..., F]
+    (rows may be padded), hidden [..., ld], A, Bn [..., F] as head_forward(want_ab=True) returned them.  Returns
+    (d_hidden [..., 2r], d_kernel_clean, d_kernel_noise); `out` = (d_kernel_clean, d_kernel_noise) to write
+    into."""
+    di = _dev_index(hidden)
+    hidden, A, Bn = (_f32c(t, n) for t, n in ((hidden, "hidden"), (A, "A"), (Bn, "Bn")))
+    kc, kn = _f32c(kernel_clean, "kernel_clean"), _f32c(kernel_noise, "kernel_noise")
+    r, F = kc.shape
+    if tuple(kn.shape) != (r, F):
+        raise ValueError("kernel_noise shape %s != kernel_clean shape %s" % (tuple(kn.shape), (r, F)))
+    ld = hidden.shape[-1]
+    rows = hidden.numel() // ld
+    dev = hidden.device
+    if h_off < 0 or ld < h_off + 2 * r or A.numel() != rows * F or Bn.numel() != rows * F:
+        raise ValueError("head_backward_cot: shape mismatch")
+    d_mask, ld_dm = _cot_ld(d_mask, tuple(hidden.shape[:-1]) + (F,), dev, "head_backward_cot")
+    dkc, dkn = (None, None) if out is None else out
+    dkc = _out(dkc, (r, F), torch.float32, dev, "d_kernel_clean")
+    dkn = _out(dkn, (r, F), torch.float32, dev, "d_kernel_noise")
+    d_hidden = torch.empty(tuple(hidden.shape[:-1]) + (2 * r,), dtype=torch.float32, device=dev)
+    ws = _workspace(_capi.lib().drnmf_loss_head_workspace_bytes(rows, F, r), dev, workspace)
+    _call("drnmf_head_backward_cot", di, rows, F, r, _capi.ptr(hidden), ld, int(h_off), _capi.ptr(kc), _capi.ptr(kn),
+          int(bool(square)), _capi.ptr(A), _capi.ptr(Bn), _capi.ptr(d_mask), ld_dm, _capi.ptr(d_hidden),
+          _capi.ptr(dkc), _capi.ptr(dkn), _capi.ptr(ws), ws.numel())
+    return d_hidden, dkc, dkn
+
+
+def lstm_head_backward_cot(d_mask, hidden, params, w_out, desc, workspace, d_hidden, d_w_out, d_b_out):
+    """The sigmoid head's backward for a given cotangent d_mask [B,T,F] of its output, after lstm_train_forward on
+    the same workspace: writes d_hidden [B,T,H], d_w_out [H,F], d_b_out [F] (device tensors, overwritten)."""
+    dev = _dev_index(hidden)
+    if desc.operand_f16:
+        raise ValueError("lstm_head_backward_cot: operand_f16 descriptors are inference only")
+    w_out = _f32c(w_out, "w_out")
+    ld = _hidden_ld(hidden, desc, "hidden")
+    d_mask, ld_dm = _cot_ld(d_mask, (desc.B, desc.T, desc.F), hidden.device, "lstm_head_backward_cot")
+    for t, shp, what in ((d_hidden, (desc.B, desc.T, desc.H), "d_hidden"), (d_w_out, (desc.H, desc.F), "d_w_out"),
+                         (d_b_out, (desc.F,), "d_b_out")):
+        _given(t, shp, torch.float32, hidden.device, what)
+    _call("drnmf_lstm_head_backward_cot", dev, C.byref(desc), _capi.ptr(d_mask), ld_dm, _capi.ptr(hidden), ld,
+          _capi.ptr(params), _capi.ptr(w_out), _capi.ptr(d_hidden), _capi.ptr(d_w_out), _capi.ptr(d_b_out),
+          _capi.ptr(workspace), workspace.numel())
