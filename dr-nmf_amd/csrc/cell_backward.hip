@@ -55,8 +55,13 @@ struct EdgeArgs {
     int ntail;
     int nparts, ppb;         // row-sum partials per row: numA (1 per 32-atom block), or in the Gram
                              // form one per 16-atom output tile (2 per block)
+    const unsigned* bits;    // BITS: relu sign bits of layer K-1's stored hiddens, frame 0 (cell_shared.h)
+    unsigned bits_tstride;   // words per frame
 };
 
+// BITS: [h_{K-1} > 0] comes from the sign bits the training forward recorded (8 bytes per lane, 16 per wave)
+// instead of the stored hidden itself; a template parameter as in bwd_a_kernel.
+template <bool BITS>
 __global__ void __launch_bounds__(256) bwd_edge_kernel(const EdgeArgs a) {
     __shared__ float sm[ROWS][ATOMS + 1];
     const int m = blockIdx.x >> 3;                          // grid layout: see cell_a_kernel
@@ -95,14 +100,21 @@ __global__ void __launch_bounds__(256) bwd_edge_kernel(const EdgeArgs a) {
             if (i < a.ntail) dtl[i] = *(const f32x2*)(a.Dtail_top + (size_t)i * a.Np + n);
         if (pair) {
             dout2 = *(const f32x2*)(a.d_out + ro * a.N + n);
-            h2 = *(const f32x2*)(a.hall + ro * KN + (size_t)(a.K - 1) * a.N + n);
+            if (!BITS) h2 = *(const f32x2*)(a.hall + ro * KN + (size_t)(a.K - 1) * a.N + n);
         } else if (lrow) {
 #pragma unroll
             for (int e = 0; e < 2; ++e)
                 if (n + e < a.N) {
                     dout2[e] = a.d_out[ro * a.N + n + e];
-                    h2[e] = a.hall[ro * KN + (size_t)(a.K - 1) * a.N + n + e];
+                    if (!BITS) h2[e] = a.hall[ro * KN + (size_t)(a.K - 1) * a.N + n + e];
                 }
+        }
+        if (BITS) {     // (padding rows and atoms carry a zero bit, as their h2 stays 0 on the other path)
+            const int l = tid & 63;
+            const u32x2 sb = *(const u32x2*)(a.bits + (size_t)t * a.bits_tstride +
+                                             (((size_t)m * a.numA + ab) * 4 + (tid >> 6)) * 4 + (l >> 5) * 2);
+            h2[0] = ((sb[0] >> (l & 31)) & 1u) ? 1.f : 0.f;
+            h2[1] = ((sb[1] >> (l & 31)) & 1u) ? 1.f : 0.f;
         }
     }
     if (c > 0) {
@@ -216,12 +228,19 @@ struct BwdAArgs {
                              // qred = 1: [MAX_TAIL][Bp], summed by the cell_b launch in between
     float* dq_out;           // [MAX_TAIL][Bp][numA] partials of layer k-1
     int ntail;
+    const unsigned* bits;    // BITS: relu sign bits of layer k-1's stored hiddens, frame 0 (cell_shared.h)
+    unsigned bits_tstride;   // words per frame
 };
 
 // (leading scalar arguments: preloaded into SGPRs, see cell_b_kernel)
 // K0 (KL / beta cell only, layer 0 = a full ISTA step from the state p): the result is d p itself --
 // no relu mask of a previous layer, nothing to store in dz_all -- left in dzp_out for bwd_edge_kernel.
-template <int G, int KS, bool QRED = false, bool K0 = false>
+// BITS: the relu mask [h_{k-1} > 0] is read from the sign bits the training forward recorded -- the same
+// comparison, made once on the value that went to the stored hiddens: 8 bytes per lane (16 per wave) behind
+// the frame counter instead of 512 KB of the stored hiddens per launch at the headline shape.  A template
+// parameter, not a runtime switch (see cell_a_kernel's QRED); the host passes BITS = false wherever the
+// forward recorded none.
+template <int G, int KS, bool QRED = false, bool K0 = false, bool BITS = false>
 __global__ void __launch_bounds__(256)
 bwd_a_kernel(const float* drpart_, const float* Dn_, const int* c_rd_, int Bp_, int Fp_, int Np_,
              int numA_, int nchunks_, const BwdAArgs a_in) {
@@ -297,7 +316,12 @@ bwd_a_kernel(const float* drpart_, const float* Dn_, const int* c_rd_, int Bp_, 
     if ((tid & 15) == 0) dps_old = a.dps_part[po];
     f32x2 hprev = {0.f, 0.f};
     if (K0) hprev = f32x2{1.f, 1.f};
-    else {
+    else if (BITS) {    // (padding rows and atoms carry a zero bit, as their hprev stays 0 on the other path)
+        const u32x2 sb = *(const u32x2*)(a.bits + (size_t)t * a.bits_tstride +
+                                         (((size_t)m * a.numA + ab) * 4 + w) * 4 + (l >> 5) * 2);
+        hprev[0] = ((sb[0] >> (l & 31)) & 1u) ? 1.f : 0.f;
+        hprev[1] = ((sb[1] >> (l & 31)) & 1u) ? 1.f : 0.f;
+    } else {
 #pragma unroll
         for (int e = 0; e < 2; ++e)
             if (rg < a.B && n + e < a.N)
@@ -471,21 +495,26 @@ struct BwdAParams {
         : p{&a.drpart, &a.Dn, &a.c_rd, &a.Bp, &a.Fp, &a.Np, &a.numA, &a.nchunks, &a} {}
 };
 
-template <int KS>
-void* bwd_a_func(int per_wave, bool qred) {
-    if (qred) return per_wave <= 2 ? (void*)&bwd_a_kernel<2, KS, true> : (void*)&bwd_a_kernel<4, KS, true>;
-    if (per_wave <= 2) return (void*)&bwd_a_kernel<2, KS>;
-    return (void*)&bwd_a_kernel<4, KS>;
+template <int KS, bool BITS>
+void* bwd_a_func_b(int per_wave, bool qred) {
+    if (qred) return per_wave <= 2 ? (void*)&bwd_a_kernel<2, KS, true, false, BITS>
+                                   : (void*)&bwd_a_kernel<4, KS, true, false, BITS>;
+    if (per_wave <= 2) return (void*)&bwd_a_kernel<2, KS, false, false, BITS>;
+    return (void*)&bwd_a_kernel<4, KS, false, false, BITS>;
 }
-void* pick_bwd_a(int nchunks, int KS, bool qred = false, bool k0 = false) {
+template <int KS>
+void* bwd_a_func(int per_wave, bool qred, bool bits) {
+    return bits ? bwd_a_func_b<KS, true>(per_wave, qred) : bwd_a_func_b<KS, false>(per_wave, qred);
+}
+void* pick_bwd_a(int nchunks, int KS, bool qred = false, bool k0 = false, bool bits = false) {
     const int per_wave = (nchunks + 3) / 4;
     if (k0)          // (the KL / beta cell: one atom range, no odd-bin side path)
         return per_wave <= 2 ? (void*)&bwd_a_kernel<2, 1, false, true> : (void*)&bwd_a_kernel<4, 1, false, true>;
     switch (KS) {
-        case 1: return bwd_a_func<1>(per_wave, qred);
-        case 2: return bwd_a_func<2>(per_wave, qred);
-        case 4: return bwd_a_func<4>(per_wave, qred);
-        default: return bwd_a_func<8>(per_wave, qred);
+        case 1: return bwd_a_func<1>(per_wave, qred, bits);
+        case 2: return bwd_a_func<2>(per_wave, qred, bits);
+        case 4: return bwd_a_func<4>(per_wave, qred, bits);
+        default: return bwd_a_func<8>(per_wave, qred, bits);
     }
 }
 
@@ -1158,6 +1187,15 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
     ea.ntail = W.gram ? 0 : W.ntail;
     ea.nparts = W.gram ? W.numO : W.numA;
     ea.ppb = W.gram ? 2 : 1;
+    // The relu masks come from the sign bits the forward recorded, where it did: the fp32 factored Euclidean
+    // training forward (the layout's rule and DRNMF_RELU_BITS, as the forward read them: CellCtx::relu_bits).
+    // Everything else -- Gram and persistent chains, the fp16-operand forward, the KL / beta cell -- reads the
+    // stored hiddens.
+    const unsigned* rbits = C.relu_bits;
+    const unsigned rb_tstride = (unsigned)relu_bits_frame_words(K, W.Bp, W.numA);
+    ea.bits = rbits ? rbits + (size_t)(K - 1) * relu_bits_layer_words(W.Bp, W.numA) : nullptr;
+    ea.bits_tstride = rb_tstride;
+    void* const edge_fn = rbits ? (void*)&bwd_edge_kernel<true> : (void*)&bwd_edge_kernel<false>;
     auto make_g = [&](int k) {       // Gram form: one launch per layer-step (cell_gram.h)
         GramBwdArgs g;
         memset(&g, 0, sizeof(g));
@@ -1223,6 +1261,8 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
         a.dq_in = qred ? (const float*)(bw + L.off_dqsum) : dq + (size_t)(k & 1) * dqstride;
         a.dq_out = dq + (size_t)((k - 1) & 1) * dqstride;
         a.ntail = W.ntail;
+        a.bits = (rbits && k >= 1) ? rbits + (size_t)(k - 1) * relu_bits_layer_words(W.Bp, W.numA) : nullptr;
+        a.bits_tstride = rb_tstride;
         return a;
     };
 
@@ -1252,7 +1292,7 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
     // one frame in reverse time: the edge kernel, then the chain down the layers
     auto frame = [&](Launcher& chain, int) -> int32_t {
         void* ke[1] = {&ea};
-        DRNMF_HIP(h, chain.add((void*)&bwd_edge_kernel, grid_a, 256, ke));
+        DRNMF_HIP(h, chain.add(edge_fn, grid_a, 256, ke));
         for (int k = K - 1; k >= kmin; --k) {
             if (W.gram) {
                 GramBwdArgs g = make_g(k);
@@ -1275,7 +1315,7 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
                                        dim3((unsigned)((size_t)W.Bp * W.Fp / 256)), 256, ks));
             }
             BwdAArgs a = make_a(k);
-            DRNMF_HIP(h, chain.add(pick_bwd_a(nft, W.KS, qred, nonlin && k == 0), grid_a, 256, BwdAParams(a).p));
+            DRNMF_HIP(h, chain.add(pick_bwd_a(nft, W.KS, qred, nonlin && k == 0, rbits != nullptr), grid_a, 256, BwdAParams(a).p));
         }
         if (edge_only) {
             int* cp = cA;
@@ -1286,7 +1326,7 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
     };
     if (!persist) {
         const std::vector<uint64_t> key = {
-            (uint64_t)W.gram, (uint64_t)d->divergence, f32_bits(beta), (uint64_t)B, (uint64_t)T, (uint64_t)F, (uint64_t)N,
+            (uint64_t)W.gram + 2 * (uint64_t)(rbits != nullptr), (uint64_t)d->divergence, f32_bits(beta), (uint64_t)B, (uint64_t)T, (uint64_t)F, (uint64_t)N,
             (uint64_t)K, (uint64_t)d->n_D, (uint64_t)(uintptr_t)params, (uint64_t)(uintptr_t)hall,
             (uint64_t)(uintptr_t)d_out, (uint64_t)(uintptr_t)fwd_workspace, (uint64_t)(uintptr_t)bwd_workspace,
             f32_bits(u0_diag), f32_bits(u0_off), f32_bits(uk_off)};
@@ -1295,7 +1335,10 @@ static int32_t cell_backward_impl(drnmf_handle_t h, const drnmf_cell_desc_t* d, 
         const int32_t grc = replay_frames(h, stream, GraphKind::Backward, key, {fpg, 1}, 0, T, frame);
         if (grc) return grc;
     }
-    if (!persist) hipLaunchKernelGGL(bwd_edge_kernel, grid_a, dim3(256), 0, stream, ea);   // t = -1
+    if (!persist) {                                                                         // t = -1
+        void* ke[1] = {&ea};
+        DRNMF_HIP(h, hipLaunchKernel(edge_fn, grid_a, dim3(256), ke, 0, stream));
+    }
     hipLaunchKernelGGL(dlogh0_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, dh0_part,
                        log_h0, d_log_h0, N, W.Np, numM, initial_state != nullptr ? 1 : 0);
     DRNMF_HIP(h, hipGetLastError());

@@ -81,6 +81,9 @@ struct CellAArgs {
                              // the saved order (common.h tile_unpermute), for the weight gradients of
                              // the BPTT (saves its recomputation as a frame-parallel GEMM); else NULL
     int out_width, out_off, write_out;
+    unsigned* bits;          // training (all-hidden, fp32): relu sign bits of this layer's stored hiddens, frame 0
+                             // (cell_shared.h, relu_bits_frame_words); NULL: not recorded
+    unsigned bits_tstride;   // words per frame
     const void* Dn_pf;       // fp16 mode: the NEXT layer's dictionary (the cell_b launch behind this one reads it),
                              // pulled into the L2s by this launch's fifth wave; NULL: no prefetch
     int pf_tiles;            // MFMA bin tiles of that cell_b launch (its workgroup (x, y) reads tile 8 y + x % 8)
@@ -603,6 +606,12 @@ cell_a_kernel(const float* rsrc_, const void* Dn_, const int* t_rd_, int Bp_, in
             gsum[0] = fmaf(rt, dt[i][0], gsum[0]);
             gsum[1] = fmaf(rt, dt[i][1], gsum[1]);
         }
+        // the rest of the saved residual's odd-bin tile is padding: the gradient GEMMs read it as zero, and
+        // nobody else writes it (as bwd_a_kernel does for d r; a memset of all of Rsave per call used to)
+        if (RSAVE && a.Rsave != nullptr && a.ntail > 0 && ab_raw == 0 && rg < a.B) {
+            const int c0 = a.ntail + (tid & 15);
+            if (c0 < 16) a.Rsave[((size_t)rg * a.T + t) * Fp + 16 * a.tail_tile + c0] = 0.f;
+        }
 
         DRNMF_STAMP(1, 7);
         // ---- fused update: soft-threshold / non-negativity projection ----------------------
@@ -617,6 +626,7 @@ cell_a_kernel(const float* rsrc_, const void* Dn_, const int* t_rd_, int Bp_, in
         }
 
         const bool row_live = live && rg < a.B;
+        f32x2 ov = hn;      // what `out` holds of this pair after the store below (a masked frame: the repeat)
 #ifdef DRNMF_EXP_NOOUT
         if (WRITE_OUT && row_live && IS_LAST) {
 #else
@@ -634,8 +644,21 @@ cell_a_kernel(const float* rsrc_, const void* Dn_, const int* t_rd_, int Bp_, in
                         float o = hn[e];
                         if (!vld[rb]) o = (t > 0) ? orow[n + e - (ptrdiff_t)a.out_width] : 0.f;
                         orow[n + e] = o;
+                        ov[e] = o;
                     }
                 }
+            }
+        }
+        // training: the BPTT masks its gradients with [stored hidden > 0] -- one bit of each value, recorded
+        // here from exactly what went to `out` (two ballots per wave, one 16-byte store by its first lane;
+        // cell_shared.h) so that bwd_a / bwd_edge need not read the stored hiddens back
+        if (ALL_HIDDEN && !HALF && a.bits != nullptr) {
+            const unsigned long long b0 = __ballot(row_live && n < a.N && ov[0] > 0.f);
+            const unsigned long long b1 = __ballot(row_live && n + 1 < a.N && ov[1] > 0.f);
+            if (live && l == 0) {
+                const u32x4 wv = {(unsigned)b0, (unsigned)b1, (unsigned)(b0 >> 32), (unsigned)(b1 >> 32)};
+                *(u32x4*)(a.bits + (size_t)t * a.bits_tstride +
+                          ((((size_t)(mb0 + rb) * a.numA + ab) * 4 + w) * 4)) = wv;
             }
         }
         if (!live) continue;
@@ -1136,9 +1159,7 @@ static int32_t factored_start(drnmf_handle_t h, const CellCtx& C, const float* x
         // fp16 mode: cell_b writes the MFMA bin tiles of Rp16 only; the padding of the last 32-bin
         // chunk (and the odd-bin tile) must be finite: it meets zero dictionary slots
         if (half) DRNMF_HIP(h, hipMemsetAsync(C.r16, 0, (size_t)W.Bp * W.Fp * 2, stream));
-        // training: the saved residuals' padding bins (past the odd bins) are never written
-        if (C.rsave && W.ntail > 0)
-            DRNMF_HIP(h, hipMemsetAsync(C.rsave, 0, (size_t)(K - 1) * d.B * d.T * W.Fp * 4, stream));
+        // (training: the padding bins of the saved residuals' odd-bin tile are written by cell_a itself)
     }
 
     // measurement aid: DRNMF_ABLATE=1 launches the same grids but every workgroup exits at once
@@ -1146,7 +1167,8 @@ static int32_t factored_start(drnmf_handle_t h, const CellCtx& C, const float* x
     const bool ablate = measure_env("DRNMF_ABLATE") != nullptr;
     out->key = {
         (uint64_t)d.B, (uint64_t)d.T, (uint64_t)d.F, (uint64_t)d.N, (uint64_t)d.K,
-        (uint64_t)d.n_D, (uint64_t)d.return_all_hidden + 2 * (uint64_t)(d.operand_f16 != 0),
+        (uint64_t)d.n_D,
+        (uint64_t)d.return_all_hidden + 2 * (uint64_t)(d.operand_f16 != 0) + 4 * (uint64_t)(C.relu_bits != nullptr),
         (uint64_t)(uintptr_t)C.pb,
         (uint64_t)(uintptr_t)h_out, (uint64_t)(uintptr_t)C.ws, (uint64_t)ablate,
         // the layout choices baked into the nodes: a sub-batch of a split call and a direct call of the same
@@ -1194,6 +1216,8 @@ static int32_t factored_start(drnmf_handle_t h, const CellCtx& C, const float* x
         a.ablate = tune_env("DRNMF_ABLATE_A") ? atoi(tune_env("DRNMF_ABLATE_A")) : 0;
 #endif
         a.Rsave = (C.rsave && k >= 1) ? C.rsave + (size_t)(k - 1) * d.B * d.T * W.Fp : nullptr;
+        a.bits = C.relu_bits ? C.relu_bits + (size_t)k * relu_bits_layer_words(W.Bp, W.numA) : nullptr;
+        a.bits_tstride = (unsigned)relu_bits_frame_words(K, W.Bp, W.numA);
         // fp16 mode, a cell_b launch behind this one: its dictionary goes into the L2s meanwhile
         a.Dn_pf = nullptr;
         a.pf_tiles = nft;

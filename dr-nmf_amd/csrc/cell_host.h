@@ -46,6 +46,9 @@ struct CellCtx {
     float* xpad = (float*)(ws + W.off_xpad);                 // one block of padded x,
     float* qb[2] = {(float*)(ws + W.off_q0), (float*)(ws + W.off_q1)};       // q ping-pong
     float* rsave = W.off_rsave ? (float*)(ws + W.off_rsave) : nullptr;       // saved residuals; NULL = absent
+    // relu sign bits of the stored hiddens (cell_shared.h); NULL = absent, or switched off for this call.  The
+    // forward that records them and the BPTT that reads them decide alike: same layout, same variable
+    unsigned* relu_bits = (W.off_bits && relu_bits_wanted()) ? (unsigned*)(ws + W.off_bits) : nullptr;
     float* xhat = W.off_xhat ? (float*)(ws + W.off_xhat) : nullptr;          // KL / beta training: x^; NULL = absent
 
     // ---- prepared block (params_layout), per layer -----------------------------------------------

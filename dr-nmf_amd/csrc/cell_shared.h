@@ -395,6 +395,23 @@ static inline bool qred_wanted(int numA, int ntail, int nft, int KS, int RB) {
     return ntail > 0 && numA > 64 && nft * KS >= 16 * RB;
 }
 
+// Relu sign bits of the training forward's stored hiddens (Workspace::off_bits).  cell_a_kernel's epilogue
+// holds the pair (row tid / 16, atoms 2 (tid % 16) + {0, 1}) it stores to the all-hidden output; two wave
+// ballots of "stored value > 0" give 2 x 64 bits per wave, kept as four 32-bit words
+//     {e = 0 lanes 0-31, e = 1 lanes 0-31, e = 0 lanes 32-63, e = 1 lanes 32-63}
+// at word ((((t * K + k) * Bp/16 + m) * numA + ab) * 4 + wave) * 4 of the buffer: T K Bp Np / 8 bytes.  bwd_a /
+// bwd_edge run the same tile geometry (ROWS x ATOMS, 256 threads): a lane finds both of its bits in the 8 bytes
+// at + 2 (lane / 32), bit lane % 32 of either word.
+static inline size_t relu_bits_frame_words(int K, int Bp, int numA) {      // words of one frame, all layers
+    return (size_t)K * (Bp / ROWS) * numA * 16;
+}
+static inline size_t relu_bits_layer_words(int Bp, int numA) { return (size_t)(Bp / ROWS) * numA * 16; }
+// DRNMF_RELU_BITS=0: the forward records no bits and the BPTT reads the stored hiddens (A/B runs, tests)
+static inline bool relu_bits_wanted() {
+    const char* e = tune_env("DRNMF_RELU_BITS");
+    return !(e && atoi(e) == 0);
+}
+
 struct Workspace {
     size_t off_xp, off_valid, off_seen, off_psum_all, off_rpart, off_h0, off_h1, off_state, off_rs,
         off_psum, off_t, total;
@@ -419,6 +436,10 @@ struct Workspace {
     size_t off_rsave;      // training forward (all hidden layers, fp32, factored): residuals r_k, k >= 1,
                            // row-major [K-1][B*T][Fp] (MFMA bin tiles in tile_unpermute order) for the
                            // BPTT's weight gradients; 0 = absent
+    size_t off_bits;       // training forward (all hidden layers, fp32, factored, Euclidean): one bit per stored
+                           // hidden, h > 0, for the BPTT's relu masks (relu_bits_index below); 0 = absent.  The
+                           // region is laid out whatever DRNMF_RELU_BITS says -- the variable decides whether
+                           // a call uses it (relu_bits_wanted), never how large the workspace is
     size_t off_xhat;       // KL / beta cell, training forward: x^_k = h_in Dn_k^T of every (frame, layer),
                            // tile-packed [T][K][Bp][Fp] (the BPTT needs dg/dx^ there); 0 = absent
     // Large inference batches (the reference predicts in slabs of 250 utterances, enhance.py:1189-1193):
@@ -535,6 +556,11 @@ Workspace workspace_layout(const drnmf_cell_desc_t* d, bool allow_split = true) 
         // (the padding bins of every row must read as zero in the gradient GEMMs: when Fp > F the
         // forward clears the buffer once per call)
         W.off_rsave = take((size_t)(d->K - 1) * d->B * d->T * W.Fp * 4);
+    }
+    W.off_bits = 0;
+    if (d->return_all_hidden && !W.half && !W.gram && d->divergence == DRNMF_DIV_ED) {
+        (void)take(256);                                      // (an offset of 0 means "absent")
+        W.off_bits = take(relu_bits_frame_words(d->K, W.Bp, W.numA) * (size_t)d->T * 4);
     }
     W.off_xhat = 0;
     if (nonlin && d->return_all_hidden) {

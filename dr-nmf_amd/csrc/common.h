@@ -15,6 +15,8 @@
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
 
 // Stores of the training chain's SAVED copies (all-hidden output, residual copy, dz / d r copies): read
 // by the time-batched phase only, never by the next launch -- nontemporal (streamed through the L2

@@ -23,7 +23,7 @@ const char* const kTuneNames[] = {
     "DRNMF_ABLATE", "DRNMF_ABLATE_A", "DRNMF_ABLATE_B", "DRNMF_CP_FULL", "DRNMF_DENSE_NW", "DRNMF_FPG",
     "DRNMF_GRAM", "DRNMF_KS", "DRNMF_LATE", "DRNMF_NO_ALLB", "DRNMF_NO_GRAPH",
     "DRNMF_PERSIST", "DRNMF_PERSIST_FAULT", "DRNMF_RB", "DRNMF_RBA", "DRNMF_SPLIT",
-    "DRNMF_THIN", "DRNMF_PF", "DRNMF_PF_SLEEP", "DRNMF_NT_XCD"};
+    "DRNMF_THIN", "DRNMF_PF", "DRNMF_PF_SLEEP", "DRNMF_NT_XCD", "DRNMF_RELU_BITS"};
 std::mutex g_tune_mu;
 // (values are never erased or overwritten in place: a pointer handed out stays valid for the
 // process lifetime; a reload appends a new generation)
