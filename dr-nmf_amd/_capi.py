@@ -4,7 +4,8 @@ device-side SDR's in include/drnmf_sdr.h; the training-data front end's in inclu
 STFT / iSTFT's in include/drnmf_stream.h; the sparse-NMF baseline's inference in include/drnmf_snmf.h, on fp16
 operands in include/drnmf_snmf_f16.h, with per-row noise atoms in include/drnmf_snmf_adapt.h, their online
 form in include/drnmf_snmf_online.h, under the KL cost in include/drnmf_snmf_kl.h; ESTOI beside STOI in include/drnmf_estoi.h;
-the device-side mixer's in include/drnmf_mix.h; the waveform losses' in include/drnmf_waveloss.h).
+the device-side mixer's in include/drnmf_mix.h; the waveform losses' in include/drnmf_waveloss.h; the device-side
+reverberator's in include/drnmf_reverb.h).
 
 The library is the product path: there is NO fallback.  If the shared object is missing or a
 call fails, an exception is raised.
@@ -301,11 +302,18 @@ WAVELOSS_SIGNATURES = {
 WAVE_LOSSES = {"wave_mse": 0, "si_sdr": 1}     # DRNMF_WAVE_LOSS_*
 WAVE_LOSS_BLOCK = 4096                         # DRNMF_WAVE_LOSS_BLOCK
 
+# name -> (restype, argtypes); mirrors include/drnmf_reverb.h one to one (a table of its own, like those above)
+REVERB_SIGNATURES = {
+    "drnmf_reverb_forward": (_i32, [_vp, _i32, _i64, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+REVERB_TILE = 2048                                 # DRNMF_REVERB_TILE
+REVERB_CHUNK = 1024                                # DRNMF_REVERB_CHUNK
+
 # every table above, one per header: lib() binds them all (a new header adds its table's name here)
 SIGNATURE_TABLES = (SIGNATURES, LSTM_SIGNATURES, SCORE_SIGNATURES, ENHANCE_SIGNATURES, SDR_SIGNATURES,
                     DATASET_SIGNATURES, STREAM_SIGNATURES, SNMF_SIGNATURES, SNMF_F16_SIGNATURES, TARGET_SIGNATURES,
                     ESTOI_SIGNATURES, SNMF_ADAPT_SIGNATURES, SNMF_KL_SIGNATURES, SNMF_ONLINE_SIGNATURES,
-                    MIX_SIGNATURES, WAVELOSS_SIGNATURES)
+                    MIX_SIGNATURES, WAVELOSS_SIGNATURES, REVERB_SIGNATURES)
 
 _lib = None
 _handles = {}

@@ -1780,7 +1780,8 @@ class _SequenceModel(object):
         return self.fit(x, y, sample_weight=w, validation_data=val, **fit_kwargs)
 
     def fit_mixtures(self, clean, noise, snr_db=None, snr_choices=None, seed=0, N=512, hop=128, maxlen=None,
-                     transform='mag', target='mag', validation_wavs=None, shuffle_seed=None, **fit_kwargs):
+                     transform='mag', target='mag', validation_wavs=None, shuffle_seed=None, rirs=None,
+                     reverb_prob=1.0, align=True, target_speech='reverberant', early_ms=50.0, fs=16000, **fit_kwargs):
         """`fit` on mixtures made on the device, a fresh draw every epoch (multi-condition training): clean and
         noise, lists of 1-D int16 / float32 arrays, go up once (ops.MixBank); before epoch ep's first batch the
         training tensors are rewritten in place with bank.tensors(bank.draw(snr_db, snr_choices, seed, epoch=ep)),
@@ -1791,7 +1792,13 @@ class _SequenceModel(object):
         one.  N, hop, maxlen, transform, target and the checks as in fit_wavs; everything else goes to fit
         unchanged (shuffle_seed, if given, as fit's own `seed`, the one that shuffles the batches), callbacks after
         the one that redraws.  Under torch.distributed every rank passes ITS shard of clean and draws with
-        seed + 104729 * rank."""
+        seed + 104729 * rank.
+
+        rirs: a list of 1-D float32 room impulse responses puts every utterance in a room before the noise is
+        added (ops.MixBank with rirs: noisy = wet + g * noise, the SNR that of the reverberant speech), a fresh
+        RIR per utterance and epoch from the same seed, dry with probability 1 - reverb_prob.  align,
+        target_speech ('reverberant', the default: y is the wet speech; 'early'; 'dry'), early_ms and fs as
+        ops.MixBank takes them.  rirs=None: as before."""
         from . import data, dp
         ops._check_target(target, transform, 'fit_mixtures')
         for k in ('sample_weight', 'validation_data'):
@@ -1807,15 +1814,20 @@ class _SequenceModel(object):
                              % (N, int(N) // 2 + 1, self._input_width()))
         ops._check_wav_side(clean, 'fit_mixtures', 'clean')
         ops._check_wav_side(noise, 'fit_mixtures', 'noise')
+        ops._check_reverb(rirs, align, target_speech, early_ms, fs, 'fit_mixtures')
         val = None
         if validation_wavs is not None:
             noisy_v, clean_v = validation_wavs
             val = ops.wavs_to_tensors(noisy_v, clean_v, N=N, hop=hop, maxlen=maxlen, transform=transform,
                                       mask_value=mv, device=self._device(), target=target)
-        bank = ops.MixBank(clean, noise, device=self._device())
+        bank = ops.MixBank(clean, noise, rirs=rirs, align=align, target_speech=target_speech, early_ms=early_ms, fs=fs,
+                           device=self._device())
         seed_eff = int(seed) + 104729 * dp.rank()
         kw = dict(N=N, hop=hop, maxlen=maxlen, transform=transform, mask_value=mv, target=target)
-        draw = lambda ep: bank.draw(snr_db=snr_db, snr_choices=snr_choices, seed=seed_eff, epoch=ep)
+        draw_kw = dict(snr_db=snr_db, snr_choices=snr_choices, seed=seed_eff)
+        if rirs is not None:
+            draw_kw['reverb_prob'] = reverb_prob
+        draw = lambda ep: bank.draw(epoch=ep, **draw_kw)
         tensors = bank.tensors(draw(0), **kw)
 
         class Redraw(object):
@@ -3346,20 +3358,25 @@ class SparseNMFModel(_SequenceModel):
 
     @classmethod
     def from_mixtures(cls, clean, noise, params_snmf, snr_db=None, snr_choices=None, seed=0, N=512, hop=128,
-                      device=None):
+                      device=None, rirs=None, reverb_prob=1.0, align=True, target_speech='reverberant', early_ms=50.0,
+                      fs=16000):
         """from_wavs on ONE draw of mixtures made on the device (ops.MixBank: clean + g * noise at SNRs uniform in
         snr_db=(lo, hi), default ops.MIX_SNR_DB, or taken from snr_choices): the packed frames of
-        bank.frames(bank.draw(snr_db, snr_choices, seed)), then the training of from_wavs."""
+        bank.frames(bank.draw(snr_db, snr_choices, seed)), then the training of from_wavs.  rirs, reverb_prob,
+        align, target_speech, early_ms, fs: reverberant mixtures, as fit_mixtures takes them."""
         from . import snmf
         ops._check_mix_snr(snr_db, snr_choices, 'from_mixtures')
         ops._check_wav_side(clean, 'from_mixtures', 'clean')
         ops._check_wav_side(noise, 'from_mixtures', 'noise')
+        ops._check_reverb(rirs, align, target_speech, early_ms, fs, 'from_mixtures')
         dev = torch.device(device if device is not None else 'cuda')
         dev = torch.device('cuda', ops._dev_of(dev))
         p = float(params_snmf.get('spectrogram_power', 1.0))
         with torch.cuda.device(dev):
-            bank = ops.MixBank(clean, noise, device=dev)
-            xf, yf = bank.frames(bank.draw(snr_db=snr_db, snr_choices=snr_choices, seed=seed), N, hop)
+            bank = ops.MixBank(clean, noise, rirs=rirs, align=align, target_speech=target_speech, early_ms=early_ms,
+                               fs=fs, device=dev)
+            draw_kw = dict(reverb_prob=reverb_prob) if rirs is not None else {}
+            xf, yf = bank.frames(bank.draw(snr_db=snr_db, snr_choices=snr_choices, seed=seed, **draw_kw), N, hop)
             x_frames = (xf ** p).t().cpu().numpy()
             y_frames = (yf ** p).t().cpu().numpy()
         W, _, _ = snmf.train_snmf(y_frames, x_frames, params_snmf, save_H=False, device=dev)

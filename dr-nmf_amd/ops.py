@@ -1521,6 +1521,131 @@ def mix_forward(speech, len_s, noise, len_n, noise_index, offset, snr_db, speech
     return (out, gain) if return_gain else out
 
 
+# ---- reverberation of a speech bank on the device (include/drnmf_reverb.h) ----------------------------------
+REVERB_TILE, REVERB_CHUNK = _capi.REVERB_TILE, _capi.REVERB_CHUNK
+TARGET_SPEECH = ('reverberant', 'early', 'dry')
+
+
+def reverb_forward(speech, len_s, rirs, len_r, rir_index, delay=None, n_early=None, out=None, early_out=None,
+                   return_early=False):
+    """drnmf_reverb_forward: wet[i] = speech[i] convolved with rirs[rir_index[i]], moved forward by that RIR's
+    delay so that it stays aligned with the dry speech, and cut to the signal's length; early[i] the same sum over
+    the RIR's first n_early taps only.  See include/drnmf_reverb.h for the definition (one ascending fmaf chain
+    per output and part) and the rows that stay dry (an index outside the bank, an empty RIR).  speech
+    [n][stride_s] int16 or float32, rirs float32 [m][stride_r], len_s / len_r int64, rir_index int32 [n], delay /
+    n_early int32 [m] or None (0 / all taps), all on the device.  Returns wet float32 [n][stride_s] (`out` if
+    given), and early (`early_out` if given) with return_early or early_out.  Enqueues only."""
+    _mix_pcm(speech, "speech")
+    if rirs.dim() != 2 or rirs.dtype != torch.float32 or not rirs.is_contiguous() or rirs.shape[0] < 1 \
+            or rirs.shape[1] < 1:
+        raise ValueError("rirs must be a contiguous 2-D float32 tensor [n_rir][stride] (got %s %s)"
+                         % (rirs.dtype, tuple(rirs.shape)))
+    n, stride_s = speech.shape
+    m, stride_r = rirs.shape
+    _mix_table(len_s, n, torch.int64, "len_s")
+    _mix_table(len_r, m, torch.int64, "len_r")
+    _mix_table(rir_index, n, torch.int32, "rir_index")
+    if delay is not None:
+        _mix_table(delay, m, torch.int32, "delay")
+    if n_early is not None:
+        _mix_table(n_early, m, torch.int32, "n_early")
+    dev = speech.device
+    out = _out(out, (n, stride_s), torch.float32, dev)
+    want_early = return_early or early_out is not None
+    early = _out(early_out, (n, stride_s), torch.float32, dev, "early_out") if want_early else None
+    for t in (len_s, rirs, len_r, rir_index, delay, n_early):
+        if t is not None and t.device != dev:
+            raise ValueError("reverb_forward: every tensor must be on %s" % dev)
+    _call("drnmf_reverb_forward", _dev_index(speech), n, stride_s, _capi.ptr(len_s), int(speech.dtype == torch.int16),
+          _capi.ptr(speech), m, stride_r, _capi.ptr(len_r), _capi.ptr(rirs), _capi.ptr(rir_index), _capi.ptr(delay),
+          _capi.ptr(n_early), _capi.ptr(out), _capi.ptr(early))
+    return (out, early) if want_early else out
+
+
+def _check_rirs(rirs, what):
+    """Host-side checks of a bank of RIRs: a non-empty list of non-empty 1-D finite float32 arrays."""
+    rows = [np.asarray(v) for v in rirs]
+    if not rows:
+        raise ValueError("%s: no RIRs" % what)
+    for v in rows:
+        if v.ndim != 1 or v.dtype != np.dtype('float32') or v.shape[0] < 1 or not np.isfinite(v).all():
+            raise ValueError("%s: every RIR must be a non-empty 1-D finite float32 array" % what)
+    return rows
+
+
+def _check_reverb(rirs, align, target_speech, early_ms, fs, what):
+    """What a bank with RIRs refuses before anything is uploaded.  Returns the RIR rows (None without RIRs)."""
+    if target_speech not in TARGET_SPEECH:
+        raise ValueError("%s: target_speech must be 'reverberant', 'early' or 'dry' (got %r)" % (what, target_speech))
+    if not (np.isfinite(early_ms) and early_ms >= 0 and np.isfinite(fs) and fs > 0):
+        raise ValueError("%s: early_ms = %r must be finite and >= 0, fs = %r positive" % (what, early_ms, fs))
+    if rirs is None:
+        return None
+    rows = _check_rirs(rirs, what)
+    if target_speech == 'dry' and not align:
+        raise ValueError("%s: target_speech='dry' needs align=True (the dry target would lag the mixture by the "
+                         "RIR's direct-path delay)" % what)
+    return rows
+
+
+def rir_delays(rirs):
+    """The index of the first maximum of |h| of every RIR of a list (its direct-path tap), int32 [n_rir], on the
+    host."""
+    return np.array([int(np.argmax(np.abs(np.asarray(v)))) for v in _check_rirs(rirs, "rir_delays")], dtype=np.int32)
+
+
+def rir_early_counts(delay, early_ms=50.0, fs=16000):
+    """The early tap counts of RIRs whose direct-path taps are `delay`: delay + 1 + round(early_ms fs / 1000), int32,
+    capped at 2^31 - 1 (the kernel clamps a count to the RIR's length, so any early_ms >= 0 is served).  On the
+    host."""
+    span = float(early_ms) * float(fs) / 1000.0
+    if not (span >= 0.0):
+        raise ValueError("rir_early_counts: early_ms = %r and fs = %r must give a span >= 0" % (early_ms, fs))
+    top = 2 ** 31 - 1
+    span = top if span >= top else int(round(span))            # before the add: the sum stays far inside an int64
+    return np.minimum(np.asarray(delay, dtype=np.int64) + 1 + span, top).astype(np.int32)
+
+
+def rir_draw(n, n_rir, seed=0, epoch=0, reverb_prob=1.0):
+    """One epoch's RIR table for n signals over n_rir RIRs, on the host and a pure function of its arguments: int32
+    [n], -1 where the utterance stays dry.  With rs = np.random.RandomState((seed * 998244353 + epoch * 7919 +
+    0x52495221) % 2**32), a generator of its own (mix_draw's tables do not move when RIRs are added): idx =
+    rs.randint(0, n_rir, n), then idx[rs.random_sample(n) >= reverb_prob] = -1."""
+    reverb_prob = float(reverb_prob)
+    if int(n) < 1 or int(n_rir) < 1 or not 0.0 <= reverb_prob <= 1.0:
+        raise ValueError("rir_draw: n = %r signals, n_rir = %r RIRs (both positive) and reverb_prob = %r in [0, 1] "
+                         "are needed" % (n, n_rir, reverb_prob))
+    n = int(n)
+    rs = np.random.RandomState((int(seed) * 998244353 + int(epoch) * 7919 + 0x52495221) % 2 ** 32)
+    idx = rs.randint(0, int(n_rir), n).astype(np.int32)
+    idx[rs.random_sample(n) >= reverb_prob] = -1
+    return idx
+
+
+SYNTHETIC_RIR_TAIL = 0.05       # standard deviation of synthetic_rirs' tail at the direct-path tap
+
+
+def synthetic_rirs(n, fs=16000, rt60=(0.2, 0.8), seed=0):
+    """n stand-in RIRs as float32 arrays, on the host: h[0] = 1 (the direct path), then white Gaussian noise of
+    standard deviation SYNTHETIC_RIR_TAIL under an exponential envelope 10^(-3 t / (rt60 fs)), which reaches -60 dB
+    at t = rt60 fs, the last tap; rt60 uniform in (lo, hi) seconds per RIR.  Reproducible from `seed`.  A stand-in
+    with the length and decay of a room's response for tests and for users without measured RIRs -- not room
+    acoustics: no early reflections, no frequency-dependent decay, no geometry."""
+    lo, hi = float(rt60[0]), float(rt60[1])
+    if int(n) < 1 or not (fs > 0 and 0 < lo <= hi and np.isfinite(hi)):
+        raise ValueError("synthetic_rirs: n = %r, fs = %r and rt60 = (%r, %r) with 0 < lo <= hi are needed"
+                         % (n, fs, lo, hi))
+    rs = np.random.RandomState((int(seed) * 69069 + 0x53594e52) % 2 ** 32)
+    out = []
+    for _ in range(int(n)):
+        taps = max(1, int(round((lo + (hi - lo) * rs.random_sample()) * fs)))
+        t = np.arange(taps, dtype=np.float64)
+        h = SYNTHETIC_RIR_TAIL * rs.standard_normal(taps) * 10.0 ** (-3.0 * t / taps)
+        h[0] = 1.0
+        out.append(h.astype(np.float32))
+    return out
+
+
 MIX_SNR_DB = (-6.0, 9.0)      # the SNR range of a draw that names neither snr_db nor snr_choices (CHiME2's)
 
 
@@ -1589,11 +1714,25 @@ class MixBank(object):
     clean, noise: lists of 1-D int16 or float32 arrays, one type per side (the sides may differ).  The clean
     side is kept as float32 (int16 converted once, v / 32768: the pair kernels take both members of a pair in one
     type), the noise side in the type it came in.  SNRs are over the whole utterance (no speech-activity
-    weighting); mixtures are not clipped and may exceed +-1."""
+    weighting); mixtures are not clipped and may exceed +-1.
 
-    def __init__(self, clean, noise, device=None):
+    rirs: a list of non-empty 1-D finite float32 arrays puts the speech in a room first (reverb_forward, include/
+    drnmf_reverb.h): noisy = wet + g * noise with wet the clean utterance convolved with the RIR a draw names for
+    it (a draw is then a 4-tuple, its last table the RIR per utterance, -1: the utterance stays dry), and the SNR
+    is that of the REVERBERANT speech in the mixture.  The RIRs, their lengths, delays and early counts go up
+    once.  align=True moves every wet signal forward by its RIR's direct-path delay (rir_delays), so that it stays
+    aligned with the dry speech; align=False is the causal convolution cut to the utterance's length.
+    target_speech: what the pair kernels get as the clean member -- 'reverberant' (wet: the CHiME2 convention, the
+    model removes noise only), 'early' (the direct path and the reflections up to early_ms after it: the model
+    also removes late reverberation) or 'dry' (the bank's clean side; needs align=True).  rirs=None: the bank of
+    before, the same launches and the same bits."""
+
+    def __init__(self, clean, noise, rirs=None, align=True, target_speech='reverberant', early_ms=50.0, fs=16000,
+                 device=None):
         ry, dty = _check_wav_side(clean, "MixBank", "clean")
         rn, dtn = _check_wav_side(noise, "MixBank", "noise")
+        rr = _check_reverb(rirs, align, target_speech, early_ms, fs, "MixBank")
+        self.target_speech, self.n_rir = target_speech, (0 if rr is None else len(rr))
         if dty == np.dtype('int16'):
             ry = [v.astype(np.float32) / np.float32(32768.0) for v in ry]
         self.n, self.n_noise = len(ry), len(rn)
@@ -1605,31 +1744,86 @@ class MixBank(object):
             self.clean, self.len_clean_dev = _upload_wav_side(ry, np.dtype('float32'), self.device)
             self.noise, self.len_noise_dev = _upload_wav_side(rn, dtn, self.device)
             self.workspace = mix_workspace(self.n, self.clean.shape[1], self.device)
-            self.energy = mix_energy(self.clean, self.len_clean_dev, workspace=self.workspace)
+            # (a bank with RIRs mixes the wet speech, whose energy changes with the draw: mix_forward computes it)
+            self.energy = None if rr is not None else mix_energy(self.clean, self.len_clean_dev,
+                                                                 workspace=self.workspace)
             self.noisy = torch.empty(tuple(self.clean.shape), dtype=torch.float32, device=self.device)
+            if rr is not None:
+                self.rirs, self.len_rir_dev = _upload_wav_side(rr, np.dtype('float32'), self.device)
+                delay = rir_delays(rr) if align else np.zeros(len(rr), dtype=np.int32)
+                taps = np.stack([delay, rir_early_counts(delay, early_ms, fs)])
+                taps_d = _upload_pinned(taps, self.device)
+                self.rir_delay, self.rir_n_early = taps_d[0], taps_d[1]
+                self.wet = torch.empty_like(self.noisy)
+                self.early = torch.empty_like(self.noisy) if target_speech == 'early' else None
         self._tables = {}
 
-    def draw(self, snr_db=None, snr_choices=None, seed=0, epoch=0):
-        """mix_draw for this bank: (noise_index, offset, snr) on the host, a pure function of the arguments."""
-        return mix_draw(self.n, self.len_noise, snr_db=snr_db, snr_choices=snr_choices, seed=seed, epoch=epoch)
+    def draw(self, snr_db=None, snr_choices=None, seed=0, epoch=0, reverb_prob=1.0):
+        """mix_draw for this bank: (noise_index, offset, snr) on the host, a pure function of the arguments.  A
+        bank with RIRs appends rir_draw's table: (noise_index, offset, snr, rir_index), the first three as
+        without RIRs; reverb_prob: the probability that an utterance is reverberated."""
+        d = mix_draw(self.n, self.len_noise, snr_db=snr_db, snr_choices=snr_choices, seed=seed, epoch=epoch)
+        if not self.n_rir:
+            return d
+        return d + (rir_draw(self.n, self.n_rir, seed=seed, epoch=epoch, reverb_prob=reverb_prob),)
 
     def _check_draw(self, draw):
+        what = "(noise_index, offset, snr, rir_index)" if self.n_rir else "(noise_index, offset, snr)"
         try:
-            idx, off, snr = draw
+            if self.n_rir:
+                idx, off, snr, ridx = draw
+            else:
+                (idx, off, snr), ridx = draw, None
         except (TypeError, ValueError):
-            raise ValueError("MixBank: a draw is (noise_index, offset, snr)")
+            raise ValueError("MixBank: a draw is %s" % what)
         idx, off, snr = np.asarray(idx), np.asarray(off), np.asarray(snr)
-        for a, dt, name in ((idx, np.int32, "noise_index"), (off, np.int64, "offset"), (snr, np.float32, "snr")):
+        tables = [(idx, np.int32, "noise_index"), (off, np.int64, "offset"), (snr, np.float32, "snr")]
+        if self.n_rir:
+            ridx = np.asarray(ridx)
+            tables.append((ridx, np.int32, "rir_index"))
+        for a, dt, name in tables:
             if a.dtype != np.dtype(dt) or a.shape != (self.n,):
                 raise ValueError("MixBank: %s must be %s [%d] (got %s %s)" % (name, np.dtype(dt), self.n, a.dtype,
                                                                               a.shape))
         if idx.min() < 0 or idx.max() >= self.n_noise:
             raise ValueError("MixBank: noise_index outside [0, %d)" % self.n_noise)
-        return idx, off, snr
+        if self.n_rir and (ridx.min() < -1 or ridx.max() >= self.n_rir):
+            raise ValueError("MixBank: rir_index outside [-1, %d)" % self.n_rir)
+        return (idx, off, snr, ridx) if self.n_rir else (idx, off, snr)
+
+    def _mix_reverberant(self, draw):
+        """mix() of a bank with RIRs: wet (and early) from the clean side, then the mixer on wet."""
+        idx, off, snr, ridx = draw
+        with torch.cuda.device(self.device):
+            # one pinned upload: offset [n] int64 | noise_index [n] int32 | snr [n] float32 | rir_index [n] int32
+            n = self.n
+            host = torch.empty(20 * n, dtype=torch.uint8, pin_memory=True)
+            hn = host.numpy()
+            hn[:8 * n].view(np.int64)[:] = off
+            hn[8 * n:12 * n].view(np.int32)[:] = idx
+            hn[12 * n:16 * n].view(np.float32)[:] = snr
+            hn[16 * n:].view(np.int32)[:] = ridx
+            d = host.to(self.device, non_blocking=True)
+            reverb_forward(self.clean, self.len_clean_dev, self.rirs, self.len_rir_dev, d[16 * n:].view(torch.int32),
+                           delay=self.rir_delay, n_early=self.rir_n_early, out=self.wet, early_out=self.early)
+            # the speech energy is the wet signal's, computed by the call: the SNR is the reverberant speech's
+            mix_forward(self.wet, self.len_clean_dev, self.noise, self.len_noise_dev, d[8 * n:12 * n].view(torch.int32),
+                        d[:8 * n].view(torch.int64), d[12 * n:16 * n].view(torch.float32), speech_energy=None,
+                        out=self.noisy, workspace=self.workspace)
+        return self.noisy, self.len_clean_dev
+
+    def _target(self):
+        """The clean member of the pairs: what target_speech names (valid after mix() for 'reverberant' and
+        'early')."""
+        if not self.n_rir or self.target_speech == 'dry':
+            return self.clean
+        return self.wet if self.target_speech == 'reverberant' else self.early
 
     def mix(self, draw):
         """(noisy float32 [n][stride], lengths int64 [n]) on the device.  noisy is the bank's own buffer: the next
-        mix overwrites it."""
+        mix overwrites it (and, with RIRs, the wet and early buffers beside it)."""
+        if self.n_rir:
+            return self._mix_reverberant(self._check_draw(draw))
         idx, off, snr = self._check_draw(draw)
         with torch.cuda.device(self.device):
             # one pinned upload: offset [n] int64 | noise_index [n] int32 | snr [n] float32
@@ -1661,7 +1855,8 @@ class MixBank(object):
 
     def tensors(self, draw, N=512, hop=128, maxlen=None, transform='mag', mask_value=None, target='mag', out=None):
         """(x, y, w) of one draw, exactly what wavs_to_tensors(self.wavs(draw), clean as float32, ...) returns, by
-        the same launches on (noisy, clean) without the download and the two uploads.  The sequence table is
+        the same launches on (noisy, clean) without the download and the two uploads (with RIRs: clean is
+        self.target_wavs(draw), the side target_speech names).  The sequence table is
         uploaded once per (N, hop, maxlen).  out=(x, y, w): tensors of an earlier call with the same arguments,
         rewritten in place and returned.  Enqueues only."""
         from . import data
@@ -1683,9 +1878,10 @@ class MixBank(object):
             w = _out(w, (n_seq, T), torch.float32, self.device, "MixBank.tensors: out[2] (w)")
             noisy, ln = self.mix(draw)
             if target == 'mag':
-                stft_pair_chunks_enqueue(noisy, self.clean, ln, ln, table_d, T, N, hop, transform, mask_value, x, y, w)
+                stft_pair_chunks_enqueue(noisy, self._target(), ln, ln, table_d, T, N, hop, transform, mask_value, x, y,
+                                         w)
             else:
-                stft_pair_target_enqueue(noisy, self.clean, ln, ln, table_d, T, N, hop, transform, target,
+                stft_pair_target_enqueue(noisy, self._target(), ln, ln, table_d, T, N, hop, transform, target,
                                          mask_value, x, y, w)
         return x, y, w
 
@@ -1698,7 +1894,7 @@ class MixBank(object):
             xf = torch.empty((int(nf.sum()), int(N) // 2 + 1), dtype=torch.float32, device=self.device)
             yf = torch.empty_like(xf)
             noisy, ln = self.mix(draw)
-            stft_pair_frames_enqueue(noisy, self.clean, ln, ln, row0, N, hop, transform, xf, yf)
+            stft_pair_frames_enqueue(noisy, self._target(), ln, ln, row0, N, hop, transform, xf, yf)
         return xf, yf
 
     def _download(self, pcm):
@@ -1713,6 +1909,13 @@ class MixBank(object):
     def clean_wavs(self):
         """The clean side as the bank holds it: a list of float32 numpy arrays (downloads)."""
         return self._download(self.clean)
+
+    def target_wavs(self, draw):
+        """The target side of one draw, what `tensors` and `frames` pair the mixtures with: the wet speech, its
+        early part or the clean side as target_speech says (the clean side without RIRs), as a list of float32
+        numpy arrays (downloads)."""
+        self.mix(draw)
+        return self._download(self._target())
 
 
 def istft_ragged_enqueue(re, im, mask, lengths_dev, sig_index_dev, N, hop, y, crop, workspace=None):
