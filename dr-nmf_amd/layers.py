@@ -1243,6 +1243,11 @@ class _SequenceModel(object):
     def _input_width(self):
         raise NotImplementedError
 
+    def _check_bins(self, what, N):
+        if int(N) // 2 + 1 != self._input_width():
+            raise ValueError('%s: N = %d gives %d bins, the model takes %d'
+                             % (what, N, int(N) // 2 + 1, self._input_width()))
+
     @staticmethod
     def _pack_waveforms(wavs, lengths, what):
         """(list of 1-D arrays | 2-D array + lengths | 2-D tensor + lengths) -> (rows, host lengths, dtype): rows
@@ -1304,8 +1309,7 @@ class _SequenceModel(object):
         if bs <= 0 or hop <= 0:
             raise ValueError('enhance: batch_size and hop must be positive')
         F = N // 2 + 1
-        if F != self._input_width():
-            raise ValueError('enhance: N = %d gives %d bins, the model takes %d' % (N, F, self._input_width()))
+        self._check_bins('enhance', N)
         if self._carries_state():
             raise NotImplementedError('enhance: a stateful model needs its rows in order and at one length; '
                                       'use predict_on_batch')
@@ -1593,100 +1597,44 @@ class _SequenceModel(object):
                 old._get()
         return loss
 
-    def train_on_batch(self, x, y, sample_weight=None, _live=True):
-        """One optimiser step.  x, y: (B,T,F); sample_weight: (B,T) (the data mask,
-        enhance.py:1148-1152).  Under torch.distributed the flat gradient + (sum, count, frames, fault)
-        are all-reduced (RCCL) before the update, so every rank applies the same step.  Returns the
-        loss as a DeviceLoss: the call enqueues the step and returns without waiting for it (float()
-        the result, as Keras' train_on_batch would have, to wait)."""
+    def _to_device(self, a):
+        """A host array as a float32 tensor on the model's device; a tensor is taken as it is."""
+        return a if isinstance(a, torch.Tensor) else \
+            torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self._device())
+
+    def _reduce_and_step(self, flat):
+        """The tail of every optimiser step: this rank's flat buffer summed over the ranks, then the fused Adam."""
         from . import dp
-        dev = self._device()
-        tt = lambda a: a if isinstance(a, torch.Tensor) else \
-            torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-        x, y = tt(x), tt(y)
-        if sample_weight is None:
-            sample_weight = torch.ones(x.shape[:2], dtype=torch.float32, device=dev)
-        flat = self.loss_and_grads(x, y, tt(sample_weight), live=_live)
         dp.allreduce_sum_(flat)
         return self.apply_gradients(flat)
 
-    def test_on_batch(self, x, y, sample_weight=None):
+    def _report_loss(self, s4, what, plain=False):
+        """The loss a test or validation pass reports, from this rank's device sums [sum, count, frames, fault]:
+        the fault word of the forwards behind them is taken, the four are all-reduced and read in ONE wait for
+        the device, and a chain that gave up on any rank raises on every rank.  plain: sum / count (a criterion
+        of its own); otherwise the compiled loss, with loss_norm's factor and the regularizers' penalty."""
         from . import dp
-        dev = self._device()
-        tt = lambda a: a if isinstance(a, torch.Tensor) else \
-            torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-        x, y = tt(x), tt(y)
-        w = tt(sample_weight) if sample_weight is not None else \
-            torch.ones(x.shape[:2], dtype=torch.float32, device=dev)
-        s3 = torch.empty(4, dtype=torch.float32, device=dev)
-        self._drop_stale_fault()
-        s3[:2].copy_(self._validation_sums(x, y, w))
-        s3[2:3].fill_(float(x.shape[0] * x.shape[1]))      # (fill_: no blocking scalar copy)
-        s3[3:].fill_(0.0)
-        ops.status_take(s3[3:])                 # fault word of this forward, all-reduced with the sums
-        dp.allreduce_sum_(s3)
-        sse, cnt, rows, fault = s3.tolist()
+        ops.status_take(s4[3:])
+        dp.allreduce_sum_(s4)
+        sse, cnt, rows, fault = s4.tolist()
         if fault != 0.0:
-            raise _capi.DrnmfError('test_on_batch: a persistent small-shape chain timed out on at least '
-                                   'one rank (DRNMF_ERR_TIMEOUT); rerun, or set DRNMF_PERSIST=0')
+            raise _capi.DrnmfError('%s: a persistent small-shape chain timed out on at least one rank '
+                                   '(DRNMF_ERR_TIMEOUT); rerun, or set DRNMF_PERSIST=0' % what)
+        if plain:
+            return sse / max(cnt, 1.0)
         scale = 1.0 / max(cnt, 1.0)
         if getattr(self, 'loss_norm', 'masked_mean') == 'keras204':
             scale *= rows / max(cnt, 1.0)
         return sse * scale + (self._regularization_loss() if hasattr(self, '_train_items') else 0.0)
 
-    def fit(self, x, y, sample_weight=None, batch_size=32, epochs=1, validation_data=None,
-            shuffle=True, seed=7654, verbose=0, callbacks=None, resident_bytes=64 << 30):
-        """Minimal keras.Model.fit: shuffled mini-batches (np.random.seed(7654), enhance.py:7),
-        Keras-style callbacks (callbacks.py: on_train_begin / on_batch_end / on_epoch_end with
-        logs {'loss', 'val_loss'}; a callback may set model.stop_training), returns {'loss': [...],
-        'val_loss': [...]} per epoch.  Under torch.distributed every rank passes ITS shard of the
-        data; batches are all-reduced per step and the ranks take the same number of steps
-        (a rank with fewer batches joins the remaining reductions with zero weights).
-        Host (numpy) data sets of up to `resident_bytes` (64 GiB: the reference's whole CHiME2 training
-        tensors are ~6 GB, the GPU has 288 GB) are uploaded ONCE and mini-batches gathered on the
-        device -- a per-batch host-to-device copy of x and y costs ~1 ms of the 10-ms step of the
-        shipped r = 100 configuration; larger sets (or resident_bytes=0) are copied batch by batch as
-        Keras does."""
+    def _run_epochs(self, what, n, batch_size, epochs, shuffle, seed, callbacks, verbose, step, validate):
+        """The epoch loop of every fit_* entry over this rank's n items: step(b, live) -> DeviceLoss enqueues
+        one optimiser step on the items `b` (index array; not live: a replayed batch that must add nothing to
+        the all-reduce), validate() -> float is the epoch's val_loss (None: no validation).  Keras-style
+        callbacks (callbacks.py) get on_train_begin / on_epoch_begin / on_batch_end / on_epoch_end with logs
+        {'loss', 'val_loss'} / on_train_end and may set model.stop_training; returns {'loss': [...],
+        'val_loss': [...]} per epoch."""
         from . import dp
-        dev = self._device()
-        # what may stay resident: at most `resident_bytes` and at most half of the device memory that is
-        # free right now (ADVICE r3: workspaces, other tenants of the GPU); a failed upload falls back to
-        # per-batch copies
-        try:
-            free_now = int(torch.cuda.mem_get_info(dev)[0])
-        except Exception:
-            free_now = 0
-        budget = min(int(resident_bytes), free_now // 2)
-
-        def upload(arrays):
-            """Device copies of the numpy members of `arrays` (one copy per distinct array: the
-            pretraining model passes y = x) if they fit the budget, else None."""
-            nonlocal budget
-            uniq = {}
-            for a in arrays:
-                if isinstance(a, np.ndarray):
-                    uniq.setdefault(id(a), a)
-            need = sum(a.size * 4 for a in uniq.values())
-            if not uniq or need > budget:
-                return None
-            try:
-                dev_of = {k: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-                          for k, a in uniq.items()}
-            except torch.cuda.OutOfMemoryError:
-                torch.cuda.empty_cache()
-                return None
-            budget -= need
-            return [dev_of[id(a)] if isinstance(a, np.ndarray) else a for a in arrays]
-        up = upload([x, y, sample_weight])
-        if up is not None:
-            x, y, sample_weight = up
-        if validation_data is not None:
-            up = upload(list(validation_data))
-            if up is not None:
-                validation_data = tuple(up)
-        take = lambda a, b: a.index_select(0, torch.as_tensor(b, dtype=torch.long, device=a.device)) \
-            if isinstance(a, torch.Tensor) else a[b]
-        n = x.shape[0]
         rng = np.random.RandomState(seed)
         hist = {'loss': [], 'val_loss': []}
         # file-writing callbacks (rank0_only: ModelCheckpoint, LossHistory) run on rank 0 only --
@@ -1705,14 +1653,14 @@ class _SequenceModel(object):
         # a callback that looks at every batch's loss needs the number: the step then waits for it, as
         # Keras does; without one the losses of an epoch are read when the epoch ends
         per_batch_cbs = [cb for cb in callbacks if hasattr(cb, 'on_batch_end')]
-        # every train_on_batch is a collective: all ranks must take the same number of steps even
+        # every step is a collective: all ranks must take the same number of steps even
         # when their shards differ in size (dp.shard hands the remainder to the first ranks)
         steps = dp.max_over_ranks(epoch_steps(n, batch_size))
         # an empty shard has no batch to replay with zero weights; every rank must learn of it HERE
         # (one that raised alone would leave the others waiting in the first all-reduce)
         if dp.max_over_ranks(1 if n == 0 else 0):
-            raise ValueError("fit(): a rank holds no sequences (%d here); give every rank at least "
-                             "one (dp.shard of fewer sequences than ranks?)" % n)
+            raise ValueError("%s: a rank holds no sequences (%d here); give every rank at least "
+                             "one (dp.shard of fewer sequences than ranks?)" % (what, n))
         for ep in range(epochs):
             for cb in callbacks:
                 if hasattr(cb, 'on_epoch_begin'):
@@ -1720,24 +1668,19 @@ class _SequenceModel(object):
             idx = rng.permutation(n) if shuffle else np.arange(n)
             ep_losses, cnt = [], 0
             for b, live in epoch_batches(idx, batch_size, steps):
-                sw = None if sample_weight is None else take(sample_weight, b)
-                if not live:
-                    # this rank has run out of data: it joins the all-reduce with zero weights
-                    # (zero gradient, zero count) on a batch it has already used
-                    sw = np.zeros((len(b), x.shape[1]), np.float32)
-                loss = self.train_on_batch(take(x, b), take(y, b), sw, _live=live)
+                loss = step(b, live)
                 ep_losses.append(loss)
                 for cb in per_batch_cbs:
                     cb.on_batch_end(cnt, {'batch': cnt, 'size': len(b), 'loss': float(loss)})
                 cnt += 1
             logs = {'loss': sum(float(l) for l in ep_losses) / max(cnt, 1)}
             hist['loss'].append(logs['loss'])
-            if validation_data is not None:
-                logs['val_loss'] = self._validate(validation_data, batch_size, take)
+            if validate is not None:
+                logs['val_loss'] = validate()
                 hist['val_loss'].append(logs['val_loss'])
             if verbose and dp.rank() == 0:
                 print('epoch %d loss %.6f%s' % (ep + 1, logs['loss'],
-                      (' val_loss %.6f' % logs['val_loss']) if validation_data else ''))
+                      (' val_loss %.6f' % logs['val_loss']) if validate is not None else ''))
             for cb in callbacks:
                 if hasattr(cb, 'on_epoch_end'):
                     cb.on_epoch_end(ep, logs)
@@ -1748,6 +1691,89 @@ class _SequenceModel(object):
                 cb.on_train_end({})
         return hist
 
+    def train_on_batch(self, x, y, sample_weight=None, _live=True):
+        """One optimiser step.  x, y: (B,T,F); sample_weight: (B,T) (the data mask,
+        enhance.py:1148-1152).  Under torch.distributed the flat gradient + (sum, count, frames, fault)
+        are all-reduced (RCCL) before the update, so every rank applies the same step.  Returns the
+        loss as a DeviceLoss: the call enqueues the step and returns without waiting for it (float()
+        the result, as Keras' train_on_batch would have, to wait)."""
+        x, y = self._to_device(x), self._to_device(y)
+        if sample_weight is None:
+            sample_weight = torch.ones(x.shape[:2], dtype=torch.float32, device=self._device())
+        return self._reduce_and_step(self.loss_and_grads(x, y, self._to_device(sample_weight), live=_live))
+
+    def test_on_batch(self, x, y, sample_weight=None):
+        x, y = self._to_device(x), self._to_device(y)
+        w = self._to_device(sample_weight) if sample_weight is not None else \
+            torch.ones(x.shape[:2], dtype=torch.float32, device=self._device())
+        s4 = torch.empty(4, dtype=torch.float32, device=self._device())
+        self._drop_stale_fault()
+        s4[:2].copy_(self._validation_sums(x, y, w))
+        s4[2:3].fill_(float(x.shape[0] * x.shape[1]))      # (fill_: no blocking scalar copy)
+        s4[3:].fill_(0.0)
+        return self._report_loss(s4, 'test_on_batch')
+
+    def fit(self, x, y, sample_weight=None, batch_size=32, epochs=1, validation_data=None,
+            shuffle=True, seed=7654, verbose=0, callbacks=None, resident_bytes=64 << 30):
+        """Minimal keras.Model.fit: shuffled mini-batches (np.random.seed(7654), enhance.py:7),
+        Keras-style callbacks (callbacks.py: on_train_begin / on_batch_end / on_epoch_end with
+        logs {'loss', 'val_loss'}; a callback may set model.stop_training), returns {'loss': [...],
+        'val_loss': [...]} per epoch.  Under torch.distributed every rank passes ITS shard of the
+        data; batches are all-reduced per step and the ranks take the same number of steps
+        (a rank with fewer batches joins the remaining reductions with zero weights).
+        Host (numpy) data sets of up to `resident_bytes` (64 GiB: the reference's whole CHiME2 training
+        tensors are ~6 GB, the GPU has 288 GB) are uploaded ONCE and mini-batches gathered on the
+        device -- a per-batch host-to-device copy of x and y costs ~1 ms of the 10-ms step of the
+        shipped r = 100 configuration; larger sets (or resident_bytes=0) are copied batch by batch as
+        Keras does."""
+        # what may stay resident: at most `resident_bytes` and at most half of the device memory that is
+        # free right now (ADVICE r3: workspaces, other tenants of the GPU); a failed upload falls back to
+        # per-batch copies
+        try:
+            free_now = int(torch.cuda.mem_get_info(self._device())[0])
+        except Exception:
+            free_now = 0
+        budget = min(int(resident_bytes), free_now // 2)
+
+        def upload(arrays):
+            """Device copies of the numpy members of `arrays` (one copy per distinct array: the
+            pretraining model passes y = x) if they fit the budget, else None."""
+            nonlocal budget
+            uniq = {}
+            for a in arrays:
+                if isinstance(a, np.ndarray):
+                    uniq.setdefault(id(a), a)
+            need = sum(a.size * 4 for a in uniq.values())
+            if not uniq or need > budget:
+                return None
+            try:
+                dev_of = {k: self._to_device(a) for k, a in uniq.items()}
+            except torch.cuda.OutOfMemoryError:
+                torch.cuda.empty_cache()
+                return None
+            budget -= need
+            return [dev_of[id(a)] if isinstance(a, np.ndarray) else a for a in arrays]
+        up = upload([x, y, sample_weight])
+        if up is not None:
+            x, y, sample_weight = up
+        if validation_data is not None:
+            up = upload(list(validation_data))
+            if up is not None:
+                validation_data = tuple(up)
+        take = lambda a, b: a.index_select(0, torch.as_tensor(b, dtype=torch.long, device=a.device)) \
+            if isinstance(a, torch.Tensor) else a[b]
+
+        def step(b, live):
+            sw = None if sample_weight is None else take(sample_weight, b)
+            if not live:
+                # this rank has run out of data: it joins the all-reduce with zero weights
+                # (zero gradient, zero count) on a batch it has already used
+                sw = np.zeros((len(b), x.shape[1]), np.float32)
+            return self.train_on_batch(take(x, b), take(y, b), sw, _live=live)
+        validate = None if validation_data is None else \
+            (lambda: self._validate(validation_data, batch_size, take))
+        return self._run_epochs('fit()', x.shape[0], batch_size, epochs, shuffle, seed, callbacks, verbose, step,
+                                validate)
 
     def fit_wavs(self, noisy, clean, N=512, hop=128, maxlen=None, transform='mag', validation_wavs=None,
                  target='mag', **fit_kwargs):
@@ -1758,26 +1784,29 @@ class _SequenceModel(object):
         must be the value this model masks: a transform whose mask value (data.get_mask_value) differs from
         the model's raises ValueError.  target: 'mag', 'psa' or 'tpsa' (ops.wavs_to_tensors), the y of the
         training AND of the validation tensors, so val_loss and whatever monitors it are against that target."""
-        from . import data
-        ops._check_target(target, transform, 'fit_wavs')
-        for k in ('sample_weight', 'validation_data'):
-            if k in fit_kwargs:
-                raise ValueError('fit_wavs: %s is built from the waveforms (validation_wavs=)' % k)
-        mv = float(data.get_mask_value(dict(transform_x=transform, transform_y=transform)))
-        if mv != float(self.mask_value):
-            raise ValueError("fit_wavs: transform %r pads with %g, the model masks %g"
-                             % (transform, mv, float(self.mask_value)))
-        if int(N) // 2 + 1 != self._input_width():
-            raise ValueError('fit_wavs: N = %d gives %d bins, the model takes %d'
-                             % (N, int(N) // 2 + 1, self._input_width()))
-        build = lambda a, b: ops.wavs_to_tensors(a, b, N=N, hop=hop, maxlen=maxlen, transform=transform,
-                                                 mask_value=mv, device=self._device(), target=target)
-        val = None
-        if validation_wavs is not None:
-            noisy_v, clean_v = validation_wavs
-            val = build(noisy_v, clean_v)
+        _, build = self._check_fit_wavs('fit_wavs', N, hop, maxlen, transform, target, fit_kwargs)
+        val = None if validation_wavs is None else build(*validation_wavs)
         x, y, w = build(noisy, clean)
         return self.fit(x, y, sample_weight=w, validation_data=val, **fit_kwargs)
+
+    def _check_fit_wavs(self, what, N, hop, maxlen, transform, target, fit_kwargs, mix_snr=None):
+        """What fit_wavs and fit_mixtures refuse before anything goes to the device; returns the transform's
+        mask value and build(noisy, clean) -> (x, y, w), ops.wavs_to_tensors with these arguments.  mix_snr:
+        fit_mixtures' (snr_db, snr_choices), checked at its place among the refusals."""
+        from . import data
+        ops._check_target(target, transform, what)
+        for k in ('sample_weight', 'validation_data'):
+            if k in fit_kwargs:
+                raise ValueError('%s: %s is built from the waveforms (validation_wavs=)' % (what, k))
+        if mix_snr is not None:
+            ops._check_mix_snr(mix_snr[0], mix_snr[1], what)
+        mv = float(data.get_mask_value(dict(transform_x=transform, transform_y=transform)))
+        if mv != float(self.mask_value):
+            raise ValueError("%s: transform %r pads with %g, the model masks %g"
+                             % (what, transform, mv, float(self.mask_value)))
+        self._check_bins(what, N)
+        return mv, lambda a, b: ops.wavs_to_tensors(a, b, N=N, hop=hop, maxlen=maxlen, transform=transform,
+                                                    mask_value=mv, device=self._device(), target=target)
 
     def fit_mixtures(self, clean, noise, snr_db=None, snr_choices=None, seed=0, N=512, hop=128, maxlen=None,
                      transform='mag', target='mag', validation_wavs=None, shuffle_seed=None, rirs=None,
@@ -1799,27 +1828,13 @@ class _SequenceModel(object):
         RIR per utterance and epoch from the same seed, dry with probability 1 - reverb_prob.  align,
         target_speech ('reverberant', the default: y is the wet speech; 'early'; 'dry'), early_ms and fs as
         ops.MixBank takes them.  rirs=None: as before."""
-        from . import data, dp
-        ops._check_target(target, transform, 'fit_mixtures')
-        for k in ('sample_weight', 'validation_data'):
-            if k in fit_kwargs:
-                raise ValueError('fit_mixtures: %s is built from the waveforms (validation_wavs=)' % k)
-        ops._check_mix_snr(snr_db, snr_choices, 'fit_mixtures')
-        mv = float(data.get_mask_value(dict(transform_x=transform, transform_y=transform)))
-        if mv != float(self.mask_value):
-            raise ValueError("fit_mixtures: transform %r pads with %g, the model masks %g"
-                             % (transform, mv, float(self.mask_value)))
-        if int(N) // 2 + 1 != self._input_width():
-            raise ValueError('fit_mixtures: N = %d gives %d bins, the model takes %d'
-                             % (N, int(N) // 2 + 1, self._input_width()))
+        from . import dp
+        mv, build = self._check_fit_wavs('fit_mixtures', N, hop, maxlen, transform, target, fit_kwargs,
+                                         mix_snr=(snr_db, snr_choices))
         ops._check_wav_side(clean, 'fit_mixtures', 'clean')
         ops._check_wav_side(noise, 'fit_mixtures', 'noise')
         ops._check_reverb(rirs, align, target_speech, early_ms, fs, 'fit_mixtures')
-        val = None
-        if validation_wavs is not None:
-            noisy_v, clean_v = validation_wavs
-            val = ops.wavs_to_tensors(noisy_v, clean_v, N=N, hop=hop, maxlen=maxlen, transform=transform,
-                                      mask_value=mv, device=self._device(), target=target)
+        val = None if validation_wavs is None else build(*validation_wavs)
         bank = ops.MixBank(clean, noise, rirs=rirs, align=align, target_speech=target_speech, early_ms=early_ms, fs=fs,
                            device=self._device())
         seed_eff = int(seed) + 104729 * dp.rank()
@@ -1884,20 +1899,18 @@ class _SequenceModel(object):
         """One optimiser step on a criterion of the caller's: loss_and_grads_cot(x, cot_fn), the all-reduce of
         `train_on_batch`, the fused Adam.  x [B,T,F] (device tensor or numpy); returns a DeviceLoss, the sum of the
         counted losses over their number."""
-        from . import dp
         self._check_cot('train_on_batch_custom')
-        x = x if isinstance(x, torch.Tensor) else \
-            torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self._device())
-        flat = self.loss_and_grads_cot(x, cot_fn)
-        dp.allreduce_sum_(flat)
-        return self.apply_gradients(flat)
+        return self._reduce_and_step(self.loss_and_grads_cot(self._to_device(x), cot_fn))
 
-    def _check_wave_args(self, what, loss, N, hop):
-        self._check_cot(what)
+    def _check_wave_args(self, what, loss, N, hop, train=True):
+        """What the waveform entries refuse first: a model they cannot take (train: _check_cot; test_on_wavs: one
+        that carries state), then the criterion, then the bin count."""
+        if train:
+            self._check_cot(what)
+        elif self._carries_state():
+            raise NotImplementedError('%s: a stateful model needs its rows in order and at one length' % what)
         ops._wave_kind(loss, what)
-        if int(N) // 2 + 1 != self._input_width():
-            raise ValueError('%s: N = %d gives %d bins, the model takes %d' % (what, N, int(N) // 2 + 1,
-                                                                              self._input_width()))
+        self._check_bins(what, N)
 
     @staticmethod
     def _wave_pieces(noisy, clean, N, hop, max_samples, what):
@@ -1971,41 +1984,29 @@ class _SequenceModel(object):
         ops.wave_loss ('si_sdr': minus the SI-SDR in dB; 'wave_mse'), ops.istft_ragged_vjp, then
         train_on_batch_custom's step -- nothing returns to the host.  Returns a DeviceLoss: the mean of the counted
         recordings' losses.  No enhancement quality is claimed for either criterion."""
-        from . import dp
         self._check_wave_args('train_on_wavs', loss, N, hop)
         bank = self._wave_bank(noisy, clean, int(N), int(hop), max_samples, 'train_on_wavs')
-        x, cot_fn = self._wave_batch(bank, np.arange(bank[3].shape[0]), int(N), int(hop), loss)
-        flat = self.loss_and_grads_cot(x, cot_fn)
-        dp.allreduce_sum_(flat)
-        return self.apply_gradients(flat)
+        return self._wave_step(bank, np.arange(bank[3].shape[0]), int(N), int(hop), loss)
+
+    def _wave_step(self, bank, b, N, hop, kind, live=True):
+        """One optimiser step on recordings `b` of a bank (not live: a replay that adds nothing to the all-reduce)."""
+        x, cot_fn = self._wave_batch(bank, b, N, hop, kind)
+        return self._reduce_and_step(self.loss_and_grads_cot(x, cot_fn, live=live))
 
     def _test_on_wave_bank(self, bank, batch_size, N, hop, loss, what):
-        from . import dp
-        dev = bank[0].device
-        s4 = torch.zeros(4, dtype=torch.float32, device=dev)
+        s4 = torch.zeros(4, dtype=torch.float32, device=bank[0].device)
         self._drop_stale_fault()
         n = bank[3].shape[0]
         for lo in range(0, n, int(batch_size)):
             x, cot_fn = self._wave_batch(bank, np.arange(lo, min(n, lo + int(batch_size))), N, hop, loss)
             s4[:2].add_(cot_fn(self.forward(x), backward=False)[0])
-        ops.status_take(s4[3:])
-        dp.allreduce_sum_(s4)
-        sse, cnt, _, fault = s4.tolist()
-        if fault != 0.0:
-            raise _capi.DrnmfError('%s: a persistent small-shape chain timed out on at least one rank '
-                                   '(DRNMF_ERR_TIMEOUT); rerun, or set DRNMF_PERSIST=0' % what)
-        return sse / max(cnt, 1.0)
+        return self._report_loss(s4, what, plain=True)
 
     def test_on_wavs(self, noisy, clean, loss='si_sdr', N=512, hop=128, max_samples=None, batch_size=8):
         """The criterion of `train_on_wavs` without a step: the mean over the counted recordings of minus the
         SI-SDR in dB, or of the waveform MSE, of the model's cropped reconstructions (a float)."""
         what = 'test_on_wavs'
-        if self._carries_state():
-            raise NotImplementedError('%s: a stateful model needs its rows in order and at one length' % what)
-        ops._wave_kind(loss, what)
-        if int(N) // 2 + 1 != self._input_width():
-            raise ValueError('%s: N = %d gives %d bins, the model takes %d' % (what, N, int(N) // 2 + 1,
-                                                                              self._input_width()))
+        self._check_wave_args(what, loss, N, hop, train=False)
         if int(batch_size) < 1:
             raise ValueError('%s: batch_size must be positive' % what)
         bank = self._wave_bank(noisy, clean, int(N), int(hop), max_samples, what)
@@ -2017,7 +2018,6 @@ class _SequenceModel(object):
         (noisy, clean), if given) go up once, every step is train_on_wavs' on batch_size of them, val_loss is
         test_on_wavs' value (minus the mean SI-SDR in dB, or the waveform MSE).  Callbacks and the returned history
         as `fit`."""
-        from . import dp
         what = 'fit_waveform'
         self._check_wave_args(what, loss, N, hop)
         N, hop, bs = int(N), int(hop), int(batch_size)
@@ -2026,52 +2026,9 @@ class _SequenceModel(object):
         bank = self._wave_bank(noisy, clean, N, hop, max_samples, what)
         vbank = None if validation_wavs is None else \
             self._wave_bank(validation_wavs[0], validation_wavs[1], N, hop, max_samples, what)
-        n = bank[3].shape[0]
-        rng = np.random.RandomState(seed)
-        hist = {'loss': [], 'val_loss': []}
-        callbacks = [cb for cb in (callbacks or []) if dp.rank() == 0 or not getattr(cb, 'rank0_only', False)]
-        self.stop_training = False
-        for cb in callbacks:
-            if hasattr(cb, 'set_model'):
-                cb.set_model(self)
-            else:
-                cb.model = self
-            if hasattr(cb, 'on_train_begin'):
-                cb.on_train_begin({})
-        per_batch_cbs = [cb for cb in callbacks if hasattr(cb, 'on_batch_end')]
-        steps = dp.max_over_ranks(epoch_steps(n, bs))
-        for ep in range(int(epochs)):
-            for cb in callbacks:
-                if hasattr(cb, 'on_epoch_begin'):
-                    cb.on_epoch_begin(ep, {})
-            idx = rng.permutation(n) if shuffle else np.arange(n)
-            ep_losses, cnt = [], 0
-            for b, live in epoch_batches(idx, bs, steps):
-                x, cot_fn = self._wave_batch(bank, b, N, hop, loss)
-                flat = self.loss_and_grads_cot(x, cot_fn, live=live)
-                dp.allreduce_sum_(flat)
-                step_loss = self.apply_gradients(flat)
-                ep_losses.append(step_loss)
-                for cb in per_batch_cbs:
-                    cb.on_batch_end(cnt, {'batch': cnt, 'size': len(b), 'loss': float(step_loss)})
-                cnt += 1
-            logs = {'loss': sum(float(l) for l in ep_losses) / max(cnt, 1)}
-            hist['loss'].append(logs['loss'])
-            if vbank is not None:
-                logs['val_loss'] = self._test_on_wave_bank(vbank, bs, N, hop, loss, what)
-                hist['val_loss'].append(logs['val_loss'])
-            if verbose and dp.rank() == 0:
-                print('epoch %d loss %.6f%s' % (ep + 1, logs['loss'],
-                      (' val_loss %.6f' % logs['val_loss']) if vbank is not None else ''))
-            for cb in callbacks:
-                if hasattr(cb, 'on_epoch_end'):
-                    cb.on_epoch_end(ep, logs)
-            if self.stop_training:
-                break
-        for cb in callbacks:
-            if hasattr(cb, 'on_train_end'):
-                cb.on_train_end({})
-        return hist
+        validate = None if vbank is None else (lambda: self._test_on_wave_bank(vbank, bs, N, hop, loss, what))
+        return self._run_epochs(what, bank[3].shape[0], bs, int(epochs), shuffle, seed, callbacks, verbose,
+                                lambda b, live: self._wave_step(bank, b, N, hop, loss, live), validate)
 
     def _validate(self, validation_data, batch_size, take):
         """Validation loss of fit(), evaluated in mini-batches of `batch_size` sequences as Keras'
@@ -2079,10 +2036,7 @@ class _SequenceModel(object):
         2 460-utterance CHiME2 validation set at N = 2000 would otherwise need a ~40 GB hidden tensor.
         The sums [sum w*loss, count, frames, fault] are accumulated on the device over the batches and
         all-reduced ONCE (every rank holds its shard), so the value is the loss of the whole set."""
-        from . import dp
-        dev = self._device()
-        tt = lambda a: a if isinstance(a, torch.Tensor) else \
-            torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        dev, tt = self._device(), self._to_device
         xv, yv = validation_data[0], validation_data[1]
         wv = validation_data[2] if len(validation_data) > 2 else None
         nv, Tv = xv.shape[0], xv.shape[1]
@@ -2117,16 +2071,7 @@ class _SequenceModel(object):
                 torch.ones(xb.shape[:2], dtype=torch.float32, device=dev)
             s4[:2].add_(self._validation_sums(xb, yb, wb))
             s4[2] += float(len(b) * Tv)          # (frames of the PADDED batch: loss_norm='keras204' divides by them)
-        ops.status_take(s4[3:])
-        dp.allreduce_sum_(s4)
-        sse, cnt, rows, fault = s4.tolist()
-        if fault != 0.0:
-            raise _capi.DrnmfError('fit(): a persistent small-shape chain timed out during validation on '
-                                   'at least one rank (DRNMF_ERR_TIMEOUT); rerun, or set DRNMF_PERSIST=0')
-        scale = 1.0 / max(cnt, 1.0)
-        if getattr(self, 'loss_norm', 'masked_mean') == 'keras204':
-            scale *= rows / max(cnt, 1.0)
-        return sse * scale + (self._regularization_loss() if hasattr(self, '_train_items') else 0.0)
+        return self._report_loss(s4, 'fit() validation')
 
 
 class EnhanceStream(object):
@@ -2354,13 +2299,31 @@ class UnfoldedSNMFModel(_SequenceModel):
         for l in (self.cell, self.clean, self.noise):
             l._weights_changed()
 
+    def _train_forward_and_head(self, x, mark=lambda name, which: None):
+        """The training forward (every layer's hidden state) and the head on the last layer's: (hall, h_off, mask,
+        A, Bn)."""
+        cell = self.cell
+        mark('cell_forward', 0)
+        hall = cell.forward_train(x, mask_value=self.mask_value)
+        mark('cell_forward', 1)
+        mark('head_and_loss', 0)
+        h_off = (cell.K_layers - 1) * cell.output_dim
+        mask, A, Bn = ops.head_forward(hall, self.clean.kernel, self.noise.kernel, square=self.square,
+                                       want_ab=True, h_off=h_off)
+        return hall, h_off, mask, A, Bn
+
+    def _bptt(self, x, hall, d_hidden, mark=lambda name, which: None, profile=None):
+        """The cell's backward from the head's d_hidden, every gradient into the flat buffer."""
+        mark('cell_backward', 0)
+        g = self.cell.backward(x, hall, d_hidden, grads=self._grad_targets[0], profile=profile)
+        mark('cell_backward', 1)
+        self._collect_grads(g)
+
     def loss_and_grads(self, x, y, sample_weight, live=True):
         """Unnormalised loss/gradients of one (local) batch into the flat buffer; returns the
         flat tensor [grads..., sum w*mse, count, frames].  `self.phase_events` (bench.py only): a
         dict that receives (start, end) torch events of the cell forward, the head + loss, and the
         BPTT, recorded on the current stream without synchronising."""
-        cell = self.cell
-        N, K = cell.output_dim, cell.K_layers
         self._drop_stale_fault()
         pe = getattr(self, 'phase_events', None)
 
@@ -2369,38 +2332,21 @@ class UnfoldedSNMFModel(_SequenceModel):
                 ev = torch.cuda.Event(enable_timing=True)
                 ev.record()
                 pe.setdefault(name, [None, None])[which] = ev
-        mark('cell_forward', 0)
-        hall = cell.forward_train(x, mask_value=self.mask_value)
-        mark('cell_forward', 1)
-        mark('head_and_loss', 0)
-        h_off = (K - 1) * N
-        mask, A, Bn = ops.head_forward(hall, self.clean.kernel, self.noise.kernel,
-                                       square=self.square, want_ab=True, h_off=h_off)
-        grads, head_out = self._grad_targets
+        hall, h_off, mask, A, Bn = self._train_forward_and_head(x, mark)
         _, d_hidden, _, _ = ops.loss_head_backward(
             x, hall, self.clean.kernel, self.noise.kernel, mask, A, Bn, y, sample_weight,
-            square=self.square, h_off=h_off, out=head_out)
+            square=self.square, h_off=h_off, out=self._grad_targets[1])
         mark('head_and_loss', 1)
-        mark('cell_backward', 0)
-        g = cell.backward(x, hall, d_hidden, grads=grads,
-                          profile=getattr(self, 'backward_profile', None))
-        mark('cell_backward', 1)
-        self._collect_grads(g)
+        self._bptt(x, hall, d_hidden, mark, profile=getattr(self, 'backward_profile', None))
         self._set_scalars(x, live)
         return self._flat
 
     def _cot_head_and_bptt(self, x, cot_fn):
-        cell = self.cell
-        N, K = cell.output_dim, cell.K_layers
-        hall = cell.forward_train(x, mask_value=self.mask_value)
-        h_off = (K - 1) * N
-        mask, A, Bn = ops.head_forward(hall, self.clean.kernel, self.noise.kernel, square=self.square,
-                                       want_ab=True, h_off=h_off)
+        hall, h_off, mask, A, Bn = self._train_forward_and_head(x)
         sums2, d_mask = cot_fn(mask)
-        grads, head_out = self._grad_targets
         d_hidden, _, _ = ops.head_backward_cot(d_mask, hall, self.clean.kernel, self.noise.kernel, A, Bn,
-                                               square=self.square, h_off=h_off, out=head_out[1:])
-        self._collect_grads(cell.backward(x, hall, d_hidden, grads=grads))
+                                               square=self.square, h_off=h_off, out=self._grad_targets[1][1:])
+        self._bptt(x, hall, d_hidden)
         return sums2
 
     @staticmethod
@@ -2505,8 +2451,7 @@ class SNMFCostPretrainModel(UnfoldedSNMFModel):
         return [ops.add(A, Bn), h]
 
     def predict_on_batch(self, x):
-        xt = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self.cell.device)
-        out = [o.cpu().numpy() for o in self.forward(xt)]
+        out = [o.cpu().numpy() for o in self.forward(self._to_device(x))]
         ops.check_status(self.cell.device)      # (the copies synchronised: a chain that timed out raises HERE)
         return out
 
@@ -2517,20 +2462,13 @@ class SNMFCostPretrainModel(UnfoldedSNMFModel):
         return [np.concatenate([p[i] for p in parts]) for i in range(2)]
 
     def loss_and_grads(self, x, y, sample_weight, live=True):
-        cell = self.cell
-        N, K = cell.output_dim, cell.K_layers
         self._drop_stale_fault()
-        hall = cell.forward_train(x, mask_value=self.mask_value)
-        h_off = (K - 1) * N
-        _, A, Bn = ops.head_forward(hall, self.clean.kernel, self.noise.kernel, want_ab=True,
-                                    h_off=h_off)
+        hall, h_off, _, A, Bn = self._train_forward_and_head(x)
         # the targets are the input itself (enhance.py:1110); y is accepted for API symmetry
-        grads, head_out = self._grad_targets
         _, d_hidden, _, _ = ops.snmf_cost_head_backward(
             self._first(y), hall, self.clean.kernel, self.noise.kernel, A, Bn,
-            self._first(sample_weight), self.loss_weights[1], h_off=h_off, out=head_out)
-        g = cell.backward(x, hall, d_hidden, grads=grads)
-        self._collect_grads(g)
+            self._first(sample_weight), self.loss_weights[1], h_off=h_off, out=self._grad_targets[1])
+        self._bptt(x, hall, d_hidden)
         self._set_scalars(x, live)
         return self._flat
 
@@ -2539,24 +2477,15 @@ class SNMFCostPretrainModel(UnfoldedSNMFModel):
         return UnfoldedSNMFModel.train_on_batch(self, x, y, self._first(sample_weight), _live=_live)
 
     def test_on_batch(self, x, y=None, sample_weight=None):
-        from . import dp
-        dev = self.cell.device
-        tt = lambda a: a if isinstance(a, torch.Tensor) else \
-            torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        tt = self._to_device
         x = tt(x)
         y = x if y is None else tt(self._first(y))
         sw = self._first(sample_weight)
-        w = tt(sw) if sw is not None else torch.ones(x.shape[:2], dtype=torch.float32, device=dev)
-        s3 = torch.zeros(3, dtype=torch.float32, device=dev)
+        w = tt(sw) if sw is not None else torch.ones(x.shape[:2], dtype=torch.float32, device=x.device)
+        s4 = torch.zeros(4, dtype=torch.float32, device=x.device)      # (the frames word stays zero: plain mean)
         self._drop_stale_fault()
-        s3[:2].copy_(self._validation_sums(x, y, w))
-        ops.status_take(s3[2:])
-        dp.allreduce_sum_(s3)
-        sse, cnt, fault = s3.tolist()
-        if fault != 0.0:
-            raise _capi.DrnmfError('test_on_batch: a persistent small-shape chain timed out on at least '
-                                   'one rank (DRNMF_ERR_TIMEOUT); rerun, or set DRNMF_PERSIST=0')
-        return sse / max(cnt, 1.0)
+        s4[:2].copy_(self._validation_sums(x, y, w))
+        return self._report_loss(s4, 'test_on_batch', plain=True)
 
     def _validation_sums(self, x, y, w):
         h = self.cell.call(x, mask_value=self.mask_value)
@@ -2877,57 +2806,55 @@ class LSTMModel(_SequenceModel):
     def _weights_replaced(self):
         self._prepared = None
 
+    def _train_prologue(self, x):
+        """(x contiguous float32, desc, prepared params, training workspace) of one batch; the workspace and
+        self._d_hidden [B,T,H] are re-made only when this batch needs them larger or of another shape."""
+        x = x.float().contiguous()
+        B, T = int(x.shape[0]), int(x.shape[1])
+        desc = self._desc(B, T)
+        params = self._params(desc)
+        need = _capi.lib().drnmf_lstm_train_workspace_bytes(ctypes.byref(desc))
+        if self._train_ws is None or self._train_ws.numel() < need:
+            self._train_ws = None
+            self._train_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if self._d_hidden is None or tuple(self._d_hidden.shape) != (B, T, desc.H):
+            self._d_hidden = torch.empty((B, T, desc.H), dtype=torch.float32, device=self.device)
+        return x, desc, params, self._train_ws
+
+    def _bptt(self, desc, ws):
+        """BPTT from self._d_hidden, every layer's gradients into their views of the flat buffer."""
+        ls, gv = self.lstms, self._gview
+        ops.lstm_backward([l.kernel for l in ls], [l.recurrent_kernel for l in ls], self._d_hidden,
+                          [gv[l.weight_names[0]] for l in ls], [gv[l.weight_names[1]] for l in ls],
+                          [gv[l.weight_names[2]] for l in ls], desc, ws)
+
     def loss_and_grads(self, x, y, sample_weight, live=True):
         """Unnormalised loss and gradients of one (local) batch into the flat buffer, which is returned:
         training forward, loss head + its backward, BPTT with the weight gradients -- all on the device."""
         if not hasattr(self, '_flat'):
             raise RuntimeError('LSTMModel: compile() before training')
         self._drop_stale_fault()
-        x = x.float().contiguous()
-        B, T = int(x.shape[0]), int(x.shape[1])
-        desc = self._desc(B, T)
-        params = self._params(desc)
-        need = _capi.lib().drnmf_lstm_train_workspace_bytes(ctypes.byref(desc))
-        if self._train_ws is None or self._train_ws.numel() < need:
-            self._train_ws = None
-            self._train_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        if self._d_hidden is None or tuple(self._d_hidden.shape) != (B, T, desc.H):
-            self._d_hidden = torch.empty((B, T, desc.H), dtype=torch.float32, device=self.device)
-        ws, gv, ns = self._train_ws, self._gview, self.N_SCALARS
+        x, desc, params, ws = self._train_prologue(x)
+        gv, ns, d = self._gview, self.N_SCALARS, self.dense
         # (stateful: the state enters as a constant of the gradient and the one this batch leaves replaces it in
         # place -- the kernels read all of the entering state before they write the leaving one, and the BPTT
         # finds its copy in the workspace)
-        st = self._state(B)
+        st = self._state(x.shape[0])
         h = ops.lstm_train_forward(x, self.mask_value, params, desc, ws, initial_state=st, final_state=st)
-        d = self.dense
         ops.lstm_loss_head_backward(y, sample_weight, h, params, d.kernel, desc, ws, self._flat[-ns:-ns + 2],
                                     self._d_hidden, gv[d.weight_names[0]], gv[d.weight_names[1]])
-        ls = self.lstms
-        ops.lstm_backward([l.kernel for l in ls], [l.recurrent_kernel for l in ls], self._d_hidden,
-                          [gv[l.weight_names[0]] for l in ls], [gv[l.weight_names[1]] for l in ls],
-                          [gv[l.weight_names[2]] for l in ls], desc, ws)
+        self._bptt(desc, ws)
         self._set_scalars(x, live)
         return self._flat
 
     def _cot_head_and_bptt(self, x, cot_fn):
-        x = x.float().contiguous()
-        B, T = int(x.shape[0]), int(x.shape[1])
-        desc = self._desc(B, T)
-        params = self._params(desc)
-        need = _capi.lib().drnmf_lstm_train_workspace_bytes(ctypes.byref(desc))
-        if self._train_ws is None or self._train_ws.numel() < need:
-            self._train_ws = None
-            self._train_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        if self._d_hidden is None or tuple(self._d_hidden.shape) != (B, T, desc.H):
-            self._d_hidden = torch.empty((B, T, desc.H), dtype=torch.float32, device=self.device)
-        ws, gv, d, ls = self._train_ws, self._gview, self.dense, self.lstms
+        x, desc, params, ws = self._train_prologue(x)
+        gv, d = self._gview, self.dense
         h = ops.lstm_train_forward(x, self.mask_value, params, desc, ws)
         sums2, d_mask = cot_fn(ops.lstm_head_forward(h, params, desc))
         ops.lstm_head_backward_cot(d_mask, h, params, d.kernel, desc, ws, self._d_hidden, gv[d.weight_names[0]],
                                    gv[d.weight_names[1]])
-        ops.lstm_backward([l.kernel for l in ls], [l.recurrent_kernel for l in ls], self._d_hidden,
-                          [gv[l.weight_names[0]] for l in ls], [gv[l.weight_names[1]] for l in ls],
-                          [gv[l.weight_names[2]] for l in ls], desc, ws)
+        self._bptt(desc, ws)
         return sums2
 
     def _after_step(self):
