@@ -58,7 +58,8 @@ NO_SCRATCH = {# (lstm_cot_rows_kernel: the head's backward for a given mask cota
               # the waveform losses: four fp64 accumulators per lane
               "waveloss.hip": "wave_loss_",
               # the ESTOI segment kernel holds a 30-frame row, then two 15-band columns, of fp64 per lane
-              "stoi.hip": "estoi_",
+              # (the STOI criterion's backward kernels: the segment kernel holds two 30-frame rows of fp64 per lane)
+              "stoi.hip": ("estoi_", "stoi_loss_"),
               # the mixer's sample passes hold four quads and an fp64 accumulator per lane; its gain kernel calls pow
               "mix.hip": "mix_",
               # the reverberator holds 8 outputs, their early parts, 16 samples and 8 taps per lane
@@ -96,7 +97,7 @@ def _deps():
                                                                      "drnmf_dataset.h", "drnmf_stream.h", "drnmf_snmf.h", "drnmf_snmf_f16.h",
                                                                      "drnmf_target.h", "drnmf_estoi.h", "drnmf_snmf_adapt.h",
                                                                      "drnmf_snmf_kl.h", "drnmf_snmf_online.h", "drnmf_mix.h",
-                                                                     "drnmf_waveloss.h", "drnmf_reverb.h")] + \
+                                                                     "drnmf_waveloss.h", "drnmf_reverb.h", "drnmf_stoi_loss.h")] + \
         [os.path.abspath(__file__)]
 
 

@@ -29,12 +29,15 @@
 //                  normalised, the 30 column products added in frame order.
 //   estoi_mean     as stoi_mean, one value per segment.
 // Plain arithmetic there too: a zero norm (a constant band, a silent stretch of the estimate) is 0 / 0 = NaN.
+// The training criterion -STOI with its exact gradient (include/drnmf_stoi_loss.h, tests/stoi_loss_ref.py) is the same
+// launches through drnmf_stoi_loss, then the stoi_loss_* kernels further down, which walk the stages backwards.
 // Matlab edge semantics (not pystoi's): fewer than 30 band frames -> NaN; fmin ignores NaN, so a segment with
 // sum Y^2 = 0 (alpha = inf, inf * 0 = NaN) takes Y' = X (1 + c) and scores 1; a zero-variance vector divides
 // 0 by 0 and the NaN reaches the mean.
 #include "common.h"
 #include "../../include/drnmf_score.h"
 #include "../../include/drnmf_estoi.h"
+#include "../../include/drnmf_stoi_loss.h"
 
 namespace {
 
@@ -47,6 +50,8 @@ constexpr double ST_CLIP = 1.0 + 5.6234132519034908;   // 1 + 10^(-beta/20), bet
 __constant__ int k_band_lo[ST_J] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174};
 __constant__ int k_band_hi[ST_J] = {9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219};
 constexpr int ST_K0 = 7, ST_K1 = 219;              // bins read by the bands
+// The bands are contiguous, k_band_hi[j] == k_band_lo[j + 1], from ST_K0 = k_band_lo[0] to ST_K1 = k_band_hi[14]:
+// stoi_loss_band_kernel finds a bin's band by counting the upper edges at or below it.
 
 struct LenChunk {
     int64_t len[ST_LEN_CHUNK];
@@ -209,23 +214,81 @@ __device__ __forceinline__ void dft4(double2 (&v)[4]) {
     v[3] = make_double2(b.x - d.y, b.y + d.x);      // b + i d
 }
 
+// One wave's 256-point complex FFT (of the 512-point real frame's sample pairs) in its LDS slice
+constexpr int FT_M = 256, FT_N = 512, FT_R = 4, FT_P = 4, FT_MP = FT_M + FT_M / 8;
+__device__ __forceinline__ int ft_pad(int i) { return i + (i >> 3); }       // index i lives at i + i/8 (bank spread)
+
+// sample t of compacted frame `frame`: the overlap-add of kept frames i (source start s0) and i -+ 1 (sp, sn),
+// windowed again
+template <typename T>
+__device__ __forceinline__ double band_sample(const T* __restrict__ src, const double* win, int64_t s0, int64_t sp,
+                                              int64_t sn, int frame, int t) {
+    const double a = (double)src[s0 + t] * win[t];
+    double b = 0.0;
+    if (t < ST_HOP) {
+        if (frame > 0) b = (double)src[sp + t + ST_HOP] * win[t + ST_HOP];
+    } else {
+        b = (double)src[sn + t - ST_HOP] * win[t - ST_HOP];
+    }
+    return (a + b) * win[t];
+}
+
+// The radix-4 Stockham passes: lane j enters with v[r] = z[j + 64 r] and the transform is left in buf (natural
+// order, padded); tw = e^{-2 pi i k / 512}, k < 256.  Wave-private: fences and wave barriers only.
+__device__ __forceinline__ void fft256_wave(double2 (&v)[FT_R], double2* buf, const double2* tw, int j) {
+    constexpr int M = FT_M, N = FT_N, R = FT_R, P = FT_P;
+    int Ns = 1;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        if (p > 0) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) v[r] = buf[ft_pad(j + r * (M / R))];
+        }
+        const int k = j & (Ns - 1);
+        if (p > 0) {                       // twiddles e^{-2 pi i k r / (Ns R)}
+            const int step = k * (N / (Ns * R));
+#pragma unroll
+            for (int r = 1; r < R; ++r) {
+                const int idx = step * r;
+                const double2 t = tw[idx & (N / 2 - 1)];
+                v[r] = zmul(v[r], idx >= N / 2 ? make_double2(-t.x, -t.y) : t);
+            }
+        }
+        dft4(v);
+        const int j0 = (j - k) * R + k;
+#pragma unroll
+        for (int r = 0; r < R; ++r) buf[ft_pad(j0 + r * Ns)] = v[r];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        Ns *= R;
+    }
+}
+
+// bin k of the real frame's spectrum from the packed transform in buf: X[k] = a - i w b
+__device__ __forceinline__ double2 real_bin(const double2* buf, const double2* tw, int k) {
+    const double2 zk = buf[ft_pad(k)];
+    const double2 zc = buf[ft_pad(FT_M - k)];
+    const double2 a = make_double2(0.5 * (zk.x + zc.x), 0.5 * (zk.y - zc.y));
+    const double2 b = make_double2(0.5 * (zk.x - zc.x), 0.5 * (zk.y + zc.y));
+    const double2 wb = zmul(b, tw[k]);
+    return make_double2(a.x + wb.y, a.y - wb.x);
+}
+
 // grid (ceil(F / 4), n_sig), one wave per band frame; env [n_sig][F][15]
 template <typename T>
 __global__ void __launch_bounds__(256)
 stoi_band_kernel(const T* __restrict__ xr, const T* __restrict__ yr, int64_t ld,
                  const int* __restrict__ kidx, const int* __restrict__ nkept, int V, int F,
                  float* __restrict__ env_x, float* __restrict__ env_y) {
-    constexpr int M = 256, N = 512, R = 4, P = 4, MP = M + M / 8;
-    __shared__ double2 tw[N / 2];              // e^{-2 pi i k / N}, k < N/2
+    __shared__ double2 tw[FT_N / 2];           // e^{-2 pi i k / N}, k < N/2
     __shared__ double win[ST_N];
-    __shared__ double2 bufs[4][MP];            // per wave; index i lives at i + i/8 (bank spread)
+    __shared__ double2 bufs[4][FT_MP];         // per wave
     __shared__ double pw[4][ST_K1 - ST_K0];    // per wave: |X_k|^2 of the band bins
-    auto pad = [](int i) { return i + (i >> 3); };
     const int tid = threadIdx.x, wv = tid >> 6, j = tid & 63;
     const int frame = blockIdx.x * 4 + wv, sig = blockIdx.y;
     {
         double sn, cs;
-        sincospi(-2.0 * (double)tid / (double)N, &sn, &cs);
+        sincospi(-2.0 * (double)tid / (double)FT_N, &sn, &cs);
         tw[tid] = make_double2(cs, sn);
         win[tid] = hanning256(tid);
     }
@@ -238,60 +301,21 @@ stoi_band_kernel(const T* __restrict__ xr, const T* __restrict__ yr, int64_t ld,
     double2* buf = bufs[wv];
     for (int which = 0; which < 2; ++which) {
         const T* __restrict__ src = (which ? yr : xr) + (size_t)sig * ld;
-        // sample t of compacted frame i: the overlap-add of kept frames i and i -+ 1, windowed again
-        auto samp = [&](int t) {
-            const double a = (double)src[s0 + t] * win[t];
-            double b = 0.0;
-            if (t < ST_HOP) {
-                if (frame > 0) b = (double)src[sp + t + ST_HOP] * win[t + ST_HOP];
-            } else {
-                b = (double)src[sn + t - ST_HOP] * win[t - ST_HOP];
-            }
-            return (a + b) * win[t];
-        };
+        auto samp = [&](int t) { return band_sample(src, win, s0, sp, sn, frame, t); };
         // pass-0 input z[n] = (s[2n], s[2n+1]), n = j + 64 r; zero padding from n = 128 on
-        double2 v[R];
+        double2 v[FT_R];
         v[0] = make_double2(samp(2 * j), samp(2 * j + 1));
         v[1] = make_double2(samp(2 * j + 128), samp(2 * j + 129));
         v[2] = make_double2(0.0, 0.0);
         v[3] = make_double2(0.0, 0.0);
-        int Ns = 1;
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-            if (p > 0) {
-#pragma unroll
-                for (int r = 0; r < R; ++r) v[r] = buf[pad(j + r * (M / R))];
-            }
-            const int k = j & (Ns - 1);
-            if (p > 0) {                       // twiddles e^{-2 pi i k r / (Ns R)}
-                const int step = k * (N / (Ns * R));
-#pragma unroll
-                for (int r = 1; r < R; ++r) {
-                    const int idx = step * r;
-                    const double2 t = tw[idx & (N / 2 - 1)];
-                    v[r] = zmul(v[r], idx >= N / 2 ? make_double2(-t.x, -t.y) : t);
-                }
-            }
-            dft4(v);
-            const int j0 = (j - k) * R + k;
-#pragma unroll
-            for (int r = 0; r < R; ++r) buf[pad(j0 + r * Ns)] = v[r];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            Ns *= R;
-        }
-        // split the real spectrum X[k] = a - i w b of the band bins; |X_k|^2 to LDS
+        fft256_wave(v, buf, tw, j);
+        // split the real spectrum of the band bins; |X_k|^2 to LDS
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int k = ST_K0 + j + 64 * i;
             if (k < ST_K1) {
-                const double2 zk = buf[pad(k)];
-                const double2 zc = buf[pad(M - k)];
-                const double2 a = make_double2(0.5 * (zk.x + zc.x), 0.5 * (zk.y - zc.y));
-                const double2 b = make_double2(0.5 * (zk.x - zc.x), 0.5 * (zk.y + zc.y));
-                const double2 wb = zmul(b, tw[k]);
-                const double re = a.x + wb.y, im = a.y - wb.x;
-                pw[wv][k - ST_K0] = re * re + im * im;
+                const double2 X = real_bin(buf, tw, k);
+                pw[wv][k - ST_K0] = X.x * X.x + X.y * X.y;
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -307,22 +331,14 @@ stoi_band_kernel(const T* __restrict__ xr, const T* __restrict__ yr, int64_t ld,
     }
 }
 
-// grid (ceil(S * 15 / 256), n_sig): lane g = segment * 15 + band; d [n_sig][S][15]
-__global__ void __launch_bounds__(256)
-stoi_segment_kernel(const float* __restrict__ env_x, const float* __restrict__ env_y,
-                    const int* __restrict__ nkept, int F, int S, double* __restrict__ d) {
-    const int sig = blockIdx.y;
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    const int seg = g / ST_J, band = g - seg * ST_J;
-    if (seg >= nkept[sig] - 1 - (ST_SEG - 1)) return;
-    const float* __restrict__ ex = env_x + ((size_t)sig * F + seg) * ST_J + band;
-    const float* __restrict__ ey = env_y + ((size_t)sig * F + seg) * ST_J + band;
-    double X[ST_SEG], Y[ST_SEG];
-#pragma unroll
-    for (int f = 0; f < ST_SEG; ++f) {
-        X[f] = (double)ex[f * ST_J];
-        Y[f] = (double)ey[f * ST_J];
-    }
+// One (segment, band) of step 4, shared by the score and by its gradient so that both take the same clip decisions.
+// X, Y enter as the 30 envelopes of the reference and the estimate and leave centred, Y clipped first (Y').
+struct SegStats {
+    double alpha, sy, mx, my, nx, ny, rho;     // sqrt(Sx / Sy), Sy, the means of X and Y', the norms, the correlation
+    unsigned u;                                // bit f: frame f is not clipped (alpha Y <= c X)
+};
+__device__ __forceinline__ SegStats segment_stats(double (&X)[ST_SEG], double (&Y)[ST_SEG]) {
+    SegStats s;
     double sx = 0.0, sy = 0.0;
 #pragma unroll
     for (int f = 0; f < ST_SEG; ++f) {
@@ -331,9 +347,12 @@ stoi_segment_kernel(const float* __restrict__ env_x, const float* __restrict__ e
     }
     const double alpha = sqrt(sx / sy);
     double mx = 0.0, my = 0.0;
+    unsigned u = 0;
 #pragma unroll
     for (int f = 0; f < ST_SEG; ++f) {
-        Y[f] = fmin(alpha * Y[f], X[f] * ST_CLIP);    // fmin: a NaN operand yields the other (Matlab min)
+        const double ay = alpha * Y[f], cx = X[f] * ST_CLIP;
+        if (ay <= cx) u |= 1u << f;
+        Y[f] = fmin(ay, cx);                       // fmin: a NaN operand yields the other (Matlab min)
         mx += X[f];
         my += Y[f];
     }
@@ -352,7 +371,27 @@ stoi_segment_kernel(const float* __restrict__ env_x, const float* __restrict__ e
     double rho = 0.0;
 #pragma unroll
     for (int f = 0; f < ST_SEG; ++f) rho = fma(X[f] / nx, Y[f] / ny, rho);
-    d[(size_t)sig * S * ST_J + g] = rho;
+    s.alpha = alpha; s.sy = sy; s.mx = mx; s.my = my; s.nx = nx; s.ny = ny; s.rho = rho; s.u = u;
+    return s;
+}
+
+// grid (ceil(S * 15 / 256), n_sig): lane g = segment * 15 + band; d [n_sig][S][15]
+__global__ void __launch_bounds__(256)
+stoi_segment_kernel(const float* __restrict__ env_x, const float* __restrict__ env_y,
+                    const int* __restrict__ nkept, int F, int S, double* __restrict__ d) {
+    const int sig = blockIdx.y;
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    const int seg = g / ST_J, band = g - seg * ST_J;
+    if (seg >= nkept[sig] - 1 - (ST_SEG - 1)) return;
+    const float* __restrict__ ex = env_x + ((size_t)sig * F + seg) * ST_J + band;
+    const float* __restrict__ ey = env_y + ((size_t)sig * F + seg) * ST_J + band;
+    double X[ST_SEG], Y[ST_SEG];
+#pragma unroll
+    for (int f = 0; f < ST_SEG; ++f) {
+        X[f] = (double)ex[f * ST_J];
+        Y[f] = (double)ey[f * ST_J];
+    }
+    d[(size_t)sig * S * ST_J + g] = segment_stats(X, Y).rho;
 }
 
 // the fp64 mean of ds[0 .. cnt) by one workgroup, in a fixed order (cnt > 0)
@@ -481,6 +520,287 @@ estoi_mean_kernel(const double* __restrict__ d, const int* __restrict__ nkept, i
     mean_fixed_order(d + (size_t)sig * S, nseg, red, out + sig);
 }
 
+// ---- the gradient of -STOI with respect to the estimate (include/drnmf_stoi_loss.h) ----------------------------
+// The forward's stages walked backwards, fp64 throughout, every sum a gather in a fixed order (no atomics): a row's
+// gradient is bitwise the same in any batch and in every run.  The silence decision and the compaction index depend
+// on the reference only, so nothing flows through them.
+//   stoi_loss_rows      one workgroup: loss = -STOI and counted = 1 where STOI is finite (0, 0 elsewhere), sums[2].
+//   stoi_loss_seg       one lane per (segment, band), the arithmetic of stoi_segment_kernel (the same clip
+//                       decisions u: the shared segment_stats), then the segment's scalars: alpha, c2 = (1/Sy) sum_u g Y', the two means and
+//                       inverse norms and d, with g = (x^ - d y^) / ||Y' - mean||.
+//   stoi_loss_env       one lane per (band frame, band): gY = -1/(S J) sum over the <= 30 segments that hold the
+//                       frame of alpha u g - c2 Y; a segment with Sy == 0 adds nothing.
+//   stoi_loss_band      one wave per band frame: the estimate's frame transformed as stoi_band_kernel does, the
+//                       band bins scaled by gY / Y (0 where Y == 0), and the adjoint w[n] Re sum_k G_k e^{+2 pi i k
+//                       n / 512} through the same passes: the Hermitian extension of G folded into a 256-point
+//                       complex inverse, run as the conjugate of the forward transform of the conjugate.
+//   stoi_loss_gather    one lane per 10 kHz sample: its <= 2 silence-detector frames, each found in the compaction
+//                       index by bisection, each gathering its <= 2 band frames.  At 10 kHz this writes g.
+//   stoi_loss_resample  one lane per input sample: the transposed polyphase filter, the taps in LDS.
+constexpr int SL_SEG_W = 7;        // doubles per (segment, band): alpha (< 0: no gradient), c2, mx, 1/nx, my, 1/ny, d
+
+__global__ void __launch_bounds__(256)
+stoi_loss_rows_kernel(const float* __restrict__ stoi, int n_sig, float* __restrict__ loss,
+                      float* __restrict__ counted, float* __restrict__ sums) {
+    __shared__ double s0[256], s1[256];
+    double tot = 0.0, cnt = 0.0;
+    for (int row = threadIdx.x; row < n_sig; row += 256) {
+        const float s = stoi[row];
+        const bool on = isfinite(s);
+        const float l = on ? -s : 0.f;
+        loss[row] = l;
+        counted[row] = on ? 1.f : 0.f;
+        if (on) {
+            tot += (double)l;
+            cnt += 1.0;
+        }
+    }
+    s0[threadIdx.x] = tot;
+    s1[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            s0[threadIdx.x] += s0[threadIdx.x + o];
+            s1[threadIdx.x] += s1[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        sums[0] = (float)s0[0];
+        sums[1] = (float)s1[0];
+    }
+}
+
+// grid as stoi_segment_kernel; sb [n_sig][S][15][SL_SEG_W]
+__global__ void __launch_bounds__(256)
+stoi_loss_seg_kernel(const float* __restrict__ env_x, const float* __restrict__ env_y,
+                     const int* __restrict__ nkept, int F, int S, double* __restrict__ sb) {
+    const int sig = blockIdx.y;
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    const int seg = g / ST_J, band = g - seg * ST_J;
+    if (seg >= nkept[sig] - 1 - (ST_SEG - 1)) return;
+    const float* __restrict__ ex = env_x + ((size_t)sig * F + seg) * ST_J + band;
+    const float* __restrict__ ey = env_y + ((size_t)sig * F + seg) * ST_J + band;
+    double X[ST_SEG], Y[ST_SEG];
+#pragma unroll
+    for (int f = 0; f < ST_SEG; ++f) {
+        X[f] = (double)ex[f * ST_J];
+        Y[f] = (double)ey[f * ST_J];
+    }
+    const SegStats st = segment_stats(X, Y);
+    const double nx = st.nx, ny = st.ny, rho = st.rho, my = st.my;
+    const unsigned u = st.u;
+    // sum over the unclipped frames of g Y', Y' = alpha Y there
+    double acc = 0.0;
+#pragma unroll
+    for (int f = 0; f < ST_SEG; ++f) {
+        const double gf = (X[f] / nx - rho * (Y[f] / ny)) / ny;
+        if ((u >> f) & 1u) acc = fma(gf, Y[f] + my, acc);
+    }
+    double* __restrict__ o = sb + ((size_t)sig * S * ST_J + g) * SL_SEG_W;
+    o[0] = st.sy > 0.0 ? st.alpha : -1.0;          // Sy == 0: scored 1, no gradient
+    o[1] = acc / st.sy;
+    o[2] = st.mx;
+    o[3] = 1.0 / nx;
+    o[4] = my;
+    o[5] = 1.0 / ny;
+    o[6] = rho;
+}
+
+// grid (ceil(F * 15 / 256), n_sig): lane e = band frame * 15 + band; gy [n_sig][F][15]
+__global__ void __launch_bounds__(256)
+stoi_loss_env_kernel(const float* __restrict__ env_x, const float* __restrict__ env_y,
+                     const int* __restrict__ nkept, int F, int S, const double* __restrict__ sb,
+                     double* __restrict__ gy) {
+    const int sig = blockIdx.y;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    const int frame = e / ST_J, band = e - frame * ST_J;
+    const int nf = nkept[sig] - 1, nseg = nf - (ST_SEG - 1);
+    if (nseg <= 0 || frame >= nf) return;
+    const double X = (double)env_x[(size_t)sig * F * ST_J + e];
+    const double Y = (double)env_y[(size_t)sig * F * ST_J + e];
+    const double cx = X * ST_CLIP;
+    const int m0 = frame - (ST_SEG - 1) > 0 ? frame - (ST_SEG - 1) : 0;
+    const int m1 = frame < nseg - 1 ? frame : nseg - 1;
+    double acc = 0.0;
+    for (int m = m0; m <= m1; ++m) {
+        const double* __restrict__ s = sb + (((size_t)sig * S + m) * ST_J + band) * SL_SEG_W;
+        const double alpha = s[0];
+        if (!(alpha >= 0.0)) continue;
+        const double ay = alpha * Y;
+        double t = -s[1] * Y;
+        if (ay <= cx) {
+            const double xh = (X - s[2]) * s[3], yh = (ay - s[4]) * s[5];
+            t = fma(alpha, (xh - s[6] * yh) * s[5], t);
+        }
+        acc += t;
+    }
+    gy[(size_t)sig * F * ST_J + e] = -acc / ((double)nseg * ST_J);
+}
+
+// grid as stoi_band_kernel, one wave per band frame; fr [n_sig][F][256]: the gradient with respect to the frame's
+// samples of the compacted estimate
+template <typename T>
+__global__ void __launch_bounds__(256)
+stoi_loss_band_kernel(const T* __restrict__ yr, int64_t ld, const int* __restrict__ kidx,
+                      const int* __restrict__ nkept, int V, int F, const double* __restrict__ gy,
+                      double* __restrict__ fr) {
+    constexpr int NB = ST_K1 - ST_K0;
+    __shared__ double2 tw[FT_N / 2];
+    __shared__ double win[ST_N];
+    __shared__ double2 bufs[4][FT_MP];
+    __shared__ double2 zs[4][NB];              // per wave: the band bins Z_k, then G_k
+    __shared__ double sc[4][16];               // per wave: gY / Y of the 15 bands
+    const int tid = threadIdx.x, wv = tid >> 6, j = tid & 63;
+    const int frame = blockIdx.x * 4 + wv, sig = blockIdx.y;
+    {
+        double sn, cs;
+        sincospi(-2.0 * (double)tid / (double)FT_N, &sn, &cs);
+        tw[tid] = make_double2(cs, sn);
+        win[tid] = hanning256(tid);
+    }
+    __syncthreads();
+    const int nf = nkept[sig] - 1;
+    if (nf < ST_SEG || frame >= nf) return;    // (whole waves: no barrier below)
+    const int* __restrict__ ki = kidx + (size_t)sig * V;
+    const int64_t s0 = (int64_t)ki[frame] * ST_HOP;
+    const int64_t sp = frame > 0 ? (int64_t)ki[frame - 1] * ST_HOP : 0;
+    const int64_t sn = (int64_t)ki[frame + 1] * ST_HOP;
+    const T* __restrict__ src = yr + (size_t)sig * ld;
+    double2* buf = bufs[wv];
+    double2* z = zs[wv];
+    auto wave_sync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+    double2 v[FT_R];
+    v[0] = make_double2(band_sample(src, win, s0, sp, sn, frame, 2 * j),
+                        band_sample(src, win, s0, sp, sn, frame, 2 * j + 1));
+    v[1] = make_double2(band_sample(src, win, s0, sp, sn, frame, 2 * j + 128),
+                        band_sample(src, win, s0, sp, sn, frame, 2 * j + 129));
+    v[2] = make_double2(0.0, 0.0);
+    v[3] = make_double2(0.0, 0.0);
+    fft256_wave(v, buf, tw, j);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int k = ST_K0 + j + 64 * i;
+        if (k < ST_K1) z[k - ST_K0] = real_bin(buf, tw, k);
+    }
+    wave_sync();
+    if (j < ST_J) {
+        double acc = 0.0;
+        for (int k = k_band_lo[j]; k < k_band_hi[j]; ++k) {
+            const double2 a = z[k - ST_K0];
+            acc += a.x * a.x + a.y * a.y;
+        }
+        const double Y = sqrt(acc);
+        sc[wv][j] = Y > 0.0 ? gy[((size_t)sig * F + frame) * ST_J + j] / Y : 0.0;
+    }
+    wave_sync();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int k = ST_K0 + j + 64 * i;
+        if (k < ST_K1) {
+            int b = 0;                         // the bands are contiguous: count the upper edges at or below k
+#pragma unroll
+            for (int t = 0; t < ST_J - 1; ++t) b += k >= k_band_hi[t];
+            const double s = sc[wv][b];
+            const double2 a = z[k - ST_K0];
+            z[k - ST_K0] = make_double2(a.x * s, a.y * s);
+        }
+    }
+    wave_sync();
+    // r[n] = Re sum_k G_k e^{+2 pi i k n / 512} = sum over the Hermitian extension H (H_k = G_k / 2, H_{512-k} its
+    // conjugate); with r packed as r[2m] + i r[2m+1] = sum_{k < 256} Q_k e^{+2 pi i k m / 256},
+    // Q_k = (H_k + H_{k+256}) + i e^{+2 pi i k / 512} (H_k - H_{k+256}).  The passes transform conj(Q).
+#pragma unroll
+    for (int r = 0; r < FT_R; ++r) {
+        const int k = j + 64 * r, kc = FT_M - k;
+        const double2 ha = k >= ST_K0 && k < ST_K1 ? z[k - ST_K0] : make_double2(0.0, 0.0);
+        double2 hb = kc >= ST_K0 && kc < ST_K1 ? z[kc - ST_K0] : make_double2(0.0, 0.0);
+        hb.y = -hb.y;
+        const double2 t = tw[k];
+        const double2 ed = zmul(make_double2(ha.x - hb.x, ha.y - hb.y), make_double2(t.x, -t.y));
+        v[r] = make_double2(0.5 * (ha.x + hb.x - ed.y), -0.5 * (ha.y + hb.y + ed.x));
+    }
+    wave_sync();                               // every lane has read z and buf
+    fft256_wave(v, buf, tw, j);
+    double2* __restrict__ out = (double2*)(fr + ((size_t)sig * F + frame) * ST_N);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int m = j + 64 * i;
+        const double2 a = buf[ft_pad(m)];      // conj(r[2m] + i r[2m+1])
+        out[m] = make_double2(win[2 * m] * a.x, -win[2 * m + 1] * a.y);
+    }
+}
+
+// grid (ceil(width / 256), n_sig): sample m of the 10 kHz estimate.  O = double: the resampled signal's gradient
+// gr [n_sig][ld_out]; O = float: g itself (fs = 10 kHz), zeros behind the length and in a row that is not counted.
+template <typename O>
+__global__ void __launch_bounds__(256)
+stoi_loss_gather_kernel(const double* __restrict__ fr, const int* __restrict__ kidx,
+                        const int* __restrict__ nkept, const int64_t* __restrict__ lens,
+                        const float* __restrict__ stoi, int p, int q, int V, int F, int64_t width,
+                        O* __restrict__ out, int64_t ld_out) {
+    __shared__ double win[ST_N];
+    win[threadIdx.x] = hanning256(threadIdx.x);
+    __syncthreads();
+    const int sig = blockIdx.y;
+    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (m >= width) return;
+    const int64_t rlen = resampled_len(lens[sig], p, q);
+    const int nk = nkept[sig], nf = nk - 1;
+    double acc = 0.0;
+    if (m < rlen && nf >= ST_SEG && isfinite(stoi[sig])) {
+        const int nv = vad_frames_dev(rlen);
+        const int* __restrict__ ki = kidx + (size_t)sig * V;
+        const double* __restrict__ f = fr + (size_t)sig * F * ST_N;
+        const int jhi = (int)(m >> 7);
+        for (int jj = jhi - 1; jj <= jhi; ++jj) {
+            if (jj < 0 || jj >= nv) continue;
+            int lo = 0, hi = nk;               // the kept index of silence-detector frame jj, if it was kept
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (ki[mid] < jj) lo = mid + 1; else hi = mid;
+            }
+            if (lo >= nk || ki[lo] != jj) continue;
+            const int n = (int)(m - (int64_t)jj * ST_HOP);
+            const int i1 = lo + (n >> 7), t = n & (ST_HOP - 1);
+            double gys = 0.0;                  // compacted sample 128 lo + n: band frames i1 - 1 and i1
+            if (i1 >= 1 && i1 - 1 < nf) gys += f[(size_t)(i1 - 1) * ST_N + t + ST_HOP];
+            if (i1 < nf) gys += f[(size_t)i1 * ST_N + t];
+            acc = fma(win[n], gys, acc);
+        }
+    }
+    out[(size_t)sig * ld_out + m] = (O)acc;
+}
+
+// grid (ceil(stride / 256), n_sig): g[k] = sum_m gr[m] h[q m + (L-1)/2 - p k] in m order, 0 behind the length and
+// in a row that is not counted
+__global__ void __launch_bounds__(256)
+stoi_loss_resample_kernel(const double* __restrict__ gr, int64_t ld_r, const int64_t* __restrict__ lens,
+                          const float* __restrict__ stoi, int p, int q, int L, const double* __restrict__ taps,
+                          float* __restrict__ g, int64_t stride) {
+    extern __shared__ double h[];
+    for (int i = threadIdx.x; i < L; i += 256) h[i] = taps[i];
+    __syncthreads();
+    const int sig = blockIdx.y;
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= stride) return;
+    const int64_t len = lens[sig];
+    double acc = 0.0;
+    if (k < len && isfinite(stoi[sig])) {
+        const int64_t half = (L - 1) / 2, lo = (int64_t)p * k - half;
+        const int64_t m0 = lo <= 0 ? 0 : (lo + q - 1) / q;
+        int64_t m1 = ((int64_t)p * k + half) / q;
+        const int64_t rlen = resampled_len(len, p, q);
+        if (m1 > rlen - 1) m1 = rlen - 1;
+        const double* __restrict__ x = gr + (size_t)sig * ld_r;
+        for (int64_t m = m0; m <= m1; ++m) acc = fma(x[m], h[q * m - lo], acc);
+    }
+    g[(size_t)sig * stride + k] = (float)acc;
+}
+
 int gcd_i(int a, int b) {
     while (b) {
         const int t = a % b;
@@ -567,9 +887,9 @@ struct StoiFront {
 
 // The checks of drnmf_stoi and drnmf_stoi_ext (`who` names the caller in the message); fills Lo and max_len.
 int32_t stoi_check(drnmf_handle_t h, const char* who, int32_t n_sig, int64_t stride, const int64_t* lengths_host,
-                   int32_t fs, const float* est, const float* ref, bool have_out, const void* workspace,
-                   StoiLayout& Lo, int64_t& max_len) {
-    if (n_sig <= 0 || n_sig > 65535 || stride <= 0 || !lengths_host || !est || !ref || !have_out || !workspace)
+                   int32_t fs, const float* est, const float* ref, bool have_out, bool have_ws, StoiLayout& Lo,
+                   int64_t& max_len) {
+    if (n_sig <= 0 || n_sig > 65535 || stride <= 0 || !lengths_host || !est || !ref || !have_out || !have_ws)
         DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "%s: bad argument (n_sig in [1, 65535], stride > 0, non-NULL)", who);
     max_len = 0;
     for (int i = 0; i < n_sig; ++i) {
@@ -652,7 +972,7 @@ extern "C" int32_t drnmf_stoi(drnmf_handle_t h, int32_t n_sig, int64_t stride, c
     StoiLayout Lo;
     int64_t max_len;
     const int32_t rc = stoi_check(h, "stoi", n_sig, stride, lengths_host, fs, est, ref, stoi_out != nullptr,
-                                  workspace, Lo, max_len);
+                                  workspace != nullptr, Lo, max_len);
     if (rc != DRNMF_OK) return rc;
     if (workspace_bytes < Lo.total)
         DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "stoi: workspace too small (%zu < %zu bytes)", workspace_bytes,
@@ -679,7 +999,7 @@ extern "C" int32_t drnmf_stoi_ext(drnmf_handle_t h, int32_t n_sig, int64_t strid
     StoiLayout Lo;
     int64_t max_len;
     const int32_t rc = stoi_check(h, "stoi_ext", n_sig, stride, lengths_host, fs, est, ref,
-                                  stoi_out != nullptr || estoi_out != nullptr, workspace, Lo, max_len);
+                                  stoi_out != nullptr || estoi_out != nullptr, workspace != nullptr, Lo, max_len);
     if (rc != DRNMF_OK) return rc;
     const size_t need = Lo.total + estoi_d_bytes(Lo, n_sig);
     if (workspace_bytes < need)
@@ -698,6 +1018,104 @@ extern "C" int32_t drnmf_stoi_ext(drnmf_handle_t h, int32_t n_sig, int64_t strid
         if (estoi_out)
             hipLaunchKernelGGL(estoi_mean_kernel, dim3((unsigned)n_sig), dim3(256), 0, stream, (const double*)d,
                                fr.nk, Lo.S, estoi_out);
+    }
+    DRNMF_HIP(h, hipGetLastError());
+    return DRNMF_OK;
+}
+
+namespace {
+
+// drnmf_stoi_loss's workspace: drnmf_stoi's, then the scores, the segment scalars, gY, the frame gradients and
+// (fs != 10 kHz) the gradient of the resampled estimate
+struct StoiLossLayout {
+    size_t off_stoi, off_sb, off_gy, off_fr, off_gr, total;
+};
+
+StoiLossLayout stoi_loss_layout(const StoiLayout& Lo, int32_t n_sig) {
+    StoiLossLayout G;
+    const size_t n = (size_t)n_sig;
+    size_t o = Lo.total;
+    auto take = [&](size_t bytes) {
+        const size_t at = o;
+        o += round_up_sz(bytes, 256);
+        return at;
+    };
+    G.off_stoi = take(n * sizeof(float));
+    G.off_sb = take(n * Lo.S * ST_J * SL_SEG_W * sizeof(double));
+    G.off_gy = take(n * Lo.F * ST_J * sizeof(double));
+    G.off_fr = take(n * Lo.F * ST_N * sizeof(double));
+    G.off_gr = take(Lo.rs ? n * Lo.rstride * sizeof(double) : 0);
+    G.total = o;
+    return G;
+}
+
+}  // namespace
+
+extern "C" size_t drnmf_stoi_loss_workspace_bytes(int32_t n_sig, int64_t max_len, int32_t fs) {
+    StoiLayout Lo;
+    return stoi_layout(n_sig, max_len, fs, Lo) ? stoi_loss_layout(Lo, n_sig).total : 0;
+}
+
+extern "C" int32_t drnmf_stoi_loss(drnmf_handle_t h, int32_t n_sig, int64_t stride, const int64_t* lengths_host,
+                                   int32_t fs, const float* est, const float* ref, int32_t kind, float* loss,
+                                   float* counted, float* g, float* sums, void* workspace, size_t workspace_bytes,
+                                   void* stream_) {
+    DRNMF_LOCK(h);
+    if (!h) return DRNMF_ERR_INVALID_ARG;
+    StoiLayout Lo;
+    int64_t max_len;
+    // (the per-sample kernels take ceil(stride / 256) workgroups in grid.x, which must stay below 2^31)
+    if (stride > ((int64_t)1 << 38))
+        DRNMF_FAIL(h, DRNMF_ERR_INVALID_ARG, "stoi_loss: bad argument (stride = %lld above 2^38)", (long long)stride);
+    const int32_t rc = stoi_check(h, "stoi_loss", n_sig, stride, lengths_host, fs, est, ref,
+                                  loss && counted && g && sums, true, Lo, max_len);
+    if (rc != DRNMF_OK) return rc;
+    if (kind != DRNMF_STOI_LOSS_STOI)
+        DRNMF_FAIL(h, DRNMF_ERR_UNSUPPORTED, "stoi_loss: kind = %d unsupported (DRNMF_STOI_LOSS_STOI only)", kind);
+    const StoiLossLayout G = stoi_loss_layout(Lo, n_sig);
+    if (!workspace || workspace_bytes < G.total)
+        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "stoi_loss: workspace too small (%zu < %zu bytes)",
+                   workspace ? workspace_bytes : (size_t)0, G.total);
+    if (((uintptr_t)workspace & 255) != 0)
+        DRNMF_FAIL(h, DRNMF_ERR_WORKSPACE, "stoi_loss: workspace is not 256-byte aligned");
+    if (h->device < 0) DRNMF_FAIL(h, DRNMF_ERR_HIP, "stoi_loss: the handle is bound to no device");
+    hipStream_t stream = (hipStream_t)stream_;
+    char* ws = (char*)workspace;
+    const StoiFront fr = stoi_front(Lo, n_sig, stride, lengths_host, max_len, est, ref, nullptr, nullptr, nullptr, ws,
+                                    stream);
+    float* stoi = (float*)(ws + G.off_stoi);
+    stoi_back(Lo, n_sig, fr, stoi, ws, stream);
+    hipLaunchKernelGGL(stoi_loss_rows_kernel, dim3(1), dim3(256), 0, stream, (const float*)stoi, n_sig, loss,
+                       counted, sums);
+    double* sb = (double*)(ws + G.off_sb);
+    double* gy = (double*)(ws + G.off_gy);
+    double* frg = (double*)(ws + G.off_fr);
+    const int64_t* lens = (const int64_t*)(ws + Lo.off_len);
+    const int* kidx = (const int*)(ws + Lo.off_kidx);
+    const int V = Lo.V > 0 ? Lo.V : 1;
+    const unsigned ns = (unsigned)n_sig;
+    hipLaunchKernelGGL(stoi_loss_seg_kernel, dim3((unsigned)((Lo.S * ST_J + 255) / 256), ns), dim3(256), 0, stream,
+                       fr.envx, fr.envy, fr.nk, Lo.F, Lo.S, sb);
+    hipLaunchKernelGGL(stoi_loss_env_kernel, dim3((unsigned)((Lo.F * ST_J + 255) / 256), ns), dim3(256), 0, stream,
+                       fr.envx, fr.envy, fr.nk, Lo.F, Lo.S, (const double*)sb, gy);
+    const dim3 band_grid((unsigned)((Lo.F + 3) / 4), ns);
+    const dim3 out_grid((unsigned)((stride + 255) / 256), ns);
+    if (Lo.rs) {
+        double* gr = (double*)(ws + G.off_gr);
+        const int64_t rmax = resampled_len_h(max_len, Lo.p, Lo.q);
+        hipLaunchKernelGGL(stoi_loss_band_kernel<double>, band_grid, dim3(256), 0, stream,
+                           (const double*)(ws + Lo.off_yr), Lo.rstride, kidx, fr.nk, V, Lo.F, (const double*)gy, frg);
+        hipLaunchKernelGGL(stoi_loss_gather_kernel<double>, dim3((unsigned)((rmax + 255) / 256 > 0 ? (rmax + 255) / 256 : 1), ns),
+                           dim3(256), 0, stream, (const double*)frg, kidx, fr.nk, lens, (const float*)stoi, Lo.p, Lo.q,
+                           V, Lo.F, rmax, gr, Lo.rstride);
+        hipLaunchKernelGGL(stoi_loss_resample_kernel, out_grid, dim3(256), (size_t)Lo.L * sizeof(double), stream,
+                           (const double*)gr, Lo.rstride, lens, (const float*)stoi, Lo.p, Lo.q, Lo.L,
+                           (const double*)(ws + Lo.off_taps), g, stride);
+    } else {
+        hipLaunchKernelGGL(stoi_loss_band_kernel<float>, band_grid, dim3(256), 0, stream, est, stride, kidx, fr.nk, V,
+                           Lo.F, (const double*)gy, frg);
+        hipLaunchKernelGGL(stoi_loss_gather_kernel<float>, out_grid, dim3(256), 0, stream, (const double*)frg, kidx,
+                           fr.nk, lens, (const float*)stoi, Lo.p, Lo.q, V, Lo.F, stride, g, stride);
     }
     DRNMF_HIP(h, hipGetLastError());
     return DRNMF_OK;

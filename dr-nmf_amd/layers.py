@@ -1861,8 +1861,8 @@ class _SequenceModel(object):
         return self.fit(x, y, sample_weight=w, validation_data=val, callbacks=callbacks, **fit_kwargs)
 
     # -- waveform criteria (include/drnmf_waveloss.h): any loss on the mask through loss_and_grads_cot, and the
-    #    SI-SDR / waveform MSE of the masked inverse STFT on top of it.  Whole recordings per row, stateless
-    #    models, float32 operands.
+    #    SI-SDR / waveform MSE of the masked inverse STFT on top of it, or minus its STOI (loss='stoi',
+    #    include/drnmf_stoi_loss.h).  Whole recordings per row, stateless models, float32 operands.
     def _check_cot(self, what):
         """What every entry of this section refuses before anything is enqueued."""
         if self._carries_state():
@@ -1902,14 +1902,16 @@ class _SequenceModel(object):
         self._check_cot('train_on_batch_custom')
         return self._reduce_and_step(self.loss_and_grads_cot(self._to_device(x), cot_fn))
 
-    def _check_wave_args(self, what, loss, N, hop, train=True):
+    def _check_wave_args(self, what, loss, N, hop, train=True, fs=16000):
         """What the waveform entries refuse first: a model they cannot take (train: _check_cot; test_on_wavs: one
-        that carries state), then the criterion, then the bin count."""
+        that carries state), then the criterion (and, for 'stoi', a sampling rate STOI does not take), then the bin
+        count."""
         if train:
             self._check_cot(what)
         elif self._carries_state():
             raise NotImplementedError('%s: a stateful model needs its rows in order and at one length' % what)
-        ops._wave_kind(loss, what)
+        if ops._wave_criterion(loss, what) == 'stoi':
+            ops.stoi_vad_frames(0, fs)
         self._check_bins(what, N)
 
     @staticmethod
@@ -1941,9 +1943,10 @@ class _SequenceModel(object):
         ref = ref.to(torch.float32) / 32768.0 if ref.dtype == torch.int16 else ref
         return pcm, ref, lens_d, np.array([v.shape[0] for v in rx], dtype=np.int64)
 
-    def _wave_batch(self, bank, b, N, hop, kind):
+    def _wave_batch(self, bank, b, N, hop, kind, fs=16000):
         """Recordings `b` (host indices) of a bank as one batch: (x [b,T,F], cot_fn).  cot_fn(mask) runs the cropped
-        inverse, the loss against the clean rows and the inverse's transpose, and returns (sums2, d_mask);
+        inverse, the loss against the clean rows (kind 'stoi': ops.stoi_loss at fs, on the host lengths of the
+        reconstructions; else ops.wave_loss) and the inverse's transpose, and returns (sums2, d_mask);
         backward=False stops behind the loss (d_mask None)."""
         pcm, ref, lens_d, lens = bank
         dev = pcm.device
@@ -1953,7 +1956,8 @@ class _SequenceModel(object):
         pcm_b = pcm.index_select(0, sel)[:, :W].contiguous()
         ref_b = ref.index_select(0, sel)[:, :W].contiguous()
         len_b = lens_d.index_select(0, sel)
-        nout_b = torch.from_numpy(ops.ragged_out_lengths(lb, N, hop, True)).to(dev)
+        nout_h = np.ascontiguousarray(ops.ragged_out_lengths(lb, N, hop, True), dtype=np.int64)
+        nout_b = torch.from_numpy(nout_h).to(dev)
         nb, F = len(b), N // 2 + 1
         T = int(max(ops.stft_frames(int(l), N, hop) for l in lb))
         idx = torch.arange(nb, dtype=torch.int32, device=dev)
@@ -1967,8 +1971,12 @@ class _SequenceModel(object):
             ops.istft_ragged_enqueue(re, im, mask, len_b, idx, N, hop, y, True)
             lo, co = (torch.empty((nb,), dtype=torch.float32, device=dev) for _ in range(2))
             g, sums = torch.empty_like(y), torch.empty((2,), dtype=torch.float32, device=dev)
-            ops.wave_loss_enqueue(y, ref_b, nout_b, ops.WAVE_LOSSES[kind], lo, co, g, sums,
-                                  ops.wave_loss_workspace(nb, W, dev))
+            if kind == 'stoi':
+                ops.stoi_loss_enqueue(y, ref_b, nout_h, fs, lo, co, g, sums,
+                                      ops.stoi_loss_workspace(nb, int(nout_h.max()), fs, dev))
+            else:
+                ops.wave_loss_enqueue(y, ref_b, nout_b, ops.WAVE_LOSSES[kind], lo, co, g, sums,
+                                      ops.wave_loss_workspace(nb, W, dev))
             if not backward:
                 return sums, None
             d_mask = torch.empty((nb, T, F), dtype=torch.float32, device=dev)
@@ -1976,59 +1984,72 @@ class _SequenceModel(object):
             return sums, d_mask
         return x, cot_fn
 
-    def train_on_wavs(self, noisy, clean, loss='si_sdr', N=512, hop=128, max_samples=None):
+    def train_on_wavs(self, noisy, clean, loss='si_sdr', N=512, hop=128, max_samples=None, fs=16000):
         """One optimiser step on a waveform criterion.  noisy, clean: lists of 1-D int16 (scaled by 1/32768) or
         float32 recordings, each pair clipped to its shorter side; recordings longer than max_samples are cut at
         the same places on both sides into pieces that count as recordings of their own.  One row per recording:
         ops.stft_ragged prepared as `enhance` prepares it, the training forward, ops.istft_ragged(crop=True),
         ops.wave_loss ('si_sdr': minus the SI-SDR in dB; 'wave_mse'), ops.istft_ragged_vjp, then
         train_on_batch_custom's step -- nothing returns to the host.  Returns a DeviceLoss: the mean of the counted
-        recordings' losses.  No enhancement quality is claimed for either criterion."""
-        self._check_wave_args('train_on_wavs', loss, N, hop)
-        bank = self._wave_bank(noisy, clean, int(N), int(hop), max_samples, 'train_on_wavs')
-        return self._wave_step(bank, np.arange(bank[3].shape[0]), int(N), int(hop), loss)
+        recordings' losses.  No enhancement quality is claimed for any criterion.
 
-    def _wave_step(self, bank, b, N, hop, kind, live=True):
+        loss='stoi': ops.stoi_loss in ops.wave_loss's place -- minus the STOI of the reconstruction against the
+        clean recording at sampling rate fs (ignored by the other two criteria), with its exact gradient.  A
+        recording, or a piece cut by max_samples, with fewer than 30 STOI band frames (shorter than about 0.41 s at
+        16 kHz once its silent frames are dropped) or a non-finite score is never counted: it adds no loss and no
+        gradient.  Stateless models and float32 operands only, as for the other two."""
+        self._check_wave_args('train_on_wavs', loss, N, hop, fs=fs)
+        bank = self._wave_bank(noisy, clean, int(N), int(hop), max_samples, 'train_on_wavs')
+        return self._wave_step(bank, np.arange(bank[3].shape[0]), int(N), int(hop), loss, fs=int(fs))
+
+    @staticmethod
+    def _wave_fs(kind, fs):
+        """fs as _wave_batch's keyword, for the one criterion that reads it."""
+        return dict(fs=int(fs)) if kind == 'stoi' else {}
+
+    def _wave_step(self, bank, b, N, hop, kind, live=True, fs=16000):
         """One optimiser step on recordings `b` of a bank (not live: a replay that adds nothing to the all-reduce)."""
-        x, cot_fn = self._wave_batch(bank, b, N, hop, kind)
+        x, cot_fn = self._wave_batch(bank, b, N, hop, kind, **self._wave_fs(kind, fs))
         return self._reduce_and_step(self.loss_and_grads_cot(x, cot_fn, live=live))
 
-    def _test_on_wave_bank(self, bank, batch_size, N, hop, loss, what):
+    def _test_on_wave_bank(self, bank, batch_size, N, hop, loss, what, fs=16000):
         s4 = torch.zeros(4, dtype=torch.float32, device=bank[0].device)
         self._drop_stale_fault()
         n = bank[3].shape[0]
         for lo in range(0, n, int(batch_size)):
-            x, cot_fn = self._wave_batch(bank, np.arange(lo, min(n, lo + int(batch_size))), N, hop, loss)
+            x, cot_fn = self._wave_batch(bank, np.arange(lo, min(n, lo + int(batch_size))), N, hop, loss,
+                                         **self._wave_fs(loss, fs))
             s4[:2].add_(cot_fn(self.forward(x), backward=False)[0])
         return self._report_loss(s4, what, plain=True)
 
-    def test_on_wavs(self, noisy, clean, loss='si_sdr', N=512, hop=128, max_samples=None, batch_size=8):
+    def test_on_wavs(self, noisy, clean, loss='si_sdr', N=512, hop=128, max_samples=None, batch_size=8, fs=16000):
         """The criterion of `train_on_wavs` without a step: the mean over the counted recordings of minus the
-        SI-SDR in dB, or of the waveform MSE, of the model's cropped reconstructions (a float)."""
+        SI-SDR in dB, of the waveform MSE, or (loss='stoi', at sampling rate fs) of minus the STOI, of the model's
+        cropped reconstructions (a float)."""
         what = 'test_on_wavs'
-        self._check_wave_args(what, loss, N, hop, train=False)
+        self._check_wave_args(what, loss, N, hop, train=False, fs=fs)
         if int(batch_size) < 1:
             raise ValueError('%s: batch_size must be positive' % what)
         bank = self._wave_bank(noisy, clean, int(N), int(hop), max_samples, what)
-        return self._test_on_wave_bank(bank, batch_size, int(N), int(hop), loss, what)
+        return self._test_on_wave_bank(bank, batch_size, int(N), int(hop), loss, what, int(fs))
 
     def fit_waveform(self, noisy, clean, loss='si_sdr', batch_size=8, epochs=1, validation_wavs=None, callbacks=None,
-                     shuffle=True, seed=0, N=512, hop=128, max_samples=None, verbose=0):
+                     shuffle=True, seed=0, N=512, hop=128, max_samples=None, verbose=0, fs=16000):
         """The epoch loop of `fit` over recordings and a waveform criterion: the recordings (and validation_wavs =
         (noisy, clean), if given) go up once, every step is train_on_wavs' on batch_size of them, val_loss is
-        test_on_wavs' value (minus the mean SI-SDR in dB, or the waveform MSE).  Callbacks and the returned history
-        as `fit`."""
+        test_on_wavs' value (minus the mean SI-SDR in dB, the waveform MSE, or minus the mean STOI of the counted
+        recordings at sampling rate fs).  Callbacks and the returned history as `fit`."""
         what = 'fit_waveform'
-        self._check_wave_args(what, loss, N, hop)
-        N, hop, bs = int(N), int(hop), int(batch_size)
+        self._check_wave_args(what, loss, N, hop, fs=fs)
+        N, hop, bs, fs = int(N), int(hop), int(batch_size), int(fs)
         if bs < 1 or int(epochs) < 0:
             raise ValueError('%s: batch_size must be positive and epochs not negative' % what)
         bank = self._wave_bank(noisy, clean, N, hop, max_samples, what)
         vbank = None if validation_wavs is None else \
             self._wave_bank(validation_wavs[0], validation_wavs[1], N, hop, max_samples, what)
-        validate = None if vbank is None else (lambda: self._test_on_wave_bank(vbank, bs, N, hop, loss, what))
+        validate = None if vbank is None else (lambda: self._test_on_wave_bank(vbank, bs, N, hop, loss, what, fs))
         return self._run_epochs(what, bank[3].shape[0], bs, int(epochs), shuffle, seed, callbacks, verbose,
-                                lambda b, live: self._wave_step(bank, b, N, hop, loss, live), validate)
+                                lambda b, live: self._wave_step(bank, b, N, hop, loss, live, fs), validate)
 
     def _validate(self, validation_data, batch_size, take):
         """Validation loss of fit(), evaluated in mini-batches of `batch_size` sequences as Keras'

@@ -2602,6 +2602,64 @@ def wave_loss(est, ref, lengths, loss='si_sdr', out=None, workspace=None):
     return lo, co, g, sums
 
 
+# ---- the STOI criterion (include/drnmf_stoi_loss.h) -----------------------------------------------------------------
+WAVE_CRITERIA = tuple(sorted(WAVE_LOSSES)) + ('stoi',)     # what train_on_wavs / test_on_wavs / fit_waveform take
+
+
+def _wave_criterion(loss, what):
+    if loss not in WAVE_CRITERIA:
+        raise ValueError("%s: loss must be one of %s (got %r)" % (what, list(WAVE_CRITERIA), loss))
+    return loss
+
+
+def stoi_loss_workspace(n_sig, max_len, fs, device, have=None):
+    return _workspace(max(_capi.lib().drnmf_stoi_loss_workspace_bytes(int(n_sig), int(max_len), int(fs)), 256),
+                      device, have)
+
+
+def stoi_loss_enqueue(est, ref, lengths_host, fs, loss, counted, g, sums, workspace):
+    """drnmf_stoi_loss on tensors the caller owns and has checked (lengths_host: a contiguous int64 numpy array):
+    enqueues, reads nothing back."""
+    n_sig, width = est.shape
+    _call("drnmf_stoi_loss", _dev_index(est), n_sig, width, lengths_host.ctypes.data_as(C.POINTER(C.c_int64)), int(fs),
+          _capi.ptr(est), _capi.ptr(ref), _capi.STOI_LOSS_STOI, _capi.ptr(loss), _capi.ptr(counted), _capi.ptr(g),
+          _capi.ptr(sums), _capi.ptr(workspace), workspace.numel())
+
+
+def stoi_loss(est, ref, lengths, fs=16000, out=None, workspace=None):
+    """Minus STOI per row and its exact gradient (include/drnmf_stoi_loss.h, tests/stoi_loss_ref.py): est, ref
+    [n_sig, width] float32 on one device, row i valid up to lengths[i] (host ints or a tensor; None: width).  Returns
+    (loss [n_sig], counted [n_sig] (1 / 0), g [n_sig, width], sums [2] = {sum of counted losses, their number}) on
+    the device, shaped and typed as `wave_loss` returns them; loss has the bits of -`stoi`; g is the gradient of
+    that SUM with respect to est, zeros behind a row's length.  A row whose STOI is not finite (fewer than 30 band
+    frames -- about 0.41 s at 16 kHz -- or a zero-variance band) is not counted: loss 0, gradient 0.  A segment-band
+    whose estimate is digitally silent scores 1 and gives no gradient; a zero band envelope passes none on.  The
+    silence decision comes from ref alone, so nothing flows through it.  A row's results are bitwise the same in any
+    batch.  `out`: that 4-tuple to write into."""
+    if est.dim() != 2 or est.shape != ref.shape or est.dtype != torch.float32 or ref.dtype != torch.float32 or \
+            est.device != ref.device:
+        raise ValueError("stoi_loss: est, ref must be float32 [n_sig, width] on one device (got %s %s, %s %s)" %
+                         (est.dtype, tuple(est.shape), ref.dtype, tuple(ref.shape)))
+    dev = est.device
+    _dev_index(est)
+    est, ref = est.contiguous(), ref.contiguous()
+    n_sig, width = est.shape
+    if n_sig < 1 or width < 1:
+        raise ValueError("stoi_loss: empty batch")
+    lh = _host_lengths(lengths, n_sig, width)
+    if lh.min() < 0 or lh.max() > width:
+        raise ValueError("stoi_loss: lengths must lie in [0, %d]" % width)
+    max_len = int(lh.max())
+    stoi_vad_frames(max_len, fs)                               # (raises for an unsupported fs)
+    lo, co, g, sums = (None, None, None, None) if out is None else out
+    lo = _out(lo, (n_sig,), torch.float32, dev, "stoi_loss: loss")
+    co = _out(co, (n_sig,), torch.float32, dev, "stoi_loss: counted")
+    g = _out(g, (n_sig, width), torch.float32, dev, "stoi_loss: g")
+    sums = _out(sums, (2,), torch.float32, dev, "stoi_loss: sums")
+    stoi_loss_enqueue(est, ref, lh, fs, lo, co, g, sums, stoi_loss_workspace(n_sig, max_len, fs, dev, workspace))
+    return lo, co, g, sums
+
+
 def _cot_ld(d_mask, shape, dev, what):
     """Row stride of a mask cotangent [..., F] whose rows may be padded (strides (.., ld, 1), ld >= F)."""
     if d_mask.dtype != torch.float32 or tuple(d_mask.shape) != shape or d_mask.device != dev:
