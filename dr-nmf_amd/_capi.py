@@ -5,7 +5,8 @@ STFT / iSTFT's in include/drnmf_stream.h; the sparse-NMF baseline's inference in
 operands in include/drnmf_snmf_f16.h, with per-row noise atoms in include/drnmf_snmf_adapt.h, their online
 form in include/drnmf_snmf_online.h, under the KL cost in include/drnmf_snmf_kl.h; ESTOI beside STOI in include/drnmf_estoi.h;
 the device-side mixer's in include/drnmf_mix.h; the waveform losses' in include/drnmf_waveloss.h; the device-side
-reverberator's in include/drnmf_reverb.h; the STOI criterion's in include/drnmf_stoi_loss.h).
+reverberator's in include/drnmf_reverb.h; the STOI criterion's in include/drnmf_stoi_loss.h; the device-side
+resampler's in include/drnmf_resample.h).
 
 The library is the product path: there is NO fallback.  If the shared object is missing or a
 call fails, an exception is raised.
@@ -317,11 +318,28 @@ STOI_LOSS_SIGNATURES = {
 }
 STOI_LOSS_STOI = 0                                 # DRNMF_STOI_LOSS_STOI
 
+# name -> (restype, argtypes); mirrors include/drnmf_resample.h one to one (a table of its own, like those above)
+RESAMPLE_SIGNATURES = {
+    "drnmf_resample_rate": (_i32, [_i64, _i64, C.POINTER(_i32), C.POINTER(_i32)]),
+    "drnmf_resample_taps_len": (_i64, [_i32, _i32, _i32]),
+    "drnmf_resample_out_len": (_i64, [_i64, _i32, _i32]),
+    "drnmf_resample_tile": (_i32, [_i32, _i32, _i32]),
+    "drnmf_resample_taps": (_i32, [_vp, _i32, _i32, _i32, C.c_double, _vp, _vp]),
+    "drnmf_resample_forward": (_i32, [_vp, _i32, _i64, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "drnmf_resample_chunk": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64,
+                                    _vp, _vp]),
+    "drnmf_resample_carry": (_i32, [_vp, _i32, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+}
+RESAMPLE_MAX_PQ = 640                              # DRNMF_RESAMPLE_MAX_PQ
+RESAMPLE_NZ, RESAMPLE_BETA = 10, 5.0               # DRNMF_RESAMPLE_NZ, DRNMF_RESAMPLE_BETA
+RESAMPLE_TILE = 2048                               # DRNMF_RESAMPLE_TILE
+
 # every table above, one per header: lib() binds them all (a new header adds its table's name here)
 SIGNATURE_TABLES = (SIGNATURES, LSTM_SIGNATURES, SCORE_SIGNATURES, ENHANCE_SIGNATURES, SDR_SIGNATURES,
                     DATASET_SIGNATURES, STREAM_SIGNATURES, SNMF_SIGNATURES, SNMF_F16_SIGNATURES, TARGET_SIGNATURES,
                     ESTOI_SIGNATURES, SNMF_ADAPT_SIGNATURES, SNMF_KL_SIGNATURES, SNMF_ONLINE_SIGNATURES,
-                    MIX_SIGNATURES, WAVELOSS_SIGNATURES, REVERB_SIGNATURES, STOI_LOSS_SIGNATURES)
+                    MIX_SIGNATURES, WAVELOSS_SIGNATURES, REVERB_SIGNATURES, STOI_LOSS_SIGNATURES,
+                    RESAMPLE_SIGNATURES)
 
 _lib = None
 _handles = {}

@@ -63,7 +63,9 @@ NO_SCRATCH = {# (lstm_cot_rows_kernel: the head's backward for a given mask cota
               # the mixer's sample passes hold four quads and an fp64 accumulator per lane; its gain kernel calls pow
               "mix.hip": "mix_",
               # the reverberator holds 8 outputs, their early parts, 16 samples and 8 taps per lane
-              "reverb.hip": "reverb_"}
+              "reverb.hip": "reverb_",
+              # the resampler's chain is an fp64 accumulator and two LDS pointers per lane
+              "resample.hip": "resample_"}
 
 
 def _check_no_scratch(src, remarks):
@@ -97,7 +99,8 @@ def _deps():
                                                                      "drnmf_dataset.h", "drnmf_stream.h", "drnmf_snmf.h", "drnmf_snmf_f16.h",
                                                                      "drnmf_target.h", "drnmf_estoi.h", "drnmf_snmf_adapt.h",
                                                                      "drnmf_snmf_kl.h", "drnmf_snmf_online.h", "drnmf_mix.h",
-                                                                     "drnmf_waveloss.h", "drnmf_reverb.h", "drnmf_stoi_loss.h")] + \
+                                                                     "drnmf_waveloss.h", "drnmf_reverb.h", "drnmf_stoi_loss.h",
+                                                                     "drnmf_resample.h")] + \
         [os.path.abspath(__file__)]
 
 

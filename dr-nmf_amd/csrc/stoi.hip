@@ -35,6 +35,7 @@
 // sum Y^2 = 0 (alpha = inf, inf * 0 = NaN) takes Y' = X (1 + c) and scores 1; a zero-variance vector divides
 // 0 by 0 and the NaN reaches the mean.
 #include "common.h"
+#include "resample_filter.h"
 #include "../../include/drnmf_score.h"
 #include "../../include/drnmf_estoi.h"
 #include "../../include/drnmf_stoi_loss.h"
@@ -73,39 +74,9 @@ __global__ void __launch_bounds__(256) stoi_lengths_kernel(LenChunk c, int n, in
     if (i < n) out[i] = c.len[i];
 }
 
-__device__ double bessel_i0(double x) {
-    double term = 1.0, sum = 1.0;
-    const double q = 0.25 * x * x;
-    for (int k = 1; k < 64; ++k) {
-        term *= q / ((double)k * (double)k);
-        sum += term;
-        if (term < 1e-18 * sum) break;
-    }
-    return sum;
-}
-
-__device__ double resample_tap(int i, int L, int mpq) {
-    const int half = (L - 1) / 2;
-    const double r = (double)(i - half) / (double)half;
-    const double kw = bessel_i0(5.0 * sqrt(fmax(0.0, 1.0 - r * r))) / bessel_i0(5.0);
-    const double x = (double)(i - half) / (double)mpq;
-    const double s = i == half ? 1.0 : sinpi(x) / (M_PI * x);
-    return kw * s / (double)mpq;
-}
-
+// bessel_i0, resample_tap and the body of the taps kernel: resample_filter.h, shared with resample.hip
 __global__ void __launch_bounds__(256) stoi_taps_kernel(int p, int mpq, int L, double* __restrict__ taps) {
-    __shared__ double red[256];
-    const int tid = threadIdx.x;
-    double s = 0.0;
-    for (int i = tid; i < L; i += 256) s += resample_tap(i, L, mpq);
-    red[tid] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    const double scale = (double)p / red[0];
-    for (int i = tid; i < L; i += 256) taps[i] = resample_tap(i, L, mpq) * scale;
+    resample_taps_body(p, mpq, L, 5.0, taps);
 }
 
 // grid (ceil(max resampled length / 256), n_sig, 2): z = 0 the reference, 1 the estimate

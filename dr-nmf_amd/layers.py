@@ -1282,7 +1282,8 @@ class _SequenceModel(object):
         return rows, np.array([w.shape[0] for w in rows], dtype=np.int64), dt
 
     def enhance(self, wavs, N=512, hop=128, batch_size=250, crop=False, dtype='int16', ref=None, fs=16000,
-                return_masks=False, lengths=None, ref_lengths=None, sdr_solver='host', extended_scores=False):
+                return_masks=False, lengths=None, ref_lengths=None, sdr_solver='host', extended_scores=False,
+                fs_in=None):
         """The reference's enhancement loop (enhance.py:1181-1203; audio_dataset.py:267-339: STFT, padding, the
         model, reconstruct_x, wavwrite) as ONE call, on the device from the samples to the samples.  wavs: a list
         of 1-D int16 (scaled by 1/32768, util.py:29-35) or float32 numpy arrays, or a 2-D array / device tensor
@@ -1302,9 +1303,16 @@ class _SequenceModel(object):
         the files it wrote and read back (audio_dataset.py:399-435, score_audio.m:184-203); SegSNR / PESQ stay
         NaN; sdr_solver= is passed on to it ('device': SDR without a host step, ops.sdr_db), and so is
         extended_scores= as extended= (True: a seventh column, ESTOI, ops.estoi).  return_masks=True
-        appends the list of (n_frames_i, F) masks.  No file IO, no resampling."""
+        appends the list of (n_frames_i, F) masks.  No file IO.
+
+        fs_in: the rate the noisy waveforms come at.  Given and different from fs, they are resampled to fs on the
+        device first (ops.resample, include/drnmf_resample.h), then enhanced, returned and scored at fs, exactly as
+        self.enhance(*ops.resample(wavs, fs_in, fs, lengths=lengths), lengths=...) would be; ref is expected at fs.
+        Going back to fs_in is one ops.resample_wavs(out, fs, fs_in).  None, or equal to fs: the call of before."""
         if dtype not in ('int16', 'float32'):
             raise ValueError("enhance: dtype must be 'int16' or 'float32'")
+        if fs_in is not None and ops.resample_rate(fs_in, fs) != (1, 1):
+            wavs, lengths = ops.resample(wavs, fs_in, fs, lengths=lengths, device=self._device())
         N, hop, bs = int(N), int(hop), int(batch_size)
         if bs <= 0 or hop <= 0:
             raise ValueError('enhance: batch_size and hop must be positive')
@@ -1810,7 +1818,8 @@ class _SequenceModel(object):
 
     def fit_mixtures(self, clean, noise, snr_db=None, snr_choices=None, seed=0, N=512, hop=128, maxlen=None,
                      transform='mag', target='mag', validation_wavs=None, shuffle_seed=None, rirs=None,
-                     reverb_prob=1.0, align=True, target_speech='reverberant', early_ms=50.0, fs=16000, **fit_kwargs):
+                     reverb_prob=1.0, align=True, target_speech='reverberant', early_ms=50.0, fs=16000, clean_fs=None,
+                     noise_fs=None, rir_fs=None, **fit_kwargs):
         """`fit` on mixtures made on the device, a fresh draw every epoch (multi-condition training): clean and
         noise, lists of 1-D int16 / float32 arrays, go up once (ops.MixBank); before epoch ep's first batch the
         training tensors are rewritten in place with bank.tensors(bank.draw(snr_db, snr_choices, seed, epoch=ep)),
@@ -1827,16 +1836,20 @@ class _SequenceModel(object):
         added (ops.MixBank with rirs: noisy = wet + g * noise, the SNR that of the reverberant speech), a fresh
         RIR per utterance and epoch from the same seed, dry with probability 1 - reverb_prob.  align,
         target_speech ('reverberant', the default: y is the wet speech; 'early'; 'dry'), early_ms and fs as
-        ops.MixBank takes them.  rirs=None: as before."""
+        ops.MixBank takes them.  rirs=None: as before.
+
+        clean_fs, noise_fs, rir_fs: the rate a side comes at where it is not fs; ops.MixBank resamples that side to
+        fs on the device while the bank is built.  validation_wavs are taken at fs."""
         from . import dp
         mv, build = self._check_fit_wavs('fit_mixtures', N, hop, maxlen, transform, target, fit_kwargs,
                                          mix_snr=(snr_db, snr_choices))
         ops._check_wav_side(clean, 'fit_mixtures', 'clean')
         ops._check_wav_side(noise, 'fit_mixtures', 'noise')
         ops._check_reverb(rirs, align, target_speech, early_ms, fs, 'fit_mixtures')
+        ops._check_side_rates(fs, clean_fs, noise_fs, rir_fs, rirs, 'fit_mixtures')
         val = None if validation_wavs is None else build(*validation_wavs)
         bank = ops.MixBank(clean, noise, rirs=rirs, align=align, target_speech=target_speech, early_ms=early_ms, fs=fs,
-                           device=self._device())
+                           device=self._device(), clean_fs=clean_fs, noise_fs=noise_fs, rir_fs=rir_fs)
         seed_eff = int(seed) + 104729 * dp.rank()
         kw = dict(N=N, hop=hop, maxlen=maxlen, transform=transform, mask_value=mv, target=target)
         draw_kw = dict(snr_db=snr_db, snr_choices=snr_choices, seed=seed_eff)
@@ -3307,22 +3320,24 @@ class SparseNMFModel(_SequenceModel):
     @classmethod
     def from_mixtures(cls, clean, noise, params_snmf, snr_db=None, snr_choices=None, seed=0, N=512, hop=128,
                       device=None, rirs=None, reverb_prob=1.0, align=True, target_speech='reverberant', early_ms=50.0,
-                      fs=16000):
+                      fs=16000, clean_fs=None, noise_fs=None, rir_fs=None):
         """from_wavs on ONE draw of mixtures made on the device (ops.MixBank: clean + g * noise at SNRs uniform in
         snr_db=(lo, hi), default ops.MIX_SNR_DB, or taken from snr_choices): the packed frames of
         bank.frames(bank.draw(snr_db, snr_choices, seed)), then the training of from_wavs.  rirs, reverb_prob,
-        align, target_speech, early_ms, fs: reverberant mixtures, as fit_mixtures takes them."""
+        align, target_speech, early_ms, fs: reverberant mixtures, as fit_mixtures takes them; clean_fs, noise_fs,
+        rir_fs: sides at other rates, resampled to fs on the device (ops.MixBank)."""
         from . import snmf
         ops._check_mix_snr(snr_db, snr_choices, 'from_mixtures')
         ops._check_wav_side(clean, 'from_mixtures', 'clean')
         ops._check_wav_side(noise, 'from_mixtures', 'noise')
         ops._check_reverb(rirs, align, target_speech, early_ms, fs, 'from_mixtures')
+        ops._check_side_rates(fs, clean_fs, noise_fs, rir_fs, rirs, 'from_mixtures')
         dev = torch.device(device if device is not None else 'cuda')
         dev = torch.device('cuda', ops._dev_of(dev))
         p = float(params_snmf.get('spectrogram_power', 1.0))
         with torch.cuda.device(dev):
             bank = ops.MixBank(clean, noise, rirs=rirs, align=align, target_speech=target_speech, early_ms=early_ms,
-                               fs=fs, device=dev)
+                               fs=fs, device=dev, clean_fs=clean_fs, noise_fs=noise_fs, rir_fs=rir_fs)
             draw_kw = dict(reverb_prob=reverb_prob) if rirs is not None else {}
             xf, yf = bank.frames(bank.draw(snr_db=snr_db, snr_choices=snr_choices, seed=seed, **draw_kw), N, hop)
             x_frames = (xf ** p).t().cpu().numpy()

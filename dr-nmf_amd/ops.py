@@ -1449,6 +1449,254 @@ def wavs_to_frames(noisy, clean, N, hop, transform='mag'):
     return xf, yf
 
 
+# ---- rate conversion on the device (include/drnmf_resample.h) ------------------------------------------------
+RESAMPLE_MAX_PQ, RESAMPLE_TILE = _capi.RESAMPLE_MAX_PQ, _capi.RESAMPLE_TILE
+RESAMPLE_NZ, RESAMPLE_BETA = _capi.RESAMPLE_NZ, _capi.RESAMPLE_BETA
+
+
+def resample_rate(fs_in, fs_out):
+    """(p, q) with p / q = fs_out / fs_in reduced (drnmf_resample_rate).  ValueError for a rate that is not a positive
+    whole number and for max(p, q) > RESAMPLE_MAX_PQ = 640."""
+    for fs in (fs_in, fs_out):
+        if isinstance(fs, bool) or not isinstance(fs, (int, float, np.integer, np.floating)) or \
+                not (np.isfinite(fs) and 0 < fs < 2 ** 62 and fs == int(fs)):
+            raise ValueError("resample: a rate must be a positive whole number (got %r)" % (fs,))
+    p, q = C.c_int32(), C.c_int32()
+    if _capi.lib().drnmf_resample_rate(int(fs_in), int(fs_out), C.byref(p), C.byref(q)) != _capi.OK:
+        raise ValueError("resample: %r -> %r reduces to p / q with max(p, q) > %d" % (fs_in, fs_out, RESAMPLE_MAX_PQ))
+    return p.value, q.value
+
+
+def resample_out_lengths(lengths, fs_in, fs_out):
+    """ceil(n p / q) for every n of `lengths`, int64, on the host."""
+    p, q = resample_rate(fs_in, fs_out)
+    n = np.asarray(lengths, dtype=np.int64)
+    if (n < 0).any():
+        raise ValueError("resample_out_lengths: a length is negative")
+    return -(-n * p // q)
+
+
+def _resample_filter_shape(p, q, nz):
+    """(L, tile) of the kernel for a reduced rate: the filter's taps (0 for p == q == 1) and the outputs per
+    workgroup.  ValueError where the library refuses nz."""
+    nz = int(nz)
+    tile = int(_capi.lib().drnmf_resample_tile(p, q, nz)) if -2 ** 31 <= nz < 2 ** 31 else 0
+    if tile < 1:
+        raise ValueError("resample: nz = %r is not a filter the kernel holds at p / q = %d / %d" % (nz, p, q))
+    return int(_capi.lib().drnmf_resample_taps_len(p, q, nz)), tile
+
+
+def resample_tile(fs_in, fs_out, nz=RESAMPLE_NZ):
+    """The outputs one workgroup of the kernel owns at this rate (drnmf_resample_tile)."""
+    return _resample_filter_shape(*resample_rate(fs_in, fs_out), nz=nz)[1]
+
+
+_resample_taps_cache = {}
+
+
+def resample_taps(p, q, nz=RESAMPLE_NZ, beta=RESAMPLE_BETA, device=None):
+    """The filter of include/drnmf_resample.h for a reduced p / q, fp64 [L] on the device: computed there once per
+    (device, p, q, nz, beta) and kept.  A later caller's stream waits for the launch that filled it."""
+    di = _dev_of('cuda' if device is None else device)
+    beta = float(beta)
+    if not 0.0 <= beta < 1e3:
+        raise ValueError("resample: beta = %r must lie in [0, 1000)" % beta)
+    key = (di, int(p), int(q), int(nz), beta)
+    if key not in _resample_taps_cache:
+        L, _ = _resample_filter_shape(int(p), int(q), nz)
+        with torch.cuda.device(di):
+            taps = torch.empty(L, dtype=torch.float64, device=torch.device('cuda', di))
+            _call("drnmf_resample_taps", di, int(p), int(q), int(nz), beta, _capi.ptr(taps))
+            ev = torch.cuda.Event()
+            ev.record()
+        _resample_taps_cache[key] = (taps, ev)
+    taps, ev = _resample_taps_cache[key]
+    torch.cuda.current_stream(di).wait_event(ev)
+    return taps
+
+
+def _resample_input(x, lengths, dev, what):
+    """(pcm [n][stride] on dev, host lengths int64 [n], device lengths or None) of what `resample` takes: a list of
+    1-D arrays, or a 2-D array / device tensor with lengths=."""
+    if isinstance(x, torch.Tensor) or (isinstance(x, np.ndarray) and x.ndim == 2):
+        if lengths is None:
+            raise ValueError("%s: a 2-D array or tensor comes with lengths=" % what)
+        lens = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths, dtype=np.int64).reshape(-1)
+        if isinstance(x, np.ndarray):
+            if x.dtype not in (np.dtype('int16'), np.dtype('float32')):
+                raise ValueError("%s: samples must be int16 or float32 (got %s)" % (what, x.dtype))
+            x = _upload_pinned(x, dev)
+        if x.dim() != 2 or x.dtype not in (torch.int16, torch.float32) or not x.is_contiguous() or x.shape[0] < 1 \
+                or x.shape[1] < 1:
+            raise ValueError("%s: samples must be a contiguous 2-D int16 or float32 tensor [n][stride] (got %s %s)"
+                             % (what, x.dtype, tuple(x.shape)))
+        if x.device != dev:
+            raise ValueError("%s: the samples are on %s, the call on %s" % (what, x.device, dev))
+        if lens.shape[0] != x.shape[0] or lens.min() < 0 or lens.max() > x.shape[1]:
+            raise ValueError("%s: lengths must be %d values in [0, %d]" % ((what,) + tuple(x.shape)))
+        return x, lens, None
+    if lengths is not None:
+        raise ValueError("%s: lengths= goes with a 2-D array, not with a list" % what)
+    rows = [np.asarray(v) for v in x]
+    if not rows:
+        raise ValueError("%s: no waveforms" % what)
+    dt = rows[0].dtype
+    if dt not in (np.dtype('int16'), np.dtype('float32')):
+        raise ValueError("%s: waveforms must be int16 or float32 (got %s)" % (what, dt))
+    for v in rows:
+        if v.ndim != 1 or v.dtype != dt:
+            raise ValueError("%s: every waveform must be a 1-D %s array (one type per call)" % (what, dt))
+    lens = np.array([v.shape[0] for v in rows], dtype=np.int64)
+    if lens.max() < 1:          # nothing to upload; a row width of one keeps the strides positive
+        tdt = torch.int16 if dt == np.dtype('int16') else torch.float32
+        return torch.zeros((len(rows), 1), dtype=tdt, device=dev), lens, torch.zeros(len(rows), dtype=torch.int64,
+                                                                                     device=dev)
+    pcm, lens_d = _upload_wav_side(rows, dt, dev)
+    return pcm, lens, lens_d
+
+
+def resample(x, fs_in, fs_out, lengths=None, out=None, nz=RESAMPLE_NZ, beta=RESAMPLE_BETA, device=None):
+    """Waveforms at fs_in converted to fs_out on the device (drnmf_resample_forward; the definition -- Matlab's
+    `resample` filter with nz zero crossings a side and Kaiser beta, one ascending fp64 chain per output, rounded
+    once to float32 -- is in include/drnmf_resample.h).  x: a list of 1-D int16 (scaled by 1/32768) or float32 numpy
+    arrays of any lengths, 0 included, or a 2-D array / device tensor [n][stride] with lengths=.  Returns (y,
+    out_lengths): float32 [n][max(1, max out_lengths)] on the device, zeros behind a row's length, and
+    out_lengths = ceil(lengths p / q) int64 on the host.  out=: a float32 [n][width] tensor at least that wide, written
+    whole and returned.  Equal rates copy (int16 converted).  Enqueues only; a list goes up in one pinned copy."""
+    p, q = resample_rate(fs_in, fs_out)
+    L, _ = _resample_filter_shape(p, q, nz)
+    if isinstance(x, torch.Tensor):
+        dev = torch.device('cuda', _dev_index(x))
+    else:
+        dev = torch.device('cuda', _dev_of('cuda' if device is None else device))
+    with torch.cuda.device(dev):
+        pcm, lens, lens_d = _resample_input(x, lengths, dev, "resample")
+        n_out = -(-lens * p // q)
+        n, need = pcm.shape[0], max(1, int(n_out.max()))
+        if out is None:
+            out = torch.empty((n, need), dtype=torch.float32, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.dim() != 2 or out.shape[0] != n or out.shape[1] < need or \
+                out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+            raise ValueError("resample: out must be a contiguous float32 tensor [%d][>= %d] on %s" % (n, need, dev))
+        if lens_d is None:
+            lens_d = _upload_pinned(lens, dev)
+        taps = resample_taps(p, q, nz, beta, dev) if L else None
+        _call("drnmf_resample_forward", _dev_index(pcm), n, pcm.shape[1], _capi.ptr(lens_d),
+              int(pcm.dtype == torch.int16), _capi.ptr(pcm), p, q, int(nz), _capi.ptr(taps), out.shape[1],
+              _capi.ptr(out))
+    return out, n_out
+
+
+def resample_wavs(x, fs_in, fs_out, lengths=None, nz=RESAMPLE_NZ, beta=RESAMPLE_BETA, device=None):
+    """`resample` and the one download: a list of float32 numpy arrays, row i ceil(len_i p / q) samples."""
+    y, n_out = resample(x, fs_in, fs_out, lengths=lengths, nz=nz, beta=beta, device=device)
+    host = y.cpu().numpy()
+    return [host[i, :int(k)].copy() for i, k in enumerate(n_out)]
+
+
+class ResampleStream(object):
+    """`resample` for audio that arrives piece by piece, n_streams recordings side by side.  push(chunks) takes one
+    chunk per stream (1-D numpy arrays of the stream's dtype, 'float32' or 'int16'; any lengths, 0 included) and
+    returns, per stream, the float32 outputs that have become final: output m is final once sample floor((q m +
+    half) / p) has arrived.  close() returns the rest, reset() starts over.  Over all pushes a stream yields
+    exactly ceil(n p / q) samples, with the bits of `resample` on the whole recording however it was cut: the same
+    kernel sums the same chain (drnmf_resample_chunk).  The samples a later output still needs -- at most about
+    (L - 1) / p + q / p + 1 a stream -- stay on the device (drnmf_resample_carry moves them to the front of the next
+    row and appends the new chunk); the counters live on the host.  A push is one pinned upload, two launches and
+    one download."""
+
+    def __init__(self, n_streams, fs_in, fs_out, dtype='float32', device=None, nz=RESAMPLE_NZ, beta=RESAMPLE_BETA):
+        if dtype not in ('int16', 'float32'):
+            raise ValueError("ResampleStream: dtype must be 'int16' or 'float32'")
+        if int(n_streams) < 1 or int(n_streams) > 65535:
+            raise ValueError("ResampleStream: n_streams = %r must lie in [1, 65535]" % (n_streams,))
+        self.n_streams, self.dtype = int(n_streams), np.dtype(dtype)
+        self.p, self.q = resample_rate(fs_in, fs_out)
+        self.nz = int(nz)
+        L, _ = _resample_filter_shape(self.p, self.q, self.nz)
+        self.L = L if L else 1                                  # the copy: a filter of one tap
+        self.half = (self.L - 1) // 2
+        self.device = torch.device('cuda', _dev_of('cuda' if device is None else device))
+        self._taps = resample_taps(self.p, self.q, self.nz, beta, self.device) if L else None
+        self.reset()
+
+    def reset(self):
+        """Every stream empty and open."""
+        n = self.n_streams
+        self.n_in = np.zeros(n, dtype=np.int64)         # samples arrived
+        self.n_out = np.zeros(n, dtype=np.int64)        # outputs returned
+        self.held_from = np.zeros(n, dtype=np.int64)    # the first sample the device row holds
+        tdt = torch.int16 if self.dtype == np.dtype('int16') else torch.float32
+        self._rows = [torch.empty((n, 1), dtype=tdt, device=self.device) for _ in range(2)]     # [0]: the history
+        self.closed = False
+
+    def _first_needed(self, m):
+        lo = self.q * m + self.half - (self.L - 1)
+        return np.maximum(-(-lo // self.p), 0)
+
+    def push(self, chunks, final=False):
+        if self.closed:
+            raise ValueError("ResampleStream: the streams are closed; reset() starts over")
+        rows = [np.asarray(c) for c in chunks]
+        n, p, q = self.n_streams, self.p, self.q
+        if len(rows) != n:
+            raise ValueError("ResampleStream: %d chunks for %d streams" % (len(rows), n))
+        for c in rows:
+            if c.ndim != 1 or c.dtype != self.dtype:
+                raise ValueError("ResampleStream: every chunk must be a 1-D %s array" % self.dtype)
+        add = np.array([c.shape[0] for c in rows], dtype=np.int64)
+        n_in = self.n_in + add
+        if final:
+            n_out = -(-n_in * p // q)
+        else:
+            n_out = np.maximum((p * n_in - 1 - self.half) // q + 1, self.n_out)
+        # the row of this push: the history from the first sample that output self.n_out needs, then the chunk
+        start = np.minimum(self._first_needed(self.n_out), self.n_in)
+        drop, keep = start - self.held_from, self.n_in - start
+        held, cnt = keep + add, n_out - self.n_out
+        amax, width = int(add.max()), max(1, int(held.max()))
+        prev, nxt = self._rows
+        with torch.cuda.device(self.device):
+            if nxt.shape[1] < width:
+                nxt = torch.empty((n, -(-width // 1024) * 1024), dtype=prev.dtype, device=self.device)
+            # one pinned upload: eight int64 tables [n] | the chunks [n][amax]
+            isz = self.dtype.itemsize
+            host = torch.empty(64 * n + n * amax * isz, dtype=torch.uint8, pin_memory=True)
+            hn = host.numpy()
+            tab = hn[:64 * n].view(np.int64).reshape(8, n)
+            for r, v in enumerate((drop, keep, add, held, start, self.n_out, cnt,
+                                   n_in if final else np.full(n, -1, dtype=np.int64))):
+                tab[r] = v
+            if amax:
+                pk = hn[64 * n:].view(self.dtype).reshape(n, amax)
+                for i, c in enumerate(rows):
+                    pk[i, :c.shape[0]] = c
+            d = host.to(self.device, non_blocking=True)
+            t = d[:64 * n].view(torch.int64).view(8, n)
+            chunk = d[64 * n:].view(prev.dtype).view(n, amax) if amax else None
+            di = _dev_of(self.device)
+            _call("drnmf_resample_carry", di, n, int(self.dtype == np.dtype('int16')), prev.shape[1], _capi.ptr(prev),
+                  amax, _capi.ptr(chunk), _capi.ptr(t[0]), _capi.ptr(t[1]), _capi.ptr(t[2]), nxt.shape[1],
+                  _capi.ptr(nxt))
+            y = None
+            if int(cnt.max()) > 0:
+                y = torch.empty((n, int(cnt.max())), dtype=torch.float32, device=self.device)
+                _call("drnmf_resample_chunk", di, n, nxt.shape[1], _capi.ptr(t[3]), _capi.ptr(t[4]), _capi.ptr(t[5]),
+                      _capi.ptr(t[6]), _capi.ptr(t[7]), int(self.dtype == np.dtype('int16')), _capi.ptr(nxt), p, q,
+                      self.nz, _capi.ptr(self._taps), y.shape[1], _capi.ptr(y))
+            self._rows = [nxt, prev]
+            self.n_in, self.n_out, self.held_from = n_in, n_out, start
+            self.closed = bool(final)
+            if y is None:
+                return [np.zeros(0, dtype=np.float32) for _ in range(n)]
+            yh = y.cpu().numpy()
+        return [yh[i, :int(k)].copy() for i, k in enumerate(cnt)]
+
+    def close(self):
+        """End every stream: the outputs still held back, cut at ceil(n p / q)."""
+        return self.push([np.zeros(0, dtype=self.dtype) for _ in range(self.n_streams)], final=True)
+
+
 # ---- mixtures of a speech bank and a noise bank on the device (include/drnmf_mix.h) -------------------------
 def _mix_pcm(t, name):
     if t.dim() != 2 or t.dtype not in (torch.int16, torch.float32) or not t.is_contiguous() or t.shape[0] < 1 \
@@ -1588,6 +1836,22 @@ def _check_reverb(rirs, align, target_speech, early_ms, fs, what):
     return rows
 
 
+def _check_side_rates(fs, clean_fs, noise_fs, rir_fs, rirs, what):
+    """The three side rates of a bank against its fs, before anything is uploaded: each None where the side is
+    taken as it is (not given, equal to fs, or rir_fs without RIRs), else a rate `resample` converts to fs."""
+    out = []
+    for side_fs, used in ((clean_fs, True), (noise_fs, True), (rir_fs, rirs is not None)):
+        if side_fs is not None:
+            try:
+                p, q = resample_rate(side_fs, fs)
+            except ValueError as e:
+                raise ValueError("%s: %s" % (what, e))
+            if (p, q) == (1, 1) or not used:
+                side_fs = None
+        out.append(side_fs)
+    return out
+
+
 def rir_delays(rirs):
     """The index of the first maximum of |h| of every RIR of a list (its direct-path tap), int32 [n_rir], on the
     host."""
@@ -1725,31 +1989,48 @@ class MixBank(object):
     target_speech: what the pair kernels get as the clean member -- 'reverberant' (wet: the CHiME2 convention, the
     model removes noise only), 'early' (the direct path and the reflections up to early_ms after it: the model
     also removes late reverberation) or 'dry' (the bank's clean side; needs align=True).  rirs=None: the bank of
-    before, the same launches and the same bits."""
+    before, the same launches and the same bits.
+
+    clean_fs, noise_fs, rir_fs: the rate a side comes at.  A side whose rate is given and differs from fs is
+    resampled to fs once, on the device, while the bank is built (`resample`, include/drnmf_resample.h), and is
+    then held as float32; everything after that -- lengths, the energy table, draws, tensors, frames, wavs -- is the
+    bank built from resample_wavs(side, side_fs, fs).  An RIR is resampled like any waveform: its samples follow the
+    definition, so its gain as a filter scales by fs / rir_fs (the SNR of a mixture is that of the wet speech either
+    way).  None (and a rate equal to fs): the side is taken as it is, the same launches and bits as before."""
 
     def __init__(self, clean, noise, rirs=None, align=True, target_speech='reverberant', early_ms=50.0, fs=16000,
-                 device=None):
+                 device=None, clean_fs=None, noise_fs=None, rir_fs=None):
         ry, dty = _check_wav_side(clean, "MixBank", "clean")
         rn, dtn = _check_wav_side(noise, "MixBank", "noise")
         rr = _check_reverb(rirs, align, target_speech, early_ms, fs, "MixBank")
+        clean_fs, noise_fs, rir_fs = _check_side_rates(fs, clean_fs, noise_fs, rir_fs, rirs, "MixBank")
         self.target_speech, self.n_rir = target_speech, (0 if rr is None else len(rr))
-        if dty == np.dtype('int16'):
+        if dty == np.dtype('int16') and clean_fs is None:
             ry = [v.astype(np.float32) / np.float32(32768.0) for v in ry]
         self.n, self.n_noise = len(ry), len(rn)
-        self.len_clean = np.array([v.shape[0] for v in ry], dtype=np.int64)
-        self.len_noise = np.array([v.shape[0] for v in rn], dtype=np.int64)
         dev = torch.device('cuda' if device is None else device)
         self.device = torch.device('cuda', _dev_of(dev))
+
+        def side(rows, dt, side_fs):
+            """(samples, lengths on the device, lengths on the host) of one side at fs"""
+            if side_fs is None:
+                return _upload_wav_side(rows, dt, self.device) + (np.array([v.shape[0] for v in rows], dtype=np.int64),)
+            y, n_out = resample(rows, side_fs, fs, device=self.device)
+            return y, _upload_pinned(n_out, self.device), n_out
         with torch.cuda.device(self.device):
-            self.clean, self.len_clean_dev = _upload_wav_side(ry, np.dtype('float32'), self.device)
-            self.noise, self.len_noise_dev = _upload_wav_side(rn, dtn, self.device)
+            self.clean, self.len_clean_dev, self.len_clean = side(ry, np.dtype('float32') if clean_fs is None else dty,
+                                                                  clean_fs)
+            self.noise, self.len_noise_dev, self.len_noise = side(rn, dtn, noise_fs)
             self.workspace = mix_workspace(self.n, self.clean.shape[1], self.device)
             # (a bank with RIRs mixes the wet speech, whose energy changes with the draw: mix_forward computes it)
             self.energy = None if rr is not None else mix_energy(self.clean, self.len_clean_dev,
                                                                  workspace=self.workspace)
             self.noisy = torch.empty(tuple(self.clean.shape), dtype=torch.float32, device=self.device)
             if rr is not None:
-                self.rirs, self.len_rir_dev = _upload_wav_side(rr, np.dtype('float32'), self.device)
+                self.rirs, self.len_rir_dev, len_rir = side(rr, np.dtype('float32'), rir_fs)
+                if rir_fs is not None and align:        # the direct-path taps are those of the RIRs at fs
+                    host = self.rirs.cpu().numpy()
+                    rr = [host[i, :int(k)] for i, k in enumerate(len_rir)]
                 delay = rir_delays(rr) if align else np.zeros(len(rr), dtype=np.int32)
                 taps = np.stack([delay, rir_early_counts(delay, early_ms, fs)])
                 taps_d = _upload_pinned(taps, self.device)
